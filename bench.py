@@ -14,7 +14,7 @@ case, the tie-heavy variant, strict depth, L1, sampled simplex), each checked ag
 run.  N > 1: `extras` holds config 3 (10^5 curves x 256 timepoints in all, strong scaling, both decompositions) and
 config 5 (10^6 points in R^3 through sharded_pointcloud).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  --dump-outputs DIR also writes the last timed step's result to DIR/*.npy (dump_outputs).
 """
 import argparse
 import glob
@@ -428,6 +428,29 @@ def extras_multi_gpu(torch, dist, dev, rank, N, reps=5):
     return out
 
 
+DUMP_LIMIT = 60 * 2**20      # bytes of array data, all files of one --dump-outputs together (< 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, counts):
+    """--dump-outputs: the step's result as its caller receives it -- the int64 containment totals [n_loc, J-1] -- written as
+    out_dir/mbd_counts.npy in float64 (exact below 2^53).  Above DUMP_LIMIT a fixed sample of rows (seed 0, sorted) is written
+    instead, with its row indices in mbd_counts_rows.npy.  Returns {name: shape} of the files written."""
+    c = counts.cpu().numpy()
+    assert c.dtype == np.int64 and np.abs(c).max(initial=0) < 2**53
+    rows = None
+    if c.nbytes > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (8 * (c.shape[1] + 1))
+        rows = np.sort(np.random.default_rng(0).choice(c.shape[0], size=keep, replace=False))
+        c = c[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"mbd_counts": c.astype(np.float64)}
+    if rows is not None:
+        arrays["mbd_counts_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def launch_plan(gpus, argv, env):
     """How `bench.py --gpus N` gets its ranks.  Under a launcher (WORLD_SIZE set: the driver's `python -m torch.distributed.run
     ...`) or at N = 1 this process IS a rank.  With N > 1 and no launcher the process becomes a parent that starts N ranks of
@@ -482,7 +505,12 @@ def main():
     ap.add_argument("--print-launch", action="store_true",
                     help="print the launch plan (the child command for --gpus N > 1 without a launcher) as JSON and exit; "
                          "touches no GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's containment counts) to "
+                         "DIR/<name>.npy as float64, at most 64 MB; the inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     plan = launch_plan(args.gpus, sys.argv[1:], os.environ)
     if args.print_launch:
@@ -580,6 +608,7 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     pairs_per_step = float(n_loc) * N * (n - 1)          # ordered (target, other) pairs, whole job
     value = pairs_per_step / (dt / args.steps)
+    dumped = dump_outputs(args.dump_outputs, outs[(args.steps - 1) % K]) if args.dump_outputs and rank == 0 else None
     replay = None
     if K > 1:                                            # the same loop on ONE matrix: the working set stays in the Infinity Cache
         rdt, rdev = timed(lambda i: step_on(0), args.steps, args.warmup, stream, torch, barrier)
@@ -648,6 +677,8 @@ def main():
         if replay:
             replay["roofline_frac"] = bytes_alg / (replay["kernel_ms"] * 1e-3) / HBM_PEAK
             line["replay"] = replay
+        if dumped:
+            line["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and N == 1:
             import oracle
             oracle.build()

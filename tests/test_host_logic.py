@@ -313,3 +313,24 @@ def test_bench_self_launch_plan():
     src = open(bench).read()
     head = src[:src.index("def main():")]
     assert "import torch" not in head
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs without a GPU: the step's int64 totals land in DIR/mbd_counts.npy as float64, unchanged; above
+    the size limit a fixed, seeded sample of rows is written beside its row indices, the same sample every time."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_module3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    counts = torch.from_numpy(np.random.default_rng(3).integers(0, 2**40, size=(1000, 2)))
+    assert bench.dump_outputs(str(tmp_path / "a"), counts) == {"mbd_counts": [1000, 2]}
+    got = np.load(tmp_path / "a" / "mbd_counts.npy")
+    assert got.dtype == np.float64 and (got.astype(np.int64) == counts.numpy()).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 24 * 100)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), counts) == {"mbd_counts": [100, 2], "mbd_counts_rows": [100]}
+    rows = np.load(tmp_path / "b" / "mbd_counts_rows.npy")
+    assert (np.diff(rows) > 0).all() and (rows == np.load(tmp_path / "c" / "mbd_counts_rows.npy")).all()
+    assert (np.load(tmp_path / "b" / "mbd_counts.npy") == counts.numpy()[rows.astype(np.int64)]).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 24 * 100 + 2 * 128
