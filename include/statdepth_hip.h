@@ -281,6 +281,24 @@ size_t sd_multi_band_workspace_bytes(int64_t n, int64_t T, int d);
 int sd_multi_band_counts(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m,
                          int64_t *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K7: Oja volume sums of a point cloud ------------------------------------------------
+ * Replaces: the subset loop of _oja_depth (_pointcloud.py:175-205, one scipy ConvexHull per simplex).  P is n x d
+ * row-major.  out[q] = sum over d-subsets S of the target's others of vol(conv(S u {x})) = |det[x_s - x]| / d!
+ * (fp64, raw sums); depth = out / ConvexHull(sample).volume on the host.  Degenerate simplices add their volume (~0).
+ *   sd_oja_volume_sums:          others = the n - 1 rows other than targets[q] (NULL = all, m == n);
+ *   sd_oja_external_volume_sums: d-subsets of ALL n rows of P against the external point Q[q] (m x d);
+ *   sd_oja_subset_volume_sums:   blocks of rows, members int32[nb*bs], -1 padded, the block's others first and its
+ *                                target LAST (the K-block sampled estimator).
+ * A target's result is bitwise independent of m, of the other targets and of the run.  d in [1, 8];
+ * SD_ERR_OVERFLOW if C(others, d) >= 2^62; SD_ERR_UNSUPPORTED for 2^31 or more others or if m * C(others, d) > 1e14
+ * (hours of work).  Every launch is bounded (at most 2^32 >> max(0, d - 5) subset volumes). */
+int sd_oja_volume_sums(const double *P, int64_t n, int d, const int64_t *targets, int64_t m,
+                       double *out, void *stream);
+int sd_oja_external_volume_sums(const double *P, int64_t n, int d, const double *Q, int64_t m,
+                                double *out, void *stream);
+int sd_oja_subset_volume_sums(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs,
+                              double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

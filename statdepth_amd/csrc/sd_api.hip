@@ -558,4 +558,50 @@ int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d, const
     return launch_multi_simplex(P, n, T, d, targets, m, relax, tol, samples, seed, (u64 *)out, (hipStream_t)stream, ws, ws_bytes);
 }
 
+// ---------------------------------------------------------------------------
+// K7
+// ---------------------------------------------------------------------------
+static constexpr double OJA_MAX_EVALS = 1e14;   // m * C(others, d): beyond this a call would run for hours
+
+static int check_oja(const double *P, i64 n, int d, i64 m, const void *out, i64 n_others) {
+    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n <= 0 || m < 0) return fail(SD_ERR_INVALID, "bad shape");
+    if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "oja volume sums cover d in [1,8], got %d", d);
+    if (n_others >= ((i64)1 << 31))                                 // subset indices are 32-bit in the kernel
+        return fail(SD_ERR_UNSUPPORTED, "oja volume sums take fewer than 2^31 other points, got %lld", (long long)n_others);
+    u64 c;
+    if (!binom_u64_checked((u64)(n_others > 0 ? n_others : 0), d, &c) || (c >> 62))
+        return fail(SD_ERR_OVERFLOW, "C(%lld,%d) subsets per target is not enumerable", (long long)n_others, d);
+    if ((double)m * (double)c > OJA_MAX_EVALS)
+        return fail(SD_ERR_UNSUPPORTED, "%lld targets x C(%lld,%d) subsets exceeds the cap of %.0e simplex volumes",
+                    (long long)m, (long long)n_others, d, OJA_MAX_EVALS);
+    return SD_OK;
+}
+
+int sd_oja_volume_sums(const double *P, int64_t n, int d, const int64_t *targets, int64_t m, double *out, void *stream) {
+    int rc = check_oja(P, n, d, m, out, n - 1);
+    if (rc) return rc;
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    if (m == 0) return SD_OK;
+    return launch_oja_volume_sums(P, n, d, targets, m, out, (hipStream_t)stream);
+}
+
+int sd_oja_external_volume_sums(const double *P, int64_t n, int d, const double *Q, int64_t m, double *out, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_oja(P, n, d, m, out, n);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_oja_external(P, n, d, Q, m, out, (hipStream_t)stream);
+}
+
+int sd_oja_subset_volume_sums(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs, double *out,
+                              void *stream) {
+    if (!members) return fail(SD_ERR_INVALID, "null pointer");
+    if (bs <= 0 || nb < 0) return fail(SD_ERR_INVALID, "bad shape");
+    int rc = check_oja(P, n, d, nb, out, bs - 1);
+    if (rc) return rc;
+    if (nb == 0) return SD_OK;
+    return launch_oja_subsets(P, n, d, members, nb, bs, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

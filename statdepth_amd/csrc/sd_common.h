@@ -118,6 +118,11 @@ size_t multi_band_workspace_bytes(i64 n, i64 T, int d);
 int launch_multi_band(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, u64 *out, void *ws, size_t ws_bytes,
                       hipStream_t s);
 
+// K7 Oja volume sums (oja.hip): out = sum of |det| / d! over the d-subsets of the others
+int launch_oja_volume_sums(const double *P, i64 n, int d, const i64 *targets, i64 m, double *out, hipStream_t s);
+int launch_oja_external(const double *P, i64 n, int d, const double *Q, i64 m, double *out, hipStream_t s);
+int launch_oja_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double *out, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

@@ -1,8 +1,11 @@
 """Point-cloud depth drivers on the HIP engine.
 
 Mirrors statdepth/depth/calculations/_pointcloud.py: `_pointwisedepth` (:14-66),
-`_samplepointwisedepth` (:68-123), `_L1_depth` (:125-150).  Mahalanobis and Oja depth
-(:152-205) are outside the containment/count hot path and are not provided.
+`_samplepointwisedepth` (:68-123), `_L1_depth` (:125-150) and `_oja_depth` (:175-205).  Oja depth is the
+reference's quantity -- the summed volumes of the simplices the point spans with every d-subset of the other
+points, over the volume of the sample's convex hull -- with the volume sums on the GPU (sd_oja_*) and the hull
+(scipy's Qhull, as in the reference) on the host; DESIGN.md §3 K7 / §4 lists where it departs from the reference.
+Mahalanobis depth (:152-173) is not provided: the reference's covariance is singular by construction.
 """
 from typing import Union
 
@@ -11,6 +14,7 @@ import pandas as pd
 from scipy.special import binom
 
 from ... import engine
+from ._helper import DepthDegeneracy
 
 __all__ = ['_pointwisedepth', '_samplepointwisedepth']
 
@@ -21,6 +25,25 @@ def _row_positions(data: pd.DataFrame, labels) -> np.ndarray:
         missing = [l for l, p in zip(labels, pos) if p < 0]
         raise KeyError(f'{missing} not in index')
     return pos.astype(np.int64)
+
+
+_OJA_HULL_MESSAGE = ('Too many collinear points to compute depth of convex hull spanned by data. '
+                     'Try another depth method or remove collinearities.')          # (:189)
+
+
+def _hull_volume(P: np.ndarray) -> float:
+    """ConvexHull(P).volume, the normaliser of Oja depth (:187-189): any failure of Qhull (d = 1, NaN / inf, a flat
+    sample, fewer than d + 1 points) is the reference's DepthDegeneracy."""
+    from scipy.spatial import ConvexHull
+    try:
+        return float(ConvexHull(P).volume)
+    except Exception as e:                       # noqa: BLE001 -- the reference's bare except (:188)
+        raise DepthDegeneracy(_OJA_HULL_MESSAGE) from e
+
+
+def _oja_check_dim(d: int) -> None:
+    if d > 8:
+        raise NotImplementedError('oja depth is implemented for d <= 8')
 
 
 def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None, containment='simplex',
@@ -45,7 +68,14 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         from ._functional import _univariate_depths
         depths = _univariate_depths(data.T, list(to_compute), 2, containment == 'linf_relax', device=device)
         return pd.Series(index=to_compute, data=depths)
-    elif containment in ('mahalanobis', 'oja'):
+    elif containment == 'oja':
+        # (:175-205) with every other row in the subsets, also for a to_compute subset
+        _oja_check_dim(d)
+        P = data.to_numpy(dtype=np.float64)
+        vol = _hull_volume(P)                                    # host first: a degenerate sample never reaches the GPU
+        sums = engine.oja_volume_sums(P, _row_positions(data, to_compute), device=device)
+        return pd.Series(index=to_compute, data=sums / vol)
+    elif containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     else:
         raise ValueError(f'{containment} is not a valid containment measure. ')   # (:63-64)
@@ -57,6 +87,10 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None) -> np.nd
     mem = np.full((len(blocks), width), -1, dtype=np.int32)
     for i, b in enumerate(blocks):
         mem[i, :len(b)] = b
+    if containment == 'oja':                             # (:187-205) on the sample: the block's own hull
+        _oja_check_dim(P.shape[1])
+        vols = np.array([_hull_volume(P[np.asarray(b)]) for b in blocks], dtype=np.float64)
+        return engine.oja_subset_volume_sums(P, mem, device=device) / vols
     if containment == 'simplex':
         d = P.shape[1]
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
@@ -75,13 +109,15 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     so the reference itself cannot run this path any more).  The draws are made first -- rows by position, from
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
     (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
-    sd_l1_subset_depth) instead of as many `_pointwisedepth` calls.
+    sd_l1_subset_depth / sd_oja_subset_volume_sums) instead of as many `_pointwisedepth` calls.
+    Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
+    normaliser (the reference's is identically 0).
     """
     if K == 1:
         return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device)
-    if containment in ('mahalanobis', 'oja'):
+    if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    if containment not in ('simplex', 'l1'):
+    if containment not in ('simplex', 'l1', 'oja'):
         raise ValueError(f'{containment} is not a valid containment measure. ')
     n, d = data.shape
     if to_compute is None:

@@ -525,6 +525,55 @@ def l1_subset_depth(P, members, device=None):
     return out.cpu().numpy()
 
 
+def oja_volume_sums(P, targets=None, device=None):
+    """float64[m]: sum over d-subsets S of the other rows of vol(conv(S u {P[target]})) (sd_oja_volume_sums)."""
+    t = torch()
+    lib = _native.require_device()
+    Pd, dev = _points_dev(P, 2, device)
+    n, d = Pd.shape
+    td, m, tp = _targets_dev(targets, n, dev)
+    out = t.empty(m, dtype=t.float64, device=dev)
+    if m == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_oja_volume_sums(Pd.data_ptr(), n, d, tp, m, out.data_ptr(), _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
+def oja_external_volume_sums(P, Q, device=None):
+    """float64[m]: sum over d-subsets S of ALL rows of P of vol(conv(S u {Q[q]})) (sd_oja_external_volume_sums)."""
+    t = torch()
+    lib = _native.require_device()
+    Pd, dev = _points_dev(P, 2, device)
+    Qd, _ = _points_dev(Q, 2, dev)
+    n, d = Pd.shape
+    if Qd.shape[1] != d:
+        raise ValueError("Q must have the same number of coordinates as P")
+    m = Qd.shape[0]
+    out = t.empty(m, dtype=t.float64, device=dev)
+    if m == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_oja_external_volume_sums(Pd.data_ptr(), n, d, Qd.data_ptr(), m, out.data_ptr(), _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
+def oja_subset_volume_sums(P, members, device=None):
+    """float64[nb]: per block (rows of `members`, -1 padded, others first, target last) the sum over d-subsets S of
+    the block's others of vol(conv(S u {target}))."""
+    t = torch()
+    lib = _native.require_device()
+    Pd, dev = _points_dev(P, 2, device)
+    n, d = Pd.shape
+    md, nb, bs = _members_dev(members, dev, n)
+    out = t.empty(nb, dtype=t.float64, device=dev)
+    if nb == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_oja_subset_volume_sums(Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, out.data_ptr(), _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
 def multi_band_counts(P, targets=None, device=None):
     """int64[m]: sum_t #{pairs of other curves whose componentwise band contains the target at t} (sd_multi_band_counts).
     P: (n, T, d) curves, NaN-free."""

@@ -177,7 +177,12 @@ def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -
         return engine.pointcloud_simplex_external_counts(Fx, Qx).astype(np.float64) / binom(n + 1, d + 1)
     if containment == 'l1':
         return engine.l1_external_depth(Fx, Qx)
-    if containment in ('mahalanobis', 'oja'):
+    if containment == 'oja':                       # subsets of F, normaliser the hull of the intact F u {g}
+        from ..depth.calculations._pointcloud import _hull_volume, _oja_check_dim
+        _oja_check_dim(d)
+        vols = np.array([_hull_volume(np.vstack([Fx, Qx[[r]]])) for r in range(Qx.shape[0])], dtype=np.float64)
+        return engine.oja_external_volume_sums(Fx, Qx) / vols
+    if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     raise ValueError(f'{containment} is not a valid containment measure. ')
 
