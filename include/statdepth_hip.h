@@ -299,6 +299,27 @@ int sd_oja_external_volume_sums(const double *P, int64_t n, int d, const double 
 int sd_oja_subset_volume_sums(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs,
                               double *out, void *stream);
 
+/* ---- K8: probabilistic depths (normal distributions, Poisson curves) ---------------------------
+ * Replaces: the two exported functions of _uncertainty.py.  Both return UNNORMALISED fp64 sums; the host divides.
+ *   sd_prob_normal_sums:  the (target, pair) quad loop of _normal_depth (:101-121).  mu, sigma: n doubles (device).
+ *       out[q] = sum over pairs i < j of the others of k = targets[q] of int (Phi_i - Phi_k Phi_j) phi_k
+ *              = sum_{m != k} Phi(h) ((n - 1 - m) - [k > m]) - sum_{m != k} Phi2(0, h; rho) (m - [k < m]),
+ *       h = (mu_k - mu_m) / sqrt(sigma_m^2 + sigma_k^2), rho = sigma_k / sqrt(2 (sigma_m^2 + sigma_k^2));
+ *       depth = out / C(n, 2).  Needs finite mu and finite sigma > 0 (the host checks the values).
+ *   sd_prob_poisson_sums: the (target, pair, row) loop of _poisson_depth (:47-61) over
+ *       _poisson_containment_simplified (:34-45).  lam: T x n row-major rates (device), row t = timepoint, column = curve.
+ *       out[q] = sum_t sum_{z=1}^{lim-1} sum over column pairs i < j, both != f = targets[q], of
+ *                P(X_f = z) P(X_i <= z) P(X_j >= z),  X_c ~ Poisson(lam[t][c]);
+ *       depth = out / C(T, 2).  Needs finite lam >= 0 (the host checks the values).  lim <= 1: zeros.
+ * targets: m int64 indices (device; the engine checks their range on the host), NULL = all (m == n).  A target's
+ * result is bitwise independent of m, of the other targets and of how the call is cut into launches (no atomics).
+ * SD_ERR_INVALID for NULL pointers or negative sizes; SD_ERR_OVERFLOW if n * m (normal) or T * n * lim (Poisson)
+ * overflows int64; SD_ERR_UNSUPPORTED beyond 10^14 of them (hours of work).  Every launch is bounded in work. */
+int sd_prob_normal_sums(const double *mu, const double *sigma, int64_t n, const int64_t *targets, int64_t m,
+                        double *out, void *stream);
+int sd_prob_poisson_sums(const double *lam, int64_t T, int64_t n, int64_t lim, const int64_t *targets, int64_t m,
+                         double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

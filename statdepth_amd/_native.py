@@ -69,6 +69,8 @@ SIGNATURES = {
     "sd_oja_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
     "sd_oja_external_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
     "sd_oja_subset_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _int, _vp, _vp]),
+    "sd_prob_normal_sums": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sd_prob_poisson_sums": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
 }
 
 

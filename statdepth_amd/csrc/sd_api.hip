@@ -604,4 +604,40 @@ int sd_oja_subset_volume_sums(const double *P, int64_t n, int d, const int32_t *
     return launch_oja_subsets(P, n, d, members, nb, bs, out, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// K8
+// ---------------------------------------------------------------------------
+static constexpr double PROB_MAX_EVALS = 1e14;  // pair or (row, column, z) evaluations: beyond this a call runs for hours
+
+int sd_prob_normal_sums(const double *mu, const double *sigma, int64_t n, const int64_t *targets, int64_t m, double *out,
+                        void *stream) {
+    if (!mu || !sigma || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n < 0 || m < 0) return fail(SD_ERR_INVALID, "bad shape");
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    i64 work;
+    if (__builtin_mul_overflow((i64)n, (i64)m, &work))
+        return fail(SD_ERR_OVERFLOW, "%lld targets x %lld distributions overflows int64", (long long)m, (long long)n);
+    if ((double)work > PROB_MAX_EVALS)
+        return fail(SD_ERR_UNSUPPORTED, "%lld targets x %lld distributions exceeds the cap of %.0e pairs", (long long)m,
+                    (long long)n, PROB_MAX_EVALS);
+    if (m == 0) return SD_OK;
+    return launch_prob_normal_sums(mu, sigma, n, targets, m, out, (hipStream_t)stream);
+}
+
+int sd_prob_poisson_sums(const double *lam, int64_t T, int64_t n, int64_t lim, const int64_t *targets, int64_t m, double *out,
+                         void *stream) {
+    if (!lam || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 0 || n < 0 || m < 0) return fail(SD_ERR_INVALID, "bad shape");
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    i64 work = 0, tn;
+    if (__builtin_mul_overflow((i64)T, (i64)n, &tn) || (lim > 1 && __builtin_mul_overflow(tn, (i64)(lim - 1), &work)))
+        return fail(SD_ERR_OVERFLOW, "%lld rows x %lld curves x lim %lld overflows int64", (long long)T, (long long)n,
+                    (long long)lim);
+    if ((double)work > PROB_MAX_EVALS)
+        return fail(SD_ERR_UNSUPPORTED, "%lld rows x %lld curves x lim %lld exceeds the cap of %.0e evaluations", (long long)T,
+                    (long long)n, (long long)lim, PROB_MAX_EVALS);
+    if (m == 0) return SD_OK;
+    return launch_prob_poisson_sums(lam, T, n, lim, targets, m, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

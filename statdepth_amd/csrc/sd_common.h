@@ -123,6 +123,11 @@ int launch_oja_volume_sums(const double *P, i64 n, int d, const i64 *targets, i6
 int launch_oja_external(const double *P, i64 n, int d, const double *Q, i64 m, double *out, hipStream_t s);
 int launch_oja_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double *out, hipStream_t s);
 
+// K8 probabilistic depths (prob_depth.hip): unnormalised sums of the reference's normal and Poisson depths
+int launch_prob_normal_sums(const double *mu, const double *sigma, i64 n, const i64 *targets, i64 m, double *out,
+                            hipStream_t s);
+int launch_prob_poisson_sums(const double *lam, i64 T, i64 n, i64 lim, const i64 *targets, i64 m, double *out, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

@@ -574,6 +574,42 @@ def oja_subset_volume_sums(P, members, device=None):
     return out.cpu().numpy()
 
 
+def prob_normal_sums(mu, sigma, targets=None, device=None):
+    """float64[m]: the reference's normal-depth pair sums, unnormalised (sd_prob_normal_sums): for k = targets[q], the sum
+    over pairs i < j of the other distributions of int (Phi_i - Phi_k Phi_j) phi_k.  depth = sums / C(n, 2)."""
+    t = torch()
+    lib = _native.require_device()
+    mud, dev = _points_dev(mu, 1, device)
+    sgd, _ = _points_dev(sigma, 1, dev)
+    n = mud.shape[0]
+    if sgd.shape[0] != n:
+        raise ValueError("mu and sigma must have the same length")
+    td, m, tp = _targets_dev(targets, n, dev)
+    out = t.empty(m, dtype=t.float64, device=dev)
+    if m == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_prob_normal_sums(mud.data_ptr(), sgd.data_ptr(), n, tp, m, out.data_ptr(), _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
+def prob_poisson_sums(lam, lim, targets=None, device=None):
+    """float64[m]: the reference's Poisson-depth sums, unnormalised (sd_prob_poisson_sums).  lam: T x n rates (rows are
+    timepoints, columns curves); for f = targets[q], the sum over rows t, z = 1 .. lim - 1 and column pairs i < j other
+    than f of P(X_f = z) P(X_i <= z) P(X_j >= z).  depth = sums / C(T, 2)."""
+    t = torch()
+    lib = _native.require_device()
+    Ld, dev = _points_dev(lam, 2, device)
+    T, n = Ld.shape
+    td, m, tp = _targets_dev(targets, n, dev)
+    out = t.empty(m, dtype=t.float64, device=dev)
+    if m == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_prob_poisson_sums(Ld.data_ptr(), T, n, int(lim), tp, m, out.data_ptr(), _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
 def multi_band_counts(P, targets=None, device=None):
     """int64[m]: sum_t #{pairs of other curves whose componentwise band contains the target at t} (sd_multi_band_counts).
     P: (n, T, d) curves, NaN-free."""
