@@ -423,11 +423,7 @@ __global__ __launch_bounds__(ST_THREADS) void strict_masks_rank_kernel(
     // 4.1 cycles each, v_and_b32 / v_lshrrev_b32 / v_or_b32 in 2.0 - 2.1.  The accumulator starts at 0 and each half is a 16-bit
     // shift register that is full after exactly 16 steps, so a plain 32-bit shift never carries a set bit from the upper half
     // into bit 15: shift, mask, or -- three two-cycle instructions (6.2 cycles) instead of rotate + insert (8.2).
-#ifdef SD_MASK_ROTATE_BFI
-#define ST_SHIFT_IN(acc, d) asm("v_alignbit_b32 %0, %0, %0, 1\n\tv_bfi_b32 %0, %2, %1, %0" : "+v"(acc) : "v"(d), "s"(H))
-#else
 #define ST_SHIFT_IN(acc, d) asm("v_lshrrev_b32 %0, 1, %0\n\tv_and_b32 %1, %2, %1\n\tv_or_b32 %0, %0, %1" : "+v"(acc), "+v"(d) : "s"(H))
-#endif
     i64 b = o.dlist ? (i64)o.dlist[z0] : z0;
     u32x16 qv = *reinterpret_cast<const u32x16 *>(Rt + (b * W32 + k) * 16);
     for (i64 z = z0; z < zend; ++z) {

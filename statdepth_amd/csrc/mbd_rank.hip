@@ -25,8 +25,6 @@
 //
 // Replaces the same reference loops as mbd_pairwise.hip (_functional.py:246-251,
 // _containment.py:75-77); results are bit-identical to it and to the oracle.
-#include <stdlib.h>
-
 #include "sd_common.h"
 
 namespace sd {
@@ -77,7 +75,7 @@ __device__ __forceinline__ double flip_sign(double v, unsigned m) {   // m = 0 o
     return __longlong_as_double(u);
 }
 
-template <int NT, int E, int SK = 0>
+template <int NT, int E>
 struct RankSorter {
     using C = RankCfg<NT, E>;
     static constexpr int LE = C::LE;
@@ -120,8 +118,8 @@ struct RankSorter {
     static __device__ __forceinline__ void windows(double (&k)[E], double *Sm, int t) {
         constexpr int B = wb(S, K);
         constexpr int HI = (K == 0) ? S - 1 : BPREV - 1;
-        if constexpr (B != BPREV && !(SK & 2)) transpose<BPREV, B>(k, Sm, t);
-        if constexpr (!(SK & 1)) levels<B, HI, B>(k);
+        if constexpr (B != BPREV) transpose<BPREV, B>(k, Sm, t);
+        levels<B, HI, B>(k);
         if constexpr (B > 0) windows<S, K + 1, B>(k, Sm, t);
     }
 
@@ -144,8 +142,7 @@ struct RankSorter {
 
 // grid = G persistent workgroups; workgroup g owns timepoints g, g+G, ...
 // partial[(g*(J-1) + j)*n + i] = sum over its timepoints of the band counts of curve i
-// PH: debug ablation mask (1 = sort, 2 = search); production launches use PH = 3
-template <int NT, int E, int J, int PH = 3>
+template <int NT, int E, int J>
 __global__ __launch_bounds__(NT) void mbd_rank_kernel(const double *__restrict__ Y, i64 T, i64 n,
                                                       u64 *__restrict__ partial) {
     using C = RankCfg<NT, E>;
@@ -176,7 +173,7 @@ __global__ __launch_bounds__(NT) void mbd_rank_kernel(const double *__restrict__
         }
         __syncthreads();                       // s_nnan zeroed; previous row's searches finished
         if (mynan) atomicAdd(&s_nnan, mynan);
-        if constexpr (PH & 1) RankSorter<NT, E, (PH >> 2)>::sort(k, Sm, t);
+        RankSorter<NT, E>::sort(k, Sm, t);
         {
             double *Sw = Sm + lds_base<0, LE>(t);
 #pragma unroll
@@ -189,7 +186,7 @@ __global__ __launch_bounds__(NT) void mbd_rank_kernel(const double *__restrict__
         for (int e = 0; e < E; ++e) {
             if ((e & 3) == 0) __builtin_amdgcn_sched_barrier(0);   // keep at most 4 searches in flight (VGPRs)
             i64 i = (i64)t + (i64)e * NT;
-            if ((PH & 2) && i < n) {
+            if (i < n) {
                 double x = row[i];
                 if (x == x) {
                     // lower bound by a fixed-depth descent; x itself is in the row, so Sm[lo] == x afterwards
@@ -263,10 +260,10 @@ static int rank_grid(i64 T) {
     return (int)g;
 }
 
-template <int NT, int E, int J, int PH = 3>
+template <int NT, int E, int J>
 static int launch_rank_cfg(const double *Y, i64 T, i64 n, u64 *partial, int G, hipStream_t s) {
     using C = RankCfg<NT, E>;
-    auto kern = mbd_rank_kernel<NT, E, J, PH>;
+    auto kern = mbd_rank_kernel<NT, E, J>;
     SD_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(G), dim3(NT), C::LDS_BYTES, s, Y, T, n, partial);
     SD_HIP(hipGetLastError());
@@ -279,16 +276,6 @@ static int launch_rank_j(const double *Y, i64 T, i64 n, u64 *partial, int G, hip
     if (n <= 2048) return launch_rank_cfg<256, 8, J>(Y, T, n, partial, G, s);
     if (n <= 4096) return launch_rank_cfg<1024, 4, J>(Y, T, n, partial, G, s);
     if (n <= 8192) return launch_rank_cfg<1024, 8, J>(Y, T, n, partial, G, s);
-    // debug knobs (timing experiments only): SD_RANK_CFG=2 -> 512x32, SD_RANK_PH = ablation mask
-    const char *cfg = getenv("SD_RANK_CFG");
-    const char *ph = getenv("SD_RANK_PH");
-    int phv = ph ? atoi(ph) : 3;
-    if (J == 2 && phv == 1) return launch_rank_cfg<1024, 16, 2, 1>(Y, T, n, partial, G, s);
-    if (J == 2 && phv == 2) return launch_rank_cfg<1024, 16, 2, 2>(Y, T, n, partial, G, s);
-    if (J == 2 && phv == 0) return launch_rank_cfg<1024, 16, 2, 0>(Y, T, n, partial, G, s);
-    if (J == 2 && phv == 5) return launch_rank_cfg<1024, 16, 2, 5>(Y, T, n, partial, G, s);    // sort without CE
-    if (J == 2 && phv == 9) return launch_rank_cfg<1024, 16, 2, 9>(Y, T, n, partial, G, s);    // sort without transposes
-    if (cfg && atoi(cfg) == 2) return launch_rank_cfg<512, 32, J>(Y, T, n, partial, G, s);
     return launch_rank_cfg<1024, 16, J>(Y, T, n, partial, G, s);
 }
 

@@ -22,7 +22,6 @@
 //     sentinel class or (non-zero) into the zero class are left to kernel B as well.
 //  B  rank_search_kernel  -- the flagged rows: sort of the plain values, then every curve binary-searches
 //     its own value (lower bound = B, upper bound gives A; ties are exact by construction).
-#include <stdlib.h>
 
 #include "sd_common.h"
 #include "rank_sort.h"
@@ -53,7 +52,7 @@ __device__ __forceinline__ double pk_dbl(u64 b) { return __longlong_as_double((l
 // ---------------------------------------------------------------------------------------------------
 // A: packed keys, rank = position.  Rows [row0, row0 + rows) of Y; AB and nnan are indexed by row - row0.
 // ---------------------------------------------------------------------------------------------------
-template <int NT, int E, int DBG = 0>
+template <int NT, int E>
 __global__ __launch_bounds__(NT) void rank_packed_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows,
                                                          u32 *__restrict__ AB, u32 *__restrict__ nnan_out) {
     using C = R2Cfg<NT, E>;
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(NT) void rank_packed_kernel(const double *__restric
             }
         }
         if (mynan) atomicAdd(&s_nnan[par], mynan);
-        if constexpr (!(DBG & 2)) Sorter::sort(k, Sm, tv, n_act, wreal, MAXK);
+        Sorter::sort(k, Sm, tv, n_act, wreal, MAXK);
 
         // ---- any class with several members?  (holders of the sorted positions, layout 0: p = t*E + e) ----
         if (wreal) firstkey[tv] = k[0];
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(NT) void rank_packed_kernel(const double *__restric
         }
         const int mode = __syncthreads_or(anytie | forcefull);
         const i64 rnext = r + gridDim.x;
-        if (mode && !(DBG & 1)) {
+        if (mode) {
             if (t == 0) nnan_out[r] = ROW_DEFERRED;
             defer = true;
             continue;
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(NT) void rank_packed_kernel(const double *__restric
 // the packed kernel marked ROW_DEFERRED -- workgroup g of this kernel looks at exactly the rows workgroup g
 // of the packed kernel owned (same grid), so no list, counter or memset is needed.
 // ---------------------------------------------------------------------------------------------------
-template <int NT, int E, int DBG = 0>
+template <int NT, int E>
 __global__ __launch_bounds__(NT) void rank_search_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows,
                                                          u32 *__restrict__ AB, u32 *__restrict__ nnan_out,
                                                          int only_deferred) {
@@ -216,7 +215,7 @@ __global__ __launch_bounds__(NT) void rank_search_kernel(const double *__restric
             }
         }
         if (mynan) atomicAdd(&s_nnan[par], mynan);
-        if constexpr (!(DBG & 2)) Sorter::sort(k, Sm, tv, n_act, wreal, INF);
+        Sorter::sort(k, Sm, tv, n_act, wreal, INF);
         if (wreal) {
             double *Sw = Sm + r2_base<0, LE>(tv);
 #pragma unroll
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(NT) void rank_search_kernel(const double *__restric
         par ^= 1;
         // every wave searches (curve t + e*NT belongs to thread t) although only the waves below n_act
         // sorted: the search is a chain of dependent LDS reads and needs all the parallelism it can get
-        if (!(DBG & 1)) {
+        {
             const double *xp = row + t;
             u32 *dst = AB + r * n + t;
 #pragma unroll
@@ -456,12 +455,6 @@ static int launch_sorts(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32
         return SD_OK;
     }
     auto kp = rank_packed_kernel<NT, E>;
-    {
-#ifdef SD_TUNING
-        const char *dbg = getenv("SD_RANKP_DBG");   // timing experiments only: 3 = no sort, ties ignored
-        if (dbg && atoi(dbg) == 3) kp = rank_packed_kernel<NT, E, 3>;
-#endif
-    }
     const size_t lds = C::LDS_BYTES + (size_t)NT * 8;
     SD_HIP(hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kp, dim3(G), dim3(NT), lds, s, Y, n, row0, rows, AB, nnan);

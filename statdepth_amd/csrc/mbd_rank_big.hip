@@ -210,16 +210,11 @@ __global__ __launch_bounds__(BIG_NT) void chunk_search_kernel(const double *__re
 // =====================================================================================================
 // route 1: value buckets
 // =====================================================================================================
-#ifndef SD_BK_CE
-#define SD_BK_CE 16                            // keys per thread of the ranking kernels = bucket capacity / 512
-#endif
+constexpr int BK_CE = 16;                      // keys per thread of the ranking kernels = bucket capacity / 512
 constexpr int BK_NT = 512, BK_E = 16;          // the search kernel's sort: 8 192 slots
-constexpr int BK_C = BK_NT * SD_BK_CE;         // bucket capacity (8 192)
+constexpr int BK_C = BK_NT * BK_CE;            // bucket capacity (8 192)
 static_assert(BK_C <= BK_NT * BK_E, "a value bucket fits the search kernel's sort");
-#ifndef SD_BK_FILL
-#define SD_BK_FILL 5500
-#endif
-constexpr int BK_FILL = SD_BK_FILL;            // target mean fill
+constexpr int BK_FILL = 5500;                  // target mean fill
 constexpr int BK_MAXNB = 1024;
 using BkCfg = R2Cfg<BK_NT, BK_E>;
 
@@ -545,10 +540,7 @@ __global__ __launch_bounds__(BK_NT) void bucket_packed_kernel(i64 n, int NB, con
 // are < / <= itself: B = (keys in earlier value buckets) + base + less, A = n_real - (... + base + le).  Ties are exact.
 // A value bucket whose keys are all equal is closed-form; one with a fine bucket above BR_CAP keys (heavy ties that
 // are not all equal, an infinity stretching the range) is flagged for bucket_search_kernel like before.
-#ifndef SD_BR_U2
-#define SD_BR_U2 3
-#endif
-constexpr int BR_NT = 512, BR_E = SD_BK_CE, BR_LNB = 12, BR_NBF = 1 << BR_LNB, BR_CAP = 63, BR_TRYB = 4, BR_U2 = SD_BR_U2, BR_PAD = 8;
+constexpr int BR_NT = 512, BR_E = BK_CE, BR_LNB = 12, BR_NBF = 1 << BR_LNB, BR_CAP = 63, BR_TRYB = 4, BR_U2 = 3, BR_PAD = 8;
 static_assert(((BR_CAP + 1) & BR_CAP) == 0, "the crowding test reads the counters' bits");
 constexpr int BR_NW = BR_NT / 64;
 static_assert(BR_NT * BR_E == BK_C, "one thread slot per key of a full value bucket");
@@ -790,10 +782,7 @@ __global__ __launch_bounds__(BR_NT) void bucket_rank_kernel(i64 n, i64 rows, int
 //                               indices): exact whatever the data, cheap because it is rare on continuous data.
 //                               Tied rows go through bucket_rank_kernel (fp64) as before.
 constexpr int TB_C = 2048;                                             // cells of the partition's look-up table
-#ifndef SD_S3_RUN
-#define SD_S3_RUN 4
-#endif
-constexpr int S3_RUN = SD_S3_RUN;                                      // neighbours per sample position (bucket_setup_kernel)
+constexpr int S3_RUN = 4;                                              // neighbours per sample position (bucket_setup_kernel)
 constexpr u32 Q_MAX = 0xFFFFFFFEu;                                     // largest image (0xFFFFFFFF = "no key" in LDS)
 
 __device__ __forceinline__ u32 tb_cell(double x, double lo, double scale) {
@@ -948,10 +937,8 @@ __global__ __launch_bounds__(SNT) void bucket_setup_kernel(const double *__restr
 }
 
 // P3: grid = (ceil(n / 3072), rows), 512 threads x 6 keys
-#ifndef SD_P3_E
-#define SD_P3_E 6                      // 8: 4 096 keys per block and three workgroups per CU -- + 2 ... 3 % at every size measured
-#endif
-constexpr int P3_NT = 512, P3_E = SD_P3_E, P3_C = P3_NT * P3_E;
+// 6 keys per thread (8: 4 096 keys per block and three workgroups per CU -- + 2 ... 3 % at every size measured)
+constexpr int P3_NT = 512, P3_E = 6, P3_C = P3_NT * P3_E;
 static inline size_t p3_lds_bytes(int NBT) {
     return (size_t)P3_C * 8 + (size_t)(2 * NBT + 2) * 8 + (size_t)TB_C * 4 + (size_t)(3 * NBT + 4 + P3_NT / 64) * 4 + (size_t)P3_C * 2 + 64;
 }
@@ -985,13 +972,6 @@ __global__ __launch_bounds__(P3_NT) void bucket_partition3_kernel(const double *
     const double *row = Y + (row0 + rb) * n;
     const i64 base = (i64)blockIdx.x * P3_C;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#ifdef SD_P3_STAGGER
-    {   // three workgroups per CU: the second and third dispatch rounds start a third / two thirds of a block late
-        const i64 lin = (i64)blockIdx.y * gridDim.x + blockIdx.x;
-        if (lin >= SD_P3_STAGGER && lin < 2 * SD_P3_STAGGER) __builtin_amdgcn_s_sleep(64);
-        if (lin >= 2 * SD_P3_STAGGER && lin < 3 * SD_P3_STAGGER) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     double x[P3_E];
 #pragma unroll
     for (int e = 0; e < P3_E; ++e) {
@@ -1011,9 +991,6 @@ __global__ __launch_bounds__(P3_NT) void bucket_partition3_kernel(const double *
     bool over = false;
     __syncthreads();
     {
-#if defined(SD_TUNING) && defined(SD_P3_STOP)
-        if (SD_P3_STOP == 1) { double a = 0; for (int e = 0; e < P3_E; ++e) a += x[e]; if (a == 1.2345e300) bidx[0] = 1; return; }
-#endif
         u32 bk[P3_E], off[P3_E], q[P3_E];
 #pragma unroll
         for (int e = 0; e < P3_E; ++e) {
@@ -1071,9 +1048,6 @@ __global__ __launch_bounds__(P3_NT) void bucket_partition3_kernel(const double *
             }
         }
         __syncthreads();                                               // B1: the block's histogram is complete
-#if defined(SD_TUNING) && defined(SD_P3_STOP)
-        if (SD_P3_STOP == 2) { u32 a = 0; for (int e = 0; e < P3_E; ++e) a ^= bk[e] ^ off[e] ^ q[e]; if (a == 0x12345678u) bidx[0] = a; return; }
-#endif
         // global base of this workgroup's run in every bucket (one returning atomic per bucket: its round trip to L2 is
         // spent under the local prefix sum and the LDS scatter, the result is only needed for the copy-out); local exclusive
         // prefix of the workgroup's counts.  Thread t owns the buckets [t * per, t * per + per), per <= 3.
@@ -1120,9 +1094,6 @@ __global__ __launch_bounds__(P3_NT) void bucket_partition3_kernel(const double *
         if (per > 1 && t * per + 1 < NBT) s_gbase[t * per + 1] = gb1;
         if (per > 2 && t * per + 2 < NBT) s_gbase[t * per + 2] = gb2;
         __syncthreads();                                               // B4
-#if defined(SD_TUNING) && defined(SD_P3_STOP)
-        if (SD_P3_STOP == 4) { if (stage[t] == 0x123456789ull && s_gbase[0] == 77u) bidx[0] = 1; return; }
-#endif
         const u32 nval = s_lbase[NBT];
         for (u32 p = t; p < nval; p += P3_NT) {
             const u32 b = sbk[p];
@@ -1150,21 +1121,15 @@ __global__ __launch_bounds__(P3_NT) void bucket_partition3_kernel(const double *
 }
 
 // A3: grid = 8 * NBT * ceil(rows / 8) (the XCD-aware mapping of bucket_rank_kernel), 512 threads x 16 keys
-constexpr int A3_NT = 512, A3_E = SD_BK_CE, A3_LNB = 12, A3_NBF = 1 << A3_LNB, A3_CAP = 63, A3_U = 2, A3_PAD = 32;
+constexpr int A3_NT = 512, A3_E = BK_CE, A3_LNB = 12, A3_NBF = 1 << A3_LNB, A3_CAP = 63, A3_U = 2, A3_PAD = 32;
 constexpr int A3_NW = A3_NT / 64;
 static_assert(A3_NT * A3_E == BK_C, "one thread slot per key of a full value bucket");
 static_assert(A3_NBF / 2 / A3_NT == 4, "one 16-byte quad of histogram words per thread");
 constexpr size_t A3_HDR = 256;
 constexpr size_t A3_LDS32 = A3_HDR + (size_t)(A3_NBF / 2 + 4) * 4 + (size_t)(BK_C + A3_PAD) * 4 + (size_t)(BK_C + A3_PAD) * 2;
-#if defined(SD_TUNING) && defined(SD_A3_EXP)
-constexpr size_t A3_LDS = A3_HDR + (size_t)(A3_NBF / 2 + 4) * 4 + (size_t)(BK_C + A3_PAD) * 4 + 64;   // timing experiment: no Jx, no tied path
-#define SD_A3_ATTR __attribute__((amdgpu_waves_per_eu(SD_A3_EXP, SD_A3_EXP)))
-#else
 constexpr size_t A3_LDS = A3_LDS32 > BR_LDS ? A3_LDS32 : BR_LDS;      // rows flagged "tied" run A' inside this kernel
-#define SD_A3_ATTR
-#endif
 
-__global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, int NBT,
+__global__ __launch_bounds__(A3_NT) void bucket_rank32_kernel(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, int NBT,
                                                               const u32 *__restrict__ bcnt,
                                                               const u32 *__restrict__ nnanrow,
                                                               const u32 *__restrict__ ovf,
@@ -1186,28 +1151,17 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
     // Infinity Cache still holds when this kernel starts (- 1 % at every size measured; blockIdx order: 0.2667 / 0.9026 ms at
     // 10^5 x 256 / x 1 000, this order 0.2631 / 0.8949)
     const int w = (int)(((gridDim.x >> 3) / NBT - 1 - (blockIdx.x >> 3) / NBT) * NBT + (blockIdx.x >> 3) % NBT) * 8 + (int)(blockIdx.x & 7);
-#ifdef SD_A3_STAGGER
-    // Two workgroups share a CU and would run their load / LDS / store phases in lock-step (the phase times of the kernel add
-    // up: profiles/r03e_phase_times_config3.txt).  The workgroups of the second dispatch round start half an item late;
-    // their successors inherit the offset.
-    if (w >= SD_A3_STAGGER && w < 2 * SD_A3_STAGGER) {
-        __builtin_amdgcn_s_sleep(127);
-        __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     const int b = (w >> 3) % NBT;
     const i64 rb = (i64)((w >> 3) / NBT) * 8 + (w & 7);
     if (rb >= rows) return;
     if (ovf[rb]) return;
     __builtin_amdgcn_s_setprio(2);                                    // load / histogram / scatter phases go first, the member pass of the
                                                                       // CU's other workgroup fills in (A3 146 -> 137 us at config 3)
-#if !(defined(SD_TUNING) && defined(SD_A3_EXP))
     if (rowtied[rb]) {                                                // block-uniform: fp64 records, A' (same LDS, same grid)
         bucket_rank_item(w, n, rows, NBT, bcnt, nnanrow, ovf, rowtied, reinterpret_cast<const double *>(rec), bidx, bflag,
                          gate, epoch, ab);
         return;
     }
-#endif
     const u32 *rowcnt = bcnt + rb * NBT;
     const int cnt = (int)rowcnt[b];
     if (cnt == 0) return;
@@ -1241,9 +1195,6 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
     mx = rb_wave_allreduce_u32<true>(mx);
     if (lane == 63) { red[2 * wave] = mn; red[2 * wave + 1] = mx; wtot[wave] = gsum; }
     __syncthreads();                                                  // barrier 1
-#if defined(SD_TUNING) && defined(SD_A3_STOP)
-    if (SD_A3_STOP == 1) { if (mn + gsum == 0x12345678u) ab.B[0] = mn; return; }   // timing experiment (results invalid)
-#endif
     u32 lo, hi, gbase;
     {
         const uint2 pmm = reinterpret_cast<const uint2 *>(red)[lane & (NW - 1)];
@@ -1268,9 +1219,6 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
         bs[e] = fb | (((old >> sh) & 0xFFFFu) << 16);
     }
     __syncthreads();                                                  // barrier 2
-#if defined(SD_TUNING) && defined(SD_A3_STOP)
-    if (SD_A3_STOP == 2) { u32 a = 0; for (int e = 0; e < E; ++e) a ^= bs[e]; if (a == 0x12345678u) ab.B[0] = a; return; }
-#endif
     // ---- (2) exclusive prefix sum; a fine bucket above A3_CAP keys: the search kernel takes the value bucket ----
     bool anyover = false;
     {
@@ -1304,9 +1252,6 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
         return;
     }
     __syncthreads();                                                  // barrier 4
-#if defined(SD_TUNING) && defined(SD_A3_STOP)
-    if (SD_A3_STOP == 3) { u32 a = H[t]; for (int e = 0; e < E; ++e) a ^= bs[e]; if (a == 0x12345678u) ab.B[0] = a; return; }
-#endif
     // ---- (3) scatter into fine-bucket order ----
     u32 bc[E];                                                        // base | count << 16; count 0: no key
     const u32 dummy = (u32)(cnt + A3_PAD - 1);
@@ -1318,15 +1263,10 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
         const bool isk = fb < (u32)NBF;
         const u32 pos = isk ? base + slot : dummy;
         S[pos] = isk ? q[e] : 0xFFFFFFFFu;
-#if !(defined(SD_TUNING) && defined(SD_A3_EXP))
         Jx[pos] = (unsigned short)(t + e * NT);
-#endif
         bc[e] = isk ? (base | ((end - base) << 16)) : 0u;
     }
     __syncthreads();                                                  // barrier 5
-#if defined(SD_TUNING) && defined(SD_A3_STOP)
-    if (SD_A3_STOP == 4) { u32 a = S[t]; for (int e = 0; e < E; ++e) a ^= bc[e] ^ id[e]; if (a == 0x12345678u) ab.B[0] = a; return; }
-#endif
     // ---- (4) rank inside the fine bucket, write B ----
     __builtin_amdgcn_s_setprio(0);
     const double *yrow = Y + (row0 + rb) * n;
@@ -1355,9 +1295,6 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
         less -= offq;                                                 // keys in front of the base: earlier fine buckets, all smaller
         if (fc) {
             if (eq == 1u) {
-#if defined(SD_TUNING) && defined(SD_A3_STOP)
-                if (SD_A3_STOP == 5) { if (gbase + base + less == 0xFFFFFFF0u) ab.B[abrow + id[e]] = 1; } else     // no store
-#endif
                 ab_store_untied(ab, abrow + id[e], gbase + base + less, nreal);
             } else {
                 // another member carries the same image: the fp64 values of those members decide
@@ -1365,11 +1302,7 @@ __global__ __launch_bounds__(A3_NT) SD_A3_ATTR void bucket_rank32_kernel(const d
                 u32 lt = 0, eqv = 0;
                 for (u32 m = base; m < base + fc; ++m) {
                     if (S[m] == x) {
-#if defined(SD_TUNING) && defined(SD_A3_EXP)
-                        const u32 im = id[e];                          // timing experiment: no partner look-up (results invalid)
-#else
                         const u32 im = (u32)(rec[slot0 + Jx[m]] >> 32);
-#endif
                         const double yv = yrow[im];
                         lt += (yv < xv) ? 1u : 0u;
                         eqv += (yv == xv) ? 1u : 0u;
@@ -1788,17 +1721,9 @@ struct BigPlan {
     size_t z_bcnt, z_nnan, z_ovf, z_bflag, z_nanf, z_tied, z_gate, z_meet;
 };
 
-#ifndef SD_BIG_SCRATCH_BYTES
-#define SD_BIG_SCRATCH_BYTES ((size_t)1 << 32)
-#endif
-#ifndef SD_S3_SMALL_NB
-#define SD_S3_SMALL_NB 24
-#endif
-constexpr int S3_SMALL_NB = SD_S3_SMALL_NB;             // up to that many value buckets: the 2 048-key sample
-#ifndef SD_S3_MID_NB
-#define SD_S3_MID_NB 72
-#endif
-constexpr int S3_MID_NB = SD_S3_MID_NB;                 // ... the 4 096-key sample; beyond: 16 384 keys
+constexpr size_t BIG_SCRATCH_BYTES = (size_t)1 << 32;   // scratch per batch (big_plan)
+constexpr int S3_SMALL_NB = 24;                         // up to that many value buckets: the 2 048-key sample
+constexpr int S3_MID_NB = 72;                           // ... the 4 096-key sample; beyond: 16 384 keys
 static BigPlan big_plan(i64 T, i64 n) {
     BigPlan p;
     p.nch = big_nchunks(n);
@@ -1810,7 +1735,7 @@ static BigPlan big_plan(i64 T, i64 n) {
     // Scratch per batch: every batch costs 40 - 45 us by itself (S3's latency in front of the partition, the kernels' tails, the
     // fold's launch; profiles/r04_experiment_rows_per_batch.txt), and 288 GB of HBM have room: 4 GiB take 10^5 curves x 1 000
     // timepoints in one batch (1.5 GiB: three).
-    i64 r = (i64)((size_t)SD_BIG_SCRATCH_BYTES / per_row);
+    i64 r = (i64)(BIG_SCRATCH_BYTES / per_row);
     const i64 vb = xswitch("SD_RANK_ROWS_PER_BATCH");          // cross-check builds: several batches on small inputs
     if (vb > 0 && vb < r) r = vb;
     if (r < 1) r = 1;

@@ -29,8 +29,6 @@
 //      partials (+ the fold of pair-image rows when the caller supplies one).
 //
 // HBM traffic per call: the matrix once (8 nT) + G partials of 8 n (J-1) bytes written and read once.
-#include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "sd_common.h"
@@ -41,22 +39,9 @@ namespace sd {
 
 constexpr u32 RB_AB_SPECIAL = 0xFFFFFFFFu;     // same encodings as mbd_rank_ab.hip
 constexpr int RB_MEDIUM_MAXN = 40960;          // rank_medium_image_kernel: 2 or 3 blocks (measured: 4 blocks lose to the large-n route)
-// RB_SMALL_E > 0 builds the kernels with at most that many keys per thread for 64 VGPRs and launches two workgroups
-// (two rows) per CU.  Measured (n = 600..4096, T = 1000): no faster than one workgroup per CU -- the kernel is bound
-// by VALU + LDS throughput, not by latency or barrier stalls -- so it is off.
-#ifndef RB_SMALL_E
-#define RB_SMALL_E 0
-#endif
-#define RB_WAVES_PER_EU(E) ((E) <= RB_SMALL_E ? 8 : 4)
-#ifndef RB_REDIRECT
-#define RB_REDIRECT 1                          // window reads a bucket does not need go to one shared NaN pair
-#endif
 // Rows whose range is much wider than their bulk (heavy tails, outlying curves): the three-piece map of rank_bucket.h.  Rounds
 // 1 - 3 clamped the tails into the two end buckets of a range clipped to the waves' innermost extremes: three outlying curves
 // were fine, heavy tails at every timepoint set every row aside for the sort (n = 14 000 Cauchy rows: 3.4 x the Gaussian time).
-#ifndef RB_TIES
-#define RB_TIES 1                              // tie-heavy rows: closed form when every bucket holds one value
-#endif
 constexpr int RB_PAD = 8;                      // NaN sentinels behind the bucket-ordered keys (never < or <= anything)
 
 // ---------------------------------------------------------------------------------------------------
@@ -131,7 +116,7 @@ struct RBCfg {
     static constexpr int QW = W / 4;                            // ... as 16-byte quads
     static_assert(W >= 4 && W % 4 == 0, "whole quads of histogram words per thread");
     static_assert(NW == 16 || NW == 8, "cross-wave reductions are laid out for rows of 16 lanes");
-    static_assert(NT == RB_SNT || NT == 512, "rb_slow_row is compiled for 1024 threads (512: two workgroups per CU, no cold path)");
+    static_assert(NT == RB_SNT, "rb_slow_row is compiled for 1024 threads");
     // positions: [0, n) keys, [n, n + RB_PAD) sentinels, DUMMY.. a scratch pair range for keys that are NaN
     static __host__ __device__ constexpr int dummy_pos(int n) { return (n + RB_PAD + 1) & ~1; }
     static __host__ __device__ constexpr size_t keys_slots(int n) { return (size_t)dummy_pos(n) + 2 * U2 + 2; }
@@ -142,20 +127,18 @@ struct RBCfg {
     static __host__ __device__ constexpr size_t lds_bytes(int n) {
         const size_t a = keys_slots(n) * 8 + (size_t)(NB / 2 + 4) * 4;
         const size_t n_act = (size_t)((n + 1023) / 1024) * 1024;
-        const size_t b = NT == RB_SNT ? (n_act + n_act / 16) * 8 : 0;  // sort image of rb_slow_row (R2Cfg<1024,16> slots)
+        const size_t b = (n_act + n_act / 16) * 8;                  // sort image of rb_slow_row (R2Cfg<1024,16> slots)
         return HDR + (a > b ? a : b);
     }
 };
 
-// DBG (timing experiments only; 1-4: results invalid): 1 = stop after the range, 2 = after the histogram, 3 = after the
-// prefix sum, 4 = after the scatter; 5 = full kernel with cycle stamps per phase printed by wave 0 of workgroup 0
 // SEL (J == 2, every curve a target): the second and last launch behind rank_bucket32_kernel (mbd_rank_bucket32.hip).
 // (1) Each workgroup sums its slice of curves over that kernel's Gsum u32 partial blocks and adds the totals to out_tot
 // (zeroed by rank_bucket32_kernel) -- the finalize step, without a launch of its own.  (2) Only when that kernel flagged
 // rows (*gate == epoch; else return): the flagged rows are ranked here in fp64 and their band counts added to out_tot
 // as well.  Every workgroup derives the same ordered list of flagged rows and takes entries g, g + G, ...
-template <int NT, int E, int LNB, int J, int CAP, int U2, int DBG = 0, bool A32 = false, bool SEL = false>
-__global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank_bucket_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows,
+template <int NT, int E, int LNB, int J, int CAP, int U2, bool A32 = false, bool SEL = false>
+__global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows,
                                                          u64 *__restrict__ partial, int p32, u32 *__restrict__ nnan_img,
                                                          const unsigned char *__restrict__ rowflag = nullptr,
                                                          const u32 *__restrict__ gate = nullptr, u32 epoch = 0,
@@ -337,20 +320,11 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
         double *rp = red + parity * 2 * NW;
         if ((t & 63) == 63) { rp[2 * (t >> 6)] = mn; rp[2 * (t >> 6) + 1] = mx; }
     };
-    long long stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;        // DBG == 5: cycles per phase, thread 0 of workgroup 0
-    auto mark = [&](int ph) {
-        if constexpr (DBG == 5) {
-            const long long now = (long long)__builtin_readcyclecounter();
-            stamp[ph] += now - tlast;
-            tlast = now;
-        }
-    };
     int par = 0;
     if ((i64)blockIdx.x < rows) {
         load_row(blockIdx.x);
         row_range(0);
     }
-    if constexpr (DBG == 5) tlast = (long long)__builtin_readcyclecounter();
     for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
         const i64 rnext = r + gridDim.x;
         // Per-row opaque copy of the thread id: every address below derives from it, so the compiler recomputes
@@ -363,9 +337,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
         double *redp = red + par * 2 * NW;
         const float2 *brkp = brk + par * NW;
         par ^= 1;
-        mark(0);
         __syncthreads();                                              // barrier 1 (histogram is zero, S is free)
-        mark(1);
         double lo, hi;
         {
             const double2 p = reinterpret_cast<const double2 *>(redp)[lane & (NW - 1)];
@@ -377,8 +349,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
         // Every decision below is block-uniform.  The next row is loaded at ONE place (two load sites would
         // keep two copies of the key registers alive across the loop).  A row with an infinity or without any
         // value is set aside for the sort behind the loop.
-        bool go = (hi >= lo) && (scale < INF) && (lo > -INF) && (hi < INF);
-        if constexpr (DBG == 1) go = false;
+        const bool go = (hi >= lo) && (scale < INF) && (lo > -INF) && (hi < INF);
         u32 bs[E];
         u32 nn = 0;                                                   // NaN others of this row (block-uniform)
         // block-uniform: a bucket above CAP keys / a bucket of 2^TRYB keys or more (ties?  see the member phase)
@@ -433,15 +404,9 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                 const u32 old = atomicAdd(&H[b >> 1], 1u << sh);
                 bs[e] = b | (((old >> sh) & 0xFFFFu) << 16);
             }
-            mark(2);
             __syncthreads();                                          // barrier 2
             uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);   // this wave's 64*QW quads, quad i*64+lane
-            if constexpr (DBG == 2) {
-#pragma unroll
-                for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-                go = false;
-            }
-            if constexpr (DBG != 2) {
+            {
                 // ---- (2) exclusive prefix sum over the counters (conflict-free 16-byte accesses: lane <-> quad);
                 //      a crowded bucket defers the row ----
                 uint4 hq[QW];
@@ -464,11 +429,10 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                     if (lane == 63) wtot[wave] = wsum | (wover ? 0x80000000u : 0u) | (wtry ? 0x40000000u : 0u);
                 };
                 prefix_a();
-                mark(3);
                 __syncthreads();                                      // barrier 3
                 u32 wt = wtot[lane & (NW - 1)];
                 crowded = __ballot((wt >> 31) != 0) != 0;
-                trypure = RB_TIES && __ballot((wt & 0x40000000u) != 0) != 0;
+                trypure = __ballot((wt & 0x40000000u) != 0) != 0;
                 if (__ballot((wt & 0x40000000u) != 0) != 0 && !m3.clip) {   // block-uniform, rare
                     // A bucket of 2^TRYB keys or more under the linear map: tie-heavy data -- or a range much wider than the
                     // row's bulk.  The bracket tells them apart; the second kind is histogrammed again under core + tails.
@@ -485,7 +449,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                         __syncthreads();
                         wt = wtot[lane & (NW - 1)];
                         crowded = __ballot((wt >> 31) != 0) != 0;
-                        trypure = RB_TIES && __ballot((wt & 0x40000000u) != 0) != 0;
+                        trypure = __ballot((wt & 0x40000000u) != 0) != 0;
                     }
                 }
                 const u32 wscan = rb_row_incl_scan(wt & 0x3FFFFFFFu);
@@ -508,36 +472,24 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                 }
             }
         }
-        if constexpr (DBG == 3) {
-            if (go) {
-                __syncthreads();
-                uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
+        if (!go) {
+            if (lo > hi) {
+                // no value at this timepoint (every curve NaN): nothing is contained, nothing to rank
+                if constexpr (J == 0) {
 #pragma unroll
-                for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-            }
-            go = false;
-        }
-        if constexpr (DBG == 0) {
-            if (!go) {
-                if (lo > hi) {
-                    // no value at this timepoint (every curve NaN): nothing is contained, nothing to rank
-                    if constexpr (J == 0) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e)
-                            if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = RB_AB_SPECIAL;
-                        if (t == 0) nnan_img[r] = (u32)n;
-                    }
-                } else {                                              // set aside: sorted behind the loop
-                    if (t == 0) defer[rowidx >> 5] |= 1u << (rowidx & 31);
-                    ++ndefer;
+                    for (int e = 0; e < E; ++e)
+                        if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = RB_AB_SPECIAL;
+                    if (t == 0) nnan_img[r] = (u32)n;
                 }
+            } else {                                                  // set aside: sorted behind the loop
+                if (t == 0) defer[rowidx >> 5] |= 1u << (rowidx & 31);
+                ++ndefer;
             }
         }
         ++rowidx;
         u32 bc[E];                                                    // base | count << 16 | slot << 24; count 0: a NaN
         u32 (&pk)[E] = bs;                                            // member phase: less | le << 16, in bs's registers
         if (go) {
-            mark(4);
             __syncthreads();                                          // barrier 4
             // ---- (3) scatter into bucket order (branch-free; NaNs write the dummy slot) ----
             const u32 nv = H[NB / 2];
@@ -565,19 +517,8 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
             if (nn && t < RB_PAD) S[nv + t] = QNAN;                   // sentinels behind a row shortened by NaNs
         }
         if (rnext < rows) load_row(rnext);                            // next row in flight under the member passes
-        if constexpr (DBG == 4) {
-            if (go) {
-                __syncthreads();
-                uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
-#pragma unroll
-                for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-            }
-            go = false;
-        }
         if (go) {
-            mark(5);
             __syncthreads();                                          // barrier 5
-            mark(6);
             // the histogram is dead until the next row's atomics (behind its barrier 1)
             {
                 uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
@@ -609,10 +550,8 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                     }
                 } else if (crowded) {
                     mode = 2;
-                    if constexpr (DBG == 0) {
-                        if (t == 0) defer[(rowidx - 1) >> 5] |= 1u << ((rowidx - 1) & 31);
-                        ++ndefer;
-                    }
+                    if (t == 0) defer[(rowidx - 1) >> 5] |= 1u << ((rowidx - 1) & 31);
+                    ++ndefer;
                 } else {
 #pragma unroll
                     for (int e = 0; e < E; ++e) {
@@ -635,11 +574,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                 const double2 *Sq = reinterpret_cast<const double2 *>(S + (base - odd));
 #pragma unroll
                 for (int u = 0; u < U2; ++u) {
-#if RB_REDIRECT
                     yw[w][u] = *((u == 0 || cnt + odd > (u32)(2 * u)) ? Sq + u : NANP);
-#else
-                    yw[w][u] = Sq[u];
-#endif
                 }
             };
             window(0, 0);
@@ -661,7 +596,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
                 more |= cnt + odd > (u32)(2 * U2);
                 if (e + 1 < E) window(e + 1, 0);
             }
-            if (__ballot(more && !(DBG == 6 && n > 0)) != 0) {   // DBG 6: never taken, code kept (timing experiment)
+            if (__ballot(more) != 0) {
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
                     u32 bce = bc[e];
@@ -716,14 +651,8 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
             if (go && t == 0) nnan_img[r] = nn;
         }
         if (rnext < rows) row_range(par);                             // the next row's keys have landed by now
-        mark(7);
     }
     t = t0;
-    if constexpr (DBG == 5) {   // in-kernel stamps (cdna_hip_programming.md, 7): where one wave's cycles go, barrier waits included
-        if (blockIdx.x == 0 && t0 == 0)
-            printf("rb stamps (cycles, wave 0 of workgroup 0): to-b1 %lld | b1-wait %lld | phase1 %lld | b2+prefixA %lld | b3+prefixB %lld | b4+scatter %lld | b5-wait %lld | members+fold+range %lld\n",
-                   stamp[0], stamp[1], stamp[2], stamp[3], stamp[4], stamp[5], stamp[6], stamp[7]);
-    }
     // ---- this workgroup's partial totals (u32 when the host found that they fit: J = 2, few rows per workgroup) ----
     u64 *P = partial + (size_t)blockIdx.x * (J > 0 ? J - 1 : 0) * n;
     // SEL: the totals of the flagged rows go to this workgroup's own u32 block (summed by the last workgroups to arrive, below)
@@ -743,8 +672,6 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
     // ---- the rows the bucket map could not spread (an infinity, all values equal, a crowded bucket): sort + search.
     //      The main loop's accumulators are already in HBM and dead here, so this cold code shares no registers
     //      with the hot loop; each thread adds its own curves' band counts to what it stored above. ----
-#ifndef RB_NO_COLD
-    if constexpr (NT == RB_SNT)
     if (ndefer) {                                                     // block-uniform
         __syncthreads();
         rowidx = 0;
@@ -769,7 +696,6 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : RB_WAVES_PER_EU(E))) void rank
             }
         }
     }
-#endif
     if constexpr (SEL) {
         // ---- the flagged rows' totals: G blocks of u32 -> out_tot.  Adding them with atomics from every workgroup costs
         //      G same-address atomics per curve (20 us at G = 256); instead each workgroup publishes its block, takes a
@@ -1151,11 +1077,7 @@ static int rb_cus() {
 
 bool mbd_rank_bucket_supported(i64 T, i64 n, int J) {
     (void)T;
-    i64 nmin = 1;                          // measured faster than the sort kernels from n = 600 to 16384
-#ifdef SD_TUNING
-    if (const char *e = getenv("SD_RB_MIN_N")) nmin = atoll(e);   // tuning experiments
-#endif
-    return n > nmin && n <= 16384 && J >= 2 && J <= 3;
+    return n > 1 && n <= 16384 && J >= 2 && J <= 3;       // measured faster than the sort kernels from n = 600 to 16384
 }
 
 // upper bound of the grid the launcher will use (the partial totals are sized by it)
@@ -1168,31 +1090,15 @@ size_t mbd_rank_bucket_workspace_bytes(i64 rows, i64 n, int J) {
     return mbd_rank_bucket_partial_bytes(n, J) + 512;
 }
 
-#ifndef RB_CAP
-#define RB_CAP 127
-#endif
+constexpr int RB_CAP = 127;
 template <int NT, int E, int LNB, int J, int U2>
 static int launch_bucket_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *partial, int p32, int G, hipStream_t s,
                              u32 *nnan_img = nullptr) {
     using C = RBCfg<NT, E, LNB, U2>;
     auto kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2>;
     if constexpr (J == 2) {
-        if (p32 == 2) kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 0, true>;
+        if (p32 == 2) kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, true>;
     }
-#ifdef SD_TUNING
-    if constexpr (E == 10 && J == 2 && LNB == 15 && U2 == 3) {
-        if (const char *d = getenv("SD_RB_DBG")) {        // timing experiments: truncated kernels (results invalid)
-            switch (atoi(d)) {
-                case 1: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 1>; break;
-                case 2: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 2>; break;
-                case 3: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 3>; break;
-                case 4: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 4>; break;
-                case 5: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 5>; break;
-                case 6: kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, 6>; break;
-            }
-        }
-    }
-#endif
     const size_t lds = C::lds_bytes((int)n);
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
     SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1208,7 +1114,7 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
                                  const u32 *gate, u32 epoch, u64 *out, int Gsum, const u32 *listbuf, u32 *fblocks, u32 *done,
                                  hipStream_t s) {
     using C = RBCfg<1024, E, LNB, 3>;
-    auto kf = rank_bucket_kernel<1024, E, LNB, 2, RB_CAP, 3, 0, true, true>;
+    auto kf = rank_bucket_kernel<1024, E, LNB, 2, RB_CAP, 3, true, true>;
     const size_t lds = C::lds_bytes((int)n) + 8192;
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
     SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1253,23 +1159,6 @@ static int launch_bucket_j(const double *Y, i64 n, i64 row0, i64 rows, u64 *part
     // J = 3 stays at 16384: the wider prefix arrays push it further into scratch); first member pass: 3 x 16 bytes
 #define RB_ARGS Y, n, row0, rows, partial, p32, G, s
     const int E = (int)((n + 1023) / 1024);
-#ifdef RB_HALF                                            // timing experiment: two 512-thread workgroups per CU (no cold path)
-    if constexpr (J == 2) {
-        if (E == 5) return launch_bucket_cfg<512, 10, 14, 2, 3>(RB_ARGS);
-    }
-#endif
-#ifdef SD_TUNING
-    if (E == 10 && J == 2) {                              // tuning experiments on the config-2 shape
-        const char *eu = getenv("SD_RB_U2"), *el = getenv("SD_RB_LNB");
-        const int u2 = eu ? atoi(eu) : 3, lnb = el ? atoi(el) : 15;
-        if (lnb == 14 && u2 == 2) return launch_bucket_cfg<1024, 10, 14, 2, 2>(RB_ARGS);
-        if (lnb == 14 && u2 == 4) return launch_bucket_cfg<1024, 10, 14, 2, 4>(RB_ARGS);
-        if (lnb == 15 && u2 == 2) return launch_bucket_cfg<1024, 10, 15, 2, 2>(RB_ARGS);
-        if (lnb == 14 && u2 == 3) return launch_bucket_cfg<1024, 10, 14, 2, 3>(RB_ARGS);
-        if (lnb == 13 && u2 == 3) return launch_bucket_cfg<1024, 10, 13, 2, 3>(RB_ARGS);
-        if (lnb == 13 && u2 == 4) return launch_bucket_cfg<1024, 10, 13, 2, 4>(RB_ARGS);
-    }
-#endif
     switch (E) {
         case 1: return launch_bucket_cfg<1024, 1, 13, J, 3>(RB_ARGS);
         case 2: return launch_bucket_cfg<1024, 2, 13, J, 3>(RB_ARGS);
@@ -1372,11 +1261,7 @@ int launch_rank_bucket_two_level(const double *Y, i64 n, i64 row0, i64 rows, u64
 // blocks) in *G_out
 int launch_rank_bucket(const double *Y, i64 n, i64 row0, i64 rows, int J, u64 *partial, int *p32_out, int *G_out,
                        hipStream_t s) {
-    // one workgroup per CU; two where the kernel is built for 64 VGPRs (few keys per thread)
-    int cus = rb_cus() * (((n + 1023) / 1024) <= RB_SMALL_E ? 2 : 1);
-#ifdef RB_HALF
-    if ((n + 1023) / 1024 == 5 && J == 2) cus = 2 * rb_cus();
-#endif
+    const int cus = rb_cus();                                         // one workgroup per CU
     const int G = (int)(rows < cus ? rows : cus);
     *G_out = G;
     if (rows > (i64)G * 2048) return fail(SD_ERR_INVALID, "bucket kernel: more than 2048 rows per workgroup in one launch");

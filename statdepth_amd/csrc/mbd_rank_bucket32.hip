@@ -23,23 +23,16 @@
 // Per-curve totals stay in registers (u32: the host checked that a workgroup's total fits); one partial block per
 // workgroup goes to HBM and the second launch (rank_bucket_kernel's SEL form) sums the blocks into the totals.  HBM traffic: the matrix once + the partial blocks.
 #include <atomic>
-#include <stdio.h>
 
 #include "sd_common.h"
 #include "rank_bucket.h"
 
 namespace sd {
 
-#ifndef R32_PRIO_LDS
-#define R32_PRIO_LDS 2                           // s_setprio in the load / histogram / prefix / scatter phases (issue on arrival)
-#define R32_PRIO_VALU 0                          // ... and in the member pass, which is bound by VALU issue
-#endif
-#ifndef R32_MIN_N
-#define R32_MIN_N 3072                           // the two-launch path is used above this n (measured: -10 % at 4 096, nothing at 3 072)
-#endif
-#ifndef R32_LNB
-#define R32_LNB 14                               // 16 384 buckets: histogram 32 KiB
-#endif
+constexpr int R32_PRIO_LDS = 2;                 // s_setprio in the load / histogram / prefix / scatter phases (issue on arrival)
+constexpr int R32_PRIO_VALU = 0;                // ... and in the member pass, which is bound by VALU issue
+constexpr int R32_MIN_N = 3072;                 // the two-launch path is used above this n (measured: -10 % at 4 096, nothing at 3 072)
+constexpr int R32_LNB = 14;                     // 16 384 buckets: histogram 32 KiB
 constexpr int R32_NT = 512, R32_NW = 8;
 constexpr int R32_LCAP = 64;                    // set-aside keys per workgroup before it hands all its rows over
 constexpr int R32_LIST_WORDS = 1 + 2 * R32_LCAP;   // a workgroup's list in the workspace: count, keys, (B0 | E0 << 16)
@@ -47,9 +40,7 @@ constexpr int R32_PAD = 12;                     // sentinel images behind the ke
 constexpr u32 R32_TB = 1024;                    // buckets of each tail
 constexpr int R32_TSH = 30;                     // tail code = (bits(d + c) - bits(c)) >> 30: 2^22 codes = 32 buckets per octave
 constexpr double R32_CDIV = 1.0 / 448.0;        // c = core width / 448: the first octave continues the core's slope (32 * 448 = 14 336)
-#ifndef R32_BETA
-#define R32_BETA 2.0                             // the central bracket of the sample is widened by this many spans on either side
-#endif
+constexpr double R32_BETA = 2.0;                // the central bracket of the sample is widened by this many spans on either side
 constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the keys: above every key image, below 2^31
 
 template <int E, int LNB>
@@ -93,10 +84,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     const u32 nm1 = (u32)n - 1u;
     const u32 ranksum = (u32)(((u64)n * (u64)(n - 1)) >> 1);          // sum of the ranks of a row without equal images
     int t = t0;
-#ifdef R32_STAMPS
-    const long long t_entry = (long long)__builtin_readcyclecounter();
-    const long long rt_entry = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
 
     if (blockIdx.x == 0 && t == 0) gate[2] = 0;                       // the second launch's arrival counter
     if (out_zero)                                                     // the second launch adds every total to out
@@ -161,12 +148,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             reinterpret_cast<float *>(wp + 2)[1] = imx;
         }
     };
-#ifdef R32_STAMPS                                  // timing experiments: cycles per phase, one wave
-    long long stamp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = (long long)__builtin_readcyclecounter();
-#define R32_MARK(ph) { const long long now_ = (long long)__builtin_readcyclecounter(); stamp[ph] += now_ - tlast; tlast = now_; }
-#else
-#define R32_MARK(ph)
-#endif
     int par = 0;
     u32 rowidx = 0, nbad = 0, expect = 0;                             // block-uniform
     bool handover = false;                                            // the list overflowed: every row of this workgroup is handed over
@@ -178,7 +159,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         asm volatile("" : "+v"(t));                                   // addresses are recomputed per row, not hoisted and spilled
         const int lane = t & 63;
         const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-        R32_MARK(0)
         // Tie-heavy / NaN-ridden data: when 8 of the first 16 workgroups have found their first row bad, everybody leaves what is left to
         // the second launch (gate[1] = epoch << 8 | count; block-uniform scalar load, a few rows stale at worst)
         if (rowidx && t == 0) misc[3] = __hip_atomic_load(gate + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ONE load per workgroup
@@ -186,11 +166,9 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         sample_issue(r);
         load_row(r);                                                  // pass (the other workgroup's, half a row away) fill in
         row_range(par);
-        R32_MARK(1)
         double *redp = red + par * 4 * NW;
         par ^= 1;
         __syncthreads();                                              // barrier 1 (histogram is zero, S is free)
-        R32_MARK(2)
         if (rowidx) {                                                 // block-uniform: everybody reads the word thread 0 fetched
             const u32 w = misc[3];
             if ((w >> 8) == (epoch & 0xFFFFFFu) && (w & 0xFFu) >= 8u) { stop = true; break; }
@@ -301,9 +279,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 asm volatile("" : "+v"(sl[e0 >> 2]));                 // packed HERE: not (old, shift) pairs kept for the scatter
                 if (e0 + 4 < E) asm volatile("" : "+v"(sl[(e0 >> 2) + 1]));
             }
-            R32_MARK(3)
             __syncthreads();                                          // barrier 2
-            R32_MARK(4)
             // ---- (2) exclusive prefix sum over the counters (conflict-free 16-byte accesses: lane <-> quad) ----
             uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
             uint4 hq[QW];
@@ -321,7 +297,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             const bool wover = __ballot((ov & 0xFFC0FFC0u) != 0) != 0;   // some bucket holds 64 keys or more
             const bool wtry = __ballot((ov & 0xFFF0FFF0u) != 0) != 0;    // ... 16 or more: ties rather than density?
             if (lane == 63) wtot[wave] = wsum | (wover ? 0x80000000u : 0u) | (wtry ? 0x40000000u : 0u);
-            R32_MARK(5)
             __syncthreads();                                          // barrier 3
             const u32 wt = wtot[lane & (NW - 1)];
             const bool crowded = __ballot((wt >> 31) != 0) != 0;
@@ -344,7 +319,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 if (i == QW - 1 && t == NT - 1) H[NB / 2] = base;     // base past the last bucket = number of non-NaN keys
             }
             __syncthreads();                                          // barrier 4
-            R32_MARK(6)
             const u32 nv = H[NB / 2];
             // block-uniform.  A crowded row (a bucket of 64 keys or more) is scattered too: its slots wrap at 256 but stay inside
             // their buckets, which is all the closed form below asks of S; its member pass is never run.
@@ -366,9 +340,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     bc[e] = isk ? base | ((end - base) << 14) : (1u << 14);
                 }
             }
-            R32_MARK(7)
             __syncthreads();                                          // barrier 5
-            R32_MARK(8)
             bool pure = false;                                        // block-uniform: the row is ranked in closed form
             if (take && (trypure || crowded)) {
                 // A bucket of 16 keys or more is tie-heavy (quantised) data more often than a dense cluster.  When a key
@@ -440,10 +412,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     }
                 }
             }
-#if defined(R32_SECPRIO)                          // timing experiment: the workgroup dispatched second to a CU one level up in the member pass
-            if (blockIdx.x >= gridDim.x / 2) __builtin_amdgcn_s_setprio(R32_PRIO_VALU + 1);
-            else
-#endif
             __builtin_amdgcn_s_setprio(R32_PRIO_VALU);
             {                                                         // the histogram is dead until the next row's atomics
                 uint4 *Hz = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
@@ -462,11 +430,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     const u32 base = bc[e] & 0x3FFFu, cnt = bc[e] >> 14;
                     const uint4 *p = S4 + (base >> 2);
                     y0 = p[0];
-#ifdef R32_NOREDIRECT
-                    y1 = p[1];
-#else
                     y1 = *((cnt + (base & 3u) > 4u) ? p + 1 : SENT);
-#endif
                 };
                 u32 sB = 0;
                 window(0);
@@ -520,9 +484,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                         // B.  The tied ones take their product back and are set aside with B0 = B and the size of their group.
                         expect = have_sum;
                         const u32 l0 = misc[0];                       // the list before this row (no push since the last barrier)
-#ifdef R32_STAMPS
-                        stamp[0] += 1000000;
-#endif
 #pragma unroll
                         for (int e = 0; e < E; ++e)
                             if (e < E - 2 || t + e * NT < n) atomicAdd(&H[kb[e] >> 1], 1u << ((kb[e] & 1u) * 16u));
@@ -542,7 +503,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                             }
                         }
                         __syncthreads();
-#ifndef R32_NO_TIEPROOF                           // (timing experiments: the list alone)
                         // (E <= 16, n <= 8 192: from E = 18 on this cold code costs the row loop two accumulators in scratch,
                         // + 5 % on config 2; there a bucket of 16 equal keys is common on such data and the closed form above runs)
                         if (E <= 16 && misc[0] > (u32)R32_LCAP) {     // block-uniform
@@ -595,7 +555,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                             }
                             __syncthreads();
                         }
-#endif
 #pragma unroll
                         for (int e = 0; e < E; ++e)
                             if (e < E - 2 || t + e * NT < n) H[kb[e] >> 1] = 0;
@@ -607,7 +566,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 bad = !pure;
             }
         }
-        R32_MARK(9)
         if (t == 0) rowflag[r] = bad ? 1 : 0;
         nbad += bad ? 1u : 0u;
         ++rowidx;
@@ -646,17 +604,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         if (t == 0) lb[0] = L;
         if ((u32)t < L) { lb[1 + t] = lkey[t]; lb[1 + R32_LCAP + t] = lbe[t]; }
     }
-#ifdef R32_STAMPS
-    __syncthreads();
-    if ((t0 & 63) == 0 && (t0 == 0 || t0 == NT - 64)) {                // the oldest and the youngest wave of the workgroup
-        u32 *dbg = listbuf + (size_t)gridDim.x * R32_LIST_WORDS + (size_t)blockIdx.x * 32 + (t0 ? 16 : 0);
-        dbg[0] = (u32)((long long)__builtin_readcyclecounter() - t_entry);
-        dbg[1] = (u32)rt_entry;
-        dbg[2] = (u32)__builtin_amdgcn_s_memrealtime();
-        dbg[3] = misc[0] | (rowidx << 16);
-        for (int i = 0; i < 10; ++i) dbg[4 + i] = (u32)stamp[i];
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -685,11 +632,7 @@ static int launch32_cfg(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial
 
 // rows [row0, row0 + rows): u32 partial totals of every curve per workgroup (G blocks of n), flags of the rows left to the
 // fp64 kernel in rowflag[rows], *gate = epoch when there is any
-#ifdef R32_STAMPS
-size_t rank_bucket32_list_bytes(int G) { return (size_t)G * R32_LIST_WORDS * 4 + (size_t)G * 128; }
-#else
 size_t rank_bucket32_list_bytes(int G) { return (size_t)G * R32_LIST_WORDS * 4; }
-#endif
 
 int launch_rank_bucket32(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
                          u64 *out_zero, u32 *listbuf, int G, hipStream_t s) {

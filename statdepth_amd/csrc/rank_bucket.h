@@ -125,9 +125,6 @@ __device__ __forceinline__ float rb3_dpp_f32(float v) {       // v = min / max(v
 // (or with values beyond float) is neutral.
 template <int E, int NT>
 __device__ __forceinline__ float2 rb3_wave_bracket(double mn, double mx) {
-#ifdef RB3_OFF                                   // timing experiments: the linear map alone
-    return make_float2(-__builtin_huge_valf(), __builtin_huge_valf());
-#endif
     float a = (float)mn, b = (float)mx;
     constexpr int GL = E >= 16 ? 1 : E >= 8 ? 2 : E >= 4 ? 4 : 16;
     if constexpr (GL == 2 || GL == 4) {
@@ -170,9 +167,6 @@ template <int NB>
 __device__ __forceinline__ Rb3 rb3_make(double lo, double hi, float2 q, int n) {
     constexpr int TB = NB / 16, NCORE = NB - 2 * TB;
     const double INF = __builtin_huge_val();
-#ifdef RB3_OFF
-    { Rb3 m0; m0.lo = lo; m0.hi = hi; m0.scale = 0.0; m0.c = 0.0; m0.cb = 0; m0.clip = false; return m0; }
-#endif
     const float l2 = rb_row_allreduce_f32<true>(q.x), h2 = rb_row_allreduce_f32<false>(q.y);
     const double a = (double)__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(l2)));
     const double b = (double)__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(h2)));

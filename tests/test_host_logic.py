@@ -63,6 +63,22 @@ def test_product_library_has_no_crosscheck_code(built):
     assert "XCHECK_LIB_PATH" not in pkg and "xcheck" not in pkg
 
 
+def test_kernel_sources_test_no_build_switches():
+    """The kernel sources are compiled one way: preprocessor conditionals test only SD_CROSSCHECK (the cross-check
+    library) and __HIPCC__.  Timing experiments live in tools/experiments/ and git history, not behind -D switches."""
+    csrc = os.path.join(ROOT, "statdepth_amd", "csrc")
+    found = set()
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h")):
+            continue
+        for line in open(os.path.join(csrc, fn)):
+            m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                expr = re.sub(r"//.*|/\*.*?\*/", "", m.group(1))
+                found |= {(fn, name) for name in re.findall(r"[A-Za-z_]\w*", expr) if name != "defined"}
+    assert {f for f in found if f[1] not in ("SD_CROSSCHECK", "__HIPCC__")} == set()
+
+
 def test_abi_version_and_error_string(built):
     lib = built.load()
     assert lib.sd_abi_version() == 1

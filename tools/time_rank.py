@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of sd_mbd_counts (rank path) on config-2-shaped data under env-selected variants.
-usage: time_rank.py [n] [T] [reps]; prints ms per call for each SD_RB_DBG level given in SD_LEVELS (default 0)."""
+"""Device time of sd_mbd_counts (rank path) on config-2-shaped data.
+usage: time_rank.py [n] [T] [reps]; prints ms per call."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,18 +20,13 @@ ROT = int(os.environ.get("SD_ROTATE", "1"))      # > 1: that many distinct matri
 Xs = [Xd] + [engine.to_device_matrix(X + float(k)) for k in range(1, ROT)]
 if os.environ.get("SD_RANK_IMPL"):
     print("SD_RANK_IMPL =", os.environ["SD_RANK_IMPL"])
-for lvl in os.environ.get("SD_LEVELS", "0").split(","):
-    if lvl != "0":
-        os.environ["SD_RB_DBG"] = lvl
-    else:
-        os.environ.pop("SD_RB_DBG", None)
-    for _ in range(3):
-        engine.mbd_counts(Xd, None, 2, algo="rank", return_tensor=True)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(reps):
-        engine.mbd_counts(Xs[i % ROT], None, 2, algo="rank", return_tensor=True)
-    e1.record()
-    torch.cuda.synchronize()
-    print(f"n={n} T={T} dbg={lvl}: {e0.elapsed_time(e1) / reps:.4f} ms per call", flush=True)
+for _ in range(3):
+    engine.mbd_counts(Xd, None, 2, algo="rank", return_tensor=True)
+torch.cuda.synchronize()
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+e0.record()
+for i in range(reps):
+    engine.mbd_counts(Xs[i % ROT], None, 2, algo="rank", return_tensor=True)
+e1.record()
+torch.cuda.synchronize()
+print(f"n={n} T={T}: {e0.elapsed_time(e1) / reps:.4f} ms per call", flush=True)
