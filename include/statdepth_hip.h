@@ -320,6 +320,26 @@ int sd_prob_normal_sums(const double *mu, const double *sigma, int64_t n, const 
 int sd_prob_poisson_sums(const double *lam, int64_t T, int64_t n, int64_t lim, const int64_t *targets, int64_t m,
                          double *out, void *stream);
 
+/* ---- K9: band depth of curves under Gaussian noise (ProbabilisticDepth) -----------------------
+ * No reference code (its prob_depth.py is empty); the quantity is the expected J = 2 band depth of random curves.
+ * mu, var: T x n row-major (device), row t = timepoint, column = curve; X_c(t) ~ N(mu[t][c], var[t][c]), independent,
+ * var = 0 a point mass.  For target i = targets[q] and a pair {j, k} of its others,
+ *     p_ijk(t) = P(min(X_j, X_k) <= X_i <= max(X_j, X_k))
+ *              = Phi(h_j) + Phi(h_k) - 2 Phi2(h_j, h_k; rho),  h_c = (mu_i - mu_c) / s_c, s_c = sqrt(var_i + var_c),
+ *                rho = var_i / (s_j s_k)  (Phi2 by Genz's BVND, evaluated as the two orthants where D_j, D_k differ in sign)
+ *     out[q] = sum_{j<k} sum_t p_ijk(t)   (relax != 0)      out[q] = sum_{j<k} prod_t p_ijk(t)   (relax == 0)
+ * depth = out / T / C(n', 2) (relax) or out / C(n', 2), n' counting the target.  Degenerate cases are exact:
+ * var_i = 0 gives p = 1 - a_j a_k - b_j b_k (a_c = P(X_c > mu_i), b_c = P(X_c < mu_i)); var_j = var_k = 0 < var_i gives
+ * Phi(hmax) - Phi(hmin); with every variance zero p is 0 or 1 and out equals the integer band counts of
+ * sd_mbd_counts / sd_bd_strict_counts.
+ * members: NULL = every other column; otherwise m x bs int32 (device) padded with -1, row q = the block of target q
+ * (the target is skipped where listed).  targets: m int64 (device; the engine checks ranges on the host), NULL = all.
+ * A target's result is bitwise independent of m, of the other targets and of how the call is cut into launches.
+ * SD_ERR_INVALID for NULL pointers or negative sizes; SD_ERR_OVERFLOW if m * C(positions, 2) * T overflows int64;
+ * SD_ERR_UNSUPPORTED beyond 10^14 pair evaluations.  Both before any device work.  Every launch is bounded in work. */
+int sd_prob_band_sums(const double *mu, const double *var, int64_t T, int64_t n, const int64_t *targets, int64_t m,
+                      const int32_t *members, int bs, int relax, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

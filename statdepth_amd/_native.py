@@ -71,6 +71,7 @@ SIGNATURES = {
     "sd_oja_subset_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _int, _vp, _vp]),
     "sd_prob_normal_sums": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sd_prob_poisson_sums": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "sd_prob_band_sums": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp]),
 }
 
 

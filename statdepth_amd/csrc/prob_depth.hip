@@ -34,20 +34,9 @@
 //
 // fp64 VALU and transcendentals (erfc, exp, log) are the hot path; the guides give no fp64 rate for this part, so the
 // costs in DESIGN §3 K8 are measured, not derived from a peak.
-#include "sd_common.h"
+#include "prob_common.h"
 
 namespace sd {
-
-// ---------------------------------------------------------------------------------------------------------------- shared
-__device__ __forceinline__ double pr_block_sum(double v, double *scratch) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int k = 0; k < 4; ++k) r += scratch[k];                    // every lane, same order (256 threads = 4 waves)
-    __syncthreads();
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- normal
 constexpr int PN_THREADS = 256;
@@ -92,7 +81,7 @@ __global__ __launch_bounds__(PN_THREADS) void pn_kernel(const double *__restrict
         if (m < n && m != k) {
             const double sm = sg[m];
             const double h = (mk - mu[m]) / hypot(sm, sk);
-            const double Ph = 0.5 * erfc(-h * M_SQRT1_2);
+            const double Ph = pr_phi(h);
             const double a = sk / hypot(M_SQRT2 * sm, sk);
             const double B = 0.5 * Ph + pn_owen_t(h, a);
             const double wa = (double)((n - 1 - m) - (k > m ? 1 : 0));
@@ -116,6 +105,13 @@ __global__ __launch_bounds__(256) void pn_fold_kernel(const double *__restrict__
     double acc = a == qb ? 0.0 : out[q];
     for (u64 v = a; v < e; ++v) acc += part[v - u0];
     out[q] = acc;
+}
+
+// the fold above as a stream launch of its own (K9's per-(target, tile) results use it too)
+hipError_t launch_prob_fold(const double *part, u64 u0, u64 u1, u64 S, double *out, hipStream_t s) {
+    const u64 q0 = u0 / S, q1 = (u1 - 1) / S;
+    hipLaunchKernelGGL(pn_fold_kernel, dim3((unsigned)((q1 - q0 + 1 + 255) / 256)), dim3(256), 0, s, part, u0, u1, S, out);
+    return hipGetLastError();
 }
 
 int launch_prob_normal_sums(const double *mu, const double *sigma, i64 n, const i64 *targets, i64 m, double *out,

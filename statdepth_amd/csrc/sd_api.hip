@@ -640,4 +640,22 @@ int sd_prob_poisson_sums(const double *lam, int64_t T, int64_t n, int64_t lim, c
     return launch_prob_poisson_sums(lam, T, n, lim, targets, m, out, (hipStream_t)stream);
 }
 
+int sd_prob_band_sums(const double *mu, const double *var, int64_t T, int64_t n, const int64_t *targets, int64_t m,
+                      const int32_t *members, int bs, int relax, double *out, void *stream) {
+    if (!mu || !var || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 0 || n < 0 || m < 0 || (members && bs < 0)) return fail(SD_ERR_INVALID, "bad shape");
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    const i64 W = members ? (i64)bs : n;                           // positions per target
+    i64 pairs = 0, work = 0;
+    if (W > 1 && (__builtin_mul_overflow(W, W - 1, &pairs) || __builtin_mul_overflow(pairs / 2, (i64)T, &work) ||
+                  __builtin_mul_overflow(work, (i64)m, &work)))
+        return fail(SD_ERR_OVERFLOW, "%lld targets x %lld pairs x %lld timepoints overflows int64", (long long)m,
+                    (long long)(W / 2) * (long long)(W - 1), (long long)T);
+    if ((double)work > PROB_MAX_EVALS)
+        return fail(SD_ERR_UNSUPPORTED, "%lld targets x %lld positions x %lld timepoints exceeds the cap of %.0e pair "
+                    "evaluations", (long long)m, (long long)W, (long long)T, PROB_MAX_EVALS);
+    if (m == 0) return SD_OK;
+    return launch_prob_band_sums(mu, var, T, n, targets, m, members, bs, relax, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -127,6 +127,12 @@ int launch_oja_subsets(const double *P, i64 n, int d, const int *members, i64 nb
 int launch_prob_normal_sums(const double *mu, const double *sigma, i64 n, const i64 *targets, i64 m, double *out,
                             hipStream_t s);
 int launch_prob_poisson_sums(const double *lam, i64 T, i64 n, i64 lim, const i64 *targets, i64 m, double *out, hipStream_t s);
+// adds part[0 .. u1 - u0) of units [u0, u1) (unit u = target u / S, chunk u % S) into out[u / S] in unit order; out holds
+// the running sum of a target whose chunks span launches
+hipError_t launch_prob_fold(const double *part, u64 u0, u64 u1, u64 S, double *out, hipStream_t s);
+// K9 band depth of curves under Gaussian noise (prob_band.hip): unnormalised pair sums (sd_prob_band_sums)
+int launch_prob_band_sums(const double *mu, const double *var, i64 T, i64 n, const i64 *targets, i64 m, const int *members,
+                          int bs, int relax, double *out, hipStream_t s);
 
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);

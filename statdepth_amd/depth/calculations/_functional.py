@@ -164,6 +164,22 @@ def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index]
     raise NotImplementedError('custom containment callables are only supported for univariate data')
 
 
+def _sample_blocks(df: pd.DataFrame, orig: pd.DataFrame, ss: int, K: int):
+    """The reference's block draws (:172-183), in draw order: for each target column of `orig`, K blocks of `ss` curves
+    drawn without replacement from the pool `df` with the global numpy RNG (`df.sample(n=ss, axis=1)`, :176), the
+    pool reset to `orig` -- it shrinks to the targets, as in the reference -- after each target.  Yields (target label,
+    the drawn frame, member labels with the target appended where it was not drawn, :178)."""
+    for col in orig.columns:
+        for _ in range(K):
+            t = df.sample(n=ss, axis=1)                  # (:176) global numpy RNG
+            df = df.drop(t.columns, axis=1)              # (:177) without replacement across blocks
+            members = list(t.columns)
+            if col not in members:
+                members.append(col)                      # (:178) force the target into the block
+            yield col, t, members
+        df = orig.copy()                                 # (:183) -- the pool shrinks to `cols`, as in the reference
+
+
 def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[list, pd.Index] = None, J=2,
                            containment='r2', relax=False, deep_check=False, quiet=True, device=None,
                            algo='auto') -> pd.Series:
@@ -196,27 +212,23 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     batched = cdef == 'r2' and (relax or (J == 2 and _BATCH_STRICT_BLOCKS))
     blocks, block_targets = [], []           # column positions (in data[0]) of every block, in draw order
     full = data[0]
-    for col in orig.columns:
-        depths = []
-        for _ in range(K):
-            t = df.sample(n=ss, axis=1)                  # (:176) global numpy RNG
-            df = df.drop(t.columns, axis=1)              # (:177) without replacement across blocks
-            members = list(t.columns)
-            if col not in members:
-                members.append(col)                      # (:178) force the target into the block
-            if batched:
-                blocks.append(full.columns.get_indexer(members))
-                block_targets.append(full.columns.get_loc(col))
-                continue
-            t = t.copy()
-            t.loc[:, col] = orig.loc[:, col]
-            if cdef == 'r2':
-                depths.append(_univariate_depths(t, [col], J, relax, device=device, algo='pairwise')[0])
-            else:
-                depths.append(_callable_band_depth(t, col, relax, cdef, J))
-        if not batched:
+    depths = []
+    for col, t, members in _sample_blocks(df, orig, ss, K):
+        if batched:
+            blocks.append(full.columns.get_indexer(members))
+            block_targets.append(full.columns.get_loc(col))
+            continue
+        t = t.copy()
+        t.loc[:, col] = orig.loc[:, col]
+        if cdef == 'r2':
+            depths.append(_univariate_depths(t, [col], J, relax, device=device, algo='pairwise')[0])
+        else:
+            depths.append(_callable_band_depth(t, col, relax, cdef, J))
+        if len(depths) == K:
             samples.append(np.mean(depths))              # (:182)
-        df = orig.copy()                                 # (:183) -- the pool shrinks to `cols`, as in the reference
+            depths = []
+    if len(orig.columns):
+        df = orig                                        # (:183) the pool the reference's loop leaves behind
     if batched:
         # every (target, block) pair of the estimator in ONE launch
         width = max(len(b) for b in blocks)

@@ -7,6 +7,10 @@ reference's sums are separated into pair terms: O(n^2) closed
 the normal depth is integrated on the host with scipy's quad, one call per (target, pair), as the reference does.
 DESIGN.md §4 lists where this departs from the reference: finite sums where its factorials overflow to NaN, `to_compute`
 honoured, and invalid parameters refused with ValueError.
+
+`_probabilistic_band_depth` is the driver of `ProbabilisticDepth`, documented by the reference (docs/index.md §5.1.3)
+but never implemented there: the expected J = 2 band depth of curves observed with independent Gaussian noise
+(sd_prob_band_sums).
 """
 import math
 import operator
@@ -15,9 +19,12 @@ from itertools import combinations
 import numpy as np
 import pandas as pd
 from scipy.integrate import quad
+from scipy.special import binom
 from scipy.stats import norm
 
 from ... import engine
+from ._functional import _positions, _require_unique_labels, _sample_blocks
+from ._helper import DepthDegeneracy, _handle_depth_errors
 
 __all__ = ['probabilistic_normal_depth', 'probabilistic_poisson_depth']
 
@@ -91,3 +98,62 @@ def probabilistic_poisson_depth(df: pd.DataFrame, to_compute=None, lim=1000, tol
     with np.errstate(divide='ignore', invalid='ignore'):
         depths = np.float64(1.0) / np.float64(math.comb(T, 2)) * sums  # (:67); T < 2: 1 / 0 = inf
     return pd.Series(index=labels, data=depths)
+
+
+def _probabilistic_band_depth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compute=None, K=None, J=2, relax=False,
+                              device=None) -> pd.Series:
+    """Expected band depth (J = 2) of the columns of `data` (T timepoints x n curves) when X_c(t) ~ N(data[t, c],
+    sigma2[t, c]) independently; a zero variance is a point mass.
+
+    With p = P(min(X_j, X_k) <= X_i <= max(X_j, X_k)) for target i and a pair {j, k} of the other curves:
+    depth_i = sum_{j<k} sum_t p / T / C(n, 2) (relax) or sum_{j<k} prod_t p / C(n, 2), n counting the target -- the
+    containment and normalisation of FunctionalDepth, which it equals bit for bit when every variance is zero.  `K`
+    draws FunctionalDepth's blocks (`_sample_blocks`, the same global numpy RNG draws) and averages the block depths."""
+    _handle_depth_errors(data=[data], J=J, containment='r2', relax=relax, deep_check=False)
+    _require_unique_labels(data)
+    if J != 2:
+        raise NotImplementedError('ProbabilisticDepth is implemented for J = 2 (J >= 3 needs trivariate orthant '
+                                  'probabilities)')
+    if not isinstance(sigma2, pd.DataFrame):
+        raise ValueError('sigma2 must be a pd.DataFrame of variances with the index and columns of data')
+    if not (sigma2.shape == data.shape and sigma2.index.equals(data.index) and sigma2.columns.equals(data.columns)):
+        raise ValueError('sigma2 must have the same index and columns as data')
+    mu = data.to_numpy(dtype=np.float64)
+    var = sigma2.to_numpy(dtype=np.float64)
+    if not np.isfinite(mu).all():
+        raise ValueError('data must be finite (no NaN or inf)')
+    if not np.isfinite(var).all():
+        raise ValueError('sigma2 must be finite (no NaN or inf)')
+    if (var < 0).any():
+        raise ValueError('sigma2 holds variances: they must be non-negative')
+    T, n = mu.shape
+    cols = data.columns if to_compute is None else to_compute
+
+    if K is None:
+        tg = _positions(data, cols)
+        sums = engine.prob_band_sums(mu, var, relax, tg, device=device)
+        counts = sums / T if relax else sums             # as _univariate_depths normalises its counts
+        depth = np.zeros(len(tg), dtype=np.float64)
+        depth += counts / binom(n, 2)
+        return pd.Series(index=cols, data=depth)
+
+    orig = data.loc[:, cols]
+    ss = n // K
+    if ss == 0:
+        raise DepthDegeneracy(f'Block size {K} is too large, not enough functions to sample.')
+    blocks, block_targets = [], []
+    for col, _, members in _sample_blocks(data, orig, ss, K):
+        blocks.append(data.columns.get_indexer(members))
+        block_targets.append(data.columns.get_loc(col))
+    if not blocks:
+        return pd.Series(index=orig.columns, data=[], dtype=np.float64)
+    width = max(len(b) for b in blocks)
+    mem = np.full((len(blocks), width), -1, dtype=np.int32)
+    for i, b in enumerate(blocks):
+        mem[i, :len(b)] = b
+    sums = engine.prob_band_sums(mu, var, relax, np.asarray(block_targets, dtype=np.int64), mem, device=device)
+    counts = sums / T if relax else sums
+    sizes = np.array([len(b) for b in blocks], dtype=np.float64)
+    depth = np.zeros(len(blocks))
+    depth += counts / binom(sizes, 2)                    # n = block size including the target
+    return pd.Series(index=orig.columns, data=[np.mean(depth[i * K:(i + 1) * K]) for i in range(len(orig.columns))])

@@ -1,7 +1,9 @@
 """Public factories and result objects (reference: statdepth/depth/depth.py).
 
 `FunctionalDepth` (:362-402) and `PointcloudDepth` (:347-359) keep the reference's
-signatures; `device=` and `algo=` are keyword-only additions.  Result classes keep
+signatures; `device=` and `algo=` are keyword-only additions.  `ProbabilisticDepth` is the
+signature the reference documents (docs/index.md §5.1.3) and lists in `__all__` (:11) without
+implementing it, plus `to_compute` and the keyword-only `device=`.  Result classes keep
 the reference's method names and conventions (:14-65,178-185,337-341), including the
 plotly views (:91-175,193-335; `_plotting.py`, host-side visualisation outside the hot path).
 """
@@ -13,9 +15,10 @@ from abc import ABC, abstractmethod
 from .calculations._functional import _functionaldepth, _samplefunctionaldepth
 from .calculations._helper import DepthDegeneracy   # noqa: F401
 from .calculations._pointcloud import _pointwisedepth, _samplepointwisedepth
+from .calculations._uncertainty import _probabilistic_band_depth
 from . import _plotting
 
-__all__ = ['FunctionalDepth', 'PointcloudDepth']
+__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth']
 
 
 class AbstractDepth(ABC):
@@ -160,3 +163,12 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     if len(data) == 1:                                   # univariate by assumption (:399-400)
         return _FunctionalDepthUnivariate(df=data[0], depths=depth)
     return _FunctionalDepthSeries(df=data[0], depths=depth)   # multivariate (:401-402)
+
+
+def ProbabilisticDepth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compute=None, K=None, J=2, relax=False, *,
+                       device=None) -> _FunctionalDepthUnivariate:
+    """Band depth (J = 2) of the univariate curves in the columns of `data` when every observation carries Gaussian
+    noise of the variance at the same place in `sigma2` (the expected band depth of the random curves; zero variances
+    give FunctionalDepth's values).  Same containment, normalisation, `to_compute` and `K` blocks as FunctionalDepth."""
+    depth = _probabilistic_band_depth(data, sigma2, to_compute=to_compute, K=K, J=J, relax=relax, device=device)
+    return _FunctionalDepthUnivariate(df=data, depths=depth)

@@ -610,6 +610,46 @@ def prob_poisson_sums(lam, lim, targets=None, device=None):
     return out.cpu().numpy()
 
 
+def prob_band_sums(mu, var, relax, targets=None, members=None, device=None):
+    """float64[m]: band sums of curves under Gaussian noise, unnormalised (sd_prob_band_sums).  mu, var: T x n (rows are
+    timepoints, columns curves; X_c(t) ~ N(mu[t, c], var[t, c]) independent, var = 0 a point mass).  For i = targets[q]
+    and the pairs j < k of its others -- every other column, or members[q] (-1 padded; the target skipped where listed) --
+    the sum over pairs of sum_t p (relax) or prod_t p, p = P(min(X_j, X_k) <= X_i <= max(X_j, X_k)).
+    depth = sums / T / C(n', 2) (relax) or sums / C(n', 2), n' counting the target."""
+    t = torch()
+    mu_h = np.ascontiguousarray(np.asarray(mu, dtype=np.float64))
+    var_h = np.ascontiguousarray(np.asarray(var, dtype=np.float64))
+    if mu_h.ndim != 2 or var_h.shape != mu_h.shape:
+        raise ValueError("mu and var must be T x n arrays of the same shape")
+    T, n = mu_h.shape
+    if targets is not None:
+        tg = np.asarray(targets, dtype=np.int64)
+        if tg.ndim != 1:
+            raise ValueError("targets must be 1-D")
+        if len(tg) and (tg.min() < 0 or tg.max() >= n):
+            raise IndexError("target index out of range")
+    m = n if targets is None else len(targets)
+    mem = None
+    if members is not None:
+        mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
+        if mem.ndim != 2 or mem.shape[0] != m:
+            raise ValueError("members must be m x bs, one row per target")
+        _check_members(mem, None, n)
+    lib = _native.require_device()
+    dev = _device(device)
+    mud, vd = t.from_numpy(mu_h).to(dev), t.from_numpy(var_h).to(dev)
+    td, m, tp = _targets_dev(targets, n, dev)
+    md = t.from_numpy(mem).to(dev) if mem is not None else None
+    out = t.empty(m, dtype=t.float64, device=dev)
+    if m == 0:
+        return out.cpu().numpy()
+    with t.cuda.device(dev):
+        check(lib.sd_prob_band_sums(mud.data_ptr(), vd.data_ptr(), T, n, tp, m, md.data_ptr() if md is not None else None,
+                                    mem.shape[1] if mem is not None else 0, int(bool(relax)), out.data_ptr(),
+                                    _stream_ptr(dev)))
+    return out.cpu().numpy()
+
+
 def multi_band_counts(P, targets=None, device=None):
     """int64[m]: sum_t #{pairs of other curves whose componentwise band contains the target at t} (sd_multi_band_counts).
     P: (n, T, d) curves, NaN-free."""
