@@ -65,6 +65,23 @@ static int check_matrix(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64
 
 static bool is_time_major_dense(i64 n, i64 st, i64 sn) { return sn == 1 && st == n; }
 
+// Workspace bytes of the time-major copy that time_major() carves for a matrix in any other layout.
+static size_t time_major_bytes(i64 T, i64 n, i64 st, i64 sn) {
+    return is_time_major_dense(n, st, sn) ? 0 : align_up((size_t)T * n * 8, 256);
+}
+
+// *Y = X when X is time-major dense; otherwise a time-major copy of X carved from cv (sized by time_major_bytes).
+static int time_major(const double *X, i64 T, i64 n, i64 st, i64 sn, Carver &cv, hipStream_t s, const double **Y) {
+    *Y = X;
+    if (is_time_major_dense(n, st, sn)) return SD_OK;
+    double *Yw = (double *)cv.take((size_t)T * n * 8);
+    if (!Yw) return fail(SD_ERR_WORKSPACE, "workspace too small for the time-major copy");
+    int rc = launch_to_time_major(X, T, n, st, sn, Yw, s);
+    if (rc) return rc;
+    *Y = Yw;
+    return SD_OK;
+}
+
 // wide[i] (two 64-bit limbs) (+)= part[i]: the chunk totals of sd_mbd_counts_wide
 __global__ void wide_add_kernel(const u64 *__restrict__ part, i64 count, u64 *__restrict__ wide, int first) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -156,8 +173,7 @@ static int resolve_mbd_algo(int algo, i64 T, i64 n, i64 m, int J) {
 
 size_t sd_mbd_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int J, int algo) {
     if (T <= 0 || n <= 0) return 0;
-    size_t b = 0;
-    if (!is_time_major_dense(n, st, sn)) b += align_up((size_t)T * n * 8, 256);
+    size_t b = time_major_bytes(T, n, st, sn);
     b += align_up((size_t)T * 4, 256);   // nan_cnt
     int a = resolve_mbd_algo(algo, T, n, m, J);
     if (a == SD_MBD_RANK || algo == SD_MBD_AUTO)
@@ -180,13 +196,8 @@ static int mbd_counts_impl(const double *X, int64_t T, int64_t n, int64_t st, in
     if (m == 0) return SD_OK;
     hipStream_t s = (hipStream_t)stream;
     Carver cv(ws, ws_bytes);
-    const double *Y = X;
-    if (!is_time_major_dense(n, st, sn)) {
-        double *Yw = (double *)cv.take((size_t)T * n * 8);
-        if (!Yw) return fail(SD_ERR_WORKSPACE, "workspace too small for the time-major copy");
-        if ((rc = launch_to_time_major(X, T, n, st, sn, Yw, s))) return rc;
-        Y = Yw;
-    }
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
     int a = resolve_mbd_algo(algo, T, n, m, J);
     if (a == SD_MBD_RANK && mbd_rank_medium_supported(T, n, J)) {
         size_t need = mbd_rank_medium_workspace_bytes(T, n, J);
@@ -321,13 +332,8 @@ int sd_above_below(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn
     if (m == 0) return SD_OK;
     hipStream_t s = (hipStream_t)stream;
     Carver cv(ws, ws_bytes);
-    const double *Y = X;
-    if (!is_time_major_dense(n, st, sn)) {
-        double *Yw = (double *)cv.take((size_t)T * n * 8);
-        if (!Yw) return fail(SD_ERR_WORKSPACE, "workspace too small for the time-major copy");
-        if ((rc = launch_to_time_major(X, T, n, st, sn, Yw, s))) return rc;
-        Y = Yw;
-    }
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
     return launch_above_below(Y, T, n, targets, m, AB, s);
 }
 
@@ -336,9 +342,7 @@ int sd_above_below(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn
 // ---------------------------------------------------------------------------
 size_t sd_bd_strict_j_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int J) {
     if (T <= 0 || n <= 0) return 0;
-    size_t b = 0;
-    if (!is_time_major_dense(n, st, sn)) b += align_up((size_t)T * n * 8, 256);
-    return b + bd_strict_workspace_bytes(T, n, m, J) + 1024;
+    return time_major_bytes(T, n, st, sn) + bd_strict_workspace_bytes(T, n, m, J) + 1024;
 }
 
 size_t sd_bd_strict_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
@@ -347,16 +351,12 @@ size_t sd_bd_strict_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn
 
 size_t sd_bd_strict_nanfree_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
     if (T <= 0 || n <= 0) return 0;
-    size_t b = 0;
-    if (!is_time_major_dense(n, st, sn)) b += align_up((size_t)T * n * 8, 256);
-    return b + bd_strict_nanfree_workspace_bytes(T, n, m, 2) + 1024;
+    return time_major_bytes(T, n, st, sn) + bd_strict_nanfree_workspace_bytes(T, n, m, 2) + 1024;
 }
 
 size_t sd_bd_strict_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int J) {
     if (T <= 0 || n <= 0) return 0;
-    size_t b = 0;
-    if (!is_time_major_dense(n, st, sn)) b += align_up((size_t)T * n * 8, 256);
-    return b + bd_strict_min_workspace_bytes(T, n, m, J) + 1024;
+    return time_major_bytes(T, n, st, sn) + bd_strict_min_workspace_bytes(T, n, m, J) + 1024;
 }
 
 int sd_bd_strict_j_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn,
@@ -370,13 +370,8 @@ int sd_bd_strict_j_counts(const double *X, int64_t T, int64_t n, int64_t st, int
     if (m == 0) return SD_OK;
     hipStream_t s = (hipStream_t)stream;
     Carver cv(ws, ws_bytes);
-    const double *Y = X;
-    if (!is_time_major_dense(n, st, sn)) {
-        double *Yw = (double *)cv.take((size_t)T * n * 8);
-        if (!Yw) return fail(SD_ERR_WORKSPACE, "workspace too small for the time-major copy");
-        if ((rc = launch_to_time_major(X, T, n, st, sn, Yw, s))) return rc;
-        Y = Yw;
-    }
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
     size_t need = cv.rest();                                   // batches are sized to what the caller passed
     void *sws = cv.take(need);
     // 6 ... 8 timepoints, J = 2: NaN-free data is counted through state classes and takes 256 bytes (a flag); whether the data

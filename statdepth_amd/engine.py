@@ -21,9 +21,16 @@ def torch():
     return _torch
 
 
+def _lib():
+    """The C library, torch imported first: imported after the library has started the HIP runtime, torch finds no
+    device."""
+    torch()
+    return _native.require_device()
+
+
 def _device(device=None):
     t = torch()
-    _native.require_device()
+    _lib()
     if not t.cuda.is_available():
         raise RuntimeError("statdepth_amd: torch reports no ROCm device")
     if device is None:
@@ -126,19 +133,24 @@ def release_workspace():
         _ws_cache.clear()
 
 
-def _check_members(mem, tg, n):
-    """Block member / target indices go to the device as they are: refuse what would read outside the data set."""
-    if mem.size and (int(mem.min()) < -1 or int(mem.max()) >= n):
-        raise IndexError("block member index out of range (valid: -1 padding, 0 .. n-1)")
-    if tg is not None and len(tg) and (int(tg.min()) < 0 or int(tg.max()) >= n):
-        raise IndexError("block target index out of range")
+def _upload(A, ndim, dev):
+    """ndarray or tensor -> contiguous fp64 tensor with `ndim` dimensions on dev (as it is, when it already is one)."""
+    t = torch()
+    if not isinstance(A, t.Tensor):
+        A = t.from_numpy(np.ascontiguousarray(np.asarray(A, dtype=np.float64)))
+    if A.dim() != ndim:
+        raise ValueError(f"expected a {ndim}-D array")
+    return A.to(dev, t.float64).contiguous()
 
 
-def _targets_dev(targets, n, dev):
+# Index arrays go to the device as they are and the kernels read X through them: both helpers refuse, on the host and
+# before the upload, what would read outside the data set.
+def _targets_dev(targets, n, dev, dtype=np.int64):
+    """(tensor, m, pointer) of the target indices on dev; targets=None means all n (NULL pointer)."""
     t = torch()
     if targets is None:
         return None, n, 0
-    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int64))
+    tg = np.ascontiguousarray(np.asarray(targets, dtype=dtype))
     if tg.ndim != 1:
         raise ValueError("targets must be 1-D")
     if len(tg) and (tg.min() < 0 or tg.max() >= n):
@@ -147,43 +159,69 @@ def _targets_dev(targets, n, dev):
     return td, len(tg), td.data_ptr()
 
 
-def mbd_counts(X, targets=None, J=2, algo="auto", device=None, return_tensor=False):
-    """int64[m, J-1]: sum over t of contained j-bands per target (sd_mbd_counts)."""
+def _members_dev(members, dev, n, rows=None):
+    """(tensor, nb, bs) of the block members on dev: nb blocks of bs indices, -1 padded.  rows: the number of blocks
+    the caller has targets for."""
     t = torch()
-    lib = _native.require_device()
-    M = to_device_matrix(X, device)
+    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
+    if mem.ndim != 2:
+        raise ValueError("members must be 2-D (blocks x block size, -1 padded, target last)")
+    if rows is not None and mem.shape[0] != rows:
+        raise ValueError("members must have one row (block) per target")
+    if mem.size and (int(mem.min()) < -1 or int(mem.max()) >= n):
+        raise IndexError("block member index out of range (valid: -1 padding, 0 .. n-1)")
+    return t.from_numpy(mem).to(dev), mem.shape[0], mem.shape[1]
+
+
+def _sized(dev, nbytes):
+    """(buffer, bytes) for an entry point that asks for nbytes of workspace."""
+    return _workspace(dev, nbytes), int(nbytes)
+
+
+def _launch(dev, fn, out, *args, workspace=None, return_tensor=False):
+    """fn(*args, out, [ws, ws_bytes,] stream) on dev's current stream; returns out as an ndarray, or the tensor itself
+    with return_tensor.  Nothing is launched when out has no rows.  workspace: None, or a function of no arguments
+    returning (buffer, bytes), asked for only when there is something to launch."""
+    t = torch()
+    if out.shape[0]:
+        ws = workspace() if workspace is not None else None
+        tail = (ws[0].data_ptr(), ws[1]) if ws is not None else ()
+        with t.cuda.device(dev):
+            check(fn(*args, out.data_ptr(), *tail, _stream_ptr(dev)))
+    return out if return_tensor else out.cpu().numpy()
+
+
+def _mbd_counts(lib, fn, M, first, m, J, algo, return_tensor):
+    """sd_mbd_counts / sd_mbd_counts_range: `first` is the targets' pointer, or the first target of the block."""
+    t = torch()
     dev = M.device
-    td, m, tp = _targets_dev(targets, M.n, dev)
     a = ALGOS[algo] if isinstance(algo, str) else int(algo)
     out = t.empty((m, J - 1), dtype=t.int64, device=dev)
-    if m == 0:
-        return out if return_tensor else out.cpu().numpy()
-    wsb = lib.sd_mbd_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_mbd_counts(M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J, a,
-                            out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    if return_tensor:
-        return out
-    return out.cpu().numpy()
+    return _launch(dev, fn, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, first, m, J, a,
+                   workspace=lambda: _sized(dev, lib.sd_mbd_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)),
+                   return_tensor=return_tensor)
+
+
+def mbd_counts(X, targets=None, J=2, algo="auto", device=None, return_tensor=False):
+    """int64[m, J-1]: sum over t of contained j-bands per target (sd_mbd_counts)."""
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    td, m, tp = _targets_dev(targets, M.n, M.device)
+    return _mbd_counts(lib, lib.sd_mbd_counts, M, tp, m, J, algo, return_tensor)
 
 
 def mbd_counts_wide(X, targets=None, J=2, algo="auto", device=None):
     """object[m, J-1] of Python ints: the totals of mbd_counts beyond int64 (sd_mbd_counts_wide, two 64-bit limbs)."""
     t = torch()
-    lib = _native.require_device()
+    lib = _lib()
     M = to_device_matrix(X, device)
     dev = M.device
     td, m, tp = _targets_dev(targets, M.n, dev)
     a = ALGOS[algo] if isinstance(algo, str) else int(algo)
     out = t.zeros((m, J - 1, 2), dtype=t.int64, device=dev)
-    if m:
-        wsb = lib.sd_mbd_wide_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)
-        ws = _workspace(dev, wsb)
-        with t.cuda.device(dev):
-            check(lib.sd_mbd_counts_wide(M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J, a,
-                                         out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    limbs = out.cpu().numpy().astype(np.uint64)
+    limbs = _launch(dev, lib.sd_mbd_counts_wide, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J, a,
+                    workspace=lambda: _sized(dev, lib.sd_mbd_wide_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)))
+    limbs = limbs.astype(np.uint64)
     res = np.empty((m, J - 1), dtype=object)
     for q in range(m):
         for j in range(J - 1):
@@ -193,137 +231,83 @@ def mbd_counts_wide(X, targets=None, J=2, algo="auto", device=None):
 
 def mbd_counts_range(X, target_begin, m, J=2, algo="auto", device=None, return_tensor=False):
     """Totals for the contiguous target block [target_begin, target_begin + m) (sd_mbd_counts_range)."""
-    t = torch()
-    lib = _native.require_device()
+    lib = _lib()
     M = to_device_matrix(X, device)
-    dev = M.device
-    a = ALGOS[algo] if isinstance(algo, str) else int(algo)
-    out = t.empty((m, J - 1), dtype=t.int64, device=dev)
-    if m == 0:
-        return out if return_tensor else out.cpu().numpy()
-    wsb = lib.sd_mbd_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_mbd_counts_range(M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, int(target_begin), int(m), J, a,
-                                  out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    if return_tensor:
-        return out
-    return out.cpu().numpy()
+    return _mbd_counts(lib, lib.sd_mbd_counts_range, M, int(target_begin), int(m), J, algo, return_tensor)
+
+
+def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes):
+    """fn(X, T, n, Q, m, *extra, out, ws, ws_bytes, stream) for the m columns of Q (T x m) against the n columns of X.
+    out: int64 (m, *cols); ws_bytes(T, n, m): the workspace size."""
+    t = torch()
+    dev = _device(device)
+    Xd, Qd = _upload(X, 2, dev), _upload(Q, 2, dev)
+    T, n = Xd.shape
+    if Qd.shape[0] != T:
+        raise ValueError("Q must have the same number of timepoints as X")
+    m = Qd.shape[1]
+    out = t.empty((m, *cols), dtype=t.int64, device=dev)
+    return _launch(dev, fn, out, Xd.data_ptr(), T, n, Qd.data_ptr(), m, *extra,
+                   workspace=lambda: _sized(dev, ws_bytes(T, n, m)))
 
 
 def mbd_external_counts(X, Q, J=2, device=None):
     """int64[m, J-1]: band totals of the m columns of Q (T x m) w.r.t. the n columns of X (sd_mbd_external_counts)."""
-    t = torch()
-    lib = _native.require_device()
-    dev = _device(device)
-    Xd = t.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float64))).to(dev)
-    Qd = t.from_numpy(np.ascontiguousarray(np.asarray(Q, dtype=np.float64))).to(dev)
-    T, n = Xd.shape
-    if Qd.dim() != 2 or Qd.shape[0] != T:
-        raise ValueError("Q must have the same number of timepoints as X")
-    m = Qd.shape[1]
-    out = t.empty((m, J - 1), dtype=t.int64, device=dev)
-    wsb = int(lib.sd_mbd_external_workspace_bytes(T, n, m, J)) + 1024
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_mbd_external_counts(Xd.data_ptr(), T, n, Qd.data_ptr(), m, J, out.data_ptr(), ws.data_ptr(), wsb,
-                                     _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _external_curves(lib.sd_mbd_external_counts, (J - 1,), X, Q, device, J,
+                            ws_bytes=lambda T, n, m: lib.sd_mbd_external_workspace_bytes(T, n, m, J) + 1024)
 
 
 def bd_strict_external_counts(X, Q, device=None):
     """int64[m]: pairs of X's n columns whose band contains column q of Q (T x m) at every t (sd_bd_strict_external_counts)."""
+    lib = _lib()
+    return _external_curves(lib.sd_bd_strict_external_counts, (), X, Q, device,
+                            ws_bytes=lib.sd_bd_strict_external_workspace_bytes)
+
+
+def _subset_curves(fn, cols, X, members, targets, device, *extra, ws_bytes=None):
+    """fn(X, T, n, members, nb, bs, targets, *extra, out, [ws, ws_bytes,] stream) for targets[k] inside the curves
+    members[k].  out: int64 (nb, *cols); ws_bytes(T, nb, bs): the workspace size, where fn takes one."""
     t = torch()
-    lib = _native.require_device()
     dev = _device(device)
-    Xd = t.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float64))).to(dev)
-    Qd = t.from_numpy(np.ascontiguousarray(np.asarray(Q, dtype=np.float64))).to(dev)
+    Xd = _upload(X, 2, dev)
     T, n = Xd.shape
-    if Qd.dim() != 2 or Qd.shape[0] != T:
-        raise ValueError("Q must have the same number of timepoints as X")
-    m = Qd.shape[1]
-    out = t.empty((m,), dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    wsb = int(lib.sd_bd_strict_external_workspace_bytes(T, n, m))
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_bd_strict_external_counts(Xd.data_ptr(), T, n, Qd.data_ptr(), m, out.data_ptr(), ws.data_ptr(), wsb,
-                                           _stream_ptr(dev)))
-    return out.cpu().numpy()
+    td, m, tp = _targets_dev(targets, n, dev, np.int32)
+    md, nb, bs = _members_dev(members, dev, n, rows=m)
+    out = t.empty((nb, *cols), dtype=t.int64, device=dev)
+    workspace = (lambda: _sized(dev, ws_bytes(T, nb, bs))) if ws_bytes is not None else None
+    return _launch(dev, fn, out, Xd.data_ptr(), T, n, md.data_ptr(), nb, bs, tp, *extra, workspace=workspace)
 
 
 def mbd_subset_counts(X, members, targets, J=2, device=None):
     """int64[nb, J-1]: band totals of targets[k] inside the curves members[k] (-1 padded) -- sd_mbd_subset_counts."""
-    t = torch()
-    lib = _native.require_device()
-    dev = _device(device)
-    Xd = X if (isinstance(X, t.Tensor) and X.is_cuda) else t.from_numpy(
-        np.ascontiguousarray(np.asarray(X, dtype=np.float64))).to(dev)
-    Xd = Xd.contiguous()
-    T, n = Xd.shape
-    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
-    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32))
-    nb, bs = mem.shape
-    if len(tg) != nb:
-        raise ValueError("one target per block")
-    _check_members(mem, tg, n)
-    out = t.empty((nb, J - 1), dtype=t.int64, device=dev)
-    if nb == 0:
-        return out.cpu().numpy()
-    md, td = t.from_numpy(mem).to(dev), t.from_numpy(tg).to(dev)
-    with t.cuda.device(dev):
-        check(lib.sd_mbd_subset_counts(Xd.data_ptr(), T, n, md.data_ptr(), nb, bs, td.data_ptr(), J, out.data_ptr(),
-                                   _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _subset_curves(lib.sd_mbd_subset_counts, (J - 1,), X, members, targets, device, J)
 
 
 def bd_strict_subset_supported(T, bs):
     """Does a block of `bs` curves x T timepoints fit sd_bd_strict_subset_counts (masks in LDS)?"""
-    return bool(_native.require_device().sd_bd_strict_subset_supported(int(T), int(bs)))
+    return bool(_lib().sd_bd_strict_subset_supported(int(T), int(bs)))
 
 
 def bd_strict_subset_counts(X, members, targets, device=None):
     """int64[nb]: pairs of members[k]'s other curves (-1 padded) containing targets[k] at every t (sd_bd_strict_subset_counts)."""
-    t = torch()
-    lib = _native.require_device()
-    dev = _device(device)
-    Xd = X if (isinstance(X, t.Tensor) and X.is_cuda) else t.from_numpy(
-        np.ascontiguousarray(np.asarray(X, dtype=np.float64))).to(dev)
-    Xd = Xd.contiguous()
-    T, n = Xd.shape
-    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
-    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32))
-    nb, bs = mem.shape
-    if len(tg) != nb:
-        raise ValueError("one target per block")
-    _check_members(mem, tg, n)
-    out = t.empty((nb,), dtype=t.int64, device=dev)
-    if nb == 0:
-        return out.cpu().numpy()
-    md, td = t.from_numpy(mem).to(dev), t.from_numpy(tg).to(dev)
-    wsb = int(lib.sd_bd_strict_subset_workspace_bytes(T, nb, bs))
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_bd_strict_subset_counts(Xd.data_ptr(), T, n, md.data_ptr(), nb, bs, td.data_ptr(), out.data_ptr(),
-                                         ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _subset_curves(lib.sd_bd_strict_subset_counts, (), X, members, targets, device,
+                          ws_bytes=lib.sd_bd_strict_subset_workspace_bytes)
 
 
 def above_below(X, targets=None, device=None):
     """uint32 -> int64 [m, T, 2] strictly-above / strictly-below counts (sd_above_below)."""
     t = torch()
-    lib = _native.require_device()
+    lib = _lib()
     M = to_device_matrix(X, device)
     dev = M.device
     td, m, tp = _targets_dev(targets, M.n, dev)
     out = t.empty((m, M.T, 2), dtype=t.int32, device=dev)
-    wsb = M.T * M.n * 8 + 1024
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_above_below(M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, out.data_ptr(),
-                             ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    ab = _launch(dev, lib.sd_above_below, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m,
+                 workspace=lambda: _sized(dev, M.T * M.n * 8 + 1024))
+    return ab.astype(np.int64) & 0xFFFFFFFF
 
 
 def _strict_workspace(lib, dev, M, m, J, budget=None):
@@ -362,235 +346,144 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
     workspace_budget: upper bound in bytes for the scratch buffer (default: the recommended size, or what the device has
     free); never below the floor of one target per batch."""
     t = torch()
-    lib = _native.require_device()
+    lib = _lib()
     M = to_device_matrix(X, device)
     dev = M.device
     td, m, tp = _targets_dev(targets, M.n, dev)
     out = t.empty((m, J - 1), dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    ws, wsb = _strict_workspace(lib, dev, M, m, J, workspace_budget)
-    with t.cuda.device(dev):
-        check(lib.sd_bd_strict_j_counts(M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J,
-                                    out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy()
-
-
-def _points_dev(P, ndim, device):
-    t = torch()
-    dev = _device(device)
-    if isinstance(P, t.Tensor):
-        Pd = P.to(dev, t.float64).contiguous()
-    else:
-        A = np.ascontiguousarray(np.asarray(P, dtype=np.float64))
-        Pd = t.from_numpy(A).to(dev)
-    if Pd.dim() != ndim:
-        raise ValueError(f"expected a {ndim}-D array")
-    return Pd, dev
+    return _launch(dev, lib.sd_bd_strict_j_counts, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J,
+                   workspace=lambda: _strict_workspace(lib, dev, M, m, J, workspace_budget))
 
 
 def l1_depth(P, targets=None, device=None):
     t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
     n, d = Pd.shape
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_l1_depth(Pd.data_ptr(), n, d, tp, m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_l1_depth, out, Pd.data_ptr(), n, d, tp, m)
 
 
 def pointcloud_simplex_counts(P, targets=None, tol=1e-7, samples=None, seed=0, device=None):
     t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
     n, d = Pd.shape
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
     if samples is None:
-        with t.cuda.device(dev):
-            check(lib.sd_pointcloud_simplex_counts(Pd.data_ptr(), n, d, tp, m, tol, out.data_ptr(), _stream_ptr(dev)))
-    else:
-        with t.cuda.device(dev):
-            wsb = int(lib.sd_simplex_sampled_workspace_bytes(n, 0, d, int(samples)))
-            ws = _workspace(dev, wsb)
-            check(lib.sd_pointcloud_simplex_sampled(Pd.data_ptr(), n, d, tp, m, tol, int(samples), int(seed),
-                                                out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy()
+        return _launch(dev, lib.sd_pointcloud_simplex_counts, out, Pd.data_ptr(), n, d, tp, m, tol)
+    return _launch(dev, lib.sd_pointcloud_simplex_sampled, out, Pd.data_ptr(), n, d, tp, m, tol, int(samples), int(seed),
+                   workspace=lambda: _sized(dev, lib.sd_simplex_sampled_workspace_bytes(n, 0, d, int(samples))))
 
 
 def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, seed=0, device=None):
     """P: (n, T, d) curves."""
     t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 3, device)
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 3, dev)
     n, T, d = Pd.shape
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
     if samples is None:
-        with t.cuda.device(dev):
-            check(lib.sd_multi_simplex_counts(Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol,
-                                          out.data_ptr(), _stream_ptr(dev)))
-    else:
-        with t.cuda.device(dev):
-            wsb = int(lib.sd_simplex_sampled_workspace_bytes(n, T, d, int(samples)))
-            ws = _workspace(dev, wsb)
-            check(lib.sd_multi_simplex_sampled(Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol, int(samples),
-                                           int(seed), out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy()
+        return _launch(dev, lib.sd_multi_simplex_counts, out, Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol)
+    return _launch(dev, lib.sd_multi_simplex_sampled, out, Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol,
+                   int(samples), int(seed),
+                   workspace=lambda: _sized(dev, lib.sd_simplex_sampled_workspace_bytes(n, T, d, int(samples))))
 
 
-def _members_dev(members, dev, n):
+def _external_points(fn, dtype, P, Q, device, *extra):
+    """fn(P, n, d, Q, m, *extra, out, stream) for the m rows of Q against ALL n rows of P; out: (m,) of dtype."""
     t = torch()
-    mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
-    if mem.ndim != 2:
-        raise ValueError("members must be 2-D (blocks x block size, -1 padded, target last)")
-    _check_members(mem, None, n)
-    return t.from_numpy(mem).to(dev), mem.shape[0], mem.shape[1]
-
-
-def pointcloud_simplex_external_counts(P, Q, tol=1e-7, device=None):
-    """int64[m]: (d+1)-subsets of ALL rows of P whose simplex contains the external point Q[q]."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    Qd, _ = _points_dev(Q, 2, dev)
+    dev = _device(device)
+    Pd, Qd = _upload(P, 2, dev), _upload(Q, 2, dev)
     n, d = Pd.shape
     if Qd.shape[1] != d:
         raise ValueError("Q must have the same number of coordinates as P")
     m = Qd.shape[0]
-    out = t.empty(m, dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_pointcloud_simplex_external_counts(Pd.data_ptr(), n, d, Qd.data_ptr(), m, tol, out.data_ptr(),
-                                                        _stream_ptr(dev)))
-    return out.cpu().numpy()
+    out = t.empty(m, dtype=dtype, device=dev)
+    return _launch(dev, fn, out, Pd.data_ptr(), n, d, Qd.data_ptr(), m, *extra)
+
+
+def _subset_points(fn, dtype, P, members, device, *extra):
+    """fn(P, n, d, members, nb, bs, *extra, out, stream) per block (rows of `members`, -1 padded, others first, target
+    last); out: (nb,) of dtype."""
+    t = torch()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
+    n, d = Pd.shape
+    md, nb, bs = _members_dev(members, dev, n)
+    out = t.empty(nb, dtype=dtype, device=dev)
+    return _launch(dev, fn, out, Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, *extra)
+
+
+def pointcloud_simplex_external_counts(P, Q, tol=1e-7, device=None):
+    """int64[m]: (d+1)-subsets of ALL rows of P whose simplex contains the external point Q[q]."""
+    lib = _lib()
+    return _external_points(lib.sd_pointcloud_simplex_external_counts, torch().int64, P, Q, device, tol)
 
 
 def pointcloud_simplex_subset_counts(P, members, tol=1e-7, device=None):
     """int64[nb]: per block (rows of `members`, -1 padded, others first, target last) the (d+1)-subsets of the
     block's others whose simplex contains its target."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    n, d = Pd.shape
-    md, nb, bs = _members_dev(members, dev, n)
-    out = t.empty(nb, dtype=t.int64, device=dev)
-    if nb == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_pointcloud_simplex_subset_counts(Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, tol, out.data_ptr(),
-                                                      _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _subset_points(lib.sd_pointcloud_simplex_subset_counts, torch().int64, P, members, device, tol)
 
 
 def l1_external_depth(P, Q, device=None):
     """float64[m]: L1 depth of the external point Q[q] inside P u {Q[q]}."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    Qd, _ = _points_dev(Q, 2, dev)
-    n, d = Pd.shape
-    if Qd.shape[1] != d:
-        raise ValueError("Q must have the same number of coordinates as P")
-    m = Qd.shape[0]
-    out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_l1_external_depth(Pd.data_ptr(), n, d, Qd.data_ptr(), m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _external_points(lib.sd_l1_external_depth, torch().float64, P, Q, device)
 
 
 def l1_subset_depth(P, members, device=None):
     """float64[nb]: L1 depth of each block's target (last row of the block) inside the block."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    n, d = Pd.shape
-    md, nb, bs = _members_dev(members, dev, n)
-    out = t.empty(nb, dtype=t.float64, device=dev)
-    if nb == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_l1_subset_depth(Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _subset_points(lib.sd_l1_subset_depth, torch().float64, P, members, device)
 
 
 def oja_volume_sums(P, targets=None, device=None):
     """float64[m]: sum over d-subsets S of the other rows of vol(conv(S u {P[target]})) (sd_oja_volume_sums)."""
     t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
     n, d = Pd.shape
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_oja_volume_sums(Pd.data_ptr(), n, d, tp, m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_oja_volume_sums, out, Pd.data_ptr(), n, d, tp, m)
 
 
 def oja_external_volume_sums(P, Q, device=None):
     """float64[m]: sum over d-subsets S of ALL rows of P of vol(conv(S u {Q[q]})) (sd_oja_external_volume_sums)."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    Qd, _ = _points_dev(Q, 2, dev)
-    n, d = Pd.shape
-    if Qd.shape[1] != d:
-        raise ValueError("Q must have the same number of coordinates as P")
-    m = Qd.shape[0]
-    out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_oja_external_volume_sums(Pd.data_ptr(), n, d, Qd.data_ptr(), m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _external_points(lib.sd_oja_external_volume_sums, torch().float64, P, Q, device)
 
 
 def oja_subset_volume_sums(P, members, device=None):
     """float64[nb]: per block (rows of `members`, -1 padded, others first, target last) the sum over d-subsets S of
     the block's others of vol(conv(S u {target}))."""
-    t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 2, device)
-    n, d = Pd.shape
-    md, nb, bs = _members_dev(members, dev, n)
-    out = t.empty(nb, dtype=t.float64, device=dev)
-    if nb == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_oja_subset_volume_sums(Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    lib = _lib()
+    return _subset_points(lib.sd_oja_subset_volume_sums, torch().float64, P, members, device)
 
 
 def prob_normal_sums(mu, sigma, targets=None, device=None):
     """float64[m]: the reference's normal-depth pair sums, unnormalised (sd_prob_normal_sums): for k = targets[q], the sum
     over pairs i < j of the other distributions of int (Phi_i - Phi_k Phi_j) phi_k.  depth = sums / C(n, 2)."""
     t = torch()
-    lib = _native.require_device()
-    mud, dev = _points_dev(mu, 1, device)
-    sgd, _ = _points_dev(sigma, 1, dev)
+    lib = _lib()
+    dev = _device(device)
+    mud, sgd = _upload(mu, 1, dev), _upload(sigma, 1, dev)
     n = mud.shape[0]
     if sgd.shape[0] != n:
         raise ValueError("mu and sigma must have the same length")
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_prob_normal_sums(mud.data_ptr(), sgd.data_ptr(), n, tp, m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_prob_normal_sums, out, mud.data_ptr(), sgd.data_ptr(), n, tp, m)
 
 
 def prob_poisson_sums(lam, lim, targets=None, device=None):
@@ -598,16 +491,13 @@ def prob_poisson_sums(lam, lim, targets=None, device=None):
     timepoints, columns curves); for f = targets[q], the sum over rows t, z = 1 .. lim - 1 and column pairs i < j other
     than f of P(X_f = z) P(X_i <= z) P(X_j >= z).  depth = sums / C(T, 2)."""
     t = torch()
-    lib = _native.require_device()
-    Ld, dev = _points_dev(lam, 2, device)
+    lib = _lib()
+    dev = _device(device)
+    Ld = _upload(lam, 2, dev)
     T, n = Ld.shape
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_prob_poisson_sums(Ld.data_ptr(), T, n, int(lim), tp, m, out.data_ptr(), _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_prob_poisson_sums, out, Ld.data_ptr(), T, n, int(lim), tp, m)
 
 
 def prob_band_sums(mu, var, relax, targets=None, members=None, device=None):
@@ -617,54 +507,32 @@ def prob_band_sums(mu, var, relax, targets=None, members=None, device=None):
     the sum over pairs of sum_t p (relax) or prod_t p, p = P(min(X_j, X_k) <= X_i <= max(X_j, X_k)).
     depth = sums / T / C(n', 2) (relax) or sums / C(n', 2), n' counting the target."""
     t = torch()
-    mu_h = np.ascontiguousarray(np.asarray(mu, dtype=np.float64))
-    var_h = np.ascontiguousarray(np.asarray(var, dtype=np.float64))
-    if mu_h.ndim != 2 or var_h.shape != mu_h.shape:
+    shape = np.shape(mu)
+    if len(shape) != 2 or tuple(np.shape(var)) != tuple(shape):
         raise ValueError("mu and var must be T x n arrays of the same shape")
-    T, n = mu_h.shape
-    if targets is not None:
-        tg = np.asarray(targets, dtype=np.int64)
-        if tg.ndim != 1:
-            raise ValueError("targets must be 1-D")
-        if len(tg) and (tg.min() < 0 or tg.max() >= n):
-            raise IndexError("target index out of range")
-    m = n if targets is None else len(targets)
-    mem = None
-    if members is not None:
-        mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
-        if mem.ndim != 2 or mem.shape[0] != m:
-            raise ValueError("members must be m x bs, one row per target")
-        _check_members(mem, None, n)
-    lib = _native.require_device()
+    T, n = shape
+    lib = _lib()
     dev = _device(device)
-    mud, vd = t.from_numpy(mu_h).to(dev), t.from_numpy(var_h).to(dev)
+    # the indices first: out-of-range ones are refused before mu and var are uploaded
     td, m, tp = _targets_dev(targets, n, dev)
-    md = t.from_numpy(mem).to(dev) if mem is not None else None
+    md, _, bs = _members_dev(members, dev, n, rows=m) if members is not None else (None, 0, 0)
+    mud, vd = _upload(mu, 2, dev), _upload(var, 2, dev)
     out = t.empty(m, dtype=t.float64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    with t.cuda.device(dev):
-        check(lib.sd_prob_band_sums(mud.data_ptr(), vd.data_ptr(), T, n, tp, m, md.data_ptr() if md is not None else None,
-                                    mem.shape[1] if mem is not None else 0, int(bool(relax)), out.data_ptr(),
-                                    _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_prob_band_sums, out, mud.data_ptr(), vd.data_ptr(), T, n, tp, m,
+                   md.data_ptr() if md is not None else None, bs, int(bool(relax)))
 
 
 def multi_band_counts(P, targets=None, device=None):
     """int64[m]: sum_t #{pairs of other curves whose componentwise band contains the target at t} (sd_multi_band_counts).
     P: (n, T, d) curves, NaN-free."""
     t = torch()
-    lib = _native.require_device()
-    Pd, dev = _points_dev(P, 3, device)
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 3, dev)
     n, T, d = Pd.shape
     if bool(t.isnan(Pd).any()):
         raise ValueError("componentwise band containment ('r2_enum') does not accept NaN values")
     td, m, tp = _targets_dev(targets, n, dev)
     out = t.empty(m, dtype=t.int64, device=dev)
-    if m == 0:
-        return out.cpu().numpy()
-    wsb = int(lib.sd_multi_band_workspace_bytes(n, T, d))
-    ws = _workspace(dev, wsb)
-    with t.cuda.device(dev):
-        check(lib.sd_multi_band_counts(Pd.data_ptr(), n, T, d, tp, m, out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr(dev)))
-    return out.cpu().numpy()
+    return _launch(dev, lib.sd_multi_band_counts, out, Pd.data_ptr(), n, T, d, tp, m,
+                   workspace=lambda: _sized(dev, lib.sd_multi_band_workspace_bytes(n, T, d)))
