@@ -143,7 +143,6 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
                                                          const unsigned char *__restrict__ rowflag = nullptr,
                                                          const u32 *__restrict__ gate = nullptr, u32 epoch = 0,
                                                          u64 *__restrict__ out_tot = nullptr, int Gsum = 0,
-                                                         const u32 *__restrict__ listbuf = nullptr,
                                                          u32 *__restrict__ fblocks = nullptr, u32 *__restrict__ done = nullptr,
                                                          int kspin = 1) {
     // J == 0: image mode (J >= 4 on the host side): no fold, the pairs (B | A << 16) of every (row, curve) go to the
@@ -179,8 +178,11 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
         {   // (1) finalize: totals of this workgroup's slice of curves = sum of the Gsum partial blocks (16-byte loads)
             const u32 *P = reinterpret_cast<const u32 *>(partial);
             u64 *redl = reinterpret_cast<u64 *>(Sm);                  // [64 slices][16 quads][4]
-            const int nst = (n + 3) & ~3, nq = nst >> 2;              // the blocks lie nst words apart: 16-byte aligned whatever n
-            const int q0 = (int)((i64)blockIdx.x * nq / gridDim.x), q1 = (int)((i64)(blockIdx.x + 1) * nq / gridDim.x);
+            // the blocks lie nst words apart, on 128-byte lines whatever n; a workgroup's slice is whole lines (8 quads), so that no
+            // line is fetched by two workgroups (a slice of 10 quads straddled three lines, shared with the neighbours)
+            const int nst = (n + 31) & ~31, nq = (n + 3) >> 2, nl = (nq + 7) >> 3;
+            const int l0 = (int)((i64)blockIdx.x * nl / gridDim.x), l1 = (int)((i64)(blockIdx.x + 1) * nl / gridDim.x);
+            const int q0 = 8 * l0 < nq ? 8 * l0 : nq, q1 = 8 * l1 < nq ? 8 * l1 : nq;
             const int qx = t0 & 15, y = t0 >> 4;
             for (int qb = q0; qb < q1; qb += 16) {
                 u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;
@@ -202,48 +204,6 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
                     atomicAdd(&out_tot[4 * (qb + (t0 >> 2)) + (t0 & 3)], tot);
                 }
                 __syncthreads();
-            }
-        }
-        {   // (1b) the keys rank_bucket32_kernel set aside (equal 32-bit images): their rows are NaN-free and finite, a group
-            //      of equal images is complete in its workgroup's list, so B and A follow from the list and the doubles.
-            //      Both lists of this workgroup at once, 64 lanes each: every lane fetches its own key's value (ONE round trip
-            //      to memory; a loop with a load per partner was a chain of them), the groups meet in LDS.
-            constexpr int LCAP = 64, LW = 1 + 2 * LCAP;               // R32_LCAP, R32_LIST_WORDS (mbd_rank_bucket32.hip)
-            double *xs = reinterpret_cast<double *>(Sm);              // [2][LCAP] values, then keys and (B0 | E0 << 16)
-            u32 *ks = reinterpret_cast<u32 *>(xs + 2 * LCAP), *bs_ = ks + 2 * LCAP;
-            const int k = t0 >> 6, i = t0 & 63;
-            for (int w0 = blockIdx.x; w0 < Gsum; w0 += 2 * (int)gridDim.x) {   // one trip: Gsum <= 2 gridDim on the host's grids
-                u32 L = 0, key = 0, be = 0;
-                double xv = 0.0;
-                if (t0 < 2 * LCAP) {
-                    const int w = w0 + k * (int)gridDim.x;
-                    if (w < Gsum) {
-                        const u32 *lb = listbuf + (size_t)w * LW;
-                        L = lb[0];
-                        if (L > (u32)LCAP) L = 0;
-                        if ((u32)i < L) {
-                            key = lb[1 + i];
-                            be = lb[1 + LCAP + i];
-                            xv = Y[(row0 + (i64)w + (i64)(key >> 14) * Gsum) * n + (key & 0x3FFFu)];
-                        }
-                    }
-                    xs[t0] = xv; ks[t0] = key; bs_[t0] = be;
-                }
-                __syncthreads();
-                if (t0 < 2 * LCAP && (u32)i < L) {
-                    u32 B = be & 0xFFFFu, A = (u32)n - B - (be >> 16);
-                    for (u32 j = 0; j < L; ++j) {
-                        const u32 kj = ks[k * LCAP + j];
-                        if (j != (u32)i && (kj >> 14) == (key >> 14) && (bs_[k * LCAP + j] & 0xFFFFu) == (be & 0xFFFFu)) {
-                            const double xj = xs[k * LCAP + j];
-                            B += (xj < xv) ? 1u : 0u;
-                            A += (xj > xv) ? 1u : 0u;
-                        }
-                    }
-                    const u64 v = (u64)n - 1;
-                    atomicAdd(&out_tot[key & 0x3FFFu], (v * (v - 1) - (u64)A * (A - 1) - (u64)B * (B - 1)) >> 1);
-                }
-                __syncthreads();                                      // the next trip, and Sm is reused below
             }
         }
         if (*gate != epoch) return;                                   // (2) nothing was flagged
@@ -1103,7 +1063,7 @@ static int launch_bucket_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *pa
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
     SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kf, dim3(G), dim3(NT), lds, s, Y, n, row0, rows, partial, p32, nnan_img, (const unsigned char *)nullptr,
-                       (const u32 *)nullptr, 0u, (u64 *)nullptr, 0, (const u32 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, 1);
+                       (const u32 *)nullptr, 0u, (u64 *)nullptr, 0, (u32 *)nullptr, (u32 *)nullptr, 1);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
@@ -1111,7 +1071,7 @@ static int launch_bucket_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *pa
 // second launch behind rank_bucket32_kernel: the rows it flagged, totals added to its partial blocks
 template <int E, int LNB>
 static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *partial, int G, const unsigned char *rowflag,
-                                 const u32 *gate, u32 epoch, u64 *out, int Gsum, const u32 *listbuf, u32 *fblocks, u32 *done,
+                                 const u32 *gate, u32 epoch, u64 *out, int Gsum, u32 *fblocks, u32 *done,
                                  hipStream_t s) {
     using C = RBCfg<1024, E, LNB, 3>;
     auto kf = rank_bucket_kernel<1024, E, LNB, 2, RB_CAP, 3, true, true>;
@@ -1145,8 +1105,8 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
         if (masked) kspin = 1;
         if (kspin < 1) kspin = 1;
     }
-    hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, partial, 2, (u32 *)nullptr, rowflag, gate, epoch, out, Gsum, listbuf,
-                       fblocks, done, kspin);
+    hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, partial, 2, (u32 *)nullptr, rowflag, gate, epoch, out, Gsum, fblocks,
+                       done, kspin);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
@@ -1200,18 +1160,17 @@ int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB
 bool rank_bucket32_supported(i64 n, i64 rows, int cus);
 size_t rank_bucket32_extra_bytes(i64 rows);
 int launch_rank_bucket32(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
-                         u64 *out_zero, u32 *listbuf, int G, hipStream_t s);
-size_t rank_bucket32_list_bytes(int G);
+                         u64 *out_zero, int G, hipStream_t s);
 u32 rank_bucket32_epoch();
 
 // J = 2, 4096 < n <= 11264, every curve a target: rank_bucket32_kernel (two workgroups per CU; zeroes out when `first`) + the
 // fp64 kernel's SEL form (sums the partial blocks into out; ranks the rows the first kernel flagged).  Two launches.  The
 // flags and the gate word sit behind the 2 * cus u32 partial blocks, inside the space sized for u64 blocks.
-// what the two-launch path carves out of the partial-block space: its u32 blocks, row flags, gate words, lists, the second
+// what the two-launch path carves out of the partial-block space: its u32 blocks, row flags, gate words, the second
 // launch's blocks -- and, last, n u64 totals of ALL curves for calls that ask for a subset of the targets
 static size_t two_level_used_bytes(i64 n, i64 rows) {
-    const size_t nst = (size_t)((n + 3) & ~3);
-    return (size_t)2 * rb_cus() * nst * 4 + align_up((size_t)rows, 64) + 64 + 256 + rank_bucket32_list_bytes(2 * rb_cus()) + 256 +
+    const size_t pst = (size_t)((n + 31) & ~31), nst = (size_t)((n + 3) & ~3);
+    return (size_t)2 * rb_cus() * pst * 4 + align_up((size_t)rows, 64) + 64 + 256 +
            (size_t)rb_cus() * nst * 4 + 256;
 }
 bool rank_bucket_two_level_supported(i64 n, i64 rows) {
@@ -1239,19 +1198,18 @@ int launch_rank_bucket_two_level(const double *Y, i64 n, i64 row0, i64 rows, u64
     const int cus = rb_cus();
     const int G = (int)(rows < 2 * cus ? rows : 2 * cus);
     u32 *P32 = reinterpret_cast<u32 *>(partial);
-    unsigned char *rowflag = reinterpret_cast<unsigned char *>(P32 + (size_t)2 * cus * ((n + 3) & ~3));
+    unsigned char *rowflag = reinterpret_cast<unsigned char *>(P32 + (size_t)2 * cus * ((n + 31) & ~31));   // blocks of whole lines
     u32 *gate = reinterpret_cast<u32 *>(rowflag + align_up((size_t)rows, 64));
-    u32 *listbuf = gate + 16;                                         // a list of set-aside keys per workgroup of the first launch
-    // the second launch's own blocks (totals of the flagged rows), 16-byte aligned, behind the lists; gate[2]: arrival counter
-    u32 *fblocks = reinterpret_cast<u32 *>(align_up((size_t)(listbuf) + rank_bucket32_list_bytes(G), 256));
+    // the second launch's own blocks (totals of the flagged rows), 16-byte aligned, behind the gate words; gate[2]: arrival counter
+    u32 *fblocks = reinterpret_cast<u32 *>(align_up((size_t)(gate + 16), 256));
     const u32 epoch = rank_bucket32_epoch();
-    int rc = launch_rank_bucket32(Y, n, row0, rows, P32, rowflag, gate, epoch, first ? out : nullptr, listbuf, G, s);
+    int rc = launch_rank_bucket32(Y, n, row0, rows, P32, rowflag, gate, epoch, first ? out : nullptr, G, s);
     if (rc) return rc;
     const int G2 = G < cus ? G : cus;
-#define RB_SEL(E_) case E_: return launch_bucket_sel_cfg<E_, 14>(Y, n, row0, rows, partial, G2, rowflag, gate, epoch, out, G, listbuf, fblocks, gate + 2, s);
+#define RB_SEL(E_) case E_: return launch_bucket_sel_cfg<E_, 14>(Y, n, row0, rows, partial, G2, rowflag, gate, epoch, out, G, fblocks, gate + 2, s);
     switch ((int)((n + 1023) / 1024)) {
         RB_SEL(3) RB_SEL(4) RB_SEL(5) RB_SEL(6) RB_SEL(7) RB_SEL(8) RB_SEL(9) RB_SEL(11)
-        case 10: return launch_bucket_sel_cfg<10, 15>(Y, n, row0, rows, partial, G2, rowflag, gate, epoch, out, G, listbuf, fblocks, gate + 2, s);
+        case 10: return launch_bucket_sel_cfg<10, 15>(Y, n, row0, rows, partial, G2, rowflag, gate, epoch, out, G, fblocks, gate + 2, s);
     }
 #undef RB_SEL
     return fail(SD_ERR_UNSUPPORTED, "two-level bucket path covers 4096 < n <= 11264");

@@ -13,7 +13,7 @@
 // row apart in phase, share a CU: one's compares run under the other's LDS traffic.  Order is decided by the images
 // wherever they differ; keys whose images coincide (two values within range / 2^31, or equal values) are NOT ranked
 // here: they are set aside with what the images do say (B0 = keys with a smaller image, E0 = keys with the same image)
-// and settled exactly, in fp64, among themselves by the second launch (a group of equal images is complete in the list).
+// and settled exactly, in fp64, among themselves at the end of the workgroup (a group of equal images is complete in the list).
 // Tie-heavy rows (quantised data: a bucket of 16 keys or more whose keys share an image) are ranked in closed form when
 // every bucket of the row provably holds one value.
 // Rows this kernel does not take -- a NaN, an infinity, a bucket of 64 keys or more, ties mixed with near-ties, and
@@ -21,7 +21,8 @@
 // SEL form in a second launch that returns at once when nothing was flagged (gate word = the call's epoch).
 //
 // Per-curve totals stay in registers (u32: the host checked that a workgroup's total fits); one partial block per
-// workgroup goes to HBM and the second launch (rank_bucket_kernel's SEL form) sums the blocks into the totals.  HBM traffic: the matrix once + the partial blocks.
+// workgroup goes to HBM, stored non-temporally, and the second launch (rank_bucket_kernel's SEL form) sums the blocks into the
+// totals.  HBM traffic: the matrix once + the partial blocks.
 #include <atomic>
 
 #include "sd_common.h"
@@ -35,7 +36,6 @@ constexpr int R32_MIN_N = 3072;                 // the two-launch path is used a
 constexpr int R32_LNB = 14;                     // 16 384 buckets: histogram 32 KiB
 constexpr int R32_NT = 512, R32_NW = 8;
 constexpr int R32_LCAP = 64;                    // set-aside keys per workgroup before it hands all its rows over
-constexpr int R32_LIST_WORDS = 1 + 2 * R32_LCAP;   // a workgroup's list in the workspace: count, keys, (B0 | E0 << 16)
 constexpr int R32_PAD = 12;                     // sentinel images behind the keys (two quads past the last partial quad)
 constexpr u32 R32_TB = 1024;                    // buckets of each tail
 constexpr int R32_TSH = 30;                     // tail code = (bits(d + c) - bits(c)) >> 30: 2^22 codes = 32 buckets per octave
@@ -55,6 +55,7 @@ struct R32Cfg {
     static constexpr size_t HDR = 8 * NW * 8 + NW * 4 + 32 + (size_t)R32_LCAP * 8;
     static_assert(HDR % 16 == 0, "the histogram starts on a 16-byte boundary");
     static __host__ __device__ constexpr int al4(int n) { return (n + 3) & ~3; }
+    static __host__ __device__ constexpr int pstride(int n) { return (n + 31) & ~31; }   // partial blocks: whole 128-byte lines
     static __host__ __device__ constexpr int dummy_pos(int n) { return al4(n) + R32_PAD; }
     static __host__ __device__ constexpr size_t lds_bytes(int n) { return HDR + (size_t)(NB / 2 + 4) * 4 + (size_t)(dummy_pos(n) + 4) * 4; }
 };
@@ -62,8 +63,7 @@ struct R32Cfg {
 template <int E, int LNB>
 __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows,
                                                                  u32 *__restrict__ partial, unsigned char *__restrict__ rowflag,
-                                                                 u32 *__restrict__ gate, u32 epoch, u64 *__restrict__ out_zero,
-                                                                 u32 *__restrict__ listbuf) {
+                                                                 u32 *__restrict__ gate, u32 epoch, u64 *__restrict__ out_zero) {
     using C = R32Cfg<E, LNB>;
     constexpr int NT = C::NT, NW = C::NW, NB = C::NB, QW = C::QW, SH = C::SH;
     constexpr u32 C0 = C::C0, C1 = C::C1, NANIMG = C::NANIMG;
@@ -583,6 +583,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     }
     t = t0;
     __syncthreads();
+    const u32 L = __builtin_amdgcn_readfirstlane(handover ? 0u : misc[0]);   // set-aside keys (an overflowing list hands over)
     if (handover) {                                                   // every row of this workgroup, ranked or not
         for (i64 rr = blockIdx.x + (i64)t * gridDim.x; rr < rows; rr += (i64)NT * gridDim.x) rowflag[rr] = 1;
         nbad = 1;
@@ -592,17 +593,38 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         for (i64 rr = r + (i64)t * gridDim.x; rr < rows; rr += (i64)NT * gridDim.x) rowflag[rr] = 1;   // rows left behind
     }
     if (t == 0 && nbad) *gate = epoch;
-    u32 *P = partial + (size_t)blockIdx.x * C::al4(n);               // blocks on 16-byte boundaries whatever n
+    // ---- keys whose images coincide, settled among themselves in fp64 (their rows are NaN-free and finite, a group of equal
+    //      images is complete in the list): wave 0, one listed key per lane, fetches the doubles (ONE round trip, issued ahead
+    //      of the block's stores), compares within the groups of equal (row, B0) through readlane and adds each key's
+    //      closed-form term to its curve's entry of the block, behind the owners' stores ----
+    u32 key = 0, be = 0;
+    double xv = 0.0;
+    if ((u32)t < L) {
+        key = lkey[t];
+        be = lbe[t];
+        xv = Y[(row0 + (i64)blockIdx.x + (i64)(key >> 14) * gridDim.x) * n + (key & 0x3FFFu)];
+    }
+    // non-temporal: the blocks stream out as the workgroups end instead of sitting dirty in L2 at the kernel boundary
+    u32 *P = partial + (size_t)blockIdx.x * C::pstride(n);           // blocks on 128-byte lines whatever n
 #pragma unroll
     for (int e = 0; e < E; ++e)
-        if (e < E - 2 || t + e * NT < n) P[t + e * NT] = acc[e];
-    // ---- keys whose images coincide go to the second launch, which settles them among themselves in fp64 (their rows are
-    //      NaN-free and finite): count, then (row index << 14 | curve), then (B0 | E0 << 16) per key ----
-    {
-        const u32 L = handover ? 0u : misc[0];
-        u32 *lb = listbuf + (size_t)blockIdx.x * R32_LIST_WORDS;
-        if (t == 0) lb[0] = L;
-        if ((u32)t < L) { lb[1 + t] = lkey[t]; lb[1 + R32_LCAP + t] = lbe[t]; }
+        if (e < E - 2 || t + e * NT < n) __builtin_nontemporal_store(acc[e], &P[t + e * NT]);
+    if (L) {                                                          // block-uniform
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the owners' stores have reached L2 (the barrier alone
+        __syncthreads();                                              // orders them only inside the CU) before the atomics
+        if (t < 64) {                                                 // L <= R32_LCAP = 64: all of them in wave 0
+            u32 B = be & 0xFFFFu, A = (u32)n - B - (be >> 16);
+            for (u32 j = 0; j < L; ++j) {
+                const u32 kj = rb_readlane(key, (int)j), bj = rb_readlane(be, (int)j);
+                const double xj = rb_readlane_f64(xv, (int)j);
+                if (j != (u32)t && (kj >> 14) == (key >> 14) && (bj & 0xFFFFu) == (be & 0xFFFFu)) {
+                    B += (xj < xv) ? 1u : 0u;                         // -0 == +0: equal values count on neither side
+                    A += (xj > xv) ? 1u : 0u;
+                }
+            }
+            // the same curve may be listed in several rows; the term replaces the product the fold took back
+            if ((u32)t < L) atomicAdd(&P[key & 0x3FFFu], (nm1 * (nm1 - 1u) - A * (A - 1u) - B * (B - 1u)) >> 1);
+        }
     }
 }
 
@@ -619,33 +641,31 @@ size_t rank_bucket32_extra_bytes(i64 rows) { return align_up((size_t)rows + 64, 
 
 template <int E>
 static int launch32_cfg(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
-                        u64 *out_zero, u32 *listbuf, int G, hipStream_t s) {
+                        u64 *out_zero, int G, hipStream_t s) {
     using C = R32Cfg<E, R32_LNB>;
     auto kf = rank_bucket32_kernel<E, R32_LNB>;
     const size_t lds = C::lds_bytes((int)n);
     if (lds > 81920) return fail(SD_ERR_UNSUPPORTED, "bucket32 kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
     SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kf, dim3(G), dim3(R32_NT), lds, s, Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf);
+    hipLaunchKernelGGL(kf, dim3(G), dim3(R32_NT), lds, s, Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
 
 // rows [row0, row0 + rows): u32 partial totals of every curve per workgroup (G blocks of n), flags of the rows left to the
 // fp64 kernel in rowflag[rows], *gate = epoch when there is any
-size_t rank_bucket32_list_bytes(int G) { return (size_t)G * R32_LIST_WORDS * 4; }
-
 int launch_rank_bucket32(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
-                         u64 *out_zero, u32 *listbuf, int G, hipStream_t s) {
+                         u64 *out_zero, int G, hipStream_t s) {
     switch ((int)((n + 1023) / 1024)) {
-        case 3: return launch32_cfg<6>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 4: return launch32_cfg<8>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 5: return launch32_cfg<10>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 6: return launch32_cfg<12>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 7: return launch32_cfg<14>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 8: return launch32_cfg<16>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 9: return launch32_cfg<18>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 10: return launch32_cfg<20>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
-        case 11: return launch32_cfg<22>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, listbuf, G, s);
+        case 3: return launch32_cfg<6>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 4: return launch32_cfg<8>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 5: return launch32_cfg<10>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 6: return launch32_cfg<12>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 7: return launch32_cfg<14>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 8: return launch32_cfg<16>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 9: return launch32_cfg<18>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 10: return launch32_cfg<20>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
+        case 11: return launch32_cfg<22>(Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero, G, s);
     }
     return fail(SD_ERR_UNSUPPORTED, "bucket32 kernel covers 3072 < n <= 11264");
 }
