@@ -1,18 +1,20 @@
-// mbd_rank_bucket32.hip -- K1+K2 bucket ranking on 32-bit key images, TWO workgroups per CU (J = 2, 3072 < n <= 11264).
+// mbd_rank_bucket32.hip -- K1+K2 bucket ranking on bucket-local key images, TWO workgroups per CU (J = 2, 3072 < n <= 11264).
 //
 // Same integers as rank_bucket_kernel (mbd_rank_bucket.hip), the pairwise kernel and the reference's enumeration
 // (_functional.py:246-251, _containment.py:75-77).  The fp64 kernel keeps one row per CU in LDS and its five
 // barrier-separated phases leave the VALU idle while the LDS works and the other way round (SQ counters: VALU busy 57 %,
-// LDS busy 37 %, together the kernel's whole time).  Here a row's keys live in LDS as 31-bit images q(x), non-decreasing in x
+// LDS busy 37 %, together the kernel's whole time).  Here a key is placed by a 31-bit image q(x), non-decreasing in x
 // whatever the data and whatever the map's constants (round 4: a THREE-PIECE map -- a linear core of 14 336 buckets over the
 // row's range, clipped to a central bracket taken from a sample of 1 024 keys when the range is much wider than the bulk
 // (heavy tails, outlying curves), and below and above the core 1 024 buckets each for a float-like code of the distance to
 // the core's edge, bits(d + c) - bits(c) with c = core width / 448: linear with the core's slope next to the edge, halving
-// per octave, 32 octaves; every piece is monotone and the pieces are ordered),
-// so that a row of up to 11 264 curves + its 16 384-bucket histogram take 77 KiB and two 512-thread workgroups, half a
-// row apart in phase, share a CU: one's compares run under the other's LDS traffic.  Order is decided by the images
-// wherever they differ; keys whose images coincide (two values within range / 2^31, or equal values) are NOT ranked
-// here: they are set aside with what the images do say (B0 = keys with a smaller image, E0 = keys with the same image)
+// per octave, 32 octaves; every piece is monotone and the pieces are ordered): its top 14 bits are the key's bucket, and LDS
+// holds a 31-bit BUCKET-LOCAL image -- q's low 17 bits followed by 14 more bits of the core's fraction, 45 bits of resolution in
+// all (a tail key keeps q's 31: its 14 extra bits are 0) -- so that a row of up to 11 264 curves + its 16 384-bucket
+// histogram take 77 KiB and two 512-thread workgroups, half a row apart in phase, share a CU: one's compares run under the
+// other's LDS traffic.  Order is decided by the images (within a bucket; buckets are ordered) wherever they differ; keys whose
+// images coincide (two core values within range / 2^45, two tail values within the tail's 31-bit resolution, or equal values)
+// are NOT ranked here: they are set aside with what the images do say (B0 = keys with a smaller image, E0 = keys with the same image)
 // and settled exactly, in fp64, among themselves at the end of the workgroup (a group of equal images is complete in the list).
 // Tie-heavy rows (quantised data: a bucket of 16 keys or more whose keys share an image) are ranked in closed form when
 // every bucket of the row provably holds one value.
@@ -41,7 +43,7 @@ constexpr u32 R32_TB = 1024;                    // buckets of each tail
 constexpr int R32_TSH = 30;                     // tail code = (bits(d + c) - bits(c)) >> 30: 2^22 codes = 32 buckets per octave
 constexpr double R32_CDIV = 1.0 / 448.0;        // c = core width / 448: the first octave continues the core's slope (32 * 448 = 14 336)
 constexpr double R32_BETA = 2.0;                // the central bracket of the sample is widened by this many spans on either side
-constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the keys: above every key image, below 2^31
+constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the keys (masked off by the member pass: any value would do)
 
 template <int E, int LNB>
 struct R32Cfg {
@@ -210,15 +212,20 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             go = fin && (wc > 0.0) && (mscale < INF) && (mc > 0.0);
             bad = bad || (fin && !go);
         }
-        // images of four keys: core keys cost fma + cvt + the core test; the tail code is computed only when some lane of the wave
-        // has a key outside the core (or a NaN: cvt gives 0)
-        auto convert4 = [&](const double (&xv)[4], u32 (&q)[4]) {
+        // images of four keys: core keys cost fma + cvt + the core test + 14 more bits; the tail code is computed only when some
+        // lane of the wave has a key outside the core (or a NaN: cvt gives 0).  Out: the bucket (top 14 bits of the 31-bit image
+        // q) in bk, the bucket-local image in q -- q's low 17 bits, then 14 more bits of the core's fraction (0 in the tails)
+        auto convert4 = [&](const double (&xv)[4], u32 (&q)[4], u32 (&bk)[4]) {
             bool anyout = false;
+            u32 fr[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const double u = __builtin_fma(xv[i], mscale, moff);
                 u32 qi;
                 asm("v_cvt_u32_f64 %0, %1" : "=v"(qi) : "v"(u));      // saturating: below -> 0, above -> 2^32 - 1, NaN -> 0
+                // floor(2^14 frac(u)): exact, and frac(u) = u - qi for a core key (0 < u < 2^31); the 45-bit image is q << 14 | fr
+                const double f = __builtin_amdgcn_fract(u) * 16384.0;
+                asm("v_cvt_u32_f64 %0, %1" : "=v"(fr[i]) : "v"(f));
                 q[i] = qi;
                 anyout = anyout || (qi - mc0 >= mcw);
             }
@@ -237,14 +244,19 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     u32 qt = low ? (mc0 - 1u) - tcc : (mc0 + mcw) + tcc;
                     qt = (xv[i] == xv[i]) ? qt : NANIMG;
                     q[i] = outc ? qt : q[i];
+                    fr[i] = outc ? 0u : fr[i];                        // a tail key keeps the 31-bit resolution
                 }
             }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bk[i] = q[i] >> SH;                                   // a NaN's image: the dummy counter NB + 2
+                q[i] = ((q[i] << (31 - SH)) & 0x7FFFFFFFu) | fr[i];
+            }
         };
-        u32 sl[(E + 3) / 4];
+        u32 bc[E];                                                    // bucket | slot << 16, then (at the scatter) base | count << 14
         if (go) {
             // ---- (1) image, bucket, slot: trunc(min(fl(fl(x - lo) * scale), TOP)), negative -> 0, is non-decreasing in x ----
-#pragma unroll
-            for (int e = 0; e < (E + 3) / 4; ++e) sl[e] = 0;
+
             // batches of 8 atomics in flight; their return values (the slots) are packed 4 to a register per batch
 #pragma unroll
             for (int e0 = 0; e0 < E; e0 += 8) {
@@ -253,20 +265,20 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 for (int h = 0; h < 8; h += 4) {
                     if (e0 + h < E) {
                         double xv[4];
-                        u32 q[4];
+                        u32 q[4], bk[4];
 #pragma unroll
                         for (int i = 0; i < 4; ++i) xv[i] = e0 + h + i < E ? x[e0 + h + i] : x[e0 + h];
-                        convert4(xv, q);
+                        convert4(xv, q, bk);
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            if (e0 + h + i < E) kb[e0 + h + i] = q[i];
+                            if (e0 + h + i < E) { kb[e0 + h + i] = q[i]; bc[e0 + h + i] = bk[i]; }
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int e = e0 + i;
                     if (e < E) {
-                        const u32 b = kb[e] >> SH;                    // a NaN's image: the dummy counter NB + 2
+                        const u32 b = bc[e];
                         old[i] = atomicAdd(&H[b >> 1], 1u << ((b & 1u) * 16u));
                     }
                 }
@@ -274,10 +286,11 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 for (int i = 0; i < 8; ++i) {
                     const int e = e0 + i;
                     if (e < E)   // a NaN key's slot is read from the wrong half: its row is not taken anyway
-                        sl[e >> 2] |= ((old[i] >> (((kb[e] >> SH) & 1u) * 16u)) & 0xFFu) << (8 * (e & 3));
+                        bc[e] |= ((old[i] >> ((bc[e] & 1u) * 16u)) & 0xFFu) << 16;
                 }
-                asm volatile("" : "+v"(sl[e0 >> 2]));                 // packed HERE: not (old, shift) pairs kept for the scatter
-                if (e0 + 4 < E) asm volatile("" : "+v"(sl[(e0 >> 2) + 1]));
+#pragma unroll
+                for (int i = 0; i < 8; ++i)                           // packed HERE: not (old, shift) pairs kept for the scatter
+                    if (e0 + i < E) asm volatile("" : "+v"(bc[e0 + i]));
             }
             __syncthreads();                                          // barrier 2
             // ---- (2) exclusive prefix sum over the counters (conflict-free 16-byte accesses: lane <-> quad) ----
@@ -323,12 +336,11 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             // block-uniform.  A crowded row (a bucket of 64 keys or more) is scattered too: its slots wrap at 256 but stay inside
             // their buckets, which is all the closed form below asks of S; its member pass is never run.
             bool take = nv == (u32)n;
-            u32 bc[E];                                                // base | count << 14
             if (take) {
                 // ---- (3) scatter into bucket order ----
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
-                    const u32 b = kb[e] >> SH, slot = (sl[e >> 2] >> (8 * (e & 3))) & 0xFFu;
+                    const u32 b = bc[e] & 0xFFFFu, slot = bc[e] >> 16;
                     // two 2-byte reads, kept apart: merged into one 4-byte read they sit on an odd halfword for every
                     // odd b, and the LDS replays such a read for 64 cycles (SQ_LDS_UNALIGNED_STALL)
                     u32 b1 = b + 1u;
@@ -420,10 +432,11 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 if (t < 2) H[NB / 2 + t] = 0;
             }
             if (take) {
-                // ---- (4) rank inside the bucket: two quads from the 16-byte boundary at or below the bucket's base; the
-                //      keys in front of the base belong to earlier buckets (smaller images) and are taken off again, keys
-                //      past the bucket's end have larger images, sentinels follow the last key.  Only `<` is counted:
-                //      equal images show in the sum of the row's ranks (fold above) ----
+                // ---- (4) rank inside the bucket: two quads from the 16-byte boundary at or below the bucket's base.  Images
+                //      are bucket-local, so only the bucket's own positions [off, off + cnt) of the window are counted (the
+                //      keys of other buckets around them are masked off; a quad of sentinels stands in for a second quad
+                //      the bucket does not reach).  Only `<` is counted: equal images show in the sum of the row's ranks
+                //      (fold below) ----
                 const uint4 *S4 = reinterpret_cast<const uint4 *>(S);
                 uint4 y0, y1;
                 auto window = [&](int e) {
@@ -438,33 +451,35 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 for (int e = 0; e < E; ++e) {
                     const u32 base = bc[e] & 0x3FFFu, cnt = bc[e] >> 14, off = base & 3u;
                     const u32 qe = kb[e];
-                    // y < q <=> bit 31 of y - q (images below 2^31); v_alignbit shifts it into a bit list: two full-rate
-                    // instructions per member and no compare -> carry chain through vcc (gfx950 pays wait states on those)
+                    // y < q <=> bit 31 of y - q (images below 2^31); v_alignbit shifts it into a bit list (window position p
+                    // at bit p): two full-rate instructions per member and no compare -> carry chain through vcc (gfx950
+                    // pays wait states on those)
                     u32 lt = 0;
-                    lt = __builtin_amdgcn_alignbit(lt, y0.x - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y0.y - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y0.z - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y0.w - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y1.x - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y1.y - qe, 31);
-                    lt = __builtin_amdgcn_alignbit(lt, y1.z - qe, 31);
                     lt = __builtin_amdgcn_alignbit(lt, y1.w - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y1.z - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y1.y - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y1.x - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y0.w - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y0.z - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y0.y - qe, 31);
+                    lt = __builtin_amdgcn_alignbit(lt, y0.x - qe, 31);
                     if (e + 1 < E) window(e + 1);
-                    u32 less = (u32)__popc(lt);
+                    u32 less = (u32)__popc(__builtin_amdgcn_ubfe(lt, off, cnt < 8u ? cnt : 8u));   // the members only
                     if (cnt + off > 8u) {                             // the rest of a long bucket (a few lanes per visit)
                         const uint4 *p = S4 + (base >> 2);
 #pragma unroll 1
                         for (u32 kk = 8; kk < cnt + off; kk += 4) {   // up to 63 + 3 positions: the bit list is counted per quad
                             const uint4 y = p[kk >> 2];
+                            const u32 rest = cnt + off - kk;          // members left: the last quad may run into the next bucket
                             u32 l4 = 0;
-                            l4 = __builtin_amdgcn_alignbit(l4, y.x - qe, 31);
-                            l4 = __builtin_amdgcn_alignbit(l4, y.y - qe, 31);
-                            l4 = __builtin_amdgcn_alignbit(l4, y.z - qe, 31);
                             l4 = __builtin_amdgcn_alignbit(l4, y.w - qe, 31);
-                            less += (u32)__popc(l4);
+                            l4 = __builtin_amdgcn_alignbit(l4, y.z - qe, 31);
+                            l4 = __builtin_amdgcn_alignbit(l4, y.y - qe, 31);
+                            l4 = __builtin_amdgcn_alignbit(l4, y.x - qe, 31);
+                            less += (u32)__popc(__builtin_amdgcn_ubfe(l4, 0u, rest < 4u ? rest : 4u));
                         }
                     }
-                    const u32 B = base - off + less;                  // keys with a smaller image
+                    const u32 B = base + less;                        // keys with a smaller image
                     kb[e] = B;
                     const bool isk = e < E - 2 || t + e * NT < n;
                     sB += isk ? B : 0u;
