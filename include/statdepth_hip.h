@@ -56,7 +56,7 @@ enum sd_mbd_algo {
 
 /* ---- library / device ---------------------------------------------------- */
 int sd_abi_version(void);
-/* 0 for the product library.  1 for libstatdepth_hip_xcheck.so, the -DSD_CROSSCHECK build of the same sources that
+/* 0 for the product library.  1 for libstatdepth_hip_xcheck.so, which links the same objects and
  * also holds the retired kernel generations and honours the SD_* environment switches selecting them (tests only). */
 int sd_is_crosscheck_build(void);
 const char *sd_last_error(void);

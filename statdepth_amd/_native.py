@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libstatdepth_hip.so")
-# The cross-check build of the same sources (-DSD_CROSSCHECK: retired kernel generations + the environment switches that
+# The cross-check library (the same objects + retired kernel generations + the environment switches that
 # select them).  TESTS ONLY: nothing in this package opens it; tests/conftest.py swaps it in for the comparisons.
 XCHECK_LIB_PATH = os.path.join(_HERE, "lib", "libstatdepth_hip_xcheck.so")
 

@@ -23,10 +23,9 @@
 // the LDS (80 KB at config 4) and serve every target of that timepoint.
 // NaN-free input only (a NaN component would need a fourth state: 4^d counters do not fit); the host refuses NaN.
 #include "sd_common.h"
+#include "rank_routes.h"
 
 namespace sd {
-
-int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s);   // mbd_rank_bucket.hip
 
 template <int D>
 struct BECfg {
@@ -201,12 +200,7 @@ int launch_multi_band(const double *P, i64 n, i64 T, int d, const i64 *targets, 
         return rc;
     }
     SD_HIP(hipMemsetAsync(out, 0, sizeof(u64) * m, s));
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    i64 qg = (2 * (i64)cus + T - 1) / T;                                            // about two blocks per CU in all
+    i64 qg = (2 * (i64)device_cus() + T - 1) / T;                                            // about two blocks per CU in all
     if (qg < 1) qg = 1;
     if (qg > m) qg = m;
     if (qg > 65535) qg = 65535;

@@ -28,18 +28,11 @@
 #include <stdlib.h>
 
 #include "sd_common.h"
+#include "rank_routes.h"
 
 namespace sd {
 
-int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s);   // mbd_rank_bucket.hip
-int launch_rank_medium_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s);   // ... its two-block form
-int launch_rank_big_image(const double *Y, i64 T, i64 n, u32 *img, u32 *nnan, void *ws, size_t ws_bytes, hipStream_t s);   // mbd_rank_big.hip
-// bd_strict_grid.hip: two to four coordinates at large n through a grid of cells instead of every pair of points
-bool bd_strict_grid_applies(i64 T, i64 n, int J);
-size_t bd_strict_grid_workspace_bytes(i64 T, i64 n, bool subset);
-int launch_bd_strict_grid(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, u64 *out, int jcols, u32 *flag, void *ws,
-                          size_t ws_bytes, hipStream_t s);
-// ... for all targets, or a subset that is not small (else the state-class kernel's O(m n) is less work)
+// the grid route (bd_strict_grid.hip) for all targets, or a subset that is not small (else the state-class kernel's O(m n) is less work)
 static inline bool strict_grid_wanted(i64 T, i64 n, i64 m, int J) {
     return bd_strict_grid_applies(T, n, J) && m * 32 >= n && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1 &&
            xswitch("SD_STRICT_NOGRID") != 1;

@@ -22,10 +22,9 @@
 // a NaN anywhere (the rank route counts them) leaves everything to the state-class kernels, which run behind this one and
 // return at once otherwise.  All points are targets, or a subset of them (the others' positions are skipped).
 #include "sd_common.h"
+#include "rank_routes.h"
 
 namespace sd {
-
-int launch_rank_big_image(const double *Y, i64 T, i64 n, u32 *img, u32 *nnan, void *ws, size_t ws_bytes, hipStream_t s);   // mbd_rank_big.hip
 
 constexpr int SG_TG = 16;                       // targets per workgroup of a slab pass
 constexpr int SG_NT = 256, SG_PTS = 4;

@@ -26,6 +26,7 @@
 // Replaces the same reference loops as mbd_pairwise.hip (_functional.py:246-251,
 // _containment.py:75-77); results are bit-identical to it and to the oracle.
 #include "sd_common.h"
+#include "rank_routes.h"
 
 namespace sd {
 
@@ -250,11 +251,7 @@ __global__ __launch_bounds__(1024) void rank_reduce_kernel(const u64 *__restrict
 }
 
 static int rank_grid(i64 T) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    const int cus = device_cus();
     i64 g = T < cus ? T : cus;
     if (g > RK_MAXG) g = RK_MAXG;
     return (int)g;
@@ -292,6 +289,12 @@ int launch_mbd_rank_v1(const double *Y, i64 T, i64 n, const i64 *targets, i64 tb
                        targets, tbegin, m, out);
     SD_HIP(hipGetLastError());
     return SD_OK;
+}
+
+// the hook launch_mbd_rank (mbd_rank_ab.hip) reaches it through
+int retired_rank_v1(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out, void *ws,
+                    size_t ws_bytes, hipStream_t s) {
+    return launch_mbd_rank_v1(Y, T, n, targets, tbegin, m, J, out, ws, ws_bytes, s);
 }
 
 }  // namespace sd

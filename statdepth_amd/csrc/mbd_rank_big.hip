@@ -2,222 +2,53 @@
 // (16 384 < n < 2^31 curves; BASELINE.json config 3, the north-star stretch case, and every multi-GPU run).
 //
 // Same integers as the other K1+K2 kernels (reference loops _functional.py:246-251, _containment.py:75-77).
-// Per row the ranks B (others strictly below) and A (strictly above) of every curve are written as a
-// (uint32, uint32) pair image; rank_accumulate2_kernel folds C(v,j) - C(A,j) - C(B,j) over the rows.
+// Per row the ranks B (others strictly below) and A (strictly above) of every curve are written as a pair image
+// (AB2, rank_big_common.h); rank_accumulate2_kernel and its wide forms fold C(v,j) - C(A,j) - C(B,j) over the rows.
 //
-// Route 1 (default): sample-partition into value buckets, so that no rank needs another bucket's keys.
-//   S  bucket_splitters_kernel  one workgroup per row sorts a 4 096-element strided sample in LDS and
-//                               publishes NB-1 splitters (NB ~ n / 5 500 buckets of capacity 8 192).
-//   P  bucket_partition_kernel  every element finds its bucket (binary search over the splitters in LDS;
-//                               equal values always land together), slots are handed out with one LDS
-//                               atomic per element and one global atomic per (workgroup, bucket); values
-//                               and curve ids are scattered into the bucket arrays.  NaNs never enter a
-//                               bucket: they are counted and marked in the pair image right here.
-//   A  bucket_packed_kernel     one workgroup per (row, bucket): packed-key sort (slot index in the low
-//                               mantissa bits, rank_sort.h), rank = bucket base + position, handed to the
-//                               slot's owner through LDS and scattered to the curve's pair.  A bucket with
-//                               ties or near-ties is flagged for
-//   B  bucket_search_kernel     sort of the plain values + binary search inside the bucket (exact for ties).
-// Route 2 (overflow fallback, SD_BIG_IMPL=1 forces it): a row whose partition overflowed a bucket (a
-//   quarter of the row tied on one value, say) is cut into chunks of 16 384 keys in curve order:
-//   chunk_sort_kernel sorts every chunk, chunk_search_kernel streams every sorted chunk of the row through
-//   LDS and sums lower/upper bounds per chunk: O((n/C)^2) chunk searches per row instead of none.
-// The product path launches B and route 2 as ONE kernel per batch, big_fallback_kernel: flagged buckets first, then -- for
-//   the rows whose partition overflowed -- chunk sort, a meeting of the (CU-resident) grid at a counter, chunk search; with
-//   nothing flagged every workgroup reads two gate words and leaves.  The separate kernels stay for the cross-check
-//   switches (chunked route for every row, earlier generations).
-// Work per row, route 1: one streaming pass + n/5 500 LDS sorts; config 3 (10^5 x 256) on one MI355X:
-// see DESIGN.md.
+// A row is sample-partitioned into value buckets, so that no rank needs another bucket's keys.  Four launches per batch:
+//   S3 bucket_setup_kernel      one workgroup per row sorts a strided sample in LDS (rank_sort.h) and publishes, per row:
+//                               NB + 1 splitters (NB ~ n / 5 500 interior buckets of capacity 8 192; the sample's extremes
+//                               are splitters too: the keys beyond them form two small end buckets), a LOOK-UP TABLE over
+//                               TB_C cells of the monotone map c(x) = trunc((x - lo) * scale) holding, per cell, the number
+//                               of splitters in earlier cells and up to this cell; a "tied" flag when the sorted sample has
+//                               two equal neighbours; and the zeroing of the row's counters (no memset launch).
+//   P3 bucket_partition3_kernel bucket(x) = number of splitters < x (equal values always land together), from the table: a
+//                               compare is needed only in cells that a splitter cuts.  Records are 8 bytes: the curve index
+//                               and a 32-bit IMAGE q of the key, monotone inside its bucket (interior buckets: linear
+//                               between the two splitters; end buckets: a float-like code of the distance to the splitter
+//                               in representable doubles) -- equal keys have equal images, different keys almost always
+//                               different ones.  Rows flagged "tied" keep 12-byte fp64 records (their images would collide
+//                               en masse).  NaNs never enter a bucket: they are counted and marked in the pair image here.
+//   A3 bucket_rank32_kernel     one workgroup per (row, bucket) ranks WITHOUT a sort on the 32-bit images: a monotone map
+//                               onto fine buckets (LDS histogram), prefix sum, scatter, and every key counts the members of
+//                               its own fine bucket below itself: 4-byte LDS slots, integer compares.  A key whose image
+//                               equals another member's settles the order of those members with their fp64 values
+//                               (gathered from the matrix through the records' curve indices): exact whatever the data,
+//                               cheap because it is rare on continuous data.  Tied rows run the fp64 form of the same
+//                               ranking (bucket_rank_item, rank_big_common.h) inside this kernel.  A bucket with a crowded
+//                               fine bucket is flagged (gate word 0).
+//   big_fallback_kernel         behind two gate words, so that with nothing flagged every workgroup reads them and leaves:
+//                               the flagged buckets (sort of the plain values + binary search inside the bucket, exact for
+//                               ties), then -- for the rows whose partition overflowed a bucket (a quarter of the row tied
+//                               on one value, say) -- the chunked route: the row is cut into chunks of 16 384 keys in curve
+//                               order, every chunk is sorted, the (CU-resident) grid meets at a counter, and every sorted
+//                               chunk of the row streams through LDS for the lower/upper bounds of every key.
+// Why the steps look like this (profiles/r02b_config3_*): a binary search over the splitters cost 91 VALU + 46 SALU per
+// key; fp64 compares run at half rate on MI355X and 8-byte LDS slots lost 63 % of their cycles to bank conflicts; separate
+// fall-back launches of full grids did nothing.  The generations that had those properties are kept as independent
+// implementations for the parity tests in mbd_rank_big_retired.hip (cross-check library only), reached through
+// retired_big_rank_batch (rank_routes.h) when a cross-check switch asks for them.
+// Work per row: one streaming pass + n/5 500 bucket rankings; config 3 (10^5 x 256) on one MI355X: see DESIGN.md.
 #include <stdlib.h>
 
 #include <atomic>
 
-#include "sd_common.h"
-#include "rank_sort.h"
-#include "rank_bucket.h"
+#include "rank_big_common.h"
+#include "rank_routes.h"
 
 namespace sd {
 
-// The pair image of a batch of rows: for every (row, curve) ONE u32 -- B (others strictly below), with bit 31 set when
-// the curve ties with another one at this timepoint -- and, for the tied keys only, A (strictly above) in a second
-// image; an untied key has A = n_real - 1 - B.  Continuous data writes and reads 4 bytes per key instead of 8 (the
-// scattered 8-byte pairs were 596 MB of the ranking kernel's traffic at config 3, profiles/r02_config3_pmc_traffic.json).
-struct AB2 {
-    u32 *B;
-    u32 *A;
-    unsigned short *H;                         // half-word image (n <= AB2_H_MAXN, fold mode) or nullptr
-};
-constexpr u32 AB2_NAN = 0xFFFFFFFFu;           // B word: the curve is NaN at this timepoint
-constexpr u32 AB2_TIE = 0x80000000u;           // B word: A is in the second image
-// The fold wants C(v, j) - C(A, j) - C(B, j), symmetric in A and B, and an untied key has A + B = nreal - 1: min(A, B) says
-// it all and fits 16 bits up to 131 070 curves -- 2 bytes per (row, curve) written and read instead of 4 (config 3: 102 MB
-// less traffic).  AB2_H_WORD: look at the B word (NaN, or a tied key with its A in the second image).
-constexpr unsigned short AB2_H_WORD = 0xFFFFu;
-constexpr i64 AB2_H_MAXN = 131070;
-
-// an untied key: A = nreal - 1 - B
-__device__ __forceinline__ void ab_store_untied(const AB2 &ab, size_t idx, u32 B, u32 nreal) {
-    if (ab.H) {
-        const u32 A = nreal - 1u - B;
-        ab.H[idx] = (unsigned short)(A < B ? A : B);
-    } else {
-        ab.B[idx] = B;
-    }
-}
-__device__ __forceinline__ void ab_store_nan(const AB2 &ab, size_t idx) {
-    ab.B[idx] = AB2_NAN;
-    if (ab.H) ab.H[idx] = AB2_H_WORD;
-}
-__device__ __forceinline__ void ab_store(const AB2 &ab, size_t idx, u32 B, u32 A, u32 nreal) {
-    if (A + B + 1u == nreal) {
-        ab_store_untied(ab, idx, B, nreal);
-    } else {
-        ab.B[idx] = B | AB2_TIE;
-        ab.A[idx] = A;
-        if (ab.H) ab.H[idx] = AB2_H_WORD;
-    }
-}
-
-// =====================================================================================================
-// route 2: chunks in curve order
-// =====================================================================================================
-constexpr int BIG_NT = 1024, BIG_E = 16;
-constexpr int BIG_C = BIG_NT * BIG_E;          // 16384 keys per chunk
-using BigCfg = R2Cfg<BIG_NT, BIG_E>;
-
-// persistent 1-D grid over (chunk, row); rowflag != nullptr: only rows with a non-zero flag (none: every workgroup reads
-// a few flags and leaves)
-__device__ __forceinline__ void chunk_sort_items(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, i64 nch,
-                                                 double *sorted, i64 sstride, u32 *nanrow,
-                                                 const u32 *__restrict__ rowflag, double *Sm) {
-    constexpr int E = BIG_E, WB = BigCfg::WB;
-    for (i64 v = blockIdx.x; v < rows * nch; v += gridDim.x) {
-    const i64 c = v % nch, rb = v / nch;
-    if (rowflag && !rowflag[rb]) continue;
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));                               // per-item opaque thread id: no address hoisted out of the loop
-    const int lane = t & 63, wave = t >> 6;
-    __syncthreads();                                          // the previous item's sort image is no longer in use
-    const i64 base = c * BIG_C;
-    const int nc = (int)((n - base) < BIG_C ? (n - base) : BIG_C);
-    const int n_act = ((nc + WB - 1) / WB) * WB;
-    const bool wreal = wave * WB < n_act;
-    const double INF = __builtin_huge_val();
-    const double *rp = Y + (row0 + rb) * n + base + (wave * WB + lane);
-    double k[E];
-    u32 mynan = 0;
-    if (wreal) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) k[e] = (wave * WB + lane + e * 64 < nc) ? rp[e * 64] : INF;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            bool isn = k[e] != k[e];
-            mynan += isn ? 1u : 0u;
-            k[e] = isn ? INF : k[e];
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) mynan += __shfl_down(mynan, o);
-    if (lane == 0 && mynan) atomicAdd(&nanrow[rb], mynan);
-    R2Sorter<BIG_NT, BIG_E>::sort(k, Sm, t, n_act, wreal, INF);
-    if (wreal) {
-        // layout 0: thread t holds sorted positions 16 t .. 16 t + 15 (two 64-byte runs per thread)
-        double *dst = sorted + rb * sstride + base + (i64)t * E;
-#pragma unroll
-        for (int r = 0; r < E; ++r) dst[r] = k[r];
-    }
-    }
-}
-
-__global__ __launch_bounds__(BIG_NT) void chunk_sort_kernel(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, i64 nch,
-                                                            double *__restrict__ sorted, i64 sstride,
-                                                            u32 *__restrict__ nanrow, const u32 *__restrict__ rowflag,
-                                                            const u32 *__restrict__ gate, u32 epoch) {
-    extern __shared__ double Sm[];
-    if (gate && *gate != epoch) return;                       // no row of this batch overflowed its value buckets
-    chunk_sort_items(Y, n, row0, rows, nch, sorted, sstride, nanrow, rowflag, Sm);
-}
-
-// persistent 1-D grid over the items (row, query chunk): the chunk's curves are searched in every sorted chunk of the row
-__device__ __forceinline__ void chunk_search_items(const double *__restrict__ Y, i64 n, i64 row0, i64 rows,
-                                                   const double *sorted, i64 sstride, const u32 *nanrow, int nchunks,
-                                                   const u32 *__restrict__ rowflag, const AB2 &ab, double *Sm,
-                                                   i64 vfirst, i64 vstride) {
-    constexpr int E = BIG_E, WB = BigCfg::WB, N = BIG_C;
-    const double INF = __builtin_huge_val();
-    for (i64 v = vfirst; v < rows * nchunks; v += vstride) {
-        const i64 rb = v / nchunks;
-        if (rowflag && !rowflag[rb]) continue;
-        int t = threadIdx.x;
-        asm volatile("" : "+v"(t));                           // per-item opaque thread id
-        const int qc = (int)(v % nchunks);
-        const i64 qbase = (i64)qc * BIG_C;
-        const int nq = (int)((n - qbase) < BIG_C ? (n - qbase) : BIG_C);
-        const double *xp = Y + (row0 + rb) * n + qbase + t;
-        double x[E];
-        u32 lo[E], hi[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            x[e] = (t + e * BIG_NT < nq) ? xp[e * BIG_NT] : INF;
-            lo[e] = 0;
-            hi[e] = 0;
-        }
-        for (int c = 0; c < nchunks; ++c) {
-            const i64 base = (i64)c * BIG_C;
-            const int nc = (int)((n - base) < BIG_C ? (n - base) : BIG_C);
-            const int n_act = ((nc + WB - 1) / WB) * WB;
-            const double *src = sorted + rb * sstride + base;
-            __syncthreads();                          // previous chunk's searches are done
-            for (int p = t; p < n_act; p += BIG_NT) Sm[r2_swz(p)] = src[p];
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                if ((e & 3) == 0) __builtin_amdgcn_sched_barrier(0);
-                if (t + e * BIG_NT < nq && x[e] == x[e]) {
-                    int l = r2_bound<N, SlotSwz, false>(Sm, n_act, x[e], INF);
-                    int h = l;
-                    // keys equal to x in this chunk?  (always true once: in x's own chunk)
-                    double nx = (l < n_act) ? Sm[r2_swz(l)] : INF;
-                    if (l < n_act && nx <= x[e]) h = r2_bound<N, SlotSwz, true>(Sm, n_act, x[e], INF);
-                    lo[e] += (u32)l;
-                    hi[e] += (u32)h;
-                }
-            }
-        }
-        const u32 nnan = nanrow[rb];
-        const size_t dst = (size_t)(rb * n + qbase + t);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            if (t + e * BIG_NT < nq) {
-                if (x[e] == x[e])
-                    ab_store(ab, dst + e * BIG_NT, lo[e], (x[e] == INF) ? 0u : (u32)(n - hi[e]) - nnan, (u32)n - nnan);
-                else
-                    ab_store_nan(ab, (size_t)(dst + e * BIG_NT));
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(BIG_NT) void chunk_search_kernel(const double *__restrict__ Y, i64 n, i64 row0,
-                                                              i64 rows, const double *__restrict__ sorted,
-                                                              i64 sstride, const u32 *__restrict__ nanrow,
-                                                              int nchunks, const u32 *__restrict__ rowflag,
-                                                              const u32 *__restrict__ gate, u32 epoch, AB2 ab) {
-    extern __shared__ double Sm[];
-    if (gate && *gate != epoch) return;                       // no row of this batch overflowed its value buckets
-    chunk_search_items(Y, n, row0, rows, sorted, sstride, nanrow, nchunks, rowflag, ab, Sm, blockIdx.x, gridDim.x);
-}
-
-// =====================================================================================================
-// route 1: value buckets
-// =====================================================================================================
-constexpr int BK_CE = 16;                      // keys per thread of the ranking kernels = bucket capacity / 512
-constexpr int BK_NT = 512, BK_E = 16;          // the search kernel's sort: 8 192 slots
-constexpr int BK_C = BK_NT * BK_CE;            // bucket capacity (8 192)
-static_assert(BK_C <= BK_NT * BK_E, "a value bucket fits the search kernel's sort");
 constexpr int BK_FILL = 5500;                  // target mean fill
-constexpr int BK_MAXNB = 1024;
-using BkCfg = R2Cfg<BK_NT, BK_E>;
-
 static inline int bucket_count(i64 n) {
     // mean fill 5 500 of 8 192; past ~300 buckets even the 16 384-value sample leaves < 50 samples per bucket and the
     // fills scatter too much: aim lower
@@ -227,560 +58,9 @@ static inline int bucket_count(i64 n) {
     return (int)nb;
 }
 
-// S: grid = rows; spl[r][0..NB-2] ascending.  SNT threads sort a strided sample of SE SNT values: 2 048 for up to 24
-// value buckets, 4 096 up to 72, 16 384 above (a bucket's fill scatters with 1 / sqrt(samples per bucket); at n = 10^6 the small
-// sample overflowed the 8 192-key buckets and sent every row to the chunked route).
-#ifdef SD_CROSSCHECK
-template <int SNT, int SE>
-__global__ __launch_bounds__(SNT) void bucket_splitters_kernel(const double *__restrict__ Y, i64 n, i64 row0, int NB,
-                                                               double *__restrict__ spl) {
-    using Cfg = R2Cfg<SNT, SE>;
-    constexpr int E = SE, LE = Cfg::LE, SS = SNT * SE;
-    extern __shared__ double Sm[];
-    const int t = threadIdx.x;
-    const i64 rb = blockIdx.x;
-    const double *row = Y + (row0 + rb) * n;
-    const double INF = __builtin_huge_val();
-    double k[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const i64 s = (i64)t * E + e;                       // sample index, any assignment of samples to slots works
-        double v = row[(s * n) / SS];
-        k[e] = (v == v) ? v : INF;
-    }
-    R2Sorter<SNT, SE>::sort(k, Sm, t, SS, true, INF);
-    double *Sw = Sm + r2_base<0, LE>(t);
-#pragma unroll
-    for (int e = 0; e < E; ++e) Sw[r2_off<0, LE>(e)] = k[e];
-    __syncthreads();
-    for (int b = t; b < NB - 1; b += SNT) {
-        const int q = (int)(((i64)(b + 1) * SS) / NB);
-        spl[rb * (NB - 1) + b] = Sm[r2_phys<LE>(q)];
-    }
-}
-
-// P: grid = (ceil(n / 16384), rows)
-__global__ __launch_bounds__(1024) void bucket_partition_kernel(const double *__restrict__ Y, i64 n, i64 row0, int NB,
-                                                                const double *__restrict__ spl,
-                                                                u32 *__restrict__ bcnt, u32 *__restrict__ nnanrow,
-                                                                u32 *__restrict__ ovf, double *__restrict__ bval,
-                                                                u32 *__restrict__ bidx, AB2 ab, int dbg) {
-    __shared__ double s_spl[BK_MAXNB];
-    __shared__ u32 s_hist[BK_MAXNB];
-    __shared__ u32 s_base[BK_MAXNB];
-    const int t = threadIdx.x;
-    const i64 rb = blockIdx.y;
-    const i64 base = (i64)blockIdx.x * 16384;
-    for (int b = t; b < NB; b += 1024) {
-        if (b < NB - 1) s_spl[b] = spl[rb * (NB - 1) + b];
-        s_hist[b] = 0;
-    }
-    __syncthreads();
-    const double *row = Y + (row0 + rb) * n;
-    double x[16];
-    u32 bk[16], off[16];
-    u32 mynan = 0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const i64 i = base + t + e * 1024;
-        x[e] = (i < n) ? row[i] : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const i64 i = base + t + e * 1024;
-        bk[e] = 0xFFFFFFFFu;
-        if (i < n) {
-            if (x[e] == x[e]) {
-                // bucket = number of splitters < x (equal values always share a bucket)
-                int lo = 0, hi = NB - 1;
-                if (dbg) lo = hi = (int)((u32)(e + t) % (u32)NB);     // timing experiment: no search (results invalid)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_spl[mid] < x[e]) lo = mid + 1;
-                    else hi = mid;
-                }
-                bk[e] = (u32)lo;
-                off[e] = atomicAdd(&s_hist[lo], 1u);
-            } else {
-                ++mynan;
-                ab_store_nan(ab, (size_t)(rb * n + i));
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) mynan += __shfl_down(mynan, o);
-    if ((t & 63) == 0 && mynan) atomicAdd(&nnanrow[rb], mynan);
-    __syncthreads();
-    for (int b = t; b < NB; b += 1024) s_base[b] = s_hist[b] ? atomicAdd(&bcnt[rb * NB + b], s_hist[b]) : 0u;
-    __syncthreads();
-    bool over = false;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        if (bk[e] != 0xFFFFFFFFu) {
-            const u32 pos = s_base[bk[e]] + off[e];
-            if (pos < (u32)BK_C) {
-                const size_t slot = ((size_t)rb * NB + bk[e]) * BK_C + pos;
-                bval[slot] = x[e];
-                bidx[slot] = (u32)(base + t + e * 1024);
-            } else {
-                over = true;
-            }
-        }
-    }
-    if (over) ovf[rb] = 1u;
-}
-
-// P' (second generation): the same partition with the scatter staged through LDS.  One workgroup takes 8 192 consecutive curves
-// of one row, orders them by value bucket inside LDS (local slot = LDS-atomic offset + local exclusive prefix of the
-// workgroup's bucket counts) and copies the ordered block out: consecutive threads write consecutive elements of a
-// bucket's run, so the 12-byte records leave as coalesced stores instead of ~19 interleaved partial runs per wave
-// instruction.  grid = (ceil(n / 8192), rows).
-constexpr int BP2_NT = 1024, BP2_E = 8, BP2_C = BP2_NT * BP2_E;
-__global__ __launch_bounds__(BP2_NT) void bucket_partition2_kernel(const double *__restrict__ Y, i64 n, i64 row0, int NB,
-                                                                   const double *__restrict__ spl,
-                                                                   u32 *__restrict__ bcnt, u32 *__restrict__ nnanrow,
-                                                                   u32 *__restrict__ ovf, double *__restrict__ bval,
-                                                                   u32 *__restrict__ bidx, AB2 ab) {
-    extern __shared__ double Sm2[];
-    double *Skey = Sm2;                                               // [BP2_C]
-    u32 *Sid = reinterpret_cast<u32 *>(Skey + BP2_C);                 // [BP2_C]
-    unsigned short *Sbk = reinterpret_cast<unsigned short *>(Sid + BP2_C);   // [BP2_C]
-    __shared__ double s_spl[BK_MAXNB];
-    __shared__ u32 s_hist[BK_MAXNB];
-    __shared__ u32 s_gbase[BK_MAXNB];
-    __shared__ u32 s_lbase[BK_MAXNB + 1];
-    __shared__ u32 s_wtot[BP2_NT / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const i64 rb = blockIdx.y;
-    const i64 base = (i64)blockIdx.x * BP2_C;
-    for (int b = t; b < BK_MAXNB; b += BP2_NT) {
-        if (b < NB - 1) s_spl[b] = spl[rb * (NB - 1) + b];
-        s_hist[b] = 0;
-    }
-    __syncthreads();
-    const double *row = Y + (row0 + rb) * n;
-    double x[BP2_E];
-    u32 bk[BP2_E], off[BP2_E];
-    u32 mynan = 0;
-#pragma unroll
-    for (int e = 0; e < BP2_E; ++e) {
-        const i64 i = base + t + e * BP2_NT;
-        x[e] = (i < n) ? row[i] : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < BP2_E; ++e) {
-        const i64 i = base + t + e * BP2_NT;
-        bk[e] = 0xFFFFFFFFu;
-        off[e] = 0;
-        if (i < n) {
-            if (x[e] == x[e]) {
-                int lo = 0, hi = NB - 1;                    // bucket = number of splitters < x (equal values share a bucket)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_spl[mid] < x[e]) lo = mid + 1;
-                    else hi = mid;
-                }
-                bk[e] = (u32)lo;
-                off[e] = atomicAdd(&s_hist[lo], 1u);
-            } else {
-                ++mynan;
-                ab_store_nan(ab, (size_t)(rb * n + i));
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) mynan += __shfl_down(mynan, o);
-    if (lane == 0 && mynan) atomicAdd(&nnanrow[rb], mynan);
-    __syncthreads();
-    // global base of this workgroup's run in every bucket; local exclusive prefix of the counts (one thread per bucket)
-    {
-        const u32 c = (t < NB) ? s_hist[t] : 0u;
-        if (t < NB) s_gbase[t] = c ? atomicAdd(&bcnt[rb * NB + t], c) : 0u;
-        const u32 incl = rb_wave_incl_scan(c);
-        if (lane == 63) s_wtot[wave] = incl;
-        __syncthreads();
-        const u32 wt = (lane < BP2_NT / 64) ? s_wtot[lane] : 0u;
-        const u32 wscan = rb_row_incl_scan(wt);
-        const u32 woff = wave ? rb_readlane(wscan, wave - 1) : 0u;
-        if (t < NB) s_lbase[t] = woff + incl - c;
-        if (t == BP2_NT - 1) s_lbase[NB] = woff + incl;             // number of non-NaN keys of the block (NB <= 1024)
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < BP2_E; ++e) {
-        if (bk[e] != 0xFFFFFFFFu) {
-            const u32 lp = s_lbase[bk[e]] + off[e];
-            Skey[lp] = x[e];
-            Sid[lp] = (u32)(base + t + e * BP2_NT);
-            Sbk[lp] = (unsigned short)bk[e];
-        }
-    }
-    __syncthreads();
-    const u32 nval = s_lbase[NB];
-    bool over = false;
-    for (u32 p = t; p < nval; p += BP2_NT) {
-        const u32 b = Sbk[p];
-        const u32 g = s_gbase[b] + (p - s_lbase[b]);
-        if (g < (u32)BK_C) {
-            const size_t slot = ((size_t)rb * NB + b) * BK_C + g;
-            bval[slot] = Skey[p];
-            bidx[slot] = Sid[p];
-        } else {
-            over = true;
-        }
-    }
-    if (over) ovf[rb] = 1u;
-}
-#endif  // SD_CROSSCHECK
-
-template <int NT, int E>
-struct BkKeys {
-    using C = R2Cfg<NT, E>;
-    static constexpr int LN = C::LN;
-    static constexpr u64 MASK = (u64)C::N - 1;
-    static constexpr u64 TOPM = ((0xFFFFFFFFFFFFFull >> LN) << LN);
-    static constexpr u64 H3 = (0x7FEull << 52) | TOPM;         // padding class (largest)
-    static constexpr u64 H1 = H3 - ((u64)2 << LN);             // +inf class (H3 - 1 class stays unused here: no NaN)
-    static constexpr u64 SIGN = 0x8000000000000000ull;
-    static constexpr u64 LOW = (u64)1 << LN;
-};
-
-__device__ __forceinline__ u64 bk_bits(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ double bk_dbl(u64 b) { return __longlong_as_double((long long)b); }
-
-// A: grid = (NB, rows)
-#ifdef SD_CROSSCHECK
-__global__ __launch_bounds__(BK_NT) void bucket_packed_kernel(i64 n, int NB, const u32 *__restrict__ bcnt,
-                                                              const u32 *__restrict__ nnanrow,
-                                                              const u32 *__restrict__ ovf,
-                                                              const double *__restrict__ bval,
-                                                              const u32 *__restrict__ bidx, u32 *__restrict__ bflag,
-                                                              AB2 ab) {
-    using C = BkCfg;
-    using K = BkKeys<BK_NT, BK_E>;
-    constexpr int E = BK_E, NT = BK_NT, LN = C::LN, WB = C::WB;
-    constexpr u64 MASK = K::MASK, CLS_PAD = K::H3 >> LN;
-    extern __shared__ double Sm[];
-    double *firstkey = Sm + C::SLOTS;
-    __shared__ u32 s_basecnt;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = blockIdx.x;
-    const i64 rb = blockIdx.y;
-    if (ovf[rb]) return;
-    const int cnt = (int)bcnt[rb * NB + b];
-    if (cnt == 0) return;
-    if (t == 0) {
-        u32 s = 0;
-        for (int q = 0; q < b; ++q) s += bcnt[rb * NB + q];
-        s_basecnt = s;
-    }
-    const int n_act = ((cnt + WB - 1) / WB) * WB;
-    const bool wreal = wave * WB < n_act;
-    const double INF = __builtin_huge_val();
-    const double MAXK = bk_dbl(K::H3 | MASK);
-    const size_t slot0 = ((size_t)rb * NB + b) * BK_C;
-    const int i0 = wave * WB + lane;
-    double k[E];
-    int forcefull = 0;
-    if (wreal) {
-        const double *rp = bval + slot0 + i0;
-#pragma unroll
-        for (int e = 0; e < E; ++e) k[e] = (i0 + e * 64 < cnt) ? rp[e * 64] : INF;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int j = i0 + e * 64;
-            const u64 bits = bk_bits(k[e]);
-            const u64 a = bits & ~K::SIGN;
-            u64 kb = bits & ~MASK;
-            if (__builtin_expect((a - K::LOW) >= (K::H1 - K::LOW), 0)) {
-                if (a == 0x7FF0000000000000ull) kb = (bits & K::SIGN) ? (K::SIGN | K::H3) : K::H1;
-                else if (a == 0) kb = 0;
-                else forcefull |= (j < cnt);
-            }
-            kb = (j < cnt) ? kb : K::H3;
-            k[e] = bk_dbl(kb | (u64)j);
-        }
-    }
-    R2Sorter<NT, E>::sort(k, Sm, t, n_act, wreal, MAXK);
-    if (wreal) firstkey[t] = k[0];
-    __syncthreads();
-    int anytie = 0;
-    if (wreal) {
-        u64 nextb = ~0ull;
-        if ((t + 1) * E < n_act) nextb = bk_bits(firstkey[t + 1]);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const u64 c0 = bk_bits(k[e]) >> LN;
-            const u64 c1 = ((e < E - 1) ? bk_bits(k[e + 1]) : nextb) >> LN;
-            anytie |= (c0 == c1) & (c0 != CLS_PAD);
-        }
-    }
-    if (__syncthreads_or(anytie | forcefull)) {
-        if (t == 0) bflag[rb * NB + b] = 1u;
-        return;
-    }
-    u32 *R = reinterpret_cast<u32 *>(Sm);
-    if (wreal) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int j = (int)(bk_bits(k[e]) & MASK);
-            if (j < cnt) R[j] = (u32)(t * E + e);
-        }
-    }
-    __syncthreads();
-    const u32 base = s_basecnt;
-    for (int j = t; j < cnt; j += NT) {
-        ab.B[rb * n + bidx[slot0 + j]] = base + R[j];               // distinct keys: A = (n - NaNs of the row) - 1 - B
-    }
-}
-#endif  // SD_CROSSCHECK
-
-
-// A' (default): grid = 8 * NB * ceil(rows / 8) (see the mapping below).  Ranks inside one value bucket WITHOUT a sort, the method of mbd_rank_bucket.hip:
-// a monotone map of the bucket's keys onto NBF fine buckets (LDS histogram, the atomic's return value is the slot),
-// exclusive prefix sum, scatter into fine-bucket order, and every key counts the members of its own fine bucket that
-// are < / <= itself: B = (keys in earlier value buckets) + base + less, A = n_real - (... + base + le).  Ties are exact.
-// A value bucket whose keys are all equal is closed-form; one with a fine bucket above BR_CAP keys (heavy ties that
-// are not all equal, an infinity stretching the range) is flagged for bucket_search_kernel like before.
-constexpr int BR_NT = 512, BR_E = BK_CE, BR_LNB = 12, BR_NBF = 1 << BR_LNB, BR_CAP = 63, BR_TRYB = 4, BR_U2 = 3, BR_PAD = 8;
-static_assert(((BR_CAP + 1) & BR_CAP) == 0, "the crowding test reads the counters' bits");
-constexpr int BR_NW = BR_NT / 64;
-static_assert(BR_NT * BR_E == BK_C, "one thread slot per key of a full value bucket");
-static_assert(BR_NBF / 2 / BR_NT == 4, "one 16-byte quad of histogram words per thread");
-constexpr size_t BR_HDR = 256;                                         // min/max partials [NW][2] doubles, wave totals [NW]
-constexpr size_t BR_LDS = BR_HDR + (size_t)(BR_NBF / 2 + 4) * 4 + (size_t)(BK_C + BR_PAD + 2 * BR_U2 + 4) * 8;
-
-__device__ __forceinline__ void bucket_rank_item(const int w, i64 n, i64 rows, int NB, const u32 *__restrict__ bcnt,
-                                                 const u32 *__restrict__ nnanrow, const u32 *__restrict__ ovf,
-                                                 const u32 *__restrict__ rowtied, const double *__restrict__ bval,
-                                                 const u32 *__restrict__ bidx, u32 *__restrict__ bflag,
-                                                 u32 *__restrict__ gate, u32 epoch, AB2 ab) {
-    constexpr int E = BR_E, NT = BR_NT, NBF = BR_NBF, NW = BR_NW, U2 = BR_U2;
-    extern __shared__ double Sm[];
-    double *red = Sm;                                                 // [NW][2]
-    u32 *wtot = reinterpret_cast<u32 *>(red + 2 * NW);                // [NW], then the sum of the earlier buckets' counts
-    u32 *H = reinterpret_cast<u32 *>(Sm + BR_HDR / 8);                // NBF packed u16 counters, then bases
-    double *S = reinterpret_cast<double *>(H + NBF / 2 + 4);          // keys in fine-bucket order + NaN sentinels
-    const unsigned short *H16 = reinterpret_cast<const unsigned short *>(H);
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    // XCD-aware mapping (workgroups go to the 8 XCDs round-robin): all value buckets of a row run on ONE XCD, close in
-    // time, so the 8-byte pair writes they scatter over that row of the image meet in that XCD's L2 and leave it as
-    // whole lines.  grid.x = 8 * NB * ceil(rows / 8).
-    const int b = (w >> 3) % NB;
-    const i64 rb = (i64)((w >> 3) / NB) * 8 + (w & 7);
-    if (rb >= rows) return;
-    if (ovf[rb]) return;
-    if (rowtied && !rowtied[rb]) return;                              // third generation: only the rows flagged "tied"
-    const u32 *rowcnt = bcnt + rb * NB;
-    const int cnt = (int)rowcnt[b];
-    if (cnt == 0) return;
-    const double INF = __builtin_huge_val();
-    const double QNAN = __builtin_nan("");
-    const size_t slot0 = ((size_t)rb * NB + b) * BK_C;
-
-    // keys of thread t: slots t, t + NT, ... (coalesced); slots beyond cnt read as NaN = "no key"
-    double k[E];
-    {
-        const double *rp = bval + slot0 + t;
-#pragma unroll
-        for (int e = 0; e < E; ++e) k[e] = (t + e * NT < cnt) ? rp[e * NT] : QNAN;
-    }
-    // keys in earlier value buckets of this row
-    u32 gsum = 0;
-    for (int q = t; q < b; q += NT) gsum += rowcnt[q];
-    gsum = rb_wave_incl_scan(gsum);
-    // LDS setup: empty histogram, sentinels behind the last key
-    reinterpret_cast<uint4 *>(H)[t] = make_uint4(0, 0, 0, 0);
-    if (t < 4) H[NBF / 2 + t] = 0;
-    if (t < BR_PAD + 2 * U2 + 4) S[cnt + t] = QNAN;
-    // range
-    double mn = INF, mx = -INF;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (e * NT >= cnt) break;                                     // block-uniform: key slots beyond the bucket's fill
-        mn = rb_mm<false>(mn, k[e]);
-        mx = rb_mm<true>(mx, k[e]);
-    }
-    mn = rb_wave_allreduce<false>(mn);
-    mx = rb_wave_allreduce<true>(mx);
-    if (lane == 63) { red[2 * wave] = mn; red[2 * wave + 1] = mx; wtot[wave] = gsum; }
-    __syncthreads();                                                  // barrier 1
-    double lo, hi;
-    u32 gbase;
-    {
-        const double2 p = reinterpret_cast<const double2 *>(red)[lane & (NW - 1)];
-        lo = rb_readlane_f64(rb_row_allreduce<false>(p.x), 0);        // rotations over 16 lanes see each of the 8 twice
-        hi = rb_readlane_f64(rb_row_allreduce<true>(p.y), 0);
-        const u32 g = (lane < NW) ? wtot[lane] : 0u;
-        gbase = rb_readlane(rb_row_incl_scan(g), 15);
-    }
-    const u32 nreal = (u32)n - nnanrow[rb];
-    const size_t abrow = (size_t)(rb * n);
-    const u32 *idp = bidx + slot0 + t;
-    if (!(hi > lo)) {
-        // every key of the bucket has the same value (or there is one key): all tied
-        if (hi == lo) {
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                if (t + e * NT < cnt) ab_store(ab, abrow + idp[e * NT], gbase, nreal - gbase - (u32)cnt, nreal);
-        } else if (t == 0) { bflag[rb * NB + b] = 1u; if (gate) gate[0] = epoch; }                   // a signalling NaN poisoned the range: sort it
-        return;
-    }
-    const double scale = (double)NBF / (hi - lo);                     // infinite range -> 0 -> one crowded fine bucket
-    if (!(scale < INF)) {                                             // block-uniform: denormal range
-        if (t == 0) { bflag[rb * NB + b] = 1u; if (gate) gate[0] = epoch; }
-        return;
-    }
-    // ---- (1) fine bucket + slot ----
-    u32 bs[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (e * NT >= cnt) break;
-        const double x = k[e];
-        double u = (x - lo) * scale;
-        u = u > 0.0 ? u : 0.0;                                        // -inf (and NaN) -> 0
-        u = u < (double)(NBF - 1) ? u : (double)(NBF - 1);
-        u32 fb = (u32)u;
-        fb = (x == x) ? fb : (u32)(NBF + 2);                          // no key: dummy counter
-        const u32 sh = (fb & 1u) * 16u;
-        const u32 old = atomicAdd(&H[fb >> 1], 1u << sh);
-        bs[e] = fb | (((old >> sh) & 0xFFFFu) << 16);
-    }
-    __syncthreads();                                                  // barrier 2
-    // ---- (2) exclusive prefix sum; a fine bucket of 2^BR_TRYB keys or more: ties?  (checked behind the scatter) ----
-    bool anyover = false, anytry = false;
-    {
-        const uint4 hq = reinterpret_cast<const uint4 *>(H)[t];
-        // some counter > BR_CAP / >= 2^BR_TRYB: bit k of a half-word of the OR is set iff some counter has it
-        constexpr u32 HIM = (0xFFFFu & ~(u32)BR_CAP) * 0x10001u, TRM = (0xFFFFu & ~((1u << BR_TRYB) - 1u)) * 0x10001u;
-        const u32 s4 = hq.x + hq.y + hq.z + hq.w;
-        const u32 ov = hq.x | hq.y | hq.z | hq.w;
-        const u32 run = (s4 & 0xFFFFu) + (s4 >> 16);
-        const u32 incl = rb_wave_incl_scan(run);
-        const bool wover = __ballot((ov & HIM) != 0) != 0, wtry = __ballot((ov & TRM) != 0) != 0;
-        if (lane == 63) wtot[wave] = incl | (wover ? 0x80000000u : 0u) | (wtry ? 0x40000000u : 0u);
-        __syncthreads();                                              // barrier 3
-        const u32 wt = (lane < NW) ? wtot[lane] : 0u;
-        anyover = __ballot((wt >> 31) != 0) != 0;                     // block-uniform
-        anytry = __ballot((wt & 0x40000000u) != 0) != 0;
-        const u32 wscan = rb_row_incl_scan(wt & 0x3FFFFFFFu);
-        u32 base = (wave ? rb_readlane(wscan, wave - 1) : 0u) + incl - run;
-        uint4 o;
-        o.x = base | ((base + (hq.x & 0xFFFFu)) << 16);
-        base += (hq.x & 0xFFFFu) + (hq.x >> 16);
-        o.y = base | ((base + (hq.y & 0xFFFFu)) << 16);
-        base += (hq.y & 0xFFFFu) + (hq.y >> 16);
-        o.z = base | ((base + (hq.z & 0xFFFFu)) << 16);
-        base += (hq.z & 0xFFFFu) + (hq.z >> 16);
-        o.w = base | ((base + (hq.w & 0xFFFFu)) << 16);
-        base += (hq.w & 0xFFFFu) + (hq.w >> 16);
-        reinterpret_cast<uint4 *>(H)[t] = o;
-        if (t == NT - 1) H[NBF / 2] = base;                           // = cnt
-    }
-    __syncthreads();                                                  // barrier 4
-    // ---- (3) scatter into fine-bucket order ----
-    u32 bc[E];                                                        // base | count << 16; count 0: no key
-    const u32 dummy = (u32)(cnt + BR_PAD + 1) & ~1u;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (e * NT >= cnt) break;
-        const u32 fb = bs[e] & 0xFFFFu, slot = bs[e] >> 16;
-        const u32 base = H16[fb], end = H16[fb + 1];
-        const bool isk = fb < (u32)NBF;
-        S[isk ? base + slot : dummy] = k[e];
-        bc[e] = isk ? (base | ((end - base) << 16)) : 0u;
-    }
-    __syncthreads();                                                  // barrier 5
-    if (anytry) {                                                     // block-uniform
-        // tie-heavy data: when every fine bucket holds ONE value, less = 0 and le = count -- no member pass.
-        // Else: the normal way, or the search kernel when a fine bucket is above BR_CAP keys.
-        bool pure = true;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            if (e * NT >= cnt) break;
-            if (bc[e] >> 16) pure = pure && (S[bc[e] & 0xFFFFu] == k[e]);
-        }
-        if (__syncthreads_and(pure)) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                if (e * NT >= cnt) break;
-                const u32 base = bc[e] & 0xFFFFu, fc = bc[e] >> 16;
-                if (fc) ab_store(ab, abrow + idp[e * NT], gbase + base, nreal - (gbase + base + fc), nreal);
-            }
-            return;
-        }
-        if (anyover) {
-            if (t == 0) { bflag[rb * NB + b] = 1u; if (gate) gate[0] = epoch; }
-            return;
-        }
-    }
-    // ---- (4) rank inside the fine bucket (the keys are still in registers), write the pairs ----
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (e * NT >= cnt) break;
-        if ((e & 1) == 0) __builtin_amdgcn_sched_barrier(0);
-        const u32 base = bc[e] & 0xFFFFu, fc = bc[e] >> 16;
-        const u32 odd = base & 1u;
-        const double x = k[e];
-        const double2 *Sq = reinterpret_cast<const double2 *>(S + (base - odd));
-        u32 less = 0, le = 0;
-#pragma unroll
-        for (int u = 0; u < U2; ++u) {
-            const double2 y = Sq[u];
-            less += (y.x < x) ? 1u : 0u;
-            le += (y.x <= x) ? 1u : 0u;
-            less += (y.y < x) ? 1u : 0u;
-            le += (y.y <= x) ? 1u : 0u;
-        }
-        less -= odd;
-        le -= odd;
-        if (fc + odd > (u32)(2 * U2)) {                               // a fine bucket longer than the window
-            for (u32 kk = 2 * U2; kk < fc + odd; kk += 2) {
-                const double2 y = Sq[kk >> 1];
-                less += (y.x < x) ? 1u : 0u;
-                le += (y.x <= x) ? 1u : 0u;
-                less += (y.y < x) ? 1u : 0u;
-                le += (y.y <= x) ? 1u : 0u;
-            }
-        }
-        if (fc) ab_store(ab, abrow + idp[e * NT], gbase + base + less, nreal - (gbase + base + le), nreal);
-    }
-}
-
-
-#ifdef SD_CROSSCHECK
-// A' as a kernel of its own (second generation, cross-check builds): grid = 8 * NB * ceil(rows / 8), every row
-__global__ __launch_bounds__(BR_NT) void bucket_rank_kernel(i64 n, i64 rows, int NB, const u32 *__restrict__ bcnt,
-                                                            const u32 *__restrict__ nnanrow,
-                                                            const u32 *__restrict__ ovf,
-                                                            const double *__restrict__ bval,
-                                                            const u32 *__restrict__ bidx, u32 *__restrict__ bflag,
-                                                            AB2 ab) {
-    bucket_rank_item(blockIdx.x, n, rows, NB, bcnt, nnanrow, ovf, nullptr, bval, bidx, bflag, nullptr, 0u, ab);
-}
-#endif
-
 // =====================================================================================================
-// route 1, third generation (round 3): 8-byte records, table-driven partition, 32-bit ranking
+// S3 / P3 / A3
 // =====================================================================================================
-// What changed against S / P' / A' above, and why (profiles/r02b_config3_*): P' spent 91 VALU + 46 SALU per key on a
-// binary search over the splitters and wrote 12-byte records; A' compared fp64 keys (half rate on MI355X) out of 8-byte
-// LDS slots with 63 % of its LDS cycles lost to bank conflicts; three fallback launches of full grids did nothing.
-//   S3 bucket_setup_kernel      the sample sort of S, then per row: NB + 1 splitters (the sample's extremes are splitters
-//                               too: the keys beyond them form two small end buckets), a LOOK-UP TABLE over TB_C cells of
-//                               the monotone map c(x) = trunc((x - lo) * scale) holding, per cell, the number of splitters
-//                               in earlier cells and up to this cell; a "tied" flag when the sorted sample has two equal
-//                               neighbours; and the zeroing of the row's counters (no memset launch).
-//   P3 bucket_partition3_kernel bucket(x) = number of splitters < x as before, but from the table: a compare is needed
-//                               only in cells that a splitter cuts.  Records are 8 bytes: the curve index and a 32-bit
-//                               IMAGE q of the key, monotone inside its bucket (interior buckets: linear between the two
-//                               splitters; end buckets: a float-like code of the distance to the splitter in representable
-//                               doubles) -- equal keys have equal images, different keys almost always different ones.
-//                               Rows flagged "tied" keep the 12-byte fp64 records (their images would collide en masse).
-//   A3 bucket_rank32_kernel     the bucket ranking of A' on the 32-bit images: 4-byte LDS slots, integer compares, no
-//                               range reduction in fp64.  A key whose image equals another member's settles the order of
-//                               those members with their fp64 values (gathered from the matrix through the records' curve
-//                               indices): exact whatever the data, cheap because it is rare on continuous data.
-//                               Tied rows go through bucket_rank_kernel (fp64) as before.
 constexpr int TB_C = 2048;                                             // cells of the partition's look-up table
 constexpr int S3_RUN = 4;                                              // neighbours per sample position (bucket_setup_kernel)
 constexpr u32 Q_MAX = 0xFFFFFFFEu;                                     // largest image (0xFFFFFFFF = "no key" in LDS)
@@ -1315,87 +595,6 @@ __global__ __launch_bounds__(A3_NT) void bucket_rank32_kernel(const double *__re
     }
 }
 
-// B: persistent 1-D grid over the (row, bucket) pairs, flagged buckets only (nothing flagged: every workgroup reads a few
-// flags and leaves).  rowtied == nullptr or rowtied[row]: fp64 records (bval, bidx); else 8-byte records whose keys are
-// gathered from the matrix through their curve indices.
-template <int NT, int E>
-__device__ __forceinline__ void bucket_search_items(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, int NB,
-                                                    const u32 *__restrict__ bcnt, const u32 *__restrict__ nnanrow,
-                                                    const u32 *__restrict__ bflag, const u32 *__restrict__ rowtied,
-                                                    const double *__restrict__ bval, const u32 *__restrict__ bidx,
-                                                    const AB2 &ab, double *Sm) {
-    using C = R2Cfg<NT, E>;
-    constexpr int LE = C::LE, WB = C::WB, N = C::N;
-    static_assert(NT * E >= BK_C, "a value bucket fits the sort");
-    __shared__ u32 s_basecnt;
-    const u64 *rec = reinterpret_cast<const u64 *>(bval);
-    for (i64 v = blockIdx.x; v < rows * NB; v += gridDim.x) {
-        if (!bflag[v]) continue;                                      // block-uniform
-        int t = threadIdx.x;
-        asm volatile("" : "+v"(t));                                   // per-item opaque thread id
-        const int lane = t & 63, wave = t >> 6;
-        const int b = (int)(v % NB);
-        const i64 rb = v / NB;
-        const bool packed = rowtied && !rowtied[rb];
-        const double *yrow = Y + (row0 + rb) * n;
-        const int cnt = (int)bcnt[rb * NB + b];
-        __syncthreads();                                              // the previous item's image is no longer read
-        if (t == 0) {
-            u32 sum = 0;
-            for (int q = 0; q < b; ++q) sum += bcnt[rb * NB + q];
-            s_basecnt = sum;
-        }
-        const int n_act = ((cnt + WB - 1) / WB) * WB;
-        const bool wreal = wave * WB < n_act;
-        const double INF = __builtin_huge_val();
-        const size_t slot0 = ((size_t)rb * NB + b) * BK_C;
-        const int i0 = wave * WB + lane;
-        double k[E];
-        if (wreal) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int j = i0 + e * 64;
-                k[e] = (j < cnt) ? (packed ? yrow[(u32)(rec[slot0 + j] >> 32)] : bval[slot0 + j]) : INF;
-            }
-        }
-        R2Sorter<NT, E>::sort(k, Sm, t, n_act, wreal, INF);
-        if (wreal) {
-            double *Sw = Sm + r2_base<0, LE>(t);
-#pragma unroll
-            for (int e = 0; e < E; ++e) Sw[r2_off<0, LE>(e)] = k[e];
-        }
-        __syncthreads();
-        const u32 base = s_basecnt;
-        const u32 nreal = (u32)n - nnanrow[rb];
-        for (int j = t; j < cnt; j += NT) {
-            const u32 id = packed ? (u32)(rec[slot0 + j] >> 32) : bidx[slot0 + j];
-            const double x = packed ? yrow[id] : bval[slot0 + j];
-            int lo = r2_bound<N, SlotPad<LE>, false, false>(Sm, n_act, x, INF);       // x is in the bucket
-            int hi = lo + 1, step = 1;
-            while (hi + step <= n_act && Sm[r2_phys<LE>(hi + step - 1)] <= x) { hi += step; step <<= 1; }
-            while (step > 1) {
-                step >>= 1;
-                if (hi + step <= n_act && Sm[r2_phys<LE>(hi + step - 1)] <= x) hi += step;
-            }
-            // values above x: everything real beyond x's tie run (x = +inf: the padding ties with it, nothing is above)
-            ab_store(ab, (size_t)(rb * n + id), base + (u32)lo, (x == INF) ? 0u : nreal - (base + (u32)hi), nreal);
-        }
-    }
-}
-
-__global__ __launch_bounds__(BK_NT) void bucket_search_kernel(const double *__restrict__ Y, i64 n, i64 row0, i64 rows, int NB,
-                                                              const u32 *__restrict__ bcnt,
-                                                              const u32 *__restrict__ nnanrow,
-                                                              const u32 *__restrict__ bflag,
-                                                              const u32 *__restrict__ rowtied,
-                                                              const double *__restrict__ bval,
-                                                              const u32 *__restrict__ bidx,
-                                                              const u32 *__restrict__ gate, u32 epoch, AB2 ab) {
-    extern __shared__ double Sm[];
-    if (gate && *gate != epoch) return;                               // no bucket of this batch was flagged
-    bucket_search_items<BK_NT, BK_E>(Y, n, row0, rows, NB, bcnt, nnanrow, bflag, rowtied, bval, bidx, ab, Sm);
-}
-
 // The three fall-backs of a batch in ONE launch (product path): flagged value buckets (gate[0]), then the chunked route for
 // the rows whose partition overflowed (gate[1]): every workgroup sorts its share of the rows' chunks, the grid meets at a
 // counter, every workgroup searches its share of (row, chunk) items.  Nothing flagged: every workgroup reads the two gate
@@ -1800,64 +999,44 @@ static int big_run(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin
     const BigPlan p = big_plan(T, n);
     if (!ws || ws_bytes < p.total) return fail(SD_ERR_WORKSPACE, "large-n rank workspace too small");
     char *w = (char *)(((size_t)ws + 255) / 256 * 256);
-    AB2 ab;                                                 // per batch: rpb * n words of B, then as many of A
-    ab.B = (u32 *)(w + p.off_ab);
-    ab.A = ab.B + (size_t)p.rpb * n;
-    ab.H = nullptr;
-    double *sorted = (double *)(w + p.off_sorted);
-    double *bval = (double *)(w + p.off_bval);
-    u32 *bidx = (u32 *)(w + p.off_bidx);
-    double *spl = (double *)(w + p.off_spl);
-    double *mk = (double *)(w + p.off_mk);
-    u32 *tab = (u32 *)(w + p.off_tab);
-    double2 *rp = (double2 *)(w + p.off_rp);
-    char *zb = w + p.off_zero;
-    u32 *bcnt = (u32 *)(zb + p.z_bcnt), *nnanrow = (u32 *)(zb + p.z_nnan), *ovf = (u32 *)(zb + p.z_ovf);
-    u32 *bflag = (u32 *)(zb + p.z_bflag), *nanf = (u32 *)(zb + p.z_nanf), *rowtied = (u32 *)(zb + p.z_tied);
-    u32 *gate = (u32 *)(zb + p.z_gate);
-    u32 *meet = (u32 *)(zb + p.z_meet);
+    BigBatch b;
+    b.Y = Y, b.n = n, b.nch = p.nch, b.sstride = p.sstride, b.NB = p.NB, b.NBT = p.NBT;
+    b.ab.B = (u32 *)(w + p.off_ab);                         // per batch: rpb * n words of B, then as many of A
+    b.ab.A = b.ab.B + (size_t)p.rpb * n;
+    b.ab.H = nullptr;
+    b.sorted = (double *)(w + p.off_sorted);
+    b.bval = (double *)(w + p.off_bval);
+    b.bidx = (u32 *)(w + p.off_bidx);
+    b.spl = (double *)(w + p.off_spl);
+    b.mk = (double *)(w + p.off_mk);
+    b.tab = (u32 *)(w + p.off_tab);
+    b.rp = (double2 *)(w + p.off_rp);
+    char *zb = b.zero = w + p.off_zero;
+    b.zero_bytes = p.zero_bytes;
+    b.bcnt = (u32 *)(zb + p.z_bcnt), b.nnanrow = (u32 *)(zb + p.z_nnan), b.ovf = (u32 *)(zb + p.z_ovf);
+    b.bflag = (u32 *)(zb + p.z_bflag), b.nanf = (u32 *)(zb + p.z_nanf), b.rowtied = (u32 *)(zb + p.z_tied);
+    b.gate = (u32 *)(zb + p.z_gate);
+    b.meet = (u32 *)(zb + p.z_meet);
     // A gate word is "set" when it holds the batch's epoch (a process-wide counter, never 0): nothing has to zero it, and
-    // stale workspace contents can at worst make a fallback kernel scan flags that S3 has zeroed -- time, never results.
+    // stale workspace contents can at worst make the fall-back kernel scan flags that S3 has zeroed -- time, never results.
     static std::atomic<u32> epoch_counter{0};
 
-    const bool buckets = xswitch("SD_BIG_IMPL") != 1;       // cross-check builds, 1: chunked route for every row
-#ifdef SD_CROSSCHECK
+    // cross-check builds: a retired generation ranks the batches (mbd_rank_big_retired.hip)
     const bool gen2 = xswitch("SD_BIG_GEN2") == 1 || xswitch("SD_BIG_SORT") == 1 || xswitch("SD_BIG_PART1") == 1;
-#else
-    const bool gen2 = false;
-#endif
+    const bool retired = gen2 || xswitch("SD_BIG_IMPL") == 1;
     // fold mode up to 131 070 curves: the half-word image (cross-check builds, SD_BIG_NOHALF = 1: B words as before; the second
     // generation's packed kernel writes B words only)
-    if (!img_out && !gen2 && n <= AB2_H_MAXN && xswitch("SD_BIG_NOHALF") != 1) ab.H = (unsigned short *)(w + p.off_h);
+    if (!img_out && !gen2 && n <= AB2_H_MAXN && xswitch("SD_BIG_NOHALF") != 1) b.ab.H = (unsigned short *)(w + p.off_h);
     const int NB = p.NB, NBT = p.NBT;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    const unsigned pgrid = (unsigned)cus;                   // small persistent grids of the fallback kernels
-    // The merged fall-back kernel's workgroups wait for each other: its grid is what the launch's CUs hold at once
-    // (one workgroup on each CU the stream may use), never more.
-    unsigned fgrid = 1;
+    // The fall-back kernel's workgroups wait for each other: its grid is what the launch's CUs hold at once
+    // (one workgroup on each CU the stream may use; a kernel that launches at all fits once), never more.
+    const int usable = stream_cus(s);
+    unsigned fgrid = (unsigned)(usable < 1 ? 1 : usable);
+    if (fgrid > (unsigned)FB_MAXGRID) fgrid = FB_MAXGRID;
     // polls (about a microsecond each) before a waiting workgroup leaves its items to the last arriver; cross-check builds:
     // SD_BIG_SPIN = 1 makes every workgroup but the last give up at once (the take-over path under test)
     u32 spin_limit = 1u << 20;
     if (xswitch("SD_BIG_SPIN") > 0) spin_limit = (u32)xswitch("SD_BIG_SPIN") - 1u;
-    {
-        int usable = cus;
-        uint32_t mask[16] = {0};
-        if (hipExtStreamGetCUMask(s, 16, mask) == hipSuccess) {
-            int bits = 0;
-            for (int i = 0; i < 16; ++i) bits += __builtin_popcount(mask[i]);
-            if (bits > 0 && bits < usable) usable = bits;
-        } else {
-            (void)hipGetLastError();
-        }
-        fgrid = (unsigned)(usable < 1 ? 1 : usable);         // one workgroup per CU (a kernel that launches at all fits once)
-        if (fgrid > (unsigned)FB_MAXGRID) fgrid = FB_MAXGRID;
-    }
-    auto k_cs = chunk_sort_kernel;
-    auto k_cq = chunk_search_kernel;
     // sample per row: 2 048 values up to 24 value buckets (>= 85 samples per bucket), 4 096 up to 72, 16 384 above.
     // The sort of the sample by ONE workgroup is pure latency in front of the partition (4 096 keys: 33 us, as 256 x 16
     // or 1024 x 4 alike), so the sample is no larger than the buckets' capacity margin needs.
@@ -1866,117 +1045,53 @@ static int big_run(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin
     auto k_s3_big = bucket_setup_kernel<1024, 16>;
     constexpr size_t lds_sp_small = R2Cfg<128, 16>::LDS_BYTES, lds_sp = R2Cfg<256, 16>::LDS_BYTES;
     constexpr size_t lds_sp_big = R2Cfg<1024, 16>::LDS_BYTES;
-    auto k_bs = bucket_search_kernel;
     const size_t lds_p3 = p3_lds_bytes(NBT);
-    SD_HIP(hipFuncSetAttribute((const void *)k_cs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BigCfg::LDS_BYTES));
-    SD_HIP(hipFuncSetAttribute((const void *)k_cq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BigCfg::LDS_BYTES));
     SD_HIP(hipFuncSetAttribute((const void *)k_s3_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp_small));
     SD_HIP(hipFuncSetAttribute((const void *)k_s3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp));
     SD_HIP(hipFuncSetAttribute((const void *)k_s3_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp_big));
     SD_HIP(hipFuncSetAttribute((const void *)bucket_partition3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p3));
     SD_HIP(hipFuncSetAttribute((const void *)bucket_rank32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A3_LDS));
-    SD_HIP(hipFuncSetAttribute((const void *)k_bs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BkCfg::LDS_BYTES));
     SD_HIP(hipFuncSetAttribute((const void *)big_fallback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BigCfg::LDS_BYTES));
-#ifdef SD_CROSSCHECK
-    auto k_br = bucket_rank_kernel;
-    SD_HIP(hipFuncSetAttribute((const void *)k_br, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BR_LDS));
-    auto k_bp = bucket_packed_kernel;
-    auto k_sp_small = bucket_splitters_kernel<128, 16>;
-    auto k_sp = bucket_splitters_kernel<256, 16>;
-    auto k_sp_big = bucket_splitters_kernel<1024, 16>;
-    const size_t lds_bk = BkCfg::LDS_BYTES + (size_t)BK_NT * 8;
-    SD_HIP(hipFuncSetAttribute((const void *)k_sp_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp_small));
-    SD_HIP(hipFuncSetAttribute((const void *)k_sp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp));
-    SD_HIP(hipFuncSetAttribute((const void *)k_sp_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp_big));
-    SD_HIP(hipFuncSetAttribute((const void *)k_bp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bk));
-    SD_HIP(hipFuncSetAttribute((const void *)bucket_partition2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)((size_t)BP2_C * 14)));
-#endif
 
     for (i64 row0 = 0; row0 < T; row0 += p.rpb) {
         const i64 rows = T - row0 < p.rpb ? T - row0 : p.rpb;
-        const u32 *fallback_rows = nullptr;                  // chunked route: every row
-        const u32 *nn_for_fold = nanf;
-        const u32 *gate_o = nullptr;                         // no gate: the chunk kernels look at every row flag
-        bool merged = false;
-        if (img_out) ab.B = img_out + (size_t)row0 * n;      // image mode: the B words straight into the caller's image
+        b.row0 = row0, b.rows = rows;
+        const u32 *nn_for_fold = b.nnanrow;
+        if (img_out) b.ab.B = img_out + (size_t)row0 * n;    // image mode: the B words straight into the caller's image
         u32 epoch = ++epoch_counter;
         if (epoch == 0) epoch = ++epoch_counter;
-        if (!buckets || gen2) SD_HIP(hipMemsetAsync(zb, 0, p.zero_bytes, s));      // (the third generation's S3 zeroes)
-        if (buckets && !gen2) {
-            // ---- third generation: S3 -> P3 -> A3 (untied rows) / A' (tied rows) ----
+        if (retired) {
+            const int rc = retired_big_rank_batch(b, s, &nn_for_fold);
+            if (rc) return rc;
+        } else {
+            // ---- S3 -> P3 -> A3 (tied rows: its fp64 form) -> the fall-backs behind their gate words ----
             if (NB <= S3_SMALL_NB)
-                hipLaunchKernelGGL(k_s3_small, dim3((unsigned)rows), dim3(128), lds_sp_small, s, Y, n, row0, NB, spl, mk, tab,
-                                   rp, rowtied, bcnt, bflag, nnanrow, ovf, nanf, meet);
+                hipLaunchKernelGGL(k_s3_small, dim3((unsigned)rows), dim3(128), lds_sp_small, s, Y, n, row0, NB, b.spl, b.mk,
+                                   b.tab, b.rp, b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
             else if (NB <= S3_MID_NB)
-                hipLaunchKernelGGL(k_s3, dim3((unsigned)rows), dim3(256), lds_sp, s, Y, n, row0, NB, spl, mk, tab, rp,
-                                   rowtied, bcnt, bflag, nnanrow, ovf, nanf, meet);
+                hipLaunchKernelGGL(k_s3, dim3((unsigned)rows), dim3(256), lds_sp, s, Y, n, row0, NB, b.spl, b.mk, b.tab, b.rp,
+                                   b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
             else
-                hipLaunchKernelGGL(k_s3_big, dim3((unsigned)rows), dim3(1024), lds_sp_big, s, Y, n, row0, NB, spl, mk, tab,
-                                   rp, rowtied, bcnt, bflag, nnanrow, ovf, nanf, meet);
+                hipLaunchKernelGGL(k_s3_big, dim3((unsigned)rows), dim3(1024), lds_sp_big, s, Y, n, row0, NB, b.spl, b.mk,
+                                   b.tab, b.rp, b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
             hipLaunchKernelGGL(bucket_partition3_kernel, dim3((unsigned)((n + P3_C - 1) / P3_C), (unsigned)rows), dim3(P3_NT),
-                               lds_p3, s, Y, n, row0, NBT, (const double *)spl, (const double *)mk, (const u32 *)tab,
-                               (const double2 *)rp, (const u32 *)rowtied, bcnt, nnanrow, ovf, (u64 *)bval, bidx, gate, epoch, ab);
+                               lds_p3, s, Y, n, row0, NBT, (const double *)b.spl, (const double *)b.mk, (const u32 *)b.tab,
+                               (const double2 *)b.rp, (const u32 *)b.rowtied, b.bcnt, b.nnanrow, b.ovf, (u64 *)b.bval, b.bidx,
+                               b.gate, epoch, b.ab);
             hipLaunchKernelGGL(bucket_rank32_kernel, dim3((unsigned)(8 * NBT * ((rows + 7) / 8))), dim3(A3_NT), A3_LDS, s, Y, n,
-                               row0, rows, NBT, (const u32 *)bcnt, (const u32 *)nnanrow, (const u32 *)ovf,
-                               (const u32 *)rowtied, (const u64 *)bval, (const u32 *)bidx, bflag, gate, epoch, ab);
-            // the fall-backs (flagged buckets; chunked route for rows whose partition overflowed) behind their gate words
+                               row0, rows, NBT, (const u32 *)b.bcnt, (const u32 *)b.nnanrow, (const u32 *)b.ovf,
+                               (const u32 *)b.rowtied, (const u64 *)b.bval, (const u32 *)b.bidx, b.bflag, b.gate, epoch, b.ab);
             hipLaunchKernelGGL(big_fallback_kernel, dim3(fgrid), dim3(BIG_NT), BigCfg::LDS_BYTES, s, Y, n, row0, rows, NBT,
-                               (const u32 *)bcnt, (const u32 *)nnanrow, (const u32 *)bflag, (const u32 *)rowtied,
-                               (const double *)bval, (const u32 *)bidx, sorted, p.sstride, nanf, (int)p.nch,
-                               (const u32 *)ovf, (const u32 *)gate, epoch, meet, spin_limit, ab);
-            fallback_rows = ovf;
-            nn_for_fold = nnanrow;
-            gate_o = gate + 1;
-            merged = true;
+                               (const u32 *)b.bcnt, (const u32 *)b.nnanrow, (const u32 *)b.bflag, (const u32 *)b.rowtied,
+                               (const double *)b.bval, (const u32 *)b.bidx, b.sorted, p.sstride, b.nanf, (int)p.nch,
+                               (const u32 *)b.ovf, (const u32 *)b.gate, epoch, b.meet, spin_limit, b.ab);
+            SD_HIP(hipGetLastError());
         }
-#ifdef SD_CROSSCHECK
-        if (buckets && gen2) {
-            // ---- second generation (cross-check builds): S -> P' (or P) -> A' (or the packed-key sort) ----
-            const bool rank_nosort = xswitch("SD_BIG_SORT") != 1;
-            if (NB <= 24)
-                hipLaunchKernelGGL(k_sp_small, dim3((unsigned)rows), dim3(128), lds_sp_small, s, Y, n, row0, NB, spl);
-            else if (NB <= 72)
-                hipLaunchKernelGGL(k_sp, dim3((unsigned)rows), dim3(256), lds_sp, s, Y, n, row0, NB, spl);
-            else
-                hipLaunchKernelGGL(k_sp_big, dim3((unsigned)rows), dim3(1024), lds_sp_big, s, Y, n, row0, NB, spl);
-            if (xswitch("SD_BIG_PART1") == 1)                    // first-generation partition (direct scatter)
-                hipLaunchKernelGGL(bucket_partition_kernel, dim3((unsigned)((n + 16383) / 16384), (unsigned)rows), dim3(1024),
-                                   0, s, Y, n, row0, NB, (const double *)spl, bcnt, nnanrow, ovf, bval, bidx, ab, 0);
-            else
-                hipLaunchKernelGGL(bucket_partition2_kernel, dim3((unsigned)((n + BP2_C - 1) / BP2_C), (unsigned)rows),
-                                   dim3(BP2_NT), (size_t)BP2_C * 14, s, Y, n, row0, NB, (const double *)spl, bcnt, nnanrow,
-                                   ovf, bval, bidx, ab);
-            if (!rank_nosort)
-                hipLaunchKernelGGL(k_bp, dim3((unsigned)NB, (unsigned)rows), dim3(BK_NT), lds_bk, s, n, NB, (const u32 *)bcnt,
-                                   (const u32 *)nnanrow, (const u32 *)ovf, (const double *)bval, (const u32 *)bidx, bflag, ab);
-            else
-                hipLaunchKernelGGL(k_br, dim3((unsigned)(8 * NB * ((rows + 7) / 8))), dim3(BR_NT), BR_LDS, s, n, rows, NB,
-                                   (const u32 *)bcnt, (const u32 *)nnanrow, (const u32 *)ovf,
-                                   (const double *)bval, (const u32 *)bidx, bflag, ab);
-            hipLaunchKernelGGL(k_bs, dim3(pgrid), dim3(BK_NT), BkCfg::LDS_BYTES, s, Y, n, row0, rows, NB, (const u32 *)bcnt,
-                               (const u32 *)nnanrow, (const u32 *)bflag, (const u32 *)nullptr, (const double *)bval,
-                               (const u32 *)bidx, (const u32 *)nullptr, 0u, ab);
-            fallback_rows = ovf;
-            nn_for_fold = nnanrow;
-        }
-#endif
-        // chunked route: every row (cross-check switches)
-        if (!merged) {
-        const unsigned csgrid = fallback_rows ? pgrid : (unsigned)(p.nch * rows < 65535 * 16 ? p.nch * rows : 65535 * 16);
-        hipLaunchKernelGGL(k_cs, dim3(csgrid), dim3(BIG_NT), BigCfg::LDS_BYTES, s, Y, n, row0, rows, p.nch,
-                           sorted, p.sstride, nanf, fallback_rows, gate_o, epoch);
-        i64 rgroups = cus / p.nch;
-        if (rgroups < 1) rgroups = 1;
-        if (rgroups > rows) rgroups = rows;
-        hipLaunchKernelGGL(k_cq, dim3((unsigned)(rgroups * p.nch)), dim3(BIG_NT), BigCfg::LDS_BYTES, s, Y, n, row0, rows,
-                           (const double *)sorted, p.sstride, (const u32 *)nanf, (int)p.nch, fallback_rows, gate_o, epoch, ab);
-        }
-        SD_HIP(hipGetLastError());
         if (img_out) {
             SD_HIP(hipMemcpyAsync(nnan_out + row0, nn_for_fold, (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
             continue;
         }
+        const AB2 &ab = b.ab;
         const int first = row0 == 0;
         if (ab.H && !targets && (n & 7) == 0 && (tbegin & 7) == 0 && J <= 3) {
             dim3 grid8((unsigned)((m + 127) / 128));

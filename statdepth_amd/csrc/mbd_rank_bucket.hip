@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "sd_common.h"
+#include "rank_routes.h"
 #include "rank_sort.h"
 #include "rank_bucket.h"
 
@@ -1023,25 +1024,13 @@ __global__ __launch_bounds__(256) void rank_finalize4_kernel(const u32 *__restri
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static int rb_cus() {
-    static int cached[64];                                // per device; 0 = not asked yet (benign race: same value)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        if (dev >= 0 && dev < 64) cached[dev] = cus;
-    }
-    return cus;
-}
-
 bool mbd_rank_bucket_supported(i64 T, i64 n, int J) {
     (void)T;
     return n > 1 && n <= 16384 && J >= 2 && J <= 3;       // measured faster than the sort kernels from n = 600 to 16384
 }
 
 // upper bound of the grid the launcher will use (the partial totals are sized by it)
-int mbd_rank_bucket_max_grid() { return 2 * rb_cus(); }
+int mbd_rank_bucket_max_grid() { return 2 * device_cus(); }
 
 // the workgroups' partial totals: all this path keeps in HBM
 size_t mbd_rank_bucket_partial_bytes(i64 n, int J) { return align_up((size_t)mbd_rank_bucket_max_grid() * (J - 1) * n * 8, 256); }
@@ -1087,16 +1076,8 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kf, 1024, lds) != hipSuccess || occ < 1) occ = 1;
             occ_cached = occ;
         }
-        int usable = rb_cus();
-        bool masked = false;
-        uint32_t mask[16] = {0};
-        if (hipExtStreamGetCUMask(s, 16, mask) == hipSuccess) {
-            int bits = 0;
-            for (int i = 0; i < 16; ++i) bits += __builtin_popcount(mask[i]);
-            if (bits > 0 && bits < usable) { usable = bits; masked = true; }
-        } else {
-            (void)hipGetLastError();
-        }
+        const int usable = stream_cus(s);
+        const bool masked = usable < device_cus();
         const long cap = (long)occ * usable;
         kspin = cap >= G ? 16 : (int)(cap - 1 < 16 ? cap - 1 : 16);
         // A masked stream: the launch's CUs are not one pool.  Workgroups are dealt to the 8 XCDs in turn and stay there, so a
@@ -1143,7 +1124,7 @@ static int launch_bucket_j(const double *Y, i64 n, i64 row0, i64 rows, u64 *part
 
 // image mode (J >= 4 on the host side): pairs of every (row, curve) to AB, NaN counts per row to nnan
 int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s) {
-    const int cus = rb_cus();
+    const int cus = device_cus();
     const int G = (int)(rows < cus ? rows : cus);
     if (rows > (i64)G * 2048) return fail(SD_ERR_INVALID, "bucket kernel: more than 2048 rows per workgroup in one launch");
     u64 *img = reinterpret_cast<u64 *>(AB);
@@ -1156,13 +1137,6 @@ int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB
     return fail(SD_ERR_UNSUPPORTED, "bucket kernel covers n <= 16384");
 }
 
-// mbd_rank_bucket32.hip: 32-bit key images, two workgroups per CU
-bool rank_bucket32_supported(i64 n, i64 rows, int cus);
-size_t rank_bucket32_extra_bytes(i64 rows);
-int launch_rank_bucket32(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
-                         u64 *out_zero, int G, hipStream_t s);
-u32 rank_bucket32_epoch();
-
 // J = 2, 4096 < n <= 11264, every curve a target: rank_bucket32_kernel (two workgroups per CU; zeroes out when `first`) + the
 // fp64 kernel's SEL form (sums the partial blocks into out; ranks the rows the first kernel flagged).  Two launches.  The
 // flags and the gate word sit behind the 2 * cus u32 partial blocks, inside the space sized for u64 blocks.
@@ -1170,12 +1144,12 @@ u32 rank_bucket32_epoch();
 // launch's blocks -- and, last, n u64 totals of ALL curves for calls that ask for a subset of the targets
 static size_t two_level_used_bytes(i64 n, i64 rows) {
     const size_t pst = (size_t)((n + 31) & ~31), nst = (size_t)((n + 3) & ~3);
-    return (size_t)2 * rb_cus() * pst * 4 + align_up((size_t)rows, 64) + 64 + 256 +
-           (size_t)rb_cus() * nst * 4 + 256;
+    return (size_t)2 * device_cus() * pst * 4 + align_up((size_t)rows, 64) + 64 + 256 +
+           (size_t)device_cus() * nst * 4 + 256;
 }
 bool rank_bucket_two_level_supported(i64 n, i64 rows) {
     // the all-totals block sits behind the largest batch's region (rank_bucket_two_level_all_totals): the same expression here
-    return rank_bucket32_supported(n, rows, rb_cus()) &&
+    return rank_bucket32_supported(n, rows, device_cus()) &&
            align_up(two_level_used_bytes(n, 4096), 256) + (size_t)n * 8 <= mbd_rank_bucket_partial_bytes(n, 2);
 }
 u64 *rank_bucket_two_level_all_totals(u64 *partial, i64 n) {        // sized for the largest batch (4 096 rows)
@@ -1195,7 +1169,7 @@ int launch_rank_gather_totals(const u64 *all, const i64 *targets, i64 tbegin, i6
 }
 
 int launch_rank_bucket_two_level(const double *Y, i64 n, i64 row0, i64 rows, u64 *partial, u64 *out, int first, hipStream_t s) {
-    const int cus = rb_cus();
+    const int cus = device_cus();
     const int G = (int)(rows < 2 * cus ? rows : 2 * cus);
     u32 *P32 = reinterpret_cast<u32 *>(partial);
     unsigned char *rowflag = reinterpret_cast<unsigned char *>(P32 + (size_t)2 * cus * ((n + 31) & ~31));   // blocks of whole lines
@@ -1219,7 +1193,7 @@ int launch_rank_bucket_two_level(const double *Y, i64 n, i64 row0, i64 rows, u64
 // blocks) in *G_out
 int launch_rank_bucket(const double *Y, i64 n, i64 row0, i64 rows, int J, u64 *partial, int *p32_out, int *G_out,
                        hipStream_t s) {
-    const int cus = rb_cus();                                         // one workgroup per CU
+    const int cus = device_cus();                                         // one workgroup per CU
     const int G = (int)(rows < cus ? rows : cus);
     *G_out = G;
     if (rows > (i64)G * 2048) return fail(SD_ERR_INVALID, "bucket kernel: more than 2048 rows per workgroup in one launch");
@@ -1525,7 +1499,7 @@ __global__ __launch_bounds__(NT) void rank_medium_image_kernel(const double *__r
 bool rank_medium_supported(i64 n) { return n > 16384 && n <= RB_MEDIUM_MAXN; }
 int launch_rank_medium_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s) {
     if (!rank_medium_supported(n)) return fail(SD_ERR_UNSUPPORTED, "medium image kernel covers 16384 < n <= %d", RB_MEDIUM_MAXN);
-    const int cus = rb_cus();
+    const int cus = device_cus();
     const int G = (int)(rows < cus ? rows : cus);
     const int nblk = (int)((n + 16383) / 16384);                                     // fewest blocks ...
     const int E = (int)((n + (i64)nblk * 1024 - 1) / ((i64)nblk * 1024));             // ... of equal size, whole thousands
@@ -1555,7 +1529,7 @@ bool mbd_rank_external_supported(i64 T, i64 n, i64 m, int J) {
 size_t mbd_rank_external_workspace_bytes(i64 T, i64 n, i64 m, int J) {
     if (!mbd_rank_external_supported(T, n, m, J)) return 0;
     const i64 mc = m < 8192 ? m : 8192;
-    return align_up((size_t)rb_cus() * (J - 1) * mc * 8, 256) + 512;
+    return align_up((size_t)device_cus() * (J - 1) * mc * 8, 256) + 512;
 }
 
 template <int E, int LNB, int J>
@@ -1583,7 +1557,7 @@ int launch_mbd_external_rank(const double *Y, i64 T, i64 n, const double *Q, i64
     if (!ws || ws_bytes < mbd_rank_external_workspace_bytes(T, n, m, J))
         return fail(SD_ERR_WORKSPACE, "external rank workspace too small");
     u64 *partial = (u64 *)(((size_t)ws + 255) / 256 * 256);
-    const int cus = rb_cus();
+    const int cus = device_cus();
     const int G = (int)(T < cus ? T : cus);
     const int E = (int)((n + 1023) / 1024);
     for (i64 q0 = 0; q0 < m; q0 += 8192) {

@@ -28,6 +28,7 @@
 #include <atomic>
 
 #include "sd_common.h"
+#include "rank_routes.h"
 #include "rank_bucket.h"
 
 namespace sd {

@@ -25,6 +25,31 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+int device_cus() {
+    static int cached[64];                                // per device; 0 = not asked yet (benign race: same value)
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) {
+        if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+        if (dev >= 0 && dev < 64) cached[dev] = cus;
+    }
+    return cus;
+}
+
+int stream_cus(hipStream_t s) {
+    int usable = device_cus();
+    uint32_t mask[16] = {0};
+    if (hipExtStreamGetCUMask(s, 16, mask) == hipSuccess) {
+        int bits = 0;
+        for (int i = 0; i < 16; ++i) bits += __builtin_popcount(mask[i]);
+        if (bits > 0 && bits < usable) usable = bits;
+    } else {
+        (void)hipGetLastError();
+    }
+    return usable;
+}
+
 bool binom_u64_checked(u64 a, int k, u64 *out) {
     if (k < 0 || (u64)k > a) { *out = 0; return true; }
     unsigned __int128 c = 1;

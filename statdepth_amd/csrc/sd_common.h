@@ -48,6 +48,11 @@ struct Carver {
 // reads the variable on every call.  xcheck.hip.
 long long xswitch(const char *name);
 
+// compute units of the current device (256 when the runtime does not say), and how many of them the stream may use (its
+// CU mask, when it has one that names fewer).  sd_api.hip.
+int device_cus();
+int stream_cus(hipStream_t s);
+
 // ---- launchers implemented in the kernel translation units ----
 // strided (t,i) -> time-major Y[t*n+i]
 int launch_to_time_major(const double *X, i64 T, i64 n, i64 st, i64 sn, double *Y, hipStream_t s);
