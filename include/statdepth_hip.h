@@ -271,7 +271,8 @@ int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d,
  * Fills: _r2_enum_containment (_containment.py:83-103), which the reference declares -- "treat each component in the
  * vector valued function as a real valued function ... if all the components are contained ... the function is
  * contained" -- and leaves as `raise NotImplementedError`; built as the predicate of _univariate_band_depth's pair
- * loop (_functional.py:238-253), J = 2, relax=True.  P is n x T x d row-major (curve, timepoint, feature), NaN-free.
+ * loop (_functional.py:238-253), relax=True; J = 2 here, J <= 4 below.  P is n x T x d row-major (curve, timepoint,
+ * feature), NaN-free.
  *   out[q] = sum_t #{pairs {a,b} of the other curves: for every feature f,
  *                    min(a_f(t), b_f(t)) <= x_q,f(t) <= max(a_f(t), b_f(t))};   depth = out / T / C(n,2) on the host
  * (d = 1 gives sd_mbd_counts' totals).  The strict form (contained at every t) is sd_bd_strict_j_counts over the
@@ -280,6 +281,18 @@ int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d,
 size_t sd_multi_band_workspace_bytes(int64_t n, int64_t T, int d);
 int sd_multi_band_counts(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m,
                          int64_t *out, void *ws, size_t ws_bytes, void *stream);
+/* The same predicate for the j-subsets of the other curves, every j = 2 .. J in one pass (J in [2, 4]): the lines
+ * _containment.py:83-103 would fill inside _univariate_band_depth's loop over j (_functional.py:238-253), relax=True.
+ *   out[q*(J-1) + j-2] = sum_t #{j-subsets S of the other curves: for every feature f,
+ *                               min_{a in S} a_f(t) <= x_q,f(t) <= max_{a in S} a_f(t)};
+ *   depth = sum_j out[q][j-2] / T / C(n,j) on the host, n counting the target (d = 1 gives sd_mbd_counts' totals).
+ * Counted without enumerating subsets: S fails at (t, f) iff all its members are strictly above x_f(t) or all strictly
+ * below, so with p in {don't care, all above, all below}^d and N_p = number of other curves matching p,
+ *   containing j-subsets at t = sum_p (-1)^(constrained features of p) C(N_p, j).
+ * Input limits and workspace (sd_multi_band_workspace_bytes) are those of sd_multi_band_counts.  SD_ERR_UNSUPPORTED for
+ * J outside [2, 4]; SD_ERR_OVERFLOW, before any launch, if T*C(n-1,J) >= 2^63 (as sd_mbd_counts). */
+int sd_multi_band_j_counts(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m, int J,
+                           int64_t *out /* m*(J-1) */, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- K7: Oja volume sums of a point cloud ------------------------------------------------
  * Replaces: the subset loop of _oja_depth (_pointcloud.py:175-205, one scipy ConvexHull per simplex).  P is n x d

@@ -65,6 +65,7 @@ SIGNATURES = {
     "sd_pointcloud_simplex_sampled": (_int, [_vp, _i64, _int, _vp, _i64, _dbl, _i64, _u64, _vp, _vp, _sz, _vp]),
     "sd_multi_band_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "sd_multi_band_counts": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sd_multi_band_j_counts": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
     "sd_multi_simplex_sampled": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _int, _dbl, _i64, _u64, _vp, _vp, _sz, _vp]),
     "sd_oja_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
     "sd_oja_external_volume_sums": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),

@@ -566,6 +566,20 @@ int sd_multi_band_counts(const double *P, int64_t n, int64_t T, int d, const int
     return launch_multi_band(P, n, T, d, targets, m, (u64 *)out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int sd_multi_band_j_counts(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m, int J,
+                           int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n <= 0 || T <= 0) return fail(SD_ERR_INVALID, "empty input");
+    if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "componentwise band containment covers d in [1,8], got %d", d);
+    if (J < 2 || J > 4) return fail(SD_ERR_UNSUPPORTED, "componentwise band containment counts j-subsets for J in [2,4], got %d", J);
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
+    int rc = check_count_range(T, n, J);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_multi_band_j(P, n, T, d, targets, m, J, (u64 *)out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m,
                              int relax, double tol, int64_t samples, uint64_t seed, int64_t *out, void *ws, size_t ws_bytes,
                              void *stream) {

@@ -122,6 +122,9 @@ bool multi_band_supported(i64 n, i64 T, int d);
 size_t multi_band_workspace_bytes(i64 n, i64 T, int d);
 int launch_multi_band(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, u64 *out, void *ws, size_t ws_bytes,
                       hipStream_t s);
+// every j = 2 .. J in one pass (J in [2, 4], checked by the caller): out[q * (J - 1) + j - 2]
+int launch_multi_band_j(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, int J, u64 *out, void *ws,
+                        size_t ws_bytes, hipStream_t s);
 
 // K7 Oja volume sums (oja.hip): out = sum of |det| / d! over the d-subsets of the others
 int launch_oja_volume_sums(const double *P, i64 n, int d, const i64 *targets, i64 m, double *out, hipStream_t s);

@@ -107,7 +107,8 @@ def _componentwise_band_depth(data: List[pd.DataFrame], to_compute, J: int, rela
 
     Built as `_univariate_band_depth` (:238-253) with that predicate: bands from j-subsets of the n-1 other curves,
     sum_j S_nj / binom(n, j) with n INCLUDING the target (:229,253) -- so one feature (d = 1) gives the univariate depth.
-    relax=True, J = 2: one launch (sd_multi_band_counts, pairs counted through the 3^d state classes).  relax=False
+    relax=True: one launch; J = 2 counts pairs through the 3^d state classes (sd_multi_band_counts), J = 3, 4 count
+    j-subsets by inclusion-exclusion over the same classes (sd_multi_band_j_counts).  relax=False
     (contained at every timepoint in every component) is the strict univariate depth of the T*d component series.
     """
     f = [i for i in range(len(data))] if to_compute is None else to_compute
@@ -116,9 +117,14 @@ def _componentwise_band_depth(data: List[pd.DataFrame], to_compute, J: int, rela
     tg = np.asarray(list(f), dtype=np.int64)
     depth = np.zeros(len(tg), dtype=np.float64)
     if relax:
-        if J != 2:
-            raise NotImplementedError("'r2_enum' with relax=True is implemented for J = 2")
-        depth += engine.multi_band_counts(P, tg, device=device).astype(np.float64) / T / binom(n, 2)
+        if J > 4:
+            raise NotImplementedError("'r2_enum' with relax=True is implemented for J <= 4")
+        if J == 2:
+            depth += engine.multi_band_counts(P, tg, device=device).astype(np.float64) / T / binom(n, 2)
+        else:
+            counts = engine.multi_band_j_counts(P, tg, J=J, device=device).astype(np.float64) / T
+            for j in range(2, J + 1):
+                depth += counts[:, j - 2] / binom(n, j)
     else:
         if J > 4:
             raise NotImplementedError('strict band depth (relax=False) is implemented for J <= 4')

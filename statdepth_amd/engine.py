@@ -536,3 +536,20 @@ def multi_band_counts(P, targets=None, device=None):
     out = t.empty(m, dtype=t.int64, device=dev)
     return _launch(dev, lib.sd_multi_band_counts, out, Pd.data_ptr(), n, T, d, tp, m,
                    workspace=lambda: _sized(dev, lib.sd_multi_band_workspace_bytes(n, T, d)))
+
+
+def multi_band_j_counts(P, targets=None, J=3, device=None):
+    """int64[m, J-1]: column j-2 = sum_t #{j-subsets of the other curves whose componentwise band contains the target at
+    t}, j = 2 .. J, J in [2, 4] (sd_multi_band_j_counts).  P: (n, T, d) curves, NaN-free."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 3, dev)
+    n, T, d = Pd.shape
+    if bool(t.isnan(Pd).any()):
+        raise ValueError("componentwise band containment ('r2_enum') does not accept NaN values")
+    td, m, tp = _targets_dev(targets, n, dev)
+    J = int(J)
+    out = t.empty((m, max(J - 1, 1)), dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_multi_band_j_counts, out, Pd.data_ptr(), n, T, d, tp, m, J,
+                   workspace=lambda: _sized(dev, lib.sd_multi_band_workspace_bytes(n, T, d)))

@@ -19,6 +19,8 @@ for c in range(cases):
     if rng.random() < 0.2: P[:, :, rng.integers(0, d)] = 0.5                   # a constant feature
     if not (engine.multi_band_counts(P) == oracle.multi_band_enum(P, None, 2, True)[:, 0]).all():
         bad += 1; print(f"K6 MISMATCH case {c}: n={n} T={T} d={d}", flush=True)
+    if not (engine.multi_band_j_counts(P, J=4) == oracle.multi_band_enum(P, None, 4, True)).all():       # j-subsets, j = 2 .. 4
+        bad += 1; print(f"K6 J=4 MISMATCH case {c}: n={n} T={T} d={d}", flush=True)
     # ---- point clouds: external targets and explicit blocks ----
     d = int(rng.integers(1, 6)); n = int(rng.integers(d + 2, d + 12)); m = int(rng.integers(1, 9))
     F = rng.normal(size=(n, d)); G = rng.normal(size=(m, d)) * 0.7

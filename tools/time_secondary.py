@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """One secondary workload, a few launches (for rocprofv3 / tools/pmc_rank.py).
-usage: time_secondary.py simplex8|simplex3|l1|strict|band [reps]"""
-import os, sys
+usage: time_secondary.py simplex8|simplex3|l1|strict|band [reps]
+band is config 4 (5 000 x 500 x 8, every target) in four legs of one run: the pair kernel (sd_multi_band_counts) and
+sd_multi_band_j_counts at J = 2, 3, 4."""
+import math, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,10 +33,16 @@ else:
     P = torch.from_numpy(rng.normal(size=(5000, 500, 8)).cumsum(axis=1)).cuda()
     fn = lambda: engine.multi_band_counts(P)
     units, label = 5000.0 * 4999 * 4998 / 2 * 500, "pair-timepoint containment tests (equivalent)"
-fn(); torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(reps): fn()
-e1.record(); torch.cuda.synchronize()
-ms = e0.elapsed_time(e1) / reps
-print(f"{what}: {ms:.3f} ms per call (incl. the D2H of the result), {units / (ms * 1e-3):.3e} {label}/s", flush=True)
+legs = [(what, fn, units, label)]
+if what == "band":
+    for J in (2, 3, 4):
+        legs.append((f"band J={J} (j-subset kernel)", lambda J=J: engine.multi_band_j_counts(P, J=J),
+                     5000.0 * sum(math.comb(4999, j) for j in range(2, J + 1)) * 500, "subset-timepoint containment tests (equivalent)"))
+for what, fn, units, label in legs:
+    fn(); torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps): fn()
+    e1.record(); torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    print(f"{what}: {ms:.3f} ms per call (incl. the D2H of the result), {units / (ms * 1e-3):.3e} {label}/s", flush=True)
