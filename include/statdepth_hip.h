@@ -353,6 +353,39 @@ int sd_prob_poisson_sums(const double *lam, int64_t T, int64_t n, int64_t lim, c
 int sd_prob_band_sums(const double *mu, const double *var, int64_t T, int64_t n, const int64_t *targets, int64_t m,
                       const int32_t *members, int bs, int relax, double *out, void *stream);
 
+/* ---- K10: halfspace (Tukey) depth of a point cloud over a fixed direction set ----------------
+ * No reference code (the reference has no halfspace depth).  P is n x d row-major, U is k x d row-major (both device).
+ *   z_r(x)   = ((x_0 u_r0 + x_1 u_r1) + x_2 u_r2) + ...   features in increasing order, every product and every sum
+ *              rounded separately to fp64 (no FMA): a numpy loop over the features gives the same bits;
+ *   ge_r(q)  = #{i : z_r(p_i) >= z_r(q)},  le_r(q) = #{i : z_r(p_i) <= z_r(q)}   (q itself and every tie counted);
+ *   out[q]   = min over r of min(ge_r(q), le_r(q))   (one direction serves u and -u);   depth = out / n on the host.
+ * This is the directional (random Tukey) depth: an upper bound of the exact halfspace depth for d >= 2, exact for
+ * d = 1 with the direction (1.0).  Projections must not be NaN (finite data and directions: the host checks).
+ *   sd_halfspace_counts:          the sample is P, targets: m int64 row indices (device), NULL = all (m == n).  Every
+ *       row is ranked in every direction whatever m is: projection (a kc x n fp64 matrix per chunk of kc directions),
+ *       sort with index payload (tiles of 2048 in LDS, then merge passes), ranks from the sorted rows, running minimum --
+ *       O(k n (d + log n)), no all-pairs pass.  kc follows from ws_bytes; sd_halfspace_workspace_bytes recommends a size,
+ *       sd_halfspace_min_workspace_bytes is the floor (one direction per chunk: about 28 n bytes), SD_ERR_WORKSPACE
+ *       below it.  The counts do not depend on the workspace size (integer minima).
+ *   sd_halfspace_pairwise_counts: the same counts by the pairwise kernel, O(m n k d) (cross-checks, timing).
+ *   sd_halfspace_external_counts: m external points Q (m x d, device) against P; the sample of Q[q] is P u {Q[q]}: the
+ *       counts are over n + 1 points (Q[q] counts itself once), depth = out / (n + 1).  Pairwise kernel.
+ *   sd_halfspace_subset_counts:   blocks of rows, members int32[nb*bs], -1 padded, the block's target LAST; the block
+ *       (target included) is the sample: depth = out / block size.  An empty block gives 0.  Pairwise kernel.
+ * SD_ERR_INVALID for NULL pointers or n, d, k < 1; SD_ERR_UNSUPPORTED for d > 8, 2^31 or more points, or more than
+ * 10^14 projections and comparisons (k n (d + log2 n), resp. m n k d).  All before any device work.  Every launch is
+ * bounded in work. */
+size_t sd_halfspace_workspace_bytes(int64_t n, int d, int64_t k);
+size_t sd_halfspace_min_workspace_bytes(int64_t n, int d, int64_t k);
+int sd_halfspace_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets, int64_t m,
+                        int64_t *out, void *ws, size_t ws_bytes, void *stream);
+int sd_halfspace_pairwise_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets,
+                                 int64_t m, int64_t *out, void *stream);
+int sd_halfspace_external_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const double *Q, int64_t m,
+                                 int64_t *out, void *stream);
+int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
+                               int64_t nb, int bs, int64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ SIGNATURES = {
     "sd_prob_normal_sums": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sd_prob_poisson_sums": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sd_prob_band_sums": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp]),
+    "sd_halfspace_workspace_bytes": (_sz, [_i64, _int, _i64]),
+    "sd_halfspace_min_workspace_bytes": (_sz, [_i64, _int, _i64]),
+    "sd_halfspace_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sd_halfspace_pairwise_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sd_halfspace_external_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sd_halfspace_subset_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
 }
 
 

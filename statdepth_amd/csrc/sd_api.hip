@@ -692,4 +692,73 @@ int sd_prob_band_sums(const double *mu, const double *var, int64_t T, int64_t n,
     return launch_prob_band_sums(mu, var, T, n, targets, m, members, bs, relax, out, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// K10
+// ---------------------------------------------------------------------------
+static constexpr double HS_MAX_WORK = 1e14;     // projections and comparisons: beyond this a call would run for hours
+
+// shape checks shared by the four entry points; `others` = points a target is compared with, work = the call's estimate
+static int check_halfspace(const double *P, i64 n, int d, const double *U, i64 k, i64 m, const void *out, i64 others,
+                           double work) {
+    if (!P || !U || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n < 1 || d < 1 || k < 1 || m < 0) return fail(SD_ERR_INVALID, "bad shape (n=%lld, d=%d, k=%lld, m=%lld)", (long long)n,
+                                                       d, (long long)k, (long long)m);
+    if (d > 8) return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
+    if (n >= ((i64)1 << 31) || others >= ((i64)1 << 31))          // counts and indices are 32-bit in the kernels
+        return fail(SD_ERR_UNSUPPORTED, "halfspace counts take fewer than 2^31 points, got %lld", (long long)n);
+    if (k >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "halfspace counts take fewer than 2^31 directions");
+    if (work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g projections and comparisons exceed the cap of %.0e", work, HS_MAX_WORK);
+    return SD_OK;
+}
+
+size_t sd_halfspace_workspace_bytes(int64_t n, int d, int64_t k) {
+    if (n < 1 || d < 1 || k < 1 || n >= ((i64)1 << 31)) return 0;
+    return halfspace_workspace_bytes(n, k);
+}
+
+size_t sd_halfspace_min_workspace_bytes(int64_t n, int d, int64_t k) {
+    if (n < 1 || d < 1 || k < 1 || n >= ((i64)1 << 31)) return 0;
+    return halfspace_min_workspace_bytes(n);
+}
+
+int sd_halfspace_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets, int64_t m,
+                        int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    double logn = 1.0;
+    for (i64 v = n; v > 1; v >>= 1) logn += 1.0;
+    int rc = check_halfspace(P, n, d, U, k, m, out, n, (double)k * (double)n * ((double)d + logn));
+    if (rc) return rc;
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    if (m == 0) return SD_OK;
+    return launch_halfspace_counts(P, n, d, U, k, targets, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int sd_halfspace_pairwise_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets,
+                                 int64_t m, int64_t *out, void *stream) {
+    int rc = check_halfspace(P, n, d, U, k, m, out, n, (double)m * (double)n * (double)k * (double)d);
+    if (rc) return rc;
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    if (m == 0) return SD_OK;
+    return launch_halfspace_pairwise(P, n, d, U, k, targets, m, out, (hipStream_t)stream);
+}
+
+int sd_halfspace_external_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const double *Q, int64_t m,
+                                 int64_t *out, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_halfspace(P, n, d, U, k, m, out, n + 1, (double)m * (double)n * (double)k * (double)d);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_halfspace_external(P, n, d, U, k, Q, m, out, (hipStream_t)stream);
+}
+
+int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
+                               int64_t nb, int bs, int64_t *out, void *stream) {
+    if (!members) return fail(SD_ERR_INVALID, "null pointer");
+    if (bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
+    int rc = check_halfspace(P, n, d, U, k, nb, out, bs, (double)nb * (double)bs * (double)k * (double)d);
+    if (rc) return rc;
+    if (nb == 0) return SD_OK;
+    return launch_halfspace_subsets(P, n, d, U, k, members, nb, bs, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -142,6 +142,18 @@ hipError_t launch_prob_fold(const double *part, u64 u0, u64 u1, u64 S, double *o
 int launch_prob_band_sums(const double *mu, const double *var, i64 T, i64 n, const i64 *targets, i64 m, const int *members,
                           int bs, int relax, double *out, hipStream_t s);
 
+// K10 halfspace (Tukey) depth over a fixed direction set (halfspace.hip): out = min over directions of min(le, ge)
+size_t halfspace_workspace_bytes(i64 n, i64 k);
+size_t halfspace_min_workspace_bytes(i64 n);
+int launch_halfspace_counts(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
+                            void *ws, size_t ws_bytes, hipStream_t s);
+int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
+                              hipStream_t s);
+int launch_halfspace_external(const double *P, i64 n, int d, const double *U, i64 k, const double *Q, i64 m, i64 *out,
+                              hipStream_t s);
+int launch_halfspace_subsets(const double *P, i64 n, int d, const double *U, i64 k, const int *members, i64 nb, int bs,
+                             i64 *out, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

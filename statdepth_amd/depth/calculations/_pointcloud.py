@@ -6,6 +6,8 @@ reference's quantity -- the summed volumes of the simplices the point spans with
 points, over the volume of the sample's convex hull -- with the volume sums on the GPU (sd_oja_*) and the hull
 (scipy's Qhull, as in the reference) on the host; DESIGN.md §3 K7 / §4 lists where it departs from the reference.
 Mahalanobis depth (:152-173) is not provided: the reference's covariance is singular by construction.
+Halfspace (Tukey) depth over a fixed direction set (containment='halfspace', sd_halfspace_*) is an extension the
+reference does not have; DESIGN.md §3 K10 states its definition.
 """
 from typing import Union
 
@@ -46,8 +48,37 @@ def _oja_check_dim(d: int) -> None:
         raise NotImplementedError('oja depth is implemented for d <= 8')
 
 
+def _halfspace_directions(directions, seed, d: int) -> np.ndarray:
+    """The k x d fp64 direction array of containment='halfspace'.  An int k: the rows of
+    `np.random.default_rng(seed).standard_normal((k, d))`, each divided by its norm (`np.linalg.norm`); d = 1 has one
+    direction up to sign, [[1.0]], whatever k is.  An array is used as given: k x d, finite, no all-zero row."""
+    if isinstance(directions, (int, np.integer)) and not isinstance(directions, bool):
+        if directions < 1:
+            raise ValueError('directions must be a positive number of directions or a (k x d) array')
+        if d == 1:
+            return np.ones((1, 1), dtype=np.float64)
+        U = np.random.default_rng(seed).standard_normal((int(directions), d))
+        return U / np.linalg.norm(U, axis=1, keepdims=True)
+    U = np.array(directions, dtype=np.float64, ndmin=2)
+    if U.ndim != 2 or U.shape[0] < 1 or U.shape[1] != d:
+        raise ValueError(f'directions must be a (k x {d}) array for data with {d} columns, got shape {U.shape}')
+    if not np.isfinite(U).all():
+        raise ValueError('directions must be finite')
+    if not U.any(axis=1).all():
+        raise ValueError('directions must not contain an all-zero row')
+    return np.ascontiguousarray(U)
+
+
+def _halfspace_check(P: np.ndarray) -> None:
+    d = P.shape[1]
+    if d > 8:
+        raise NotImplementedError('halfspace depth is implemented for d <= 8')
+    if not np.isfinite(P).all():
+        raise ValueError('halfspace depth does not accept NaN or infinite values')
+
+
 def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None, containment='simplex',
-                    quiet=True, device=None) -> pd.Series:
+                    quiet=True, device=None, directions=1000, seed=0) -> pd.Series:
     n, d = data.shape
     if to_compute is None:
         to_compute = data.index                          # (:41-42)
@@ -75,13 +106,22 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         vol = _hull_volume(P)                                    # host first: a degenerate sample never reaches the GPU
         sums = engine.oja_volume_sums(P, _row_positions(data, to_compute), device=device)
         return pd.Series(index=to_compute, data=sums / vol)
+    elif containment == 'halfspace':
+        # An extension (no such string in the reference): min over the directions of min(#{p.u <= x.u}, #{p.u >= x.u}),
+        # the point itself and ties counted, over n -- the random Tukey depth, an upper bound of the exact halfspace
+        # depth for d >= 2 and exact for d = 1
+        P = data.to_numpy(dtype=np.float64)
+        _halfspace_check(P)
+        U = _halfspace_directions(directions, seed, d)
+        counts = engine.halfspace_counts(P, U, _row_positions(data, to_compute), device=device)
+        return pd.Series(index=to_compute, data=counts.astype(np.float64) / n)
     elif containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     else:
         raise ValueError(f'{containment} is not a valid containment measure. ')   # (:63-64)
 
 
-def _block_depths(P: np.ndarray, blocks, containment: str, device=None) -> np.ndarray:
+def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directions=None) -> np.ndarray:
     """Depth of each block's target (its LAST row) inside the block, every block in one launch."""
     width = max(len(b) for b in blocks)
     mem = np.full((len(blocks), width), -1, dtype=np.int32)
@@ -91,6 +131,9 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None) -> np.nd
         _oja_check_dim(P.shape[1])
         vols = np.array([_hull_volume(P[np.asarray(b)]) for b in blocks], dtype=np.float64)
         return engine.oja_subset_volume_sums(P, mem, device=device) / vols
+    if containment == 'halfspace':                       # the block, its target included, is the sample
+        sizes = np.array([len(b) for b in blocks], dtype=np.float64)
+        return engine.halfspace_subset_counts(P, mem, directions, device=device).astype(np.float64) / sizes
     if containment == 'simplex':
         d = P.shape[1]
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
@@ -100,7 +143,7 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None) -> np.nd
 
 
 def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, containment='simplex',
-                          quiet=True, device=None) -> pd.Series:
+                          quiet=True, device=None, directions=1000, seed=0) -> pd.Series:
     """K-block sampled point-cloud depth (:68-123).
 
     Same sampling rule and RNG consumption as the reference: `ss = n // K` (:107) and, per point, `ss`
@@ -109,17 +152,23 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     so the reference itself cannot run this path any more).  The draws are made first -- rows by position, from
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
     (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
-    sd_l1_subset_depth / sd_oja_subset_volume_sums) instead of as many `_pointwisedepth` calls.
+    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts) instead of as many `_pointwisedepth` calls.
     Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
-    normaliser (the reference's is identically 0).
+    normaliser (the reference's is identically 0).  Halfspace: one direction set (directions, seed) for
+    every block; it takes nothing from the global RNG.
     """
     if K == 1:
-        return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device)
+        return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device,
+                               directions=directions, seed=seed)
     if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    if containment not in ('simplex', 'l1', 'oja'):
+    if containment not in ('simplex', 'l1', 'oja', 'halfspace'):
         raise ValueError(f'{containment} is not a valid containment measure. ')
     n, d = data.shape
+    U = None
+    if containment == 'halfspace':                       # host checks first: bad input never reaches the RNG or the GPU
+        _halfspace_check(data.to_numpy(dtype=np.float64))
+        U = _halfspace_directions(directions, seed, d)
     if to_compute is None:
         to_compute = data.index
     ss = n // K
@@ -132,5 +181,5 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
         for _ in range(ss):
             drawn = rows.sample(n=ss).to_numpy()
             blocks.append(np.append(drawn[drawn != tp], tp))          # others in draw order, the point last
-    depth = _block_depths(data.to_numpy(dtype=np.float64), blocks, containment, device=device)
+    depth = _block_depths(data.to_numpy(dtype=np.float64), blocks, containment, device=device, directions=U)
     return pd.Series(index=to_compute, data=depth.reshape(len(targets), ss).mean(axis=1))

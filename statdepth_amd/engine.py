@@ -553,3 +553,77 @@ def multi_band_j_counts(P, targets=None, J=3, device=None):
     out = t.empty((m, max(J - 1, 1)), dtype=t.int64, device=dev)
     return _launch(dev, lib.sd_multi_band_j_counts, out, Pd.data_ptr(), n, T, d, tp, m, J,
                    workspace=lambda: _sized(dev, lib.sd_multi_band_workspace_bytes(n, T, d)))
+
+
+def _directions_dev(U, d, dev):
+    """The k x d direction array on dev (k >= 1 rows of d coordinates)."""
+    Ud = _upload(U, 2, dev)
+    if Ud.shape[0] < 1 or Ud.shape[1] != d:
+        raise ValueError(f"directions must be a k x {d} array with k >= 1")
+    return Ud
+
+
+def halfspace_workspace_bytes(n, d, k):
+    """(recommended, floor) workspace sizes of sd_halfspace_counts; the floor holds one direction per chunk."""
+    lib = _native.load()
+    return (int(lib.sd_halfspace_workspace_bytes(int(n), int(d), int(k))),
+            int(lib.sd_halfspace_min_workspace_bytes(int(n), int(d), int(k))))
+
+
+def halfspace_counts(P, U, targets=None, device=None, workspace_budget=None, algo="rank"):
+    """int64[m]: min over the rows u of U (k x d) of min(#{i: p_i.u <= x.u}, #{i: p_i.u >= x.u}) for x = P[targets[q]], the
+    target and every tie counted (sd_halfspace_counts); depth = counts / n.  workspace_budget: upper bound in bytes for
+    the scratch buffer (default: the recommended size), never below the floor of one direction per chunk; the counts do
+    not depend on it.  algo='pairwise': the same counts from the pairwise kernel (sd_halfspace_pairwise_counts)."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
+    n, d = Pd.shape
+    Ud = _directions_dev(U, d, dev)
+    k = Ud.shape[0]
+    td, m, tp = _targets_dev(targets, n, dev)
+    out = t.empty(m, dtype=t.int64, device=dev)
+    if algo == "pairwise":
+        return _launch(dev, lib.sd_halfspace_pairwise_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), k, tp, m)
+    if algo != "rank":
+        raise ValueError("algo must be 'rank' or 'pairwise'")
+
+    def sized():
+        want, floor = halfspace_workspace_bytes(n, d, k)
+        if workspace_budget is not None:
+            want = max(floor, min(want, int(workspace_budget)))
+        return _sized(dev, want)
+    return _launch(dev, lib.sd_halfspace_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), k, tp, m, workspace=sized)
+
+
+def halfspace_external_counts(P, Q, U, device=None):
+    """int64[m]: the halfspace counts of the external point Q[q] inside P u {Q[q]} (n + 1 points, Q[q] counted once) over
+    the directions U (sd_halfspace_external_counts); depth = counts / (n + 1)."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    Pd, Qd = _upload(P, 2, dev), _upload(Q, 2, dev)
+    n, d = Pd.shape
+    if Qd.shape[1] != d:
+        raise ValueError("Q must have the same number of coordinates as P")
+    Ud = _directions_dev(U, d, dev)
+    m = Qd.shape[0]
+    out = t.empty(m, dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_halfspace_external_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), Ud.shape[0],
+                   Qd.data_ptr(), m)
+
+
+def halfspace_subset_counts(P, members, U, device=None):
+    """int64[nb]: per block (rows of `members`, -1 padded, target last) the halfspace counts of the block's target inside
+    the block over the directions U (sd_halfspace_subset_counts); depth = counts / block size."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    Pd = _upload(P, 2, dev)
+    n, d = Pd.shape
+    Ud = _directions_dev(U, d, dev)
+    md, nb, bs = _members_dev(members, dev, n)
+    out = t.empty(nb, dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_halfspace_subset_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), Ud.shape[0],
+                   md.data_ptr(), nb, bs)

@@ -182,6 +182,11 @@ def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -
         _oja_check_dim(d)
         vols = np.array([_hull_volume(np.vstack([Fx, Qx[[r]]])) for r in range(Qx.shape[0])], dtype=np.float64)
         return engine.oja_external_volume_sums(Fx, Qx) / vols
+    if containment == 'halfspace':                 # counted inside F u {g}: n + 1 points, PointcloudDepth's default directions
+        from ..depth.calculations._pointcloud import _halfspace_check, _halfspace_directions
+        _halfspace_check(Fx)
+        _halfspace_check(Qx)
+        return engine.halfspace_external_counts(Fx, Qx, _halfspace_directions(1000, 0, d)).astype(np.float64) / (n + 1)
     if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     raise ValueError(f'{containment} is not a valid containment measure. ')
