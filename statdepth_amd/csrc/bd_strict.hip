@@ -1,137 +1,26 @@
-// bd_strict.hip -- K3: strict band depth (relax=False, the reference's default).
-//
-// Replaces the subset loop of _univariate_band_depth (_functional.py:246-251) with
-// `containment // len(curve)` (_containment.py:80): a j-subset of the other curves
-// counts only if its band contains the target at EVERY timepoint.
+// bd_strict.hip -- K3: strict band depth (relax=False, the reference's default): the route plan, the workspace layout and
+// the mask / matching pipeline.
+// Replaces the subset loop of _univariate_band_depth (_functional.py:246-251) with `containment // len(curve)`
+// (_containment.py:80): a j-subset of the other curves counts only if its band contains the target at EVERY timepoint.
 //
 // Per target, every curve i gets two T-bit masks over the timepoints:
 //   UN_i[t] = (x_i > x_q) or x_i is NaN,   DN_i[t] = (x_i < x_q) or x_i is NaN.
-// With pandas' skipna min/max (_containment.py:68-69) a subset fails at t iff all
-// its members are in UN or all are in DN, so it is contained at every t iff
-//   AND_members(UN) == 0 and AND_members(DN) == 0      (as T-bit masks).
-// A NaN in the target fails everything (count 0).
+// With pandas' skipna min/max (_containment.py:68-69) a subset fails at t iff all its members are in UN or all are in DN, so
+// it is contained at every t iff AND_members(UN) == 0 and AND_members(DN) == 0 (as T-bit masks).  A NaN in the target fails
+// everything (count 0).
 //
-// What runs, by case (launch_bd_strict_impl):
-//   J = 2, 6 <= T <= 8, any n, NaN-free   strict_class_wg_kernel: the same classes counted by a workgroup per few targets
-//   J = 2, T <= 5, any n      strict_class_kernel: the masks ARE classes (4^T or 3^T of them); per target one pass over
-//                             the curves and a class transform.  The L-infinity depth of point clouds.
-//   J = 2, n <= 131 071       per batch of targets: masks (strict_masks_rank_kernel from the bucket kernel's rank image
-//                             for n <= 32 767, else strict_masks2_kernel from the values) -> digests of the canonical
-//                             masks (strict_hash_kernel) -> pairs of CLEAN curves counted by grouping complementary
-//                             masks (strict_match_lds_kernel; global-memory table behind it) -> pairs with a DIRTY
-//                             curve (tie / NaN) tested by strict_pairs2_kernel, for the targets that have any.
-//                             T > 1024: those targets through the first generation instead.
-//   J = 2, n > 131 071        pair kernel for every pair (refused when that would take hours).
-//   J = 3, 4                  first-generation masks + prefix enumeration (small n, like the reference).
-//   external targets, explicit blocks: launch_bd_strict_external, launch_bd_strict_subsets.
+// Which route a call takes is strict_plan's decision (StrictPlan, strict_routes.h, names them all).  This file has the general
+// one, per batch of targets: masks (from a rank image where there is one) -> digests of the canonical masks -> pairs of CLEAN
+// curves counted by grouping complementary masks -> pairs with a DIRTY curve (tie / NaN) tested, for the targets that have
+// any; and the first generation behind it (T > 1024, J = 3, 4).  Short series: bd_strict_class.hip, bd_strict_grid.hip;
+// explicit blocks: bd_strict_subsets.hip.
 // Integer / compare work throughout: VALU-issue and LDS bound, no MFMA.
-#include <stdlib.h>
-
 #include "sd_common.h"
 #include "rank_routes.h"
 
 namespace sd {
 
-// the grid route (bd_strict_grid.hip) for all targets, or a subset that is not small (else the state-class kernel's O(m n) is less work)
-static inline bool strict_grid_wanted(i64 T, i64 n, i64 m, int J) {
-    return bd_strict_grid_applies(T, n, J) && m * 32 >= n && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1 &&
-           xswitch("SD_STRICT_NOGRID") != 1;
-}
-// 32 767 < n <= 131 071: 32-bit ranks from the large-n route's B image (strict_masks_rank32_kernel)
-static inline bool strict_rank32_applies(i64 T, i64 n, int J) {
-    return J == 2 && n > 32767 && n <= 131071 && mbd_rank_big_supported(T, n, 2);
-}
-constexpr i64 ST_RANK_MAXN = 32767;          // ranks below 2^15 (two per register in the mask kernel); images: bucket kernel up to
-                                             // 16 384 curves, its column-block form beyond
-
-constexpr int ST_THREADS = 256;
-constexpr int ST_WREG = 16;          // mask words kept in registers (T <= 1024)
-
-static inline i64 strict_words(i64 T) { return (T + 63) / 64; }
-
-// complement matching: the global-memory table behind the LDS one (strict_match_insert_kernel): slot = 64-bit key + two counters
-constexpr i64 ST_MATCH_MAXN = 131071;                    // the keys carry a 17-bit curve id
-static inline i64 strict_table_slots(i64 n) {
-    i64 s = 64;
-    while (s < 2 * n) s <<= 1;
-    return s;
-}
-// a series is "short" for the class kernel up to 5 timepoints: 81 / 243 counters per lane leave two to six waves per CU, and
-// still O(n) per target beats masks + matching at every size (10^5 x 4: 21 against 755 ms; 10^4 x 5: 1.3 against 2.7 ms)
-static inline bool strict_class_applies(i64 T, i64 n, int J) {
-    (void)n;
-    return J == 2 && T <= 5;
-}
-// 6 ... 8 timepoints: 729 ... 6 561 three-state classes per target are too many for a histogram per lane; a workgroup takes a
-// few targets and counts into shared histograms (strict_class_wg_kernel).  NaN-free data only: four states would be 4^T
-// counters (256 KB at T = 8), so data with NaN goes the way it went before (masks + matching up to 131 071 curves).
-static inline bool strict_class_wg_applies(i64 T, int J) { return J == 2 && T >= 6 && T <= 8; }
-// ... and beyond the matching's reach, with more pairs than the pair kernel is allowed, they are the ONLY route
-static inline bool strict_class_wg_only(i64 T, i64 n, i64 m, int J) {
-    return strict_class_wg_applies(T, J) && n > 131071 && (double)m * (double)n * (double)n * 0.5 > 2.0e14;
-}
-static inline bool strict_match_applies(i64 T, i64 n, int J) { return J == 2 && (T + 31) / 32 <= 65535 && n <= ST_MATCH_MAXN; }
-
-static i64 strict_batch(i64 T, i64 n, i64 m) {
-    size_t per = (size_t)n * 2 * strict_words(T) * 8 + (size_t)strict_table_slots(n) * 16 + 20 + (size_t)((n + 63) / 64) * 8 + (size_t)((T + 31) / 32) * 256 + (size_t)n * 13 + 16;
-    i64 b = (i64)(((size_t)2048 << 20) / (per ? per : 1));   // up to 2 GiB of masks and tables per batch ...
-    if (b < 1024) {                                           // ... or 16 GiB when that is what 1024 targets take: the matching
-        const i64 b16 = (i64)(((size_t)16384 << 20) / (per ? per : 1));   // kernel runs one workgroup per target
-        b = b16 < 1024 ? b16 : 1024;
-    }
-    if (b < 1) b = 1;
-    if (b > m) b = m;
-    if (b > 65535) b = 65535;
-    return b;
-}
-
-// bytes of the mask pipeline's workspace for batches of b targets (the layout launch_bd_strict_impl carves)
-static size_t strict_ws_for_batch(i64 T, i64 n, i64 b) {
-    return align_up((size_t)b * n * 2 * strict_words(T) * 8, 256) + align_up((size_t)b * 4, 256) +
-           align_up((size_t)b * (strict_table_slots(n) * 16 + 16 + ((n + 63) / 64) * 8), 256) +
-           align_up((size_t)((T + 31) / 32) * 4, 256) + align_up((size_t)b * ((T + 31) / 32) * 256, 256) +
-           align_up((size_t)b * n * 8, 256) + align_up((size_t)b * n, 256) + align_up((size_t)(b + 1) * 4, 256) +
-           align_up((size_t)b * (n + 4) * 4, 256) +
-           (n <= ST_RANK_MAXN ? align_up((size_t)T * n * 4, 256) + 2 * align_up((size_t)T * 4, 256) : 0) +
-           (strict_rank32_applies(T, n, 2) ? align_up((size_t)T * n * 4, 256) + 2 * align_up((size_t)T * 4, 256) +
-                                                 align_up(mbd_rank_big_workspace_bytes(T, n, 2), 256) : 0) + 2560;
-}
-
-// The RECOMMENDED size (batches of strict_batch targets).  The launchers take any workspace that holds a batch of one
-// target and size their batches to what they are given (strict_batch_for_ws), so a caller short of memory may pass less:
-// bd_strict_min_workspace_bytes is the floor.
-size_t bd_strict_workspace_bytes(i64 T, i64 n, i64 m, int J) {
-    // short series go through the class kernel (launch_bd_strict_classes): a flag, no images -- three coordinates at large n
-    // through the grid of cells (rank image, records in three orders, cell histogram, class counts)
-    if (strict_grid_wanted(T, n, m, J)) return bd_strict_grid_workspace_bytes(T, n, m < n) + 4096;
-    if (strict_class_applies(T, n, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1) return 4096;
-    // 6 ... 8 timepoints: the class kernel's flag in front of what the mask pipeline takes should the data hold NaN (beyond
-    // the matching's reach there is no such fallback: the flag only)
-    if (strict_class_wg_only(T, n, m, J)) return 4096;
-    return strict_ws_for_batch(T, n, strict_batch(T, n, m)) + (strict_class_wg_applies(T, J) ? 256 : 0);
-}
-// what a caller who KNOWS the data NaN-free needs: the flag alone where the state classes of 6 ... 8 timepoints take such data
-size_t bd_strict_nanfree_workspace_bytes(i64 T, i64 n, i64 m, int J) {
-    if (strict_class_wg_applies(T, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1) return 4096;
-    return bd_strict_workspace_bytes(T, n, m, J);
-}
-size_t bd_strict_min_workspace_bytes(i64 T, i64 n, i64 m, int J) {
-    if (strict_class_applies(T, n, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1) return 4096;
-    if (strict_class_wg_only(T, n, m, J)) return 4096;
-    return strict_ws_for_batch(T, n, 1) + (strict_class_wg_applies(T, J) ? 256 : 0);
-}
-// largest batch (<= the recommended one) whose layout fits ws_bytes; 0: not even one target fits
-static i64 strict_batch_for_ws(i64 T, i64 n, i64 m, size_t ws_bytes) {
-    i64 hi = strict_batch(T, n, m);
-    if (strict_ws_for_batch(T, n, hi) <= ws_bytes) return hi;
-    if (strict_ws_for_batch(T, n, 1) > ws_bytes) return 0;
-    i64 lo = 1;                                               // fits
-    while (hi - lo > 1) {
-        const i64 mid = lo + (hi - lo) / 2;
-        if (strict_ws_for_batch(T, n, mid) <= ws_bytes) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+constexpr int ST_WREG = 16;          // first generation: mask words kept in registers (T <= 1024)
 
 // masks[b][i][0..W) = UN, masks[b][i][W..2W) = DN
 __global__ __launch_bounds__(ST_THREADS) void strict_masks_kernel(
@@ -757,9 +646,6 @@ __device__ __forceinline__ void strict_pairs2_target(const u32 *__restrict__ m32
     if (threadIdx.x == 0 && tot) atomicAdd(&out[q * jcols], tot);
 }
 
-// Without matching: grid = (a tiles, b chunks, nb), block z = target z.  With matching: grid.z is a fixed number of
-// layers that share out the batch's targets WITH dirty curves (dlist, *dcount: appended by the matching kernels) --
-// continuous data has none, and a grid over all targets would cost more in empty blocks than everything else here.
 // The same count over the target's LIST of curves that can be in a pair the matching has not counted (strict_match_lds_kernel
 // writes it): the dirty curves (ties / NaN with the target; bit 31 of their entry) and the clean curves that cross the target.
 // A clean curve that stays below (above) the target throughout contains it with a dirty curve a exactly when a is never
@@ -939,7 +825,6 @@ __global__ __launch_bounds__(ST_P3_THREADS) void strict_pairs3_kernel(
         __syncthreads();                           // the item's shared arrays are reused by the next one
     }
 }
-
 
 // ---------------------------------------------------------------------------------------------------
 // J = 2 by complement matching: O(n T) per target instead of O(n^2 T).
@@ -1319,501 +1204,350 @@ __global__ __launch_bounds__(ST_THREADS) void strict_subsets_kernel(
     if (threadIdx.x == 0 && tot) atomicAdd(&out[q * jcols + (J - 2)], tot);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Strict band depth (J = 2) of one target inside an explicit subset of the curves, for nb (subset, target) pairs in one
-// launch: the K-block sampled estimator with the reference's default relax=False (_samplefunctionaldepth,
-// _functional.py:170-182 calls _univariate_band_depth on n*K small blocks).  One workgroup per pair: the block's masks
-// against its target are built in LDS (u32[members][2 W32 + 1], the + 1 keeps rows on different banks), then every
-// thread walks the pairs (a, b > a) of its members a with an early exit per four words.  Blocks are small (n / K
-// curves), so the whole pair fits the LDS: members * (2 W32 + 1) * 4 + bs * 4 bytes; larger ones keep their masks in a
-// slice of the workspace instead (strict_subset_big_kernel below; refused only when bs * 4 + 64 exceeds the LDS).
-// ---------------------------------------------------------------------------------------------------
-constexpr int ST_SUB_THREADS = 512;
-constexpr int ST_SUB_GRID = 2048;                               // workgroups (and scratch slices) of the large-block form
-static inline size_t strict_subset_lds(i64 T, int bs) { return (size_t)bs * (2 * ((T + 31) / 32) + 1) * 4 + (size_t)bs * 4 + 64; }
-bool bd_strict_subsets_supported(i64 T, int bs) { return strict_subset_lds(T, bs) <= 160 * 1024 - 2048; }
-// blocks whose masks do not fit the LDS keep them in a slice of the workspace (L2-resident: a slice is read bs times)
-size_t bd_strict_subsets_workspace_bytes(i64 T, i64 nb, int bs) {
-    if (bd_strict_subsets_supported(T, bs)) return 0;
-    const i64 g = nb < ST_SUB_GRID ? nb : ST_SUB_GRID;
-    return (size_t)g * bs * (2 * ((T + 31) / 32) + 1) * 4 + 256;
+// ---- host side: which routes a call takes, what workspace they need, and the launches ----
+constexpr i64 ST_RANK_MAXN = 32767;  // ranks below 2^15 (two per register in the mask kernel); images: bucket kernel up to 16 384 curves, its column-block form beyond
+// 32 767 < n <= 131 071: 32-bit ranks from the large-n route's B image (strict_masks_rank32_kernel)
+static inline bool strict_rank32_applies(i64 T, i64 n, int J) { return J == 2 && n > ST_RANK_MAXN && n <= 131071 && mbd_rank_big_supported(T, n, 2); }
+static inline i64 strict_words(i64 T) { return (T + 63) / 64; }
+static inline i64 strict_words32(i64 T) { return (T + 31) / 32; }
+// complement matching: the global-memory table behind the LDS one (strict_match_insert_kernel): slot = 64-bit key + two counters
+static inline i64 strict_table_slots(i64 n) { i64 s = 64; while (s < 2 * n) s <<= 1; return s; }
+
+// The route plan: the only place of the strict path that reads a cross-check switch.
+StrictPlan strict_plan(i64 T, i64 n, i64 m, int J, bool external) {
+    const bool v1 = xswitch("SD_STRICT_V1") == 1;                          // the first-generation kernels only
+    const bool noclass = v1 || xswitch("SD_STRICT_NOCLASS") == 1;          // short series through the mask kernels like any other
+    const bool fp64 = v1 || xswitch("SD_STRICT_FP64_MASKS") == 1;          // masks from the fp64 values at any n
+    StrictPlan p;
+    p.classes = !noclass && strict_class_applies(T, n, J);
+    // all targets, or a subset that is not small (else the state-class kernel's O(m n) is less work)
+    p.grid = !noclass && !external && bd_strict_grid_applies(T, n, J) && m * 32 >= n && xswitch("SD_STRICT_NOGRID") != 1;
+    p.laneclass = xswitch("SD_STRICT_LANECLASS") == 1;
+    p.class_wg = !noclass && strict_class_wg_applies(T, J);
+    p.class_wg_only = strict_class_wg_only(T, n, m, J);
+    p.match = !v1 && strict_match_applies(T, n, J) && xswitch("SD_STRICT_NOMATCH") != 1;
+    p.rankmasks = !fp64 && !external && n >= 2 && n <= ST_RANK_MAXN && J == 2;
+    p.rank32 = !fp64 && !external && strict_rank32_applies(T, n, J);
+    p.gen2 = !v1 && J == 2 && strict_words32(T) <= ST_W32;
+    p.force_global = xswitch("SD_STRICT_GLOBAL_TABLE") == 1;
+    p.pairs2 = xswitch("SD_STRICT_PAIRS2") == 1;
+    return p;
 }
 
-// grid-stride over the (subset, target) pairs; scratch == nullptr: masks in LDS
-__global__ __launch_bounds__(ST_SUB_THREADS) void strict_subset_kernel(const double *__restrict__ Y, i64 T, i64 n,
-                                                                      const int *__restrict__ members, i64 nb, int bs,
-                                                                      const int *__restrict__ target, u32 *__restrict__ scratch,
-                                                                      u64 *__restrict__ out) {
-    extern __shared__ u32 sm[];
-    __shared__ u64 red[ST_SUB_THREADS / 64];
-    __shared__ int s_cnt;
-    const int W32 = (int)((T + 31) / 32);
-    const int RW = 2 * W32 + 1;
-    int *ids = reinterpret_cast<int *>(sm);                     // [bs] the block's other members
-    u32 *mk = scratch ? scratch + (size_t)blockIdx.x * bs * RW : sm + bs;     // [cnt][RW]
-    const int tid = threadIdx.x;
-    for (i64 k = blockIdx.x; k < nb; k += gridDim.x) {
-        __syncthreads();                                        // the previous pair's ids / masks / sums are done with
-        const int tg = target[k];
-        if (tid == 0) {
-            int c = 0;
-            for (int e = 0; e < bs; ++e) {
-                const int col = members[k * bs + e];
-                if (col >= 0 && col != tg) ids[c++] = col;
-            }
-            s_cnt = c;
-        }
-        bool tnan = false;
-        for (i64 t = tid; t < T; t += ST_SUB_THREADS) {
-            const double q = Y[t * n + tg];
-            tnan |= q != q;
-        }
-        const bool anynan = __syncthreads_or(tnan) != 0;        // also publishes ids / s_cnt
-        if (anynan) {                                           // NaN in the target: nothing is contained
-            if (tid == 0) out[k] = 0;
-            continue;
-        }
-        const int cnt = s_cnt;
-        for (int e = tid; e < cnt * W32; e += ST_SUB_THREADS) {
-            const int c = e / W32, w = e % W32;
-            const i64 col = ids[c];
-            u32 un = 0, dn = 0;
-            const i64 t0 = (i64)w * 32;
-            const int tl = (int)(T - t0 < 32 ? T - t0 : 32);
-            for (int t = 0; t < tl; ++t) {
-                const double x = Y[(t0 + t) * n + col], q = Y[(t0 + t) * n + tg];
-                const bool isn = x != x;
-                un |= (x > q || isn) ? (1u << t) : 0u;
-                dn |= (x < q || isn) ? (1u << t) : 0u;
-            }
-            mk[c * RW + w] = un;
-            mk[c * RW + W32 + w] = dn;
-        }
-        __syncthreads();                                        // (global stores of this workgroup are visible to it after the barrier)
-        u64 good = 0;
-        for (int a = tid; a < cnt; a += ST_SUB_THREADS) {
-            const u32 *ra = mk + (size_t)a * RW;
-            for (int b = a + 1; b < cnt; ++b) {
-                const u32 *rb = mk + (size_t)b * RW;
-                u32 bad = 0;
-                for (int w = 0; w < W32 && !bad; w += 4) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (w + j < W32) bad |= (ra[w + j] & rb[w + j]) | (ra[W32 + w + j] & rb[W32 + w + j]);
-                }
-                good += bad == 0;
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) good += __shfl_down(good, o);
-        if ((tid & 63) == 0) red[tid >> 6] = good;
-        __syncthreads();
-        if (tid == 0) {
-            u64 tot = 0;
-            for (int j = 0; j < ST_SUB_THREADS / 64; ++j) tot += red[j];
-            out[k] = tot;
-        }
-    }
-}
-
-int launch_bd_strict_subsets(const double *Y, i64 T, i64 n, const int *members, i64 nb, int bs, const int *target, u64 *out,
-                             void *ws, size_t ws_bytes, hipStream_t s) {
-    const bool in_lds = bd_strict_subsets_supported(T, bs);
-    if ((size_t)bs * 4 + 64 > 160 * 1024 - 2048)
-        return fail(SD_ERR_UNSUPPORTED, "strict subset depth: blocks of %d curves (the member list alone exceeds the LDS)", bs);
-    u32 *scratch = nullptr;
-    if (!in_lds) {
-        const size_t need = bd_strict_subsets_workspace_bytes(T, nb, bs);
-        if (!ws || ws_bytes < need)
-            return fail(SD_ERR_WORKSPACE, "strict subset depth: %zu bytes of workspace for blocks of %d curves x %lld timepoints "
-                        "(sd_bd_strict_subset_workspace_bytes)", need, bs, (long long)T);
-        scratch = (u32 *)(((size_t)ws + 255) / 256 * 256);
-    }
-    const size_t lds = in_lds ? strict_subset_lds(T, bs) : (size_t)bs * 4 + 64;
-    SD_HIP(hipFuncSetAttribute((const void *)strict_subset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const i64 g = in_lds ? (nb < 65535 * 16 ? nb : 65535 * 16) : (nb < ST_SUB_GRID ? nb : ST_SUB_GRID);
-    hipLaunchKernelGGL(strict_subset_kernel, dim3((unsigned)g), dim3(ST_SUB_THREADS), lds, s, Y, T, n, members, nb, bs, target, scratch,
-                       out);
-    SD_HIP(hipGetLastError());
-    return SD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// J = 2 over at most three timepoints, any n: the L-infinity / box containment of point clouds (SURVEY 8 P4:
-// FunctionalDepth([points.T]) -- "curves" = points, "timepoints" = coordinates; config 5 is 10^6 points in R^3, where
-// the reference's default relax=False asks for the pairs of points whose bounding box contains the target).
-// Per (target, other point) a STATE per coordinate in two bits -- above, below, neither (tie), both (NaN) -- i.e. a
-// class c < 4^T; a pair is contained at every coordinate iff c_a & c_b == 0.  With h[c] = points per class,
-//     ordered contained pairs = sum over c, c' with c & c' == 0 of h[c] h[c'] = sum over masks (-1)^popc(mask) U[mask]^2,
-// U = superset sums of h (inclusion-exclusion over the 2T bits), so a target costs one pass over the points and a
-// 64-entry transform -- O(n) per target instead of O(n^2), exact, no limit on n.
-// Lanes = targets (coordinates in VGPRs, a private 4^T-counter histogram per lane in LDS: [class][lane], no atomics
-// between lanes); the points stream through the scalar cache, eight per load, the same for every lane of the block.
-// ---------------------------------------------------------------------------------------------------
-constexpr int ST_CL_THREADS = 128;
-// lanes (= targets) per block: the private histograms of a block must fit the LDS -- 3^T (NaN-free) or 4^T counters per lane
-__host__ __device__ constexpr int st_cl_threads(int TT, bool NANS) {
-    return TT <= 3 ? ST_CL_THREADS : (TT == 4 ? (NANS ? 64 : 128) : (NANS ? 32 : 64));
-}
-
-// is there a NaN anywhere in the data?  (flag[0] = 1)  NaN-free data -- the rule -- needs three states per coordinate
-// instead of four: 27 counters per lane instead of 64 at T = 3, and 2.4 x the waves per SIMD that hide this kernel's
-// LDS and scalar-load latencies.
-__global__ __launch_bounds__(ST_THREADS) void strict_any_nan_kernel(const double *__restrict__ A, i64 na, const double *__restrict__ B,
-                                                                   i64 nbv, u32 *__restrict__ flag) {
-    bool isn = false;
-    for (i64 i = (i64)blockIdx.x * ST_THREADS + threadIdx.x; i < na + nbv; i += (i64)gridDim.x * ST_THREADS) {
-        const double v = i < na ? A[i] : B[i - na];
-        isn |= v != v;
-    }
-    if (__syncthreads_or(isn) && threadIdx.x == 0) flag[0] = 1u;
-}
-
-template <int TT, bool NANS>
-__global__ __launch_bounds__(st_cl_threads(TT, NANS)) void strict_class_kernel(const double *__restrict__ Y, i64 n, const i64 *__restrict__ targets,
-                                                                    const double *__restrict__ Q, i64 m, const u32 *__restrict__ nanflag,
-                                                                    u64 *__restrict__ out, int jcols) {
-    if ((nanflag[0] != 0) != NANS) return;                                   // the other instantiation serves this data
-    constexpr int P3 = TT == 1 ? 3 : (TT == 2 ? 9 : (TT == 3 ? 27 : (TT == 4 ? 81 : 243)));
-    constexpr int NC = NANS ? (1 << (2 * TT)) : P3;
-    constexpr int CLT = st_cl_threads(TT, NANS);
-    __shared__ u32 hist[NC][CLT];
-    const int tid = threadIdx.x;
-    const i64 q = (i64)blockIdx.x * CLT + tid;
-    const bool active = q < m;
-    const i64 tg = (active && !Q) ? (targets ? targets[q] : q) : -1;        // its own column is not one of the others
-    double x[TT];
-    bool tnan = false;
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-        x[t] = !active ? 0.0 : (Q ? Q[t * m + q] : Y[t * n + tg]);
-        tnan |= x[t] != x[t];
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) hist[c][tid] = 0;
-    // Per (target, point): 2 T fp64 compares turned into the class code (two bits per coordinate, NaN coordinates of the
-    // point -- a scalar: the point is the same for every lane -- set both; or base 3 without NaN), one increment of the
-    // lane's own counter.  The target meets itself in the stream (class 0: every coordinate ties) and is taken off
-    // afterwards.  (Measured and not kept: compare + add-with-carry chains, one instruction per bit instead of two, and
-    // ds_add instead of read / add / write: 1.9 and 1.8 s against 1.46 s at 10^6 points.)
-    auto visit = [&](const double (&p)[TT]) {
-        u32 code = 0;
-        if constexpr (NANS) {
-            u32 nanbits = 0;
-#pragma unroll
-            for (int t = TT - 1; t >= 0; --t) {
-                const unsigned long long pb = (unsigned long long)__double_as_longlong(p[t]);
-                const u32 hi = (u32)(pb >> 32) & 0x7FFFFFFFu, lo = (u32)pb;     // 32-bit tests: scalar ALU
-                nanbits = (nanbits << 2) | ((hi > 0x7FF00000u || (hi == 0x7FF00000u && lo != 0u)) ? 3u : 0u);
-                code |= (p[t] > x[t] ? 1u : 0u) << (2 * t);                      // above
-                code |= (p[t] < x[t] ? 2u : 0u) << (2 * t);                      // below
-            }
-            code |= nanbits;
-        } else {
-#pragma unroll
-            for (int t = TT - 1; t >= 0; --t) code = code * 3u + (p[t] > x[t] ? 1u : 0u) + (p[t] < x[t] ? 2u : 0u);
-        }
-        hist[code][tid] += 1u;                                               // own counter: no atomic needed
-    };
-    i64 i = 0;
-    for (; i + 8 <= n; i += 8) {
-        double blkp[TT][8];
-#pragma unroll
-        for (int t = 0; t < TT; ++t)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) blkp[t][k] = Y[t * n + i + k];      // wave-uniform addresses: scalar loads
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            double p[TT];
-#pragma unroll
-            for (int t = 0; t < TT; ++t) p[t] = blkp[t][k];
-            visit(p);
-        }
-    }
-    for (; i < n; ++i) {
-        double p[TT];
-#pragma unroll
-        for (int t = 0; t < TT; ++t) p[t] = Y[t * n + i];
-        visit(p);
-    }
-    if (!active) return;
-    if (tg >= 0 && !tnan) hist[0][tid] -= 1u;                                // the target itself (a NaN target counts nothing)
-    // class 0 = the points that tie with the target in every coordinate: the only ones compatible with themselves
-    const u64 ties = hist[0][tid];
-    long long total = 0;
-    if constexpr (NANS) {
-        // superset sums over the 2T bits, in place, then inclusion-exclusion
-#pragma unroll
-        for (int bit = 1; bit < NC; bit <<= 1)
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (!(c & bit)) hist[c][tid] += hist[c | bit][tid];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const long long u = (long long)hist[c][tid];
-            total += (__builtin_popcount((unsigned)c) & 1) ? -u * u : u * u;
-        }
-    } else if constexpr (TT >= 4) {
-        // three states, 81 / 243 classes: too many for registers.  A pair is compatible iff in no coordinate both are above or
-        // both below: prod_t (1 - [both above at t] - [both below at t]) = sum over subsets S of the coordinates of (-1)^|S| [equal
-        // and strict on S].  In place, per coordinate, the tie slot becomes the sum of the three states (a wild card); entry c
-        // then counts the points that match c's strict digits, and the ordered pairs are sum_c (-1)^(strict digits of c) entry(c)^2.
-#pragma unroll 1
-        for (int stride = 1; stride < NC; stride *= 3)
-#pragma unroll 1
-            for (int g = 0; g < NC / 3; ++g) {
-                const int base = (g / stride) * stride * 3 + (g % stride);
-                hist[base][tid] += hist[base + stride][tid] + hist[base + 2 * stride][tid];
-            }
-#pragma unroll 1
-        for (int c = 0; c < NC; ++c) {
-            int strict_digits = 0;
-            for (int d = c; d; d /= 3) strict_digits += (d % 3) != 0;
-            const long long u = (long long)hist[c][tid];
-            total += (strict_digits & 1) ? -u * u : u * u;
-        }
-    } else {
-        // three states: z = (M x ... x M) h in registers (tie ~ all, above ~ {tie, below}, below ~ {tie, above}), then h . z
-        u64 h[NC], z[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { h[c] = hist[c][tid]; z[c] = h[c]; }
-#pragma unroll
-        for (int stride = 1; stride < NC; stride *= 3)
-#pragma unroll
-            for (int g = 0; g < NC / 3; ++g) {
-                const int base = (g / stride) * stride * 3 + (g % stride);
-                const u64 s0 = z[base], s1 = z[base + stride], s2 = z[base + 2 * stride];
-                z[base] = s0 + s1 + s2;
-                z[base + stride] = s0 + s2;
-                z[base + 2 * stride] = s0 + s1;
-            }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) total += (long long)(h[c] * z[c]);
-    }
-    out[q * jcols] = tnan ? 0ull : ((u64)total - ties) / 2;                  // NaN in the target: nothing is contained
-}
-
-template <int TT>
-static int launch_class_wg(const double *Y, i64 n, const i64 *targets, const double *Q, i64 m, const u32 *nanflag, u64 *out, int jcols,
-                           hipStream_t s);
-
-int launch_bd_strict_classes(const double *Y, i64 T, i64 n, const i64 *targets, const double *Q, i64 m, u64 *out, int jcols,
-                             void *ws, size_t ws_bytes, hipStream_t s) {
-    Carver cv(ws, ws_bytes);
-    u32 *flag = (u32 *)cv.take(256);
-    if (!flag) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
-    SD_HIP(hipMemsetAsync(flag, 0, 4, s));
-#define ST_CL_LAUNCH(TT_)                                                                                                      \
-    hipLaunchKernelGGL((strict_class_kernel<TT_, false>), dim3((unsigned)((m + st_cl_threads(TT_, false) - 1) / st_cl_threads(TT_, false))), \
-                       dim3(st_cl_threads(TT_, false)), 0, s, Y, n, targets, Q, m, (const u32 *)flag, out, jcols);             \
-    hipLaunchKernelGGL((strict_class_kernel<TT_, true>), dim3((unsigned)((m + st_cl_threads(TT_, true) - 1) / st_cl_threads(TT_, true))),   \
-                       dim3(st_cl_threads(TT_, true)), 0, s, Y, n, targets, Q, m, (const u32 *)flag, out, jcols);
-#define ST_CL_NAN(TT_)                                                                                                         \
-    hipLaunchKernelGGL((strict_class_kernel<TT_, true>), dim3((unsigned)((m + st_cl_threads(TT_, true) - 1) / st_cl_threads(TT_, true))),   \
-                       dim3(st_cl_threads(TT_, true)), 0, s, Y, n, targets, Q, m, (const u32 *)flag, out, jcols);
-    // two to four coordinates at large n, external targets aside: the grid of cells (bd_strict_grid.hip) when the workspace holds it (a
-    // caller that passed the floor keeps the O(m n) kernels); it sets the flag itself from the rank route's NaN counts
-    if (!Q && strict_grid_wanted(T, n, m, 2) && ws_bytes >= bd_strict_grid_workspace_bytes(T, n, targets != nullptr)) {
-        int rc = launch_bd_strict_grid(Y, T, n, targets, m, out, jcols, flag, ws, ws_bytes, s);
-        if (rc) return rc;
-        // data with NaN (the flag is set): the four-state lane kernel, which returns at once otherwise
-        if (T == 2) { ST_CL_NAN(2) } else if (T == 3) { ST_CL_NAN(3) } else { ST_CL_NAN(4) }
-        SD_HIP(hipGetLastError());
-        return SD_OK;
-    }
-    hipLaunchKernelGGL(strict_any_nan_kernel, dim3(1024), dim3(ST_THREADS), 0, s, Y, T * n, Q ? Q : Y, Q ? T * m : (i64)0, flag);
-    switch ((int)T) {
-        case 1: ST_CL_LAUNCH(1) break;
-        case 2: ST_CL_LAUNCH(2) break;
-        case 3:
-        // T = 3, 4, 5 without NaN: the workgroup form (lanes = points, shared histograms: 10^5 x 3 / 4 / 5 in 4.9 / 6.7 / 8.5 ms against
-        // 10.7 / 21 / 46 with a histogram per lane; 10^6 x 3: 427 against 506 ms); with NaN the four-state lane kernel.  Cross-check
-        // builds, SD_STRICT_LANECLASS = 1: the lane kernel for both.
-        case 4:
-        case 5:
-            if (xswitch("SD_STRICT_LANECLASS") == 1) {
-                if (T == 3) { ST_CL_LAUNCH(3) } else if (T == 4) { ST_CL_LAUNCH(4) } else { ST_CL_LAUNCH(5) }
-                break;
-            }
-#define ST_CL_WG(TT_)                                                                                                          \
-            {                                                                                                                  \
-                int rc = launch_class_wg<TT_>(Y, n, targets, Q, m, flag, out, jcols, s);                                       \
-                if (rc) return rc;                                                                                             \
-                hipLaunchKernelGGL((strict_class_kernel<TT_, true>),                                                           \
-                                   dim3((unsigned)((m + st_cl_threads(TT_, true) - 1) / st_cl_threads(TT_, true))),            \
-                                   dim3(st_cl_threads(TT_, true)), 0, s, Y, n, targets, Q, m, (const u32 *)flag, out, jcols);   \
-            }
-            if (T == 3) ST_CL_WG(3) else if (T == 4) ST_CL_WG(4) else ST_CL_WG(5)
-#undef ST_CL_WG
-            break;
-        default: return fail(SD_ERR_UNSUPPORTED, "the class kernel covers up to five timepoints");
-    }
-#undef ST_CL_LAUNCH
-#undef ST_CL_NAN
-    SD_HIP(hipGetLastError());
-    return SD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// J = 2 over 6 ... 8 timepoints, NaN-free data, any n: the same state classes, counted by a WORKGROUP per G targets.
-// Lanes = points (their coordinates in VGPRs, SCW_PTS points per thread and trip, coalesced loads that serve all G targets);
-// the target's coordinates are wave-uniform (SGPRs), a pair costs 2 T compares, the base-3 code and one LDS atomic on the
-// target's histogram (3^T counters).  Then the in-place wild-card transform of strict_class_kernel, coordinate by
-// coordinate with the workgroup's threads, and sum_c (-1)^(strict digits of c) entry(c)^2.
-// ---------------------------------------------------------------------------------------------------
-constexpr int SCW_PTS = 4;
-template <int TT> struct ScwCfg {
-    static constexpr int NC = TT == 3 ? 27 : (TT == 4 ? 81 : (TT == 5 ? 243 : (TT == 6 ? 729 : (TT == 7 ? 2187 : 6561))));
-    static constexpr int G = TT <= 5 ? 16 : (TT <= 7 ? 8 : 4);          // (T >= 6:) 46 / 70 / 105 KB of histograms
-    static constexpr int NT = TT == 8 ? 1024 : 512;                     // three / two / one workgroup per CU
-    // few classes: the lanes of a wave meet on the same counter (most points are strictly above or below in every coordinate:
-    // 2^T classes) and the LDS serialises them -- R copies of a target's histogram, a lane counts into copy lane % R
-    // T = 6: 8 targets x 2 copies against 16 x 1: 10.1 against 15.6 ms on random walks (correlated coordinates: fewer classes
-    // occur), the same on independent ones; T = 7 / 8 with copies (4 x 2 / 2 x 2 targets): 13.2 / 23.3 against 15.1 / 20.0 on walks,
-    // 13.1 / 23.4 against 12.2 / 18.5 on independent coordinates -- not taken
-    // (T = 3: 16 copies; 8 the same, 32 slower; 32 targets per workgroup slower)
-    static constexpr int R = TT == 3 ? 16 : (TT == 4 ? 8 : (TT == 5 ? 4 : (TT == 6 ? 2 : 1)));
-    static constexpr size_t LDS = (size_t)G * R * NC * 4;
+// The workspace of the mask pipeline for batches of b targets: every buffer, its size and its place, stated once.  The size
+// functions read `total` (null base); the launcher gives the base and uses the pointers.  plan.rankmasks / plan.rank32 say
+// which rank image is laid out; nothing else of the plan changes the layout.
+struct StrictWs {
+    i64 b, slots;                        // targets per batch; slots of a target's global-memory table
+    u64 *masks;                          // first generation: u64 [b][n][2 W]; second: the u32 word-major image over the same bytes
+    u32 *xnan, *cmask;                   // [b] NaN in the target; timepoints that do not count
+    unsigned long long *keys;            // global-memory table: keys [b][slots] | counters [b][slots][2] | per target
+    u32 *cnt, *dirty; u64 *dbits;        //   {dirty, below, above, overflow} | dirty bitmaps [b][ceil(n / 64)]
+    double *Yt; u64 *HF;                 // the batch's targets, gathered (values or ranks); hash + flags per (target, curve)
+    unsigned char *dflag;                // dirty (target, curve) pairs
+    u32 *dlist, *dcount, *ilist;         // dirty targets of the batch | their number; per target the pair kernel's list of curves
+    u32 *R, *rnan, *tiemask;             // rank image [T][n], NaN counts per row, timepoints with ties (rank masks only)
+    void *bigws;                         // the large-n route's scratch for its image (32-bit ranks only)
+    size_t bigws_bytes, total;
 };
-__device__ __forceinline__ double scw_uniform(double v) {               // a wave-uniform double into SGPRs
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)b), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+static StrictWs strict_layout(const StrictPlan &plan, i64 T, i64 n, i64 b, void *base) {
+    StrictWs w{};
+    size_t o = 0;                        // (integer arithmetic: the size functions lay out from a null base)
+    auto take = [&](size_t bytes) { const uintptr_t p = (uintptr_t)base + o; o += align_up(bytes, 256); return p; };
+    const i64 W32 = strict_words32(T), dwords = (n + 63) / 64;
+    w.b = b, w.slots = strict_table_slots(n);
+    w.masks = (u64 *)take((size_t)b * n * 2 * strict_words(T) * 8);
+    w.xnan = (u32 *)take((size_t)b * 4);
+    const uintptr_t tab = take((size_t)b * (w.slots * 16 + 16 + dwords * 8));
+    w.keys = (unsigned long long *)tab;
+    w.cnt = (u32 *)(tab + (size_t)b * w.slots * 8);
+    w.dirty = (u32 *)(tab + (size_t)b * w.slots * 16);
+    w.dbits = (u64 *)(tab + (size_t)b * (w.slots * 16 + 16));
+    w.cmask = (u32 *)take((size_t)W32 * 4);
+    w.Yt = (double *)take((size_t)b * W32 * 256);
+    w.HF = (u64 *)take((size_t)b * n * 8);
+    w.dflag = (unsigned char *)take((size_t)b * n);
+    w.dlist = (u32 *)take((size_t)(b + 1) * 4);
+    w.dcount = (u32 *)((uintptr_t)w.dlist + (size_t)b * 4);
+    w.ilist = (u32 *)take((size_t)b * (n + 4) * 4);
+    if (plan.rankmasks || plan.rank32) {
+        w.R = (u32 *)take((size_t)T * n * 4);
+        w.rnan = (u32 *)take((size_t)T * 4);
+        w.tiemask = (u32 *)take((size_t)T * 4);              // W32 words are used; T words have always been reserved
+    }
+    if (plan.rank32) w.bigws = (void *)take(w.bigws_bytes = mbd_rank_big_workspace_bytes(T, n, 2));
+    w.total = o + 2560;                                      // ten buffers' worth of alignment slack, reserved since the first layout
+    return w;
+}
+// What the size functions report: the layout of the most demanding plan of the shape -- the rank image whenever n allows it,
+// whatever J, the targets and the switches -- so the launcher's own layout never takes more than was asked for.
+static size_t strict_ws_for_batch(i64 T, i64 n, i64 b) {
+    StrictPlan most{};
+    most.rankmasks = n <= ST_RANK_MAXN;
+    most.rank32 = strict_rank32_applies(T, n, 2);
+    return strict_layout(most, T, n, b, nullptr).total;
+}
+// The recommended batch: up to 2 GiB of masks and tables.  `per` approximates what one more target adds to strict_layout (the
+// b-proportional buffers without their alignment); a closed formula because the batch sizes it gives are what callers see.
+static i64 strict_batch(i64 T, i64 n, i64 m) {
+    size_t per = (size_t)n * 2 * strict_words(T) * 8 + (size_t)strict_table_slots(n) * 16 + 20 + (size_t)((n + 63) / 64) * 8 + (size_t)strict_words32(T) * 256 + (size_t)n * 13 + 16;
+    i64 b = (i64)(((size_t)2048 << 20) / (per ? per : 1));
+    if (b < 1024) {                                           // ... or 16 GiB when that is what 1024 targets take: the matching
+        const i64 b16 = (i64)(((size_t)16384 << 20) / (per ? per : 1));   // kernel runs one workgroup per target
+        b = b16 < 1024 ? b16 : 1024;
+    }
+    if (b < 1) b = 1;
+    if (b > m) b = m;
+    return b > 65535 ? 65535 : b;
+}
+// largest batch (<= the recommended one) whose layout fits ws_bytes; 0: not even one target fits
+static i64 strict_batch_for_ws(i64 T, i64 n, i64 m, size_t ws_bytes) {
+    i64 hi = strict_batch(T, n, m);
+    if (strict_ws_for_batch(T, n, hi) <= ws_bytes) return hi;
+    if (strict_ws_for_batch(T, n, 1) > ws_bytes) return 0;
+    i64 lo = 1;                                               // fits
+    while (hi - lo > 1) {
+        const i64 mid = lo + (hi - lo) / 2;
+        if (strict_ws_for_batch(T, n, mid) <= ws_bytes) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
-template <int TT>
-__global__ __launch_bounds__(ScwCfg<TT>::NT) void strict_class_wg_kernel(const double *__restrict__ Y, i64 n,
-                                                                         const i64 *__restrict__ targets,
-                                                                         const double *__restrict__ Q, i64 m,
-                                                                         const u32 *__restrict__ nanflag,
-                                                                         u64 *__restrict__ out, int jcols) {
-    if (nanflag && nanflag[0] != 0) return;                             // (T <= 5: the four-state kernel serves this data)
-    using C = ScwCfg<TT>;
-    constexpr int NC = C::NC, G = C::G, NT = C::NT, NW = NT / 64, R = C::R, GS = R * NC;
-    extern __shared__ u32 scw_hist[];                                   // [G][R][NC]
-    __shared__ double xs[G][8];
-    __shared__ long long red[G][NW];
-    __shared__ u32 s_ties[G];
-    u32 *hist = scw_hist;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const i64 q0 = (i64)blockIdx.x * G;
-    const int gc = (int)(m - q0 < G ? m - q0 : G);                      // targets of this workgroup
-    for (int c = tid; c < G * GS; c += NT) hist[c] = 0;
-    if (tid < G * TT) {
-        const int g = tid / TT, t = tid % TT;
-        double v = 0.0;
-        if (g < gc) {
-            const i64 q = q0 + g;
-            v = Q ? Q[t * m + q] : Y[t * n + (targets ? targets[q] : q)];
-        }
-        xs[g][t] = v;
-    }
-    __syncthreads();
-    for (i64 i0 = tid; i0 < n; i0 += (i64)NT * SCW_PTS) {
-        double p[SCW_PTS][TT];
-        bool ok[SCW_PTS];
-#pragma unroll
-        for (int k = 0; k < SCW_PTS; ++k) {
-            const i64 i = i0 + (i64)k * NT;
-            ok[k] = i < n;
-#pragma unroll
-            for (int t = 0; t < TT; ++t) p[k][t] = ok[k] ? Y[t * n + i] : 0.0;
-        }
-#pragma unroll 1
-        for (int g = 0; g < gc; ++g) {
-            double x[TT];
-#pragma unroll
-            for (int t = 0; t < TT; ++t) x[t] = scw_uniform(xs[g][t]);
-            u32 *hg = hist + g * GS + (lane & (R - 1)) * NC;
-#pragma unroll
-            for (int k = 0; k < SCW_PTS; ++k) {
-                u32 code = 0;
-#pragma unroll
-                for (int t = TT - 1; t >= 0; --t) code = code * 3u + (p[k][t] > x[t] ? 1u : 0u) + (p[k][t] < x[t] ? 2u : 0u);
-                if (ok[k]) atomicAdd(&hg[code], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    // the target itself met in the stream as class 0 (every coordinate ties): taken off; class 0 = the points that tie with
-    // the target everywhere, the only ones compatible with themselves
-    if constexpr (R > 1) {
-        for (int w = tid; w < gc * NC; w += NT) {
-            u32 *h = hist + (w / NC) * GS + (w % NC);
-            u32 v = h[0];
-#pragma unroll
-            for (int r = 1; r < R; ++r) v += h[r * NC];
-            h[0] = v;
-        }
-        __syncthreads();
-    }
-    if (tid < gc) {
-        const bool self = !Q && (targets ? targets[q0 + tid] : q0 + tid) >= 0;
-        if (self) hist[tid * GS] -= 1u;
-        s_ties[tid] = hist[tid * GS];
-    }
-    __syncthreads();
-    // per coordinate the tie slot becomes the sum of the three states (see strict_class_kernel)
-#pragma unroll 1
-    for (int stride = 1; stride < NC; stride *= 3) {
-        for (int w = tid; w < gc * (NC / 3); w += NT) {
-            const int g = w / (NC / 3), idx = w % (NC / 3);
-            u32 *h = hist + g * GS + (idx / stride) * stride * 3 + (idx % stride);
-            h[0] += h[stride] + h[2 * stride];
-        }
-        __syncthreads();
-    }
-    long long acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = 0;
-    for (int c = tid; c < NC; c += NT) {
-        int strict_digits = 0;
-#pragma unroll
-        for (int t = 0, d = c; t < TT; ++t, d /= 3) strict_digits += (d % 3) != 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const long long u = (long long)hist[g * GS + c];
-            acc[g] += (strict_digits & 1) ? -u * u : u * u;
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        long long v = acc[g];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0) red[g][wave] = v;
-    }
-    __syncthreads();
-    if (tid < gc) {
-        long long total = 0;
-        for (int w = 0; w < NW; ++w) total += red[tid][w];
-        out[(q0 + tid) * jcols] = ((u64)total - (u64)s_ties[tid]) / 2;
-    }
+// The RECOMMENDED size (batches of strict_batch targets).  The launchers take any workspace that holds a batch of one target and
+// size their batches to what they are given (strict_batch_for_ws): bd_strict_min_workspace_bytes is the floor.
+size_t bd_strict_workspace_bytes(i64 T, i64 n, i64 m, int J) {
+    const StrictPlan p = strict_plan(T, n, m, J, false);
+    // short series go through the class kernels: a flag, no images -- or through the grid of cells (rank image, records in
+    // three orders, cell histogram, class counts)
+    if (p.grid) return bd_strict_grid_workspace_bytes(T, n, m < n) + 4096;
+    if (p.classes || p.class_wg_only) return 4096;
+    // 6 ... 8 timepoints: the class kernel's flag in front of what the mask pipeline takes should the data hold NaN
+    return strict_ws_for_batch(T, n, strict_batch(T, n, m)) + (strict_class_wg_applies(T, J) ? 256 : 0);
 }
+// what a caller who KNOWS the data NaN-free needs: the flag alone where the state classes of 6 ... 8 timepoints take such data
+size_t bd_strict_nanfree_workspace_bytes(i64 T, i64 n, i64 m, int J) {
+    return strict_plan(T, n, m, J, false).class_wg ? (size_t)4096 : bd_strict_workspace_bytes(T, n, m, J);
+}
+size_t bd_strict_min_workspace_bytes(i64 T, i64 n, i64 m, int J) {
+    const StrictPlan p = strict_plan(T, n, m, J, false);
+    if (p.classes || p.class_wg_only) return 4096;
+    return strict_ws_for_batch(T, n, 1) + (strict_class_wg_applies(T, J) ? 256 : 0);
+}
+// what launch_bd_strict needs to be called at all: 6 ... 8 timepoints get by with the flag when the data is NaN-free, which the
+// launcher finds out itself; data with NaN then meets the mask pipeline's own check of what it was given
+size_t bd_strict_launch_floor_bytes(i64 T, i64 n, i64 m, int J) {
+    return strict_class_wg_applies(T, J) ? (size_t)256 : bd_strict_min_workspace_bytes(T, n, m, J);
+}
+size_t bd_strict_external_workspace_bytes(i64 T, i64 n, i64 m) { return bd_strict_workspace_bytes(T, n, m, 2) + align_up((size_t)m * 8, 256); }
 
-template <int TT>
-static int launch_class_wg(const double *Y, i64 n, const i64 *targets, const double *Q, i64 m, const u32 *nanflag, u64 *out, int jcols,
-                           hipStream_t s) {
-    using C = ScwCfg<TT>;
-    auto k = strict_class_wg_kernel<TT>;
-    SD_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
-    hipLaunchKernelGGL(k, dim3((unsigned)((m + C::G - 1) / C::G)), dim3(C::NT), C::LDS, s, Y, n, targets, Q, m, nanflag, out, jcols);
-    SD_HIP(hipGetLastError());
+// One call of the mask pipeline: its arguments, plan and buffers.  Every stage is a fixed sequence of launches on s; run()
+// strings them together per batch of nb targets from q0.
+struct StrictRun {
+    const double *Y, *Q;         // Q non-null: the m targets are EXTERNAL curves (T x m, time-major); every curve of Y is an "other"
+    const i64 *targets;
+    i64 T, n, m;
+    int J, jcols;                // jcols = J - 1 columns of out per target
+    u64 *out;
+    hipStream_t s;
+    StrictPlan p;
+    StrictWs w;                  // laid out for batches of w.b targets
+    const u32 *m32() const { return (const u32 *)w.masks; }   // the second generation's view of the mask buffer
+    dim3 curves(i64 nb) const { return dim3((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)nb); }
+    dim3 pairs(i64 nb) const { return dim3((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)((n + ST_BCHUNK - 1) / ST_BCHUNK), (unsigned)nb); }
+    int rank_images() const;
+    void gather_targets(i64 q0, i64 nb) const;
+    void masks_gen2(i64 q0, i64 nb, const StrictMaskOut &mo) const;
+    int matching(i64 q0, i64 nb) const;
+    void pairs_gen2(i64 q0, i64 nb, bool matched) const;
+    void first_generation(i64 q0, i64 nb, const u32 *gate, bool gathered) const;
+    int run() const;
+};
+
+// The integer rank image the mask kernels compare instead of the values, and the timepoints at which any two curves tie
+int StrictRun::rank_images() const {
+    if (!p.rankmasks && !p.rank32) return SD_OK;
+    if (int rc = p.rank32 ? launch_rank_big_image(Y, T, n, w.R, w.rnan, w.bigws, w.bigws_bytes, s) : SD_OK) return rc;
+    const i64 step = 2048 * 64;                               // the 16-bit image launchers take at most 2048 rows per workgroup
+    for (i64 r0 = 0; p.rankmasks && r0 < T; r0 += step) {
+        const i64 rows = T - r0 < step ? T - r0 : step;
+        if (int rc = n <= 16384 ? launch_rank_bucket_image(Y, n, r0, rows, w.R + r0 * n, w.rnan + r0, s)
+                                : launch_rank_medium_image(Y, n, r0, rows, w.R + r0 * n, w.rnan + r0, s)) return rc;
+    }
+    SD_HIP(hipMemsetAsync(w.tiemask, 0, (size_t)strict_words32(T) * 4, s));
+    if (p.rankmasks)
+        hipLaunchKernelGGL(strict_row_ties_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, (const u32 *)w.R, (const u32 *)w.rnan, n, w.tiemask);
+    else
+        hipLaunchKernelGGL(strict_row_ties32_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, (const u32 *)w.R, n, w.tiemask);
     return SD_OK;
 }
 
-// Q != nullptr: the m targets are EXTERNAL curves (T x m, time-major), every curve of Y is an "other" (J = 2 only).
-static int launch_bd_strict_impl(const double *Y, i64 T, i64 n, const i64 *targets, const double *Q, i64 m, int J,
-                                 u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
+// The batch's targets gathered into Yt -- ranks or values, as the plan's mask kernel reads them; xnan notes a NaN target
+void StrictRun::gather_targets(i64 q0, i64 nb) const {
+    const dim3 g((unsigned)nb), t(ST_THREADS);
+    if (p.rankmasks)
+        hipLaunchKernelGGL(strict_gather_rank_targets_kernel, g, t, 0, s, (const u32 *)w.R, T, n, targets, q0, (u32 *)w.Yt, w.xnan);
+    else if (p.rank32)
+        hipLaunchKernelGGL(strict_gather_rank32_targets_kernel, g, t, 0, s, (const u32 *)w.R, T, n, targets, q0, (u32 *)w.Yt, w.xnan);
+    else
+        hipLaunchKernelGGL(strict_gather_targets_kernel, g, t, 0, s, Y, T, n, targets, q0, Q, m, w.Yt, w.xnan);
+}
+// Second-generation masks (32-bit words, word-major image over the bytes of w.masks: 2 W32 n u32 <= 2 W n u64) as `mo` asks.
+// The pass over every target of the batch (no list) gathers the targets first; the pass over the listed ones reuses them.
+void StrictRun::masks_gen2(i64 q0, i64 nb, const StrictMaskOut &mo) const {
+    const dim3 g((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)strict_words32(T), (unsigned)((nb + ST_TG - 1) / ST_TG)), t(ST_THREADS);
+    if (!mo.dlist) gather_targets(q0, nb);
+    if (p.rankmasks)
+        hipLaunchKernelGGL(strict_masks_rank_kernel, g, t, 0, s, (const u32 *)w.R, (const u32 *)w.Yt, T, n, nb, mo);
+    else if (p.rank32)
+        hipLaunchKernelGGL(strict_masks_rank32_kernel, g, t, 0, s, (const u32 *)w.R, (const u32 *)w.Yt, T, n, nb, mo);
+    else
+        hipLaunchKernelGGL(strict_masks2_kernel, g, t, 0, s, Y, (const double *)w.Yt, T, n, nb, mo);
+}
 
-int launch_bd_strict(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int J,
-                     u64 *out, void *ws, size_t ws_bytes, hipStream_t s) {
+// Complement matching over the UN masks of the batch: digests, the LDS table per target, and behind it the global-memory table for
+// the targets the LDS kernel flags.  Leaves the clean-clean counts in out, the dirty curves per target in w.dirty / w.dbits / w.ilist
+// and the targets that have any in w.dlist.
+int StrictRun::matching(i64 q0, i64 nb) const {
+    const dim3 t(ST_THREADS);
+    const int whole_targets = p.gen2 ? 0 : 1;                 // T > 1024: the first generation counts ALL pairs of a dirty target
+    hipLaunchKernelGGL(strict_hash_kernel, curves(nb), t, 0, s, m32(), T, n, w.xnan, (const u32 *)w.cmask, (const unsigned char *)w.dflag, w.HF);
+    SD_HIP(hipMemsetAsync(w.dirty, 0, (size_t)w.b * 16, s));
+    SD_HIP(hipMemsetAsync(w.dcount, 0, 4, s));
+    const i64 lslots = strict_lds_slots(n);
+    const size_t tb = (size_t)lslots * 8 + 2 * (ST_ML_SEEN / 8);
+    SD_HIP(hipFuncSetAttribute((const void *)strict_match_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
+    hipLaunchKernelGGL(strict_match_lds_kernel, dim3((unsigned)nb), dim3(ST_ML_THREADS), tb, s, m32(), (const u64 *)w.HF, T, n, targets, q0,
+                       w.xnan, (const u32 *)w.cmask, w.dirty, w.dbits, w.dlist, w.dcount, (int)lslots, whole_targets, p.force_global ? 1 : 0,
+                       out, jcols, (p.gen2 && !p.pairs2) ? w.ilist : (u32 *)nullptr);
+    if (p.force_global || n > ST_MATCH_LDS_CAP) {
+        hipLaunchKernelGGL(strict_match_clear_kernel, dim3((unsigned)((w.slots + 4095) / 4096), (unsigned)nb), t, 0, s, (const u32 *)w.dirty,
+                           w.keys, w.cnt, w.slots);
+        hipLaunchKernelGGL(strict_match_insert_kernel, curves(nb), t, 0, s, m32(), (const u64 *)w.HF, T, n, targets, q0, w.xnan,
+                           (const u32 *)w.cmask, (const u32 *)w.dirty, w.keys, w.cnt, w.slots);
+        hipLaunchKernelGGL(strict_match_total_kernel, dim3((unsigned)nb, (unsigned)((w.slots + ST_TOTAL_CHUNK - 1) / ST_TOTAL_CHUNK)), t, 0, s,
+                           (const u32 *)w.cnt, w.slots, q0, w.xnan, (const u32 *)w.dirty, whole_targets, out, jcols);
+    }
+    return SD_OK;
+}
+
+// Second generation, the pairs the matching has not counted: with matching the pairs with a dirty curve of the targets on
+// the work list, without it every pair of every target
+void StrictRun::pairs_gen2(i64 q0, i64 nb, bool matched) const {
+    const dim3 g2 = pairs(nb), t(ST_THREADS);
+    if (!matched) {
+        hipLaunchKernelGGL(strict_pairs2_kernel, g2, t, 0, s, m32(), T, n, targets, q0, w.xnan, (const u32 *)nullptr, (const u32 *)nullptr,
+                           (const u64 *)nullptr, out, jcols);
+    } else if (p.pairs2) {
+        // about 8 192 blocks in all (32 layers at least while a layer is small): with no dirty target every block only reads
+        // the list's length and leaves
+        const i64 per_layer = (i64)g2.x * g2.y;
+        i64 layers = (8192 + per_layer - 1) / per_layer;
+        if (layers < ST_PAIR_LAYERS && per_layer <= 256) layers = ST_PAIR_LAYERS;
+        if (layers > nb) layers = nb;
+        hipLaunchKernelGGL(strict_pairs2_kernel, dim3(g2.x, g2.y, (unsigned)layers), t, 0, s, m32(), T, n, targets, q0, w.xnan,
+                           (const u32 *)w.dlist, (const u32 *)w.dcount, (const u64 *)w.dbits, out, jcols);
+    } else {
+        const int tiles = (int)((n + ST_P3_THREADS - 1) / ST_P3_THREADS);
+        const int chunks = n > 4096 ? 8 : (n > 1024 ? 4 : 1);
+        const i64 items = (i64)nb * tiles * chunks, grid = items > 1024 ? 1024 : items;
+        hipLaunchKernelGGL(strict_pairs3_kernel, dim3((unsigned)grid), dim3(ST_P3_THREADS), 0, s, m32(), T, n, q0, (const u32 *)w.dlist,
+                           (const u32 *)w.dcount, (const u32 *)w.ilist, out, jcols, tiles, chunks);
+    }
+}
+
+// First generation: u64 masks in its own layout (over the image the second generation has consumed: stream order), every pair
+// tested, prefixes enumerated for J = 3, 4.  gate: the matching's per-target dirty counts (null: every target) -- past 1 024
+// timepoints the second generation's pair kernel does not apply.  gathered: Yt holds the external targets' values already.
+void StrictRun::first_generation(i64 q0, i64 nb, const u32 *gate, bool gathered) const {
+    const dim3 g2 = pairs(nb), t(ST_THREADS);
+    if (Q && !gathered) gather_targets(q0, nb);             // external targets reach the first generation through their gathered copy
+    hipLaunchKernelGGL(strict_masks_kernel, curves(nb), t, 0, s, Y, T, n, targets, q0, w.masks, w.xnan, gate,
+                       Q ? (const double *)w.Yt : (const double *)nullptr);
+    if (strict_words(T) <= ST_WREG)
+        hipLaunchKernelGGL((strict_pairs_kernel<true>), g2, t, 0, s, w.masks, T, n, targets, q0, w.xnan, gate, out, jcols);
+    else
+        hipLaunchKernelGGL((strict_pairs_kernel<false>), g2, t, 0, s, w.masks, T, n, targets, q0, w.xnan, gate, out, jcols);
+    if (J >= 3) {
+        const dim3 g3((unsigned)((n * n + ST_THREADS - 1) / ST_THREADS), 1, (unsigned)nb);
+        hipLaunchKernelGGL((strict_subsets_kernel<3>), g3, t, 0, s, w.masks, T, n, targets, q0, w.xnan, out, jcols);
+    }
+    if (J >= 4) {
+        const dim3 g4((unsigned)((n * n * n + ST_THREADS - 1) / ST_THREADS), 1, (unsigned)nb);
+        hipLaunchKernelGGL((strict_subsets_kernel<4>), g4, t, 0, s, w.masks, T, n, targets, q0, w.xnan, out, jcols);
+    }
+}
+
+// The whole pipeline in batches of w.b targets
+int StrictRun::run() const {
+    const i64 B = w.b;
+    SD_HIP(hipMemsetAsync(out, 0, sizeof(u64) * m * jcols, s));
+    if (J >= 3 && (double)n * (double)n * (J >= 4 ? (double)n : 1.0) > 4.0e9)      // one thread per (J-1)-prefix
+        return fail(SD_ERR_UNSUPPORTED, "strict J=%d enumeration too large for n=%lld", J, (long long)n);
+    if (p.match) {
+        SD_HIP(hipMemsetAsync(w.cmask, 0, (size_t)strict_words32(T) * 4, s));
+        // (an external target does not share a value all of Y's curves share: every timepoint counts for it)
+        if (!Q) hipLaunchKernelGGL(strict_const_rows_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, Y, T, n, w.cmask);
+    }
+    if (int rc = rank_images()) return rc;
+    for (i64 q0 = 0; q0 < m; q0 += B) {
+        const i64 nb = m - q0 < B ? m - q0 : B;
+        SD_HIP(hipMemsetAsync(w.xnan, 0, (size_t)nb * 4, s));
+        const u32 *gate = nullptr;
+        if (p.gen2 || p.match) {
+            // with matching, the first pass stores UN words and dirty flags only (see StrictMaskOut)
+            if (p.match) SD_HIP(hipMemsetAsync(w.dflag, 0, (size_t)nb * n, s));
+            masks_gen2(q0, nb, StrictMaskOut{(u32 *)w.masks, p.match ? w.dflag : nullptr, w.cmask, w.tiemask, nullptr, nullptr});
+            if (p.match) {
+                if (int rc = matching(q0, nb)) return rc;
+                gate = w.dirty;
+                // second pass: full masks (UN and DN) for the targets on the pair kernel's work list
+                if (p.gen2) masks_gen2(q0, nb, StrictMaskOut{(u32 *)w.masks, nullptr, w.cmask, w.tiemask, w.dlist, w.dcount});
+            }
+        }
+        if (p.gen2) pairs_gen2(q0, nb, gate != nullptr);
+        else first_generation(q0, nb, gate, p.match);
+        SD_HIP(hipGetLastError());
+    }
+    return SD_OK;
+}
+
+static int launch_bd_strict_impl(const double *Y, i64 T, i64 n, const i64 *targets, const double *Q, i64 m, int J, u64 *out, void *ws, size_t ws_bytes, hipStream_t s) {
+    StrictRun r{Y, Q, targets, T, n, m, J, J - 1, out, s, strict_plan(T, n, m, J, Q != nullptr), StrictWs{}};
+    if (r.p.classes) return launch_bd_strict_classes(r.p, Y, T, n, Q ? nullptr : targets, Q, m, out, 1, ws, ws_bytes, s);
+    // 6 ... 8 timepoints: the workgroup form of the class kernel when no value is NaN.  That is a property of the data: the flag comes
+    // back to the host (one 4-byte copy and a wait: the only route that waits); data with NaN goes on behind the 256-byte flag
+    if (r.p.class_wg && m > 0 && n > 0) {
+        if (!ws || ws_bytes < 256) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
+        u32 *flag = (u32 *)ws, hflag = 0;
+        SD_HIP(hipMemsetAsync(flag, 0, 4, s));
+        launch_strict_any_nan(Y, T, n, Q, m, flag, s);
+        SD_HIP(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, s));
+        SD_HIP(hipStreamSynchronize(s));
+        if (!hflag) return launch_bd_strict_class_wg(Y, T, n, Q ? nullptr : targets, Q, m, nullptr, out, 1, s);
+        if (r.p.class_wg_only)
+            return fail(SD_ERR_UNSUPPORTED, "strict band depth of %lld curves over %lld timepoints with NaN in the data: the state "
+                        "classes of 6 to 8 timepoints take NaN-free data, matching takes up to %lld curves", (long long)n,
+                        (long long)T, (long long)ST_MATCH_MAXN);
+        ws = (char *)ws + 256;
+        ws_bytes -= 256;
+    }
+    const i64 B = strict_batch_for_ws(T, n, m, ws_bytes);     // the recommended batch, or what the caller's workspace holds
+    if (B < 1) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small: %zu bytes, one target takes %zu "
+                           "(sd_bd_strict_min_workspace_bytes)", ws_bytes, strict_ws_for_batch(T, n, 1));
+    if (!r.p.match && J == 2 && strict_pair_tests_refused(n, m))
+        return fail(SD_ERR_UNSUPPORTED, "strict band depth of %lld curves over %lld timepoints: pairs are counted by matching for up to "
+                    "%lld curves (any number for T <= 5, and for T <= 8 without NaN); beyond that every pair is tested, %.1e tests here", (long long)n,
+                    (long long)T, (long long)ST_MATCH_MAXN, strict_pair_tests(n, m));
+    r.w = strict_layout(r.p, T, n, B, ws);                    // within what strict_batch_for_ws measured for B
+    if (!ws || r.w.total > ws_bytes) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
+    return r.run();
+}
+
+int launch_bd_strict(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int J, u64 *out, void *ws, size_t ws_bytes, hipStream_t s) {
     return launch_bd_strict_impl(Y, T, n, targets, nullptr, m, J, out, ws, ws_bytes, s);
 }
 
-size_t bd_strict_external_workspace_bytes(i64 T, i64 n, i64 m) { return bd_strict_workspace_bytes(T, n, m, 2) + align_up((size_t)m * 8, 256); }
-
-int launch_bd_strict_external(const double *Y, i64 T, i64 n, const double *Q, i64 m, u64 *out, void *ws, size_t ws_bytes,
-                              hipStream_t s) {
+int launch_bd_strict_external(const double *Y, i64 T, i64 n, const double *Q, i64 m, u64 *out, void *ws, size_t ws_bytes, hipStream_t s) {
     // the kernels exclude "the target itself" from the others by its column index: -1 for every external target
     Carver cv(ws, ws_bytes);
     i64 *none = (i64 *)cv.take((size_t)m * 8);
@@ -1822,244 +1556,6 @@ int launch_bd_strict_external(const double *Y, i64 T, i64 n, const double *Q, i6
     if (!none || !sws) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small (sd_bd_strict_external_workspace_bytes)");
     SD_HIP(hipMemsetAsync(none, 0xFF, (size_t)m * 8, s));
     return launch_bd_strict_impl(Y, T, n, none, Q, m, 2, out, sws, need, s);
-}
-
-static int launch_bd_strict_impl(const double *Y, i64 T, i64 n, const i64 *targets, const double *Q, i64 m, int J,
-                                 u64 *out, void *ws, size_t ws_bytes, hipStream_t s) {
-    // cross-check builds, SD_STRICT_NOCLASS = 1: short series through the mask kernels like any other
-    if (strict_class_applies(T, n, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1)
-        return launch_bd_strict_classes(Y, T, n, Q ? nullptr : targets, Q, m, out, 1, ws, ws_bytes, s);
-    // 6 ... 8 timepoints: the workgroup form of the class kernel when no value is NaN.  That is a property of the data: the
-    // flag comes back to the host (one 4-byte copy and a wait on the stream -- the only route that waits), data with NaN goes
-    // on to the mask pipeline below
-    if (strict_class_wg_applies(T, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOCLASS") != 1 && m > 0 && n > 0) {
-        if (!ws || ws_bytes < 256) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
-        u32 *flag = (u32 *)ws;
-        u32 hflag = 0;
-        SD_HIP(hipMemsetAsync(flag, 0, 4, s));
-        hipLaunchKernelGGL(strict_any_nan_kernel, dim3(1024), dim3(ST_THREADS), 0, s, Y, T * n, Q ? Q : Y, Q ? T * m : (i64)0, flag);
-        SD_HIP(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, s));
-        SD_HIP(hipStreamSynchronize(s));
-        if (!hflag) {
-            const i64 *tg = Q ? nullptr : targets;
-            switch ((int)T) {
-                case 6: return launch_class_wg<6>(Y, n, tg, Q, m, nullptr, out, 1, s);
-                case 7: return launch_class_wg<7>(Y, n, tg, Q, m, nullptr, out, 1, s);
-                default: return launch_class_wg<8>(Y, n, tg, Q, m, nullptr, out, 1, s);
-            }
-        }
-        if (strict_class_wg_only(T, n, m, J))
-            return fail(SD_ERR_UNSUPPORTED, "strict band depth of %lld curves over %lld timepoints with NaN in the data: the state "
-                        "classes of 6 to 8 timepoints take NaN-free data, matching takes up to %lld curves", (long long)n,
-                        (long long)T, (long long)ST_MATCH_MAXN);
-        ws = (char *)ws + 256;
-        ws_bytes -= 256;
-    }
-    i64 W = strict_words(T);
-    const i64 B = strict_batch_for_ws(T, n, m, ws_bytes);     // the recommended batch, or what the caller's workspace holds
-    if (B < 1) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small: %zu bytes, one target takes %zu "
-                           "(sd_bd_strict_min_workspace_bytes)", ws_bytes, strict_ws_for_batch(T, n, 1));
-    Carver cv(ws, ws_bytes);
-    u64 *masks = (u64 *)cv.take((size_t)B * n * 2 * W * 8);
-    u32 *xnan = (u32 *)cv.take((size_t)B * 4);
-    const i64 slots = strict_table_slots(n);
-    // cross-check builds, SD_STRICT_NOMATCH = 1: every target through the pair kernel
-    const bool match = strict_match_applies(T, n, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_NOMATCH") != 1;
-    // Without matching every pair of curves is tested for every target: refuse what would keep the GPU for hours
-    // (m n^2 / 2 pair tests at ~2e11 per second) instead of starting it
-    if (!match && J == 2 && (double)m * (double)n * (double)n * 0.5 > 2.0e14)
-        return fail(SD_ERR_UNSUPPORTED, "strict band depth of %lld curves over %lld timepoints: pairs are counted by matching for up to "
-                    "%lld curves (any number for T <= 5, and for T <= 8 without NaN); beyond that every pair is tested, %.1e tests here", (long long)n,
-                    (long long)T, (long long)ST_MATCH_MAXN, (double)m * (double)n * (double)n * 0.5);
-    const i64 dwords = (n + 63) / 64;
-    // keys | counters | per target {dirty, below, above, -} | dirty bitmaps
-    unsigned char *tab = (unsigned char *)cv.take((size_t)B * (slots * 16 + 16 + dwords * 8));
-    u32 *cmask = (u32 *)cv.take((size_t)((T + 31) / 32) * 4);
-    double *Yt = (double *)cv.take((size_t)B * ((T + 31) / 32) * 256);
-    u64 *HF = (u64 *)cv.take((size_t)B * n * 8);                                    // hash + flags per (target, curve)
-    unsigned char *dflag = (unsigned char *)cv.take((size_t)B * n);                 // dirty (target, curve) pairs
-    u32 *dlist = (u32 *)cv.take((size_t)(B + 1) * 4);                               // dirty targets of the batch | their number
-    u32 *ilist = (u32 *)cv.take((size_t)B * (n + 4) * 4);                           // per target: the pair kernel's list of curves
-    if (!masks || !xnan || !tab || !cmask || !Yt || !HF || !dflag || !dlist || !ilist)
-        return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
-    u32 *dcount = dlist + B;
-    // cross-check builds, SD_STRICT_FP64_MASKS = 1: masks from the fp64 values at any n
-    const bool rankmasks = !Q && n >= 2 && n <= ST_RANK_MAXN && J == 2 && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_FP64_MASKS") != 1;
-    const bool rank32 = !Q && strict_rank32_applies(T, n, J) && xswitch("SD_STRICT_V1") != 1 && xswitch("SD_STRICT_FP64_MASKS") != 1;
-    u32 *R = nullptr, *rnan = nullptr, *tiemask = nullptr;
-    void *bigws = nullptr;
-    size_t bigws_bytes = 0;
-    if (rank32) {
-        R = (u32 *)cv.take((size_t)T * n * 4);
-        rnan = (u32 *)cv.take((size_t)T * 4);
-        tiemask = (u32 *)cv.take((size_t)((T + 31) / 32) * 4);
-        bigws_bytes = mbd_rank_big_workspace_bytes(T, n, 2);
-        bigws = cv.take(bigws_bytes);
-        if (!R || !rnan || !tiemask || !bigws) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
-    }
-    if (rankmasks) {
-        R = (u32 *)cv.take((size_t)T * n * 4);
-        rnan = (u32 *)cv.take((size_t)T * 4);
-        tiemask = (u32 *)cv.take((size_t)((T + 31) / 32) * 4);
-        if (!R || !rnan || !tiemask) return fail(SD_ERR_WORKSPACE, "strict-depth workspace too small");
-    }
-    // cross-check builds, SD_STRICT_GLOBAL_TABLE = 1: every target's groups through the global-memory table (the route
-    // of targets with more candidates than the LDS table takes)
-    const bool force_global = xswitch("SD_STRICT_GLOBAL_TABLE") == 1;
-    const bool global_possible = match && (force_global || n > ST_MATCH_LDS_CAP);
-    u64 *dbits = (u64 *)(tab + (size_t)B * (slots * 16 + 16));
-    unsigned long long *keys = (unsigned long long *)tab;
-    u32 *cnt = (u32 *)(tab + (size_t)B * slots * 8);
-    u32 *dirty = (u32 *)(tab + (size_t)B * slots * 16);
-    int jcols = J - 1;
-    SD_HIP(hipMemsetAsync(out, 0, sizeof(u64) * m * jcols, s));
-    if (J >= 3) {
-        double threads = 1.0;
-        for (int k = 0; k < J - 1; ++k) threads *= (double)n;
-        if (threads > 4.0e9) return fail(SD_ERR_UNSUPPORTED, "strict J=%d enumeration too large for n=%lld", J, (long long)n);
-    }
-    if (match) {
-        SD_HIP(hipMemsetAsync(cmask, 0, (size_t)((T + 31) / 32) * 4, s));
-        // (an external target does not share a value all of Y's curves share: every timepoint counts for it)
-        if (!Q) hipLaunchKernelGGL(strict_const_rows_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, Y, T, n, cmask);
-    }
-    if (rankmasks) {
-        // the image launcher takes at most 2048 rows per workgroup
-        const i64 step = 2048 * 64;
-        for (i64 r0 = 0; r0 < T; r0 += step) {
-            const i64 rows = T - r0 < step ? T - r0 : step;
-            int rc = n <= 16384 ? launch_rank_bucket_image(Y, n, r0, rows, R + r0 * n, rnan + r0, s)
-                                : launch_rank_medium_image(Y, n, r0, rows, R + r0 * n, rnan + r0, s);
-            if (rc) return rc;
-        }
-        SD_HIP(hipMemsetAsync(tiemask, 0, (size_t)((T + 31) / 32) * 4, s));
-        hipLaunchKernelGGL(strict_row_ties_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, (const u32 *)R, (const u32 *)rnan, n,
-                           tiemask);
-    }
-    if (rank32) {
-        int rc = launch_rank_big_image(Y, T, n, R, rnan, bigws, bigws_bytes, s);
-        if (rc) return rc;
-        SD_HIP(hipMemsetAsync(tiemask, 0, (size_t)((T + 31) / 32) * 4, s));
-        hipLaunchKernelGGL(strict_row_ties32_kernel, dim3((unsigned)T), dim3(ST_THREADS), 0, s, (const u32 *)R, n, tiemask);
-    }
-    for (i64 q0 = 0; q0 < m; q0 += B) {
-        i64 nb = m - q0 < B ? m - q0 : B;
-        SD_HIP(hipMemsetAsync(xnan, 0, (size_t)nb * 4, s));
-        dim3 g1((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)nb);
-        dim3 g2((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)((n + ST_BCHUNK - 1) / ST_BCHUNK), (unsigned)nb);
-        const i64 W32 = (T + 31) / 32;
-        // cross-check builds, SD_STRICT_V1 = 1: the first-generation kernels only (they serve J > 2 anyway)
-        const bool gen2 = xswitch("SD_STRICT_V1") != 1 && J == 2 && W32 <= ST_W32;
-        const u32 *gate = nullptr;
-        if (gen2 || match) {
-            // second generation: 32-bit words, word-major image (fits the same workspace: 2 W32 n u32 <= 2 W n u64)
-            dim3 g1b((unsigned)((n + ST_THREADS - 1) / ST_THREADS), (unsigned)W32, (unsigned)((nb + ST_TG - 1) / ST_TG));
-            // with matching, the first pass stores UN words and dirty flags only (see StrictMaskOut)
-            StrictMaskOut mo{(u32 *)masks, match ? dflag : nullptr, cmask, tiemask, nullptr, nullptr};
-            if (match) SD_HIP(hipMemsetAsync(dflag, 0, (size_t)nb * n, s));
-            if (rankmasks) {
-                hipLaunchKernelGGL(strict_gather_rank_targets_kernel, dim3((unsigned)nb), dim3(ST_THREADS), 0, s, (const u32 *)R, T, n,
-                                   targets, q0, (u32 *)Yt, xnan);
-                hipLaunchKernelGGL(strict_masks_rank_kernel, g1b, dim3(ST_THREADS), 0, s, (const u32 *)R, (const u32 *)Yt, T, n, nb, mo);
-            } else if (rank32) {
-                hipLaunchKernelGGL(strict_gather_rank32_targets_kernel, dim3((unsigned)nb), dim3(ST_THREADS), 0, s, (const u32 *)R, T, n,
-                                   targets, q0, (u32 *)Yt, xnan);
-                hipLaunchKernelGGL(strict_masks_rank32_kernel, g1b, dim3(ST_THREADS), 0, s, (const u32 *)R, (const u32 *)Yt, T, n, nb, mo);
-            } else {
-                hipLaunchKernelGGL(strict_gather_targets_kernel, dim3((unsigned)nb), dim3(ST_THREADS), 0, s, Y, T, n, targets, q0, Q, m,
-                                   Yt, xnan);
-                hipLaunchKernelGGL(strict_masks2_kernel, g1b, dim3(ST_THREADS), 0, s, Y, (const double *)Yt, T, n, nb, mo);
-            }
-            if (match) {
-                hipLaunchKernelGGL(strict_hash_kernel, g1, dim3(ST_THREADS), 0, s, (const u32 *)masks, T, n, xnan, (const u32 *)cmask,
-                                   (const unsigned char *)dflag, HF);
-                SD_HIP(hipMemsetAsync(dirty, 0, (size_t)B * 16, s));
-                SD_HIP(hipMemsetAsync(dcount, 0, 4, s));
-                const i64 lslots = strict_lds_slots(n);
-                const size_t tb = (size_t)lslots * 8 + 2 * (ST_ML_SEEN / 8);
-                SD_HIP(hipFuncSetAttribute((const void *)strict_match_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
-                hipLaunchKernelGGL(strict_match_lds_kernel, dim3((unsigned)nb), dim3(ST_ML_THREADS), tb, s, (const u32 *)masks,
-                                   (const u64 *)HF, T, n, targets, q0, xnan, (const u32 *)cmask, dirty, dbits, dlist, dcount,
-                                   (int)lslots, gen2 ? 0 : 1, force_global ? 1 : 0, out, jcols,
-                                   (gen2 && xswitch("SD_STRICT_PAIRS2") != 1) ? ilist : (u32 *)nullptr);
-                if (global_possible) {
-                    hipLaunchKernelGGL(strict_match_clear_kernel, dim3((unsigned)((slots + 4095) / 4096), (unsigned)nb), dim3(ST_THREADS),
-                                       0, s, (const u32 *)dirty, keys, cnt, slots);
-                    hipLaunchKernelGGL(strict_match_insert_kernel, g1, dim3(ST_THREADS), 0, s, (const u32 *)masks, (const u64 *)HF, T, n,
-                                       targets, q0, xnan, (const u32 *)cmask, (const u32 *)dirty, keys, cnt, slots);
-                    hipLaunchKernelGGL(strict_match_total_kernel,
-                                       dim3((unsigned)nb, (unsigned)((slots + ST_TOTAL_CHUNK - 1) / ST_TOTAL_CHUNK)), dim3(ST_THREADS),
-                                       0, s, (const u32 *)cnt, slots, q0, xnan, (const u32 *)dirty, gen2 ? 0 : 1, out, jcols);
-                }
-                gate = dirty;
-                if (gen2) {
-                    // second pass: full masks (UN and DN) for the targets on the pair kernel's work list
-                    StrictMaskOut mf{(u32 *)masks, nullptr, cmask, tiemask, dlist, dcount};
-                    if (rankmasks)
-                        hipLaunchKernelGGL(strict_masks_rank_kernel, g1b, dim3(ST_THREADS), 0, s, (const u32 *)R, (const u32 *)Yt, T, n, nb,
-                                           mf);
-                    else if (rank32)
-                        hipLaunchKernelGGL(strict_masks_rank32_kernel, g1b, dim3(ST_THREADS), 0, s, (const u32 *)R, (const u32 *)Yt, T, n,
-                                           nb, mf);
-                    else
-                        hipLaunchKernelGGL(strict_masks2_kernel, g1b, dim3(ST_THREADS), 0, s, Y, (const double *)Yt, T, n, nb, mf);
-                }
-            }
-            if (gen2) {
-                if (gate) {
-                    // about 8 192 blocks in all (32 layers at least while a layer is small): with no dirty target every
-                    // block only reads the list's length and leaves
-                    const i64 per_layer = (i64)g2.x * g2.y;
-                    i64 layers = (8192 + per_layer - 1) / per_layer;
-                    if (layers < ST_PAIR_LAYERS && per_layer <= 256) layers = ST_PAIR_LAYERS;
-                    if (layers > nb) layers = nb;
-                    dim3 g2m(g2.x, g2.y, (unsigned)layers);
-                    // cross-check builds, SD_STRICT_PAIRS2 = 1: every partner of a dirty curve through the mask test
-                    if (xswitch("SD_STRICT_PAIRS2") == 1)
-                        hipLaunchKernelGGL(strict_pairs2_kernel, g2m, dim3(ST_THREADS), 0, s, (const u32 *)masks, T, n, targets, q0, xnan,
-                                           (const u32 *)dlist, (const u32 *)dcount, (const u64 *)dbits, out, jcols);
-                    else
-                    {
-                        const int tiles = (int)((n + ST_P3_THREADS - 1) / ST_P3_THREADS);
-                        const int chunks = n > 4096 ? 8 : (n > 1024 ? 4 : 1);
-                        i64 grid = (i64)nb * tiles * chunks;
-                        if (grid > 1024) grid = 1024;
-                        hipLaunchKernelGGL(strict_pairs3_kernel, dim3((unsigned)grid), dim3(ST_P3_THREADS), 0, s, (const u32 *)masks, T, n,
-                                           q0, (const u32 *)dlist, (const u32 *)dcount, (const u32 *)ilist, out, jcols, tiles, chunks);
-                    }
-                } else {
-                    hipLaunchKernelGGL(strict_pairs2_kernel, g2, dim3(ST_THREADS), 0, s, (const u32 *)masks, T, n, targets, q0, xnan,
-                                       (const u32 *)nullptr, (const u32 *)nullptr, (const u64 *)nullptr, out, jcols);
-                }
-                SD_HIP(hipGetLastError());
-                continue;
-            }
-            // T > 1024: the pair kernel of the second generation keeps 2 x 32 words in registers and does not apply; the
-            // targets that matching could not take (ties, NaN) go through the first generation below, which rebuilds
-            // their masks in its own layout over the image just consumed (stream order)
-        }
-        if (Q && !(gen2 || match))      // external targets reach the first generation through their gathered copy
-            hipLaunchKernelGGL(strict_gather_targets_kernel, dim3((unsigned)nb), dim3(ST_THREADS), 0, s, Y, T, n, targets, q0, Q, m,
-                               Yt, xnan);
-        hipLaunchKernelGGL(strict_masks_kernel, g1, dim3(ST_THREADS), 0, s, Y, T, n, targets, q0, masks, xnan, gate,
-                           Q ? (const double *)Yt : (const double *)nullptr);
-        if (W <= ST_WREG)
-            hipLaunchKernelGGL((strict_pairs_kernel<true>), g2, dim3(ST_THREADS), 0, s, masks, T, n, targets, q0, xnan, gate, out, jcols);
-        else
-            hipLaunchKernelGGL((strict_pairs_kernel<false>), g2, dim3(ST_THREADS), 0, s, masks, T, n, targets, q0, xnan, gate, out, jcols);
-        if (J >= 3) {
-            i64 flat = n * n;
-            dim3 g3((unsigned)((flat + ST_THREADS - 1) / ST_THREADS), 1, (unsigned)nb);
-            hipLaunchKernelGGL((strict_subsets_kernel<3>), g3, dim3(ST_THREADS), 0, s, masks, T, n, targets, q0, xnan, out, jcols);
-        }
-        if (J >= 4) {
-            i64 flat = n * n * n;
-            dim3 g4((unsigned)((flat + ST_THREADS - 1) / ST_THREADS), 1, (unsigned)nb);
-            hipLaunchKernelGGL((strict_subsets_kernel<4>), g4, dim3(ST_THREADS), 0, s, masks, T, n, targets, q0, xnan, out, jcols);
-        }
-        SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
 }
 
 }  // namespace sd

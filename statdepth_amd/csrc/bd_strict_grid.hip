@@ -3,7 +3,7 @@
 // in R^3).  Written out for three coordinates below; two and four work the same way (2 048 / 64 cells per coordinate, 9 / 81 classes).
 //
 // Per target x the quantity is a function of the 27 counts h[c] of the OTHER points by state vector c in {tie, above, below}^3
-// (strict_class_wg_kernel, bd_strict.hip: contained ordered pairs = sum over compatible classes, by the wild-card transform).
+// (strict_class_wg_kernel, bd_strict_class.hip: contained ordered pairs = sum over compatible classes, by the wild-card transform).
 // That kernel classifies every point against every target: O(n^2), 427 ms at n = 10^6.  Here the counts come from a GRID:
 //   * every coordinate is replaced by its integer rank B (points strictly below; equal values share B): the large-n rank
 //     route's image mode, one pass over the 3 x n matrix (mbd_rank_big.hip).  Comparing ranks IS comparing values, ties included.

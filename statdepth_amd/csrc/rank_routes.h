@@ -1,7 +1,9 @@
-// rank_routes.h -- what the translation units of the rank routes and of the strict path call in each other (internal; the
-// launchers sd_api.hip dispatches to are in sd_common.h).  One declaration per signature.
+// rank_routes.h -- what the translation units of the rank routes call in each other, and what the strict path calls of them
+// (internal; the launchers sd_api.hip dispatches to are in sd_common.h; the strict path's own routes: strict_routes.h).  One
+// declaration per signature.
 #pragma once
 #include "sd_common.h"
+#include "strict_routes.h"
 
 namespace sd {
 
@@ -34,12 +36,6 @@ u32 rank_bucket32_epoch();
 
 // ---- mbd_rank_big.hip: the B words of every (row, curve) to img[T][n], the rows' NaN counts to nnan[T] ----
 int launch_rank_big_image(const double *Y, i64 T, i64 n, u32 *img, u32 *nnan, void *ws, size_t ws_bytes, hipStream_t s);
-
-// ---- bd_strict_grid.hip: two to four coordinates at large n through a grid of cells instead of every pair of points ----
-bool bd_strict_grid_applies(i64 T, i64 n, int J);
-size_t bd_strict_grid_workspace_bytes(i64 T, i64 n, bool subset);
-int launch_bd_strict_grid(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, u64 *out, int jcols, u32 *flag, void *ws,
-                          size_t ws_bytes, hipStream_t s);
 
 // ---- the retired generations, one hook per point where a cross-check switch diverts a product route ----
 // libstatdepth_hip_xcheck.so: defined next to the retired kernels (mbd_rank_ab_retired.hip, mbd_rank.hip,

@@ -399,10 +399,7 @@ int sd_bd_strict_j_counts(const double *X, int64_t T, int64_t n, int64_t st, int
     if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
     size_t need = cv.rest();                                   // batches are sized to what the caller passed
     void *sws = cv.take(need);
-    // 6 ... 8 timepoints, J = 2: NaN-free data is counted through state classes and takes 256 bytes (a flag); whether the data
-    // is NaN-free the launcher finds out itself, and data with NaN then meets the mask pipeline's own check of what it was given
-    const size_t floor = (J == 2 && T >= 6 && T <= 8) ? (size_t)256 : bd_strict_min_workspace_bytes(T, n, m, J);
-    if (!sws || need < floor)
+    if (!sws || need < bd_strict_launch_floor_bytes(T, n, m, J))
         return fail(SD_ERR_WORKSPACE, "workspace too small for the strict-depth masks (sd_bd_strict_min_workspace_bytes)");
     return launch_bd_strict(Y, T, n, targets, m, J, (u64 *)out, sws, need, s);
 }

@@ -96,6 +96,7 @@ int launch_mbd_rank_big(const double *Y, i64 T, i64 n, const i64 *targets, i64 t
 size_t bd_strict_workspace_bytes(i64 T, i64 n, i64 m, int J);
 size_t bd_strict_min_workspace_bytes(i64 T, i64 n, i64 m, int J);
 size_t bd_strict_nanfree_workspace_bytes(i64 T, i64 n, i64 m, int J);
+size_t bd_strict_launch_floor_bytes(i64 T, i64 n, i64 m, int J);    // what launch_bd_strict needs at least to be called
 int launch_bd_strict(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int J,
                      u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
 size_t bd_strict_external_workspace_bytes(i64 T, i64 n, i64 m);

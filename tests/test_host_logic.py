@@ -257,6 +257,44 @@ def test_bench_contract_and_committed_evidence():
     assert abs(line["roofline"]["frac"] - line["roofline"]["achieved"] / line["roofline"]["peak"]) < 1e-9
 
 
+def test_strict_workspace_sizes_are_pinned(built):
+    """The strict path's workspace sizes are part of what callers see: the batch size a launcher picks for a given buffer,
+    and with it the launch sequence, follows from them.  Literal values per branch of the sizing code (contiguous strides
+    st = n, sn = 1), recorded from the build before the route plan and the single layout function replaced the hand-written
+    sums; pure host code, no GPU."""
+    import ctypes
+    lib = ctypes.CDLL(built.LIB_PATH)
+    i64 = ctypes.c_int64
+    for name in ("sd_bd_strict_j_workspace_bytes", "sd_bd_strict_min_workspace_bytes", "sd_bd_strict_nanfree_workspace_bytes",
+                 "sd_bd_strict_external_workspace_bytes"):
+        getattr(lib, name).restype = ctypes.c_size_t
+    # (T, n, m, J), recommended, floor, NaN-free (J = 2), external targets (J = 2)
+    pinned = [
+        ((1, 2, 2, 2), 5120, 5120, 5120, 4864),                                   # state classes: a flag
+        ((3, 1000, 1000, 2), 5120, 5120, 5120, 12800),
+        ((7, 5000, 5000, 2), 2040505600, 553984, 5120, 2040545280),               # 6 ... 8 timepoints: flag + mask pipeline
+        ((7, 140000, 140000, 2), 5120, 5120, 5120, 1124608),                      # ... beyond matching and the pair limit: flag only
+        ((70, 300, 300, 2), 9309184, 121088, 9309184, 9311232),                   # 16-bit rank image
+        ((70, 300, 7, 2), 305408, 121088, 305408, 305152),                        # ... batch capped by m
+        ((45, 40000, 40000, 2), 3428533248, 90787840, 3428533248, 3428852736),    # 32-bit rank image + the large-n route's scratch
+        ((40, 140000, 10, 2), 124671232, 12471296, 124671232, 124670976),         # no image (n > 131 071)
+        ((1100, 200, 200, 2), 16378880, 971776, 16378880, 16380160),              # T > 1024
+        ((2100, 150, 150, 2), 17227264, 1388544, 17227264, 17228032),
+        ((6, 12, 12, 3), 25856, 7936, None, None),                                # J = 3, 4
+        ((6, 12, 12, 4), 25856, 7936, None, None),
+        ((1000, 10000, 10000, 2), 3341158912, 43236864, 3341158912, 3341238528),  # batch below 1024 at 2 GiB: the 16 GiB rule
+        ((3, 100000, 100000, 2), 97100288, 5120, 97100288, 97899776),             # the grid of cells (m = n)
+        ((3, 100000, 3000, 2), 5120, 5120, 5120, 28672),                          # ... not for a small subset (32 m < n)
+    ]
+    for (T, n, m, J), full, floor, nanfree, external in pinned:
+        shape = (T, n, m, J)
+        assert lib.sd_bd_strict_j_workspace_bytes(i64(T), i64(n), i64(n), i64(1), i64(m), J) == full, shape
+        assert lib.sd_bd_strict_min_workspace_bytes(i64(T), i64(n), i64(n), i64(1), i64(m), J) == floor, shape
+        if J == 2:
+            assert lib.sd_bd_strict_nanfree_workspace_bytes(i64(T), i64(n), i64(n), i64(1), i64(m)) == nanfree, shape
+            assert lib.sd_bd_strict_external_workspace_bytes(i64(T), i64(n), i64(m)) == external, shape
+
+
 def test_committed_profiles_are_of_the_shipped_kernels():
     """The newest committed kernel statistics of the headline workload must not predate the last commit that touched the
     kernels it measures: a stale profile is evidence of another build."""
@@ -294,9 +332,12 @@ def test_committed_profiles_are_of_the_shipped_kernels():
     iss = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("issue_strict.json"))
     assert iss
     t_iss = last_commit_time([os.path.join("profiles", iss[-1])])
-    t_strict = last_commit_time(["statdepth_amd/csrc/bd_strict.hip"])
+    strict_files = sorted(os.path.join("statdepth_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "statdepth_amd", "csrc"))
+                          if re.fullmatch(r"bd_strict.*\.hip", f))
+    assert len(strict_files) >= 2
+    t_strict = last_commit_time(strict_files)               # the newest commit among them
     if t_iss is not None:
-        assert t_iss >= t_strict, f"profiles/{iss[-1]} predates the last change of bd_strict.hip: run tools/issue_strict.py"
+        assert t_iss >= t_strict, f"profiles/{iss[-1]} predates the last change of the bd_strict*.hip files: run tools/issue_strict.py"
     roof = bench.strict_roofline()
     assert roof and roof["counter_file"] == os.path.join("profiles", iss[-1])
 

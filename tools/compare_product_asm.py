@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 device code of the product rank kernels between two source trees.
+"""Compare the gfx950 device code of the product kernels between two source trees.
 
     python tools/compare_product_asm.py --parent <checkout of the parent commit> [--new <tree>] [--out FILE]
 
-For both trees the product build (the Makefile's CXXFLAGS, no -DSD_CROSSCHECK) of FILES is compiled with
---cuda-device-only -S.  Per kernel symbol the instruction stream (comments dropped, local labels renumbered per kernel) and
-the .amdhsa_ resource block (VGPRs, SGPRs, LDS, scratch, ...) must be identical.  Kernels may disappear from the product
-only when they are named in ALLOWED_TO_LEAVE, and then they must be in one of the new tree's XONLY translation units (the
-cross-check library).  Needs hipcc only, no GPU.  Exit status 0: all of that holds.
+For both trees the product build (the Makefile's CXXFLAGS, no -DSD_CROSSCHECK) of the translation units is compiled with
+--cuda-device-only -S: each tree's own SHARED list by default, so a file that was split or renamed needs no mention here.
+Kernels are compared by symbol over the union of a tree's files -- one that moved to another product file is still the same
+kernel: its instruction stream (comments dropped, local labels renumbered per kernel) and its .amdhsa_ resource block (VGPRs,
+SGPRs, LDS, scratch, ...) must be identical.  Kernels may disappear from the product only when they are named in
+MOVED_TO_XONLY, and then they must be in one of the new tree's XONLY translation units (the cross-check library).  Needs hipcc
+only, no GPU.  Exit status 0: all of that holds.
 """
 import argparse
 import concurrent.futures
@@ -17,8 +19,7 @@ import subprocess
 import sys
 import tempfile
 
-FILES = ("mbd_rank_ab.hip", "mbd_rank_big.hip", "mbd_rank_bucket.hip", "band_enum.hip")
-ALLOWED_TO_LEAVE = ("chunk_sort_kernel", "chunk_search_kernel", "bucket_search_kernel")
+MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
 
 
 def make_var(makefile, name):
@@ -94,41 +95,52 @@ def main():
     ok = True
     with tempfile.TemporaryDirectory() as tmpdir:
         tmp = a.workdir or tmpdir
-        xonly = make_var(os.path.join(a.new, "statdepth_amd", "csrc", "Makefile"), "XONLY").split()
+        def unit_list(root, var):
+            return make_var(os.path.join(root, "statdepth_amd", "csrc", "Makefile"), var).split()
+        units = {"parent": unit_list(a.parent, "SHARED"), "new": unit_list(a.new, "SHARED"), "xonly": unit_list(a.new, "XONLY")}
+        roots = {"parent": a.parent, "new": a.new, "xonly": a.new}
         jobs = {}
         with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
-            for tag, root, fns in (("parent", a.parent, FILES), ("new", a.new, FILES), ("xonly", a.new, xonly)):
+            for tag, fns in units.items():
                 os.makedirs(os.path.join(tmp, tag), exist_ok=True)
                 for fn in fns:
-                    jobs[(tag, fn)] = ex.submit(emit, root, fn, os.path.join(tmp, tag), a.reuse)
-        asm = {k: kernels(f.result()) for k, f in jobs.items()}
-        xonly_names = {demangle(s) for (tag, _), ks in asm.items() if tag == "xonly" for s in ks}
-        for fn in FILES:
-            old, new = asm[("parent", fn)], asm[("new", fn)]
-            same = 0
-            for sym in sorted(old):
-                name = demangle(sym)
-                if sym not in new:
-                    short = name.split("::")[-1].split("<")[0]
-                    allowed = short in ALLOWED_TO_LEAVE and name in xonly_names
-                    ok &= allowed
-                    report.append(f"{fn}: {name}: left the product, " +
-                                  ("present in an XONLY unit: allowed" if allowed else "NOT ALLOWED"))
-                    continue
-                code = old[sym][0] == new[sym][0]
-                resources = old[sym][1] == new[sym][1]
-                if code and resources:
-                    same += 1
-                else:
-                    ok = False
-                    report.append(f"{fn}: {name}: DIFFERS (instructions {'same' if code else 'differ'}, "
-                                  f"resource block {'same' if resources else 'differs'})")
-            for sym in sorted(set(new) - set(old)):
+                    jobs[(tag, fn)] = ex.submit(emit, roots[tag], fn, os.path.join(tmp, tag), a.reuse)
+        where, asm = {}, {}                              # per tree: symbol -> file, symbol -> (instructions, resources)
+        for (tag, fn), f in jobs.items():
+            for sym, k in kernels(f.result()).items():
+                assert sym not in asm.setdefault(tag, {}), f"{sym} is defined in two {tag} units"
+                asm[tag][sym] = k
+                where.setdefault(tag, {})[sym] = fn
+        old, new = asm.get("parent", {}), asm.get("new", {})
+        xonly_names = {demangle(s) for s in asm.get("xonly", {})}
+        same = moved = 0
+        for sym in sorted(old):
+            name = demangle(sym)
+            if sym not in new:
+                short = name.split("::")[-1].split("<")[0]
+                allowed = short in MOVED_TO_XONLY and name in xonly_names
+                ok &= allowed
+                report.append(f"{where['parent'][sym]}: {name}: left the product, " +
+                              ("present in an XONLY unit: allowed" if allowed else "NOT ALLOWED"))
+                continue
+            code = old[sym][0] == new[sym][0]
+            resources = old[sym][1] == new[sym][1]
+            if code and resources:
+                same += 1
+                if where["parent"][sym] != where["new"][sym]:
+                    moved += 1
+                    report.append(f"{name}: identical, moved {where['parent'][sym]} -> {where['new'][sym]}")
+            else:
                 ok = False
-                report.append(f"{fn}: {demangle(sym)}: NEW in the product")
-            insts = sum(len(old[s][0]) for s in old if s in new)
-            report.append(f"{fn}: {len(old)} kernels in the parent, {len(new)} in the new tree, {same} identical "
-                          f"(instruction stream, {insts} lines, and .amdhsa_ block)")
+                report.append(f"{where['new'][sym]}: {name}: DIFFERS (instructions {'same' if code else 'differ'}, "
+                              f"resource block {'same' if resources else 'differs'})")
+        for sym in sorted(set(new) - set(old)):
+            ok = False
+            report.append(f"{where['new'][sym]}: {demangle(sym)}: NEW in the product")
+        insts = sum(len(old[s][0]) for s in old if s in new)
+        report.append(f"{len(units['parent'])} product files in the parent, {len(units['new'])} in the new tree")
+        report.append(f"{len(old)} kernels in the parent, {len(new)} in the new tree, {same} identical (instruction stream, "
+                      f"{insts} lines, and .amdhsa_ block), {moved} of them in another file")
     report.append("RESULT: " + ("product kernels unchanged" if ok else "MISMATCH"))
     text = "\n".join(report) + "\n"
     sys.stdout.write(text)
