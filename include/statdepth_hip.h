@@ -386,6 +386,48 @@ int sd_halfspace_external_counts(const double *P, int64_t n, int d, const double
 int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
                                int64_t nb, int bs, int64_t *out, void *stream);
 
+/* ---- K11: exact halfspace (Tukey) depth of a point cloud in the plane ------------------------
+ * No reference code.  P is n x 2 row-major fp64 (device).  For a target q and every sample point p_i:
+ *   v_i   = (fl(p_i0 - q0), fl(p_i1 - q1))   one rounded fp64 subtraction per component;
+ *   c0    = #{i : v_i = (0, 0)}   (q itself when it is a row of the sample; an external q adds one);
+ *   cross(a, b) = a0 b1 - a1 b0,  dot(a, b) = a0 b0 + a1 b1,  of which only the EXACT signs are used;
+ *   for every nonzero v_j, over the nonzero v_k:
+ *     L_j = #{cross(v_j, v_k) > 0}              R_j = #{cross(v_j, v_k) < 0}
+ *     S_j = #{cross = 0 and dot > 0} (j itself)  O_j = #{cross = 0 and dot < 0}
+ *   out[q] = c0 + min over j of min(L_j + O_j, R_j + S_j, L_j + S_j, R_j + O_j);   out[q] = c0 when no v is nonzero.
+ * The four candidates are the open sides of the line through q along v_j turned a hair to either side; the count of a
+ * closed halfplane is upper semicontinuous in its direction, so the minimum over all closed halfplanes through q is
+ * reached at such lines: out / n is the halfspace depth of q in the sample, not a bound of it.
+ * Predicate: sign(a b - c d) from p1 = fl(a b), p2 = fl(c d): where p1 != p2 the sign of p1 - p2 (rounding is monotone),
+ * otherwise the sign of e1 - e2 with the exact rounding errors e = fma(a, b, -p).  Exact while no product overflows or
+ * underflows: the data must be finite with |coordinate| <= 2^500 (the host layer raises otherwise), and every nonzero
+ * coordinate difference must be at least 2^-500 in magnitude -- NOT checked: the differences are not known before the
+ * kernel forms them.  The sign of the rounded cross product is not a substitute (it is wrong for nearly collinear triples).
+ * algo: 0 = auto, 1 = sweep, 2 = pairwise; the same integers from both.
+ *   sweep     one workgroup per target: the nonzero v in LDS (16 bytes each), each read through its image in the
+ *             half-plane y > 0 or (y = 0, x > 0) (exact negation, the flip recomputed from v), sorted by angle with the
+ *             predicate as comparator; cuts where neighbours have cross != 0 and after the last element; for a cut after
+ *             position s, A = #{i <= s unflipped} + #{i > s flipped}, B likewise with the flags exchanged;
+ *             out = c0 + min over cuts of min(A, B).  Capacity tiers of 64 / 512 / 2048 / 8192 sample points
+ *             (64 / 256 / 512 / 1024 threads); samples of at most 8192 points.  O(n log^2 n) per target.
+ *   pairwise  the definition as it stands, O(n^2) predicate pairs per target: any n below 2^31.
+ *   auto      the sweep up to 8192 sample points, the pairwise kernel above.
+ *   sd_halfspace2_counts:          the sample is P; targets: m int64 row indices (device), NULL = all (m == n).
+ *   sd_halfspace2_external_counts: m external points Q (m x 2, device); the sample of Q[q] is P u {Q[q]}, n + 1 points,
+ *       Q[q] adds one to c0; depth = out / (n + 1).
+ *   sd_halfspace2_subset_counts:   blocks of rows, members int32[nb*bs], -1 padded at the end, the block's target LAST;
+ *       the block (target included) is the sample: depth = out / block size.  An empty block gives 0.
+ * SD_ERR_INVALID for NULL pointers, n < 1, bs < 1 or an unknown algo; SD_ERR_UNSUPPORTED for 2^31 or more points, for
+ * algo = 1 on a sample (n, resp. bs) above 8192 points, or beyond 10^14 predicate evaluations on the route that would run
+ * (pairwise: m n^2; sweep: m (C / 2) log2 C (log2 C + 1) / 2 at capacity tier C).  All before any device work.  Every
+ * launch is bounded in work. */
+int sd_halfspace2_counts(const double *P, int64_t n, const int64_t *targets, int64_t m, int algo, int64_t *out,
+                         void *stream);
+int sd_halfspace2_external_counts(const double *P, int64_t n, const double *Q, int64_t m, int algo, int64_t *out,
+                                  void *stream);
+int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
+                                int64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

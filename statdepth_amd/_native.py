@@ -79,6 +79,9 @@ SIGNATURES = {
     "sd_halfspace_pairwise_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sd_halfspace_external_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sd_halfspace_subset_counts": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_halfspace2_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_halfspace2_external_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_halfspace2_subset_counts": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
 }
 
 

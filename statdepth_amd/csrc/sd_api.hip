@@ -758,4 +758,56 @@ int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *
     return launch_halfspace_subsets(P, n, d, U, k, members, nb, bs, out, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// K11
+// ---------------------------------------------------------------------------
+// shape checks shared by the three entry points; cnt_max = the largest sample in P, others = points a target is counted
+// among; *route = the route that runs (1 sweep, 2 pairwise)
+static int check_halfspace2(const double *P, i64 n, i64 m, int algo, const void *out, i64 cnt_max, i64 others, int *route) {
+    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n < 1 || m < 0) return fail(SD_ERR_INVALID, "bad shape (n=%lld, m=%lld)", (long long)n, (long long)m);
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (sweep), 2 (pairwise)", algo);
+    if (n >= ((i64)1 << 31) || others >= ((i64)1 << 31))          // counts and indices are 32-bit in the kernels
+        return fail(SD_ERR_UNSUPPORTED, "exact halfspace counts take fewer than 2^31 points, got %lld", (long long)n);
+    *route = halfspace2_route(algo, cnt_max);
+    if (*route == 0)
+        return fail(SD_ERR_UNSUPPORTED, "the sweep holds samples of up to %lld points, got %lld (algo 0 or 2 takes them)",
+                    (long long)HX_SWEEP_CAPACITY, (long long)cnt_max);
+    const double work = halfspace2_work(*route, m, cnt_max);
+    if (work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g predicate evaluations exceed the cap of %.0e", work, HS_MAX_WORK);
+    return SD_OK;
+}
+
+int sd_halfspace2_counts(const double *P, int64_t n, const int64_t *targets, int64_t m, int algo, int64_t *out,
+                         void *stream) {
+    int route = 0;
+    int rc = check_halfspace2(P, n, m, algo, out, n, n, &route);
+    if (rc) return rc;
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    if (m == 0) return SD_OK;
+    return launch_halfspace2(P, n, targets, m, route, out, (hipStream_t)stream);
+}
+
+int sd_halfspace2_external_counts(const double *P, int64_t n, const double *Q, int64_t m, int algo, int64_t *out,
+                                  void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int route = 0;
+    int rc = check_halfspace2(P, n, m, algo, out, n, n + 1, &route);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_halfspace2_external(P, n, Q, m, route, out, (hipStream_t)stream);
+}
+
+int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
+                                int64_t *out, void *stream) {
+    if (!members) return fail(SD_ERR_INVALID, "null pointer");
+    if (bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
+    int route = 0;
+    int rc = check_halfspace2(P, n, nb, algo, out, bs, bs, &route);
+    if (rc) return rc;
+    if (nb == 0) return SD_OK;
+    return launch_halfspace2_subsets(P, n, members, nb, bs, route, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -155,6 +155,15 @@ int launch_halfspace_external(const double *P, i64 n, int d, const double *U, i6
 int launch_halfspace_subsets(const double *P, i64 n, int d, const double *U, i64 k, const int *members, i64 nb, int bs,
                              i64 *out, hipStream_t s);
 
+// K11 exact halfspace depth in the plane (halfspace_exact.hip): route 1 = angular sweep in LDS, 2 = pairwise L/R/S/O
+constexpr i64 HX_SWEEP_CAPACITY = 8192;                             // sample points one sweep workgroup holds
+int halfspace2_route(int algo, i64 cnt_max);                       // 0: algo = 1 (sweep) above the capacity
+double halfspace2_work(int route, i64 m, i64 cnt_max);             // predicate evaluations
+int launch_halfspace2(const double *P, i64 n, const i64 *targets, i64 m, int route, i64 *out, hipStream_t s);
+int launch_halfspace2_external(const double *P, i64 n, const double *Q, i64 m, int route, i64 *out, hipStream_t s);
+int launch_halfspace2_subsets(const double *P, i64 n, const int *members, i64 nb, int bs, int route, i64 *out,
+                              hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

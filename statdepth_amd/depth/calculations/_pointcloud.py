@@ -7,7 +7,8 @@ points, over the volume of the sample's convex hull -- with the volume sums on t
 (scipy's Qhull, as in the reference) on the host; DESIGN.md §3 K7 / §4 lists where it departs from the reference.
 Mahalanobis depth (:152-173) is not provided: the reference's covariance is singular by construction.
 Halfspace (Tukey) depth over a fixed direction set (containment='halfspace', sd_halfspace_*) is an extension the
-reference does not have; DESIGN.md §3 K10 states its definition.
+reference does not have; DESIGN.md §3 K10 states its definition.  directions='exact' asks for the exact halfspace depth
+(d = 2: sd_halfspace2_*; d = 1: the direction (1.0), which is exact already).
 """
 from typing import Union
 
@@ -77,6 +78,26 @@ def _halfspace_check(P: np.ndarray) -> None:
         raise ValueError('halfspace depth does not accept NaN or infinite values')
 
 
+def _halfspace_setup(P: np.ndarray, directions, seed):
+    """Host checks of containment='halfspace', then the k x d direction array -- or None for the exact depth of a planar
+    cloud (directions='exact', d = 2: no direction set, K11)."""
+    _halfspace_check(P)
+    d = P.shape[1]
+    if not isinstance(directions, str):
+        return _halfspace_directions(directions, seed, d)
+    if directions != 'exact':
+        raise ValueError(f"directions must be a positive number of directions, a (k x {d}) array or 'exact', "
+                         f"got {directions!r}")
+    if d == 1:
+        return np.ones((1, 1), dtype=np.float64)         # one direction up to sign: exact already
+    if d != 2:
+        raise NotImplementedError("exact halfspace depth (directions='exact') is implemented for the plane "
+                                  f"(d = 2; d = 1 is exact with any directions), got d = {d}")
+    if P.size and np.abs(P).max() > 2.0 ** 500:          # the exact predicate's products must not overflow
+        raise ValueError('exact halfspace depth needs coordinates of magnitude at most 2^500')
+    return None
+
+
 def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None, containment='simplex',
                     quiet=True, device=None, directions=1000, seed=0) -> pd.Series:
     n, d = data.shape
@@ -110,10 +131,13 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         # An extension (no such string in the reference): min over the directions of min(#{p.u <= x.u}, #{p.u >= x.u}),
         # the point itself and ties counted, over n -- the random Tukey depth, an upper bound of the exact halfspace
         # depth for d >= 2 and exact for d = 1
+        # directions='exact': the halfspace depth itself for d <= 2, seed unused
         P = data.to_numpy(dtype=np.float64)
-        _halfspace_check(P)
-        U = _halfspace_directions(directions, seed, d)
-        counts = engine.halfspace_counts(P, U, _row_positions(data, to_compute), device=device)
+        U = _halfspace_setup(P, directions, seed)
+        if U is None:
+            counts = engine.halfspace_exact_counts(P, _row_positions(data, to_compute), device=device)
+        else:
+            counts = engine.halfspace_counts(P, U, _row_positions(data, to_compute), device=device)
         return pd.Series(index=to_compute, data=counts.astype(np.float64) / n)
     elif containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
@@ -133,6 +157,8 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directio
         return engine.oja_subset_volume_sums(P, mem, device=device) / vols
     if containment == 'halfspace':                       # the block, its target included, is the sample
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
+        if directions is None:                           # directions='exact' in the plane
+            return engine.halfspace_exact_subset_counts(P, mem, device=device).astype(np.float64) / sizes
         return engine.halfspace_subset_counts(P, mem, directions, device=device).astype(np.float64) / sizes
     if containment == 'simplex':
         d = P.shape[1]
@@ -152,10 +178,11 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     so the reference itself cannot run this path any more).  The draws are made first -- rows by position, from
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
     (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
-    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts) instead of as many `_pointwisedepth` calls.
+    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts / sd_halfspace2_subset_counts) instead
+    of as many `_pointwisedepth` calls.
     Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
     normaliser (the reference's is identically 0).  Halfspace: one direction set (directions, seed) for
-    every block; it takes nothing from the global RNG.
+    every block, or none (directions='exact'); neither takes anything from the global RNG.
     """
     if K == 1:
         return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device,
@@ -167,8 +194,7 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     n, d = data.shape
     U = None
     if containment == 'halfspace':                       # host checks first: bad input never reaches the RNG or the GPU
-        _halfspace_check(data.to_numpy(dtype=np.float64))
-        U = _halfspace_directions(directions, seed, d)
+        U = _halfspace_setup(data.to_numpy(dtype=np.float64), directions, seed)
     if to_compute is None:
         to_compute = data.index
     ss = n // K

@@ -145,7 +145,9 @@ class _PointwiseDepth(_FunctionalDepthSeries):
 def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, containment='simplex', quiet=True,
                     *, device=None, directions=1000, seed=0) -> _PointwiseDepth:
     """`directions` and `seed` belong to containment='halfspace' (every other containment ignores them): an int k asks
-    for k unit directions drawn from `np.random.default_rng(seed)`, a (k x d) array is used as given."""
+    for k unit directions drawn from `np.random.default_rng(seed)`, a (k x d) array is used as given -- both give the
+    directional depth, an upper bound of the halfspace depth once d >= 2.  'exact' gives the halfspace depth itself for
+    d <= 2 (`seed` is ignored; d >= 3 raises NotImplementedError)."""
     if K is not None:
         depth = _samplepointwisedepth(data=data, to_compute=to_compute, K=K, containment=containment,
                                       device=device, directions=directions, seed=seed)

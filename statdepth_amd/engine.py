@@ -627,3 +627,73 @@ def halfspace_subset_counts(P, members, U, device=None):
     out = t.empty(nb, dtype=t.int64, device=dev)
     return _launch(dev, lib.sd_halfspace_subset_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), Ud.shape[0],
                    md.data_ptr(), nb, bs)
+
+
+HALFSPACE2_ALGOS = {"auto": 0, "sweep": 1, "pairwise": 2}
+_HALFSPACE2_MAX_ABS = 2.0 ** 500
+
+
+def _halfspace2_algo(algo):
+    if algo not in HALFSPACE2_ALGOS:
+        raise ValueError("algo must be 'auto', 'sweep' or 'pairwise'")
+    return HALFSPACE2_ALGOS[algo]
+
+
+def _plane_points(A, dev, what="P"):
+    """The n x 2 point array on dev: finite, |coordinate| <= 2^500 (the exact predicate's products must not overflow)."""
+    t = torch()
+    Ad = _upload(A, 2, dev)
+    if Ad.shape[1] != 2:
+        raise ValueError(f"exact halfspace counts are defined for points in the plane: {what} must be n x 2")
+    if Ad.numel() and not bool((Ad.abs() <= _HALFSPACE2_MAX_ABS).all()):      # NaN fails the comparison too
+        raise ValueError("exact halfspace counts need finite coordinates of magnitude at most 2^500")
+    return Ad
+
+
+def _index_as_value_error(fn, *args):
+    """K11's entry points report an index outside the sample as a ValueError, like their other argument checks."""
+    try:
+        return fn(*args)
+    except IndexError as e:
+        raise ValueError(str(e)) from e
+
+
+def halfspace_exact_counts(P, targets=None, device=None, algo="auto"):
+    """int64[m]: the exact halfspace (Tukey) counts of x = P[targets[q]] inside the planar sample P (n x 2): the fewest
+    sample points in a closed halfplane with x on its boundary, x and its duplicates counted (sd_halfspace2_counts);
+    depth = counts / n.  algo: 'auto', 'sweep' (samples of at most 8192 points) or 'pairwise'; the same integers."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    a = _halfspace2_algo(algo)
+    Pd = _plane_points(P, dev)
+    n = Pd.shape[0]
+    td, m, tp = _index_as_value_error(_targets_dev, targets, n, dev)
+    out = t.empty(m, dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_halfspace2_counts, out, Pd.data_ptr(), n, tp, m, a)
+
+
+def halfspace_exact_external_counts(P, Q, device=None, algo="auto"):
+    """int64[m]: the exact halfspace counts of the external point Q[q] inside P u {Q[q]} (n + 1 points, Q[q] counted once;
+    sd_halfspace2_external_counts); depth = counts / (n + 1)."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    a = _halfspace2_algo(algo)
+    Pd, Qd = _plane_points(P, dev), _plane_points(Q, dev, "Q")
+    m = Qd.shape[0]
+    out = t.empty(m, dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_halfspace2_external_counts, out, Pd.data_ptr(), Pd.shape[0], Qd.data_ptr(), m, a)
+
+
+def halfspace_exact_subset_counts(P, members, device=None, algo="auto"):
+    """int64[nb]: per block (rows of `members`, -1 padded, target last) the exact halfspace counts of the block's target
+    inside the block (sd_halfspace2_subset_counts); depth = counts / block size."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    a = _halfspace2_algo(algo)
+    Pd = _plane_points(P, dev)
+    md, nb, bs = _index_as_value_error(_members_dev, members, dev, Pd.shape[0])
+    out = t.empty(nb, dtype=t.int64, device=dev)
+    return _launch(dev, lib.sd_halfspace2_subset_counts, out, Pd.data_ptr(), Pd.shape[0], md.data_ptr(), nb, bs, a)
