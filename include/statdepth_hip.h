@@ -207,7 +207,9 @@ int sd_l1_depth(const double *P, int64_t n, int d, const int64_t *targets, int64
 int sd_l1_external_depth(const double *P, int64_t n, int d, const double *Q, int64_t m, double *out, void *stream);
 /* ... and inside explicit BLOCKS of rows, nb (block, target) pairs in one launch: the K-block sampled estimator
  * (_samplepointwisedepth, _pointcloud.py:107-121) calls _pointwisedepth on len(to_compute) * (n // K) samples.
- * members: int32[nb*bs] row indices, -1 = padding; in every block the OTHER rows first and the target LAST.
+ * members: int32[nb*bs] row indices, -1 = padding AT THE END of a block; in every block the OTHER rows first and the
+ * target LAST.  A block's members are the entries before its first -1 (so for every block form of a point cloud below:
+ * simplex, Oja, halfspace, exact halfspace); a block without members gives NaN.
  * out[k] = 1 - ||sum over the block's others|| / (block size). */
 int sd_l1_subset_depth(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs, double *out,
                        void *stream);
@@ -300,8 +302,8 @@ int sd_multi_band_j_counts(const double *P, int64_t n, int64_t T, int d, const i
  * (fp64, raw sums); depth = out / ConvexHull(sample).volume on the host.  Degenerate simplices add their volume (~0).
  *   sd_oja_volume_sums:          others = the n - 1 rows other than targets[q] (NULL = all, m == n);
  *   sd_oja_external_volume_sums: d-subsets of ALL n rows of P against the external point Q[q] (m x d);
- *   sd_oja_subset_volume_sums:   blocks of rows, members int32[nb*bs], -1 padded, the block's others first and its
- *                                target LAST (the K-block sampled estimator).
+ *   sd_oja_subset_volume_sums:   blocks of rows, members int32[nb*bs], -1 padded at the end, the block's others
+ *                                first and its target LAST (the K-block sampled estimator).
  * A target's result is bitwise independent of m, of the other targets and of the run.  d in [1, 8];
  * SD_ERR_OVERFLOW if C(others, d) >= 2^62; SD_ERR_UNSUPPORTED for 2^31 or more others or if m * C(others, d) > 1e14
  * (hours of work).  Every launch is bounded (at most 2^32 >> max(0, d - 5) subset volumes). */
@@ -370,8 +372,8 @@ int sd_prob_band_sums(const double *mu, const double *var, int64_t T, int64_t n,
  *   sd_halfspace_pairwise_counts: the same counts by the pairwise kernel, O(m n k d) (cross-checks, timing).
  *   sd_halfspace_external_counts: m external points Q (m x d, device) against P; the sample of Q[q] is P u {Q[q]}: the
  *       counts are over n + 1 points (Q[q] counts itself once), depth = out / (n + 1).  Pairwise kernel.
- *   sd_halfspace_subset_counts:   blocks of rows, members int32[nb*bs], -1 padded, the block's target LAST; the block
- *       (target included) is the sample: depth = out / block size.  An empty block gives 0.  Pairwise kernel.
+ *   sd_halfspace_subset_counts:   blocks of rows, members int32[nb*bs], -1 padded at the end, the block's target LAST;
+ *       the block (target included) is the sample: depth = out / block size.  An empty block gives 0.  Pairwise kernel.
  * SD_ERR_INVALID for NULL pointers or n, d, k < 1; SD_ERR_UNSUPPORTED for d > 8, 2^31 or more points, or more than
  * 10^14 projections and comparisons (k n (d + log2 n), resp. m n k d).  All before any device work.  Every launch is
  * bounded in work. */

@@ -36,6 +36,7 @@
 // (16 KB at d = 8).  256 threads (4 wave64) per workgroup everywhere.  Every launch is bounded: a ranking launch covers at
 // most max(n, 2^25) values, a pairwise launch at most HS_UNITS workgroups of HS_SLICE x 256 projections each.
 #include "sd_common.h"
+#include "point_select.h"
 
 namespace sd {
 
@@ -314,20 +315,11 @@ static int launch_hs_counts_d(const double *P, i64 n, const double *U, i64 k, co
 }
 
 // ---------------------------------------------------------------------------------------------- pairwise route
-// Which rows are counted and where the target lies:
-//   default -- all n rows, target row targets[q] (NULL: q);   Q -- all n rows, external point Q[q] (+ itself, self = 1);
-//   members -- block q's rows (int32[bs], -1 padded, target LAST and counted as a member).
-struct HsSel {
-    const i64 *targets;
-    const double *Q;
-    const int *members;
-    int bs;
-};
-
+// The targets are selected by a PointSel (point_select.h); the whole sample is counted, the target's row included.
 // unit = q0 * C * S + u0 + blockIdx.x = ((target q) * C + direction chunk c) * S + slice sl;  acc[(q - q0) * k + r][le, ge]
 template <int D>
 __global__ __launch_bounds__(HS_THREADS) void hs_pairwise_kernel(const double *__restrict__ P, i64 n,
-                                                                 const double *__restrict__ U, i64 k, HsSel sel, i64 q0,
+                                                                 const double *__restrict__ U, i64 k, PointSel sel, i64 q0,
                                                                  u64 u0, u64 C, u64 S, u32 *__restrict__ acc) {
     __shared__ double tile[HS_PTILE * D];
     const u64 u = u0 + blockIdx.x;
@@ -335,20 +327,10 @@ __global__ __launch_bounds__(HS_THREADS) void hs_pairwise_kernel(const double *_
     const i64 q = q0 + ql;
     const i64 c = (i64)(u / S % C);
     const i64 sl = (i64)(u % S);
-    const int *mem = nullptr;
-    const double *xp;
-    i64 cnt = n;
-    if (sel.members) {
-        mem = sel.members + q * sel.bs;
-        int cm = 0;
-        while (cm < sel.bs && mem[cm] >= 0) ++cm;
-        cnt = cm;
-        xp = P + (i64)(cm > 0 ? mem[cm - 1] : 0) * D;
-    } else if (sel.Q) {
-        xp = sel.Q + q * D;
-    } else {
-        xp = P + (sel.targets ? sel.targets[q] : q) * D;
-    }
+    const PointView v = point_view(sel, P, n, D, q);
+    const int *mem = v.mem;
+    const double *xp = v.x;
+    const i64 cnt = v.cnt;
     const i64 i_begin = sl * HS_SLICE;
     const i64 i_end = i_begin + HS_SLICE < cnt ? i_begin + HS_SLICE : cnt;
     if (i_begin >= i_end) return;                                  // (block-uniform) a shorter block of the members form
@@ -411,8 +393,8 @@ __global__ __launch_bounds__(HS_THREADS) void hs_reduce_kernel(const u32 *__rest
 }
 
 template <int D>
-static int launch_hs_pairwise_d(const double *P, i64 n, const double *U, i64 k, const HsSel &sel, i64 m, i64 cnt_max, i64 *out,
-                                hipStream_t s) {
+static int launch_hs_pairwise_d(const double *P, i64 n, const double *U, i64 k, const PointSel &sel, i64 m, i64 *out, hipStream_t s) {
+    const i64 cnt_max = sel_cnt_max(sel, n);
     const u64 C = (u64)((k + HS_THREADS - 1) / HS_THREADS);
     const u64 S = (u64)((cnt_max + HS_SLICE - 1) / HS_SLICE);
     i64 mq = (i64)(HS_ACC_BYTES / ((size_t)k * 8));                 // targets per batch: what the accumulator holds
@@ -441,37 +423,16 @@ static int launch_hs_pairwise_d(const double *P, i64 n, const double *U, i64 k, 
     return SD_OK;
 }
 
-#define HS_DISPATCH(d, CALL)                                                                     \
-    switch (d) {                                                                                 \
-        case 1: { constexpr int D_ = 1; return CALL; }                                           \
-        case 2: { constexpr int D_ = 2; return CALL; }                                           \
-        case 3: { constexpr int D_ = 3; return CALL; }                                           \
-        case 4: { constexpr int D_ = 4; return CALL; }                                           \
-        case 5: { constexpr int D_ = 5; return CALL; }                                           \
-        case 6: { constexpr int D_ = 6; return CALL; }                                           \
-        case 7: { constexpr int D_ = 7; return CALL; }                                           \
-        case 8: { constexpr int D_ = 8; return CALL; }                                           \
-    }                                                                                            \
-    return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
-
 int launch_halfspace_counts(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
                             void *ws, size_t ws_bytes, hipStream_t s) {
-    HS_DISPATCH(d, launch_hs_counts_d<D_>(P, n, U, k, targets, m, out, ws, ws_bytes, s))
+    SD_DISPATCH_D(d, return launch_hs_counts_d<D_>(P, n, U, k, targets, m, out, ws, ws_bytes, s))
+    return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
 }
 
-int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
+int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, i64 *out,
                               hipStream_t s) {
-    HS_DISPATCH(d, launch_hs_pairwise_d<D_>(P, n, U, k, HsSel{targets, nullptr, nullptr, 0}, m, n, out, s))
-}
-
-int launch_halfspace_external(const double *P, i64 n, int d, const double *U, i64 k, const double *Q, i64 m, i64 *out,
-                              hipStream_t s) {
-    HS_DISPATCH(d, launch_hs_pairwise_d<D_>(P, n, U, k, HsSel{nullptr, Q, nullptr, 0}, m, n, out, s))
-}
-
-int launch_halfspace_subsets(const double *P, i64 n, int d, const double *U, i64 k, const int *members, i64 nb, int bs,
-                             i64 *out, hipStream_t s) {
-    HS_DISPATCH(d, launch_hs_pairwise_d<D_>(P, n, U, k, HsSel{nullptr, nullptr, members, bs}, nb, bs, out, s))
+    SD_DISPATCH_D(d, return launch_hs_pairwise_d<D_>(P, n, U, k, sel, m, out, s))
+    return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
 }
 
 }  // namespace sd

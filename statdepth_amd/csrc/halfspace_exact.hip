@@ -13,8 +13,8 @@
 // comparison of e1 with e2 decides.  Exact while no product overflows or underflows: |coordinates| <= 2^500 (the host
 // checks) and nonzero coordinate differences >= 2^-500 in magnitude (not checked: they are not known before they are formed).
 //
-// Two kernels over one selector (HxSel: a row of P against all rows; an external Q[q] against all rows with one added to
-// c0; a block's last member against the block's members), the same integers from both:
+// Two kernels over one selector (PointSel, point_select.h: a row of P against all rows; an external Q[q] against all rows
+// with one added to c0; a block's last member against the block's members), the same integers from both:
 //
 // hx_sweep_kernel<CAP, NT>   one workgroup per target or block, samples of up to CAP = 64 / 512 / 2048 / 8192 points with
 //   NT = 64 / 256 / 512 / 1024 threads.  The sample is streamed once: v formed, the nonzero vectors compacted into LDS (wave
@@ -38,6 +38,7 @@
 // Bounded launches: a sweep launch covers at most 2^34 comparator evaluations, a pairwise launch at most 2^36 predicate
 // pairs or one workgroup (256 x n pairs; the 10^14 cap of the entry points keeps n below 10^7 on that route).
 #include "sd_common.h"
+#include "point_select.h"
 
 namespace sd {
 
@@ -45,52 +46,6 @@ constexpr int HX_PT = 256;                                         // pairwise: 
 constexpr double HX_SWEEP_LAUNCH = 17179869184.0;                  // 2^34 comparator evaluations per sweep launch
 constexpr double HX_PAIR_LAUNCH = 68719476736.0;                   // 2^36 predicate pairs per pairwise launch
 constexpr int HX_NONE = 0x7fffffff;
-
-// Which rows are counted and where the target lies:
-//   default -- all n rows, target row targets[q] (NULL: q);   Q -- all n rows, external point Q[q] (self = 1);
-//   members -- block q's rows (int32[bs], -1 padded at the end, target LAST and counted as a member).
-struct HxSel {
-    const i64 *targets;
-    const double *Q;
-    const int *members;
-    int bs;
-};
-
-struct HxView {
-    double qx, qy;                                                  // the target
-    const int *mem;                                                 // the block's members, or nullptr: rows 0 .. cnt - 1
-    int cnt;                                                        // sample points in P
-    int self;                                                       // 1: the target is not among them and counts itself
-};
-
-// block-cooperative (two barriers in the members form; sel is a kernel argument, so the branch is uniform)
-template <int NT>
-__device__ __forceinline__ HxView hx_view(const double *__restrict__ P, i64 n, const HxSel &sel, i64 q, int *s_cnt) {
-    HxView w;
-    w.mem = nullptr;
-    w.cnt = (int)n;
-    w.self = 0;
-    const double *xp;
-    if (sel.members) {
-        w.mem = sel.members + q * sel.bs;
-        if (threadIdx.x == 0) *s_cnt = 0;
-        __syncthreads();
-        int c = 0;
-        for (int i = threadIdx.x; i < sel.bs; i += NT) c += w.mem[i] >= 0 ? 1 : 0;
-        if (c) atomicAdd(s_cnt, c);
-        __syncthreads();
-        w.cnt = *s_cnt;
-        xp = P + (i64)(w.cnt > 0 ? w.mem[w.cnt - 1] : 0) * 2;
-    } else if (sel.Q) {
-        xp = sel.Q + q * 2;
-        w.self = 1;
-    } else {
-        xp = P + (sel.targets ? sel.targets[q] : q) * 2;
-    }
-    w.qx = xp[0];
-    w.qy = xp[1];
-    return w;
-}
 
 // exact sign of a b - c d (see the header of this file)
 __device__ __forceinline__ int hx_sign_diff(double a, double b, double c, double d) {
@@ -123,7 +78,7 @@ __device__ __forceinline__ int hx_wave_min(int v) {
 
 // ---------------------------------------------------------------------------------------------- sweep
 template <int CAP, int NT>
-__global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__ P, i64 n, HxSel sel, i64 q0,
+__global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__ P, i64 n, PointSel sel, i64 q0,
                                                       i64 *__restrict__ out) {
     static_assert(CAP % 64 == 0 && NT % 64 == 0 && CAP / 64 <= 128, "one wave scans the runs of 64, two per lane at most");
     __shared__ double sx[CAP];
@@ -132,19 +87,21 @@ __global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__
     __shared__ int s_cnt, s_nz, s_min, s_t1;
     const int t = threadIdx.x, lane = t & 63;
     const i64 q = q0 + blockIdx.x;
-    const HxView w = hx_view<NT>(P, n, sel, q, &s_cnt);            // w.cnt <= CAP: the launcher chose the tier
+    const PointView w = point_view_coop<NT>(sel, P, n, 2, q, &s_cnt);
+    const double qx = w.x[0], qy = w.x[1];
+    const int wcnt = (int)w.cnt;                                    // <= CAP: the launcher chose the tier
     if (t == 0) {
         s_nz = 0;
         s_min = HX_NONE;
     }
     __syncthreads();
-    for (int i0 = 0; i0 < w.cnt; i0 += NT) {                        // compaction of the nonzero vectors, in any order
+    for (int i0 = 0; i0 < wcnt; i0 += NT) {                         // compaction of the nonzero vectors, in any order
         const int i = i0 + t;
         double vx = 0.0, vy = 0.0;
-        if (i < w.cnt) {
+        if (i < wcnt) {
             const i64 src = w.mem ? (i64)w.mem[i] : (i64)i;
-            vx = __dsub_rn(P[src * 2], w.qx);
-            vy = __dsub_rn(P[src * 2 + 1], w.qy);
+            vx = __dsub_rn(P[src * 2], qx);
+            vy = __dsub_rn(P[src * 2 + 1], qy);
         }
         const bool nz = vx != 0.0 || vy != 0.0;
         const u64 mask = __ballot(nz);
@@ -159,7 +116,7 @@ __global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__
     }
     __syncthreads();
     const int cnt = s_nz;
-    const int c0 = w.cnt - cnt + w.self;
+    const int c0 = wcnt - cnt + w.self();
     if (cnt == 0) {                                                 // (block-uniform) also the empty block: 0
         if (t == 0) out[q] = (i64)c0;
         return;
@@ -254,7 +211,7 @@ static inline double hx_sweep_wg_work(int cap) {                    // comparato
 static inline int hx_tier(i64 cnt_max) { return cnt_max <= 64 ? 64 : cnt_max <= 512 ? 512 : cnt_max <= 2048 ? 2048 : 8192; }
 
 template <int CAP, int NT>
-static int hx_launch_sweep(const double *P, i64 n, const HxSel &sel, i64 m, i64 *out, hipStream_t s) {
+static int hx_launch_sweep(const double *P, i64 n, const PointSel &sel, i64 m, i64 *out, hipStream_t s) {
     double per = HX_SWEEP_LAUNCH / hx_sweep_wg_work(CAP);
     per = per > 1048576.0 ? 1048576.0 : per;
     const i64 g = (i64)per;
@@ -268,7 +225,7 @@ static int hx_launch_sweep(const double *P, i64 n, const HxSel &sel, i64 m, i64 
 
 // ---------------------------------------------------------------------------------------------- pairwise
 // unit = u0 + blockIdx.x = (target q) * C + (chunk c of 256 values of j)
-__global__ __launch_bounds__(HX_PT) void hx_pairwise_kernel(const double *__restrict__ P, i64 n, HxSel sel, u64 u0, u64 C,
+__global__ __launch_bounds__(HX_PT) void hx_pairwise_kernel(const double *__restrict__ P, i64 n, PointSel sel, u64 u0, u64 C,
                                                             unsigned long long *__restrict__ out) {
     __shared__ double tx[HX_PT];
     __shared__ double ty[HX_PT];
@@ -277,29 +234,31 @@ __global__ __launch_bounds__(HX_PT) void hx_pairwise_kernel(const double *__rest
     const u64 u = u0 + blockIdx.x;
     const i64 q = (i64)(u / C);
     const i64 c = (i64)(u % C);
-    const HxView w = hx_view<HX_PT>(P, n, sel, q, &s_cnt);
-    if (c > 0 && c * HX_PT >= (i64)w.cnt) return;                   // (block-uniform) a shorter block of the members form
+    const PointView w = point_view_coop<HX_PT>(sel, P, n, 2, q, &s_cnt);
+    const double qx = w.x[0], qy = w.x[1];
+    const int wcnt = (int)w.cnt;
+    if (c > 0 && c * HX_PT >= wcnt) return;                         // (block-uniform) a shorter block of the members form
     if (t == 0) {
         s_zero = 0;
         s_min = HX_NONE;
     }
     const i64 j = c * HX_PT + t;
     double jx = 0.0, jy = 0.0;
-    if (j < (i64)w.cnt) {
+    if (j < wcnt) {
         const i64 src = w.mem ? (i64)w.mem[j] : j;
-        jx = __dsub_rn(P[src * 2], w.qx);
-        jy = __dsub_rn(P[src * 2 + 1], w.qy);
+        jx = __dsub_rn(P[src * 2], qx);
+        jy = __dsub_rn(P[src * 2 + 1], qy);
     }
     const bool active = jx != 0.0 || jy != 0.0;
     u32 L = 0, R = 0, S = 0, O = 0;
     int zeros = 0;
-    for (i64 k0 = 0; k0 < (i64)w.cnt; k0 += HX_PT) {
-        const int tc = (int)((i64)w.cnt - k0 < HX_PT ? (i64)w.cnt - k0 : HX_PT);
+    for (i64 k0 = 0; k0 < wcnt; k0 += HX_PT) {
+        const int tc = (int)(wcnt - k0 < HX_PT ? wcnt - k0 : HX_PT);
         __syncthreads();
         if (t < tc) {
             const i64 src = w.mem ? (i64)w.mem[k0 + t] : k0 + t;
-            const double vx = __dsub_rn(P[src * 2], w.qx);
-            const double vy = __dsub_rn(P[src * 2 + 1], w.qy);
+            const double vx = __dsub_rn(P[src * 2], qx);
+            const double vy = __dsub_rn(P[src * 2 + 1], qy);
             tx[t] = vx;
             ty[t] = vy;
             zeros += vx == 0.0 && vy == 0.0 ? 1 : 0;
@@ -330,8 +289,8 @@ __global__ __launch_bounds__(HX_PT) void hx_pairwise_kernel(const double *__rest
     if ((t & 63) == 0 && best != HX_NONE) atomicMin(&s_min, best);
     __syncthreads();
     if (t == 0) {
-        const int c0 = s_zero + w.self;
-        if (s_zero == w.cnt) {                                      // no nonzero vector (also the empty block: 0)
+        const int c0 = s_zero + w.self();
+        if (s_zero == wcnt) {                                       // no nonzero vector (also the empty block: 0)
             if (c == 0) atomicMin(&out[q], (unsigned long long)c0);
         } else if (s_min != HX_NONE) {
             atomicMin(&out[q], (unsigned long long)c0 + (unsigned long long)s_min);
@@ -339,7 +298,8 @@ __global__ __launch_bounds__(HX_PT) void hx_pairwise_kernel(const double *__rest
     }
 }
 
-static int hx_launch_pairwise(const double *P, i64 n, const HxSel &sel, i64 m, i64 cnt_max, i64 *out, hipStream_t s) {
+static int hx_launch_pairwise(const double *P, i64 n, const PointSel &sel, i64 m, i64 *out, hipStream_t s) {
+    const i64 cnt_max = sel_cnt_max(sel, n);
     const u64 C = (u64)((cnt_max + HX_PT - 1) / HX_PT);
     SD_HIP(hipMemsetAsync(out, 0xff, (size_t)m * 8, s));
     double per = HX_PAIR_LAUNCH / ((double)HX_PT * (double)cnt_max);
@@ -371,27 +331,14 @@ double halfspace2_work(int route, i64 m, i64 cnt_max) {
     return (double)m * hx_sweep_wg_work(hx_tier(cnt_max));
 }
 
-static int hx_launch(const double *P, i64 n, const HxSel &sel, i64 m, i64 cnt_max, int route, i64 *out, hipStream_t s) {
-    if (route == 2) return hx_launch_pairwise(P, n, sel, m, cnt_max, out, s);
-    switch (hx_tier(cnt_max)) {
+int launch_halfspace2(const double *P, i64 n, const PointSel &sel, i64 m, int route, i64 *out, hipStream_t s) {
+    if (route == 2) return hx_launch_pairwise(P, n, sel, m, out, s);
+    switch (hx_tier(sel_cnt_max(sel, n))) {
         case 64: return hx_launch_sweep<64, 64>(P, n, sel, m, out, s);
         case 512: return hx_launch_sweep<512, 256>(P, n, sel, m, out, s);
         case 2048: return hx_launch_sweep<2048, 512>(P, n, sel, m, out, s);
     }
     return hx_launch_sweep<8192, 1024>(P, n, sel, m, out, s);
-}
-
-int launch_halfspace2(const double *P, i64 n, const i64 *targets, i64 m, int route, i64 *out, hipStream_t s) {
-    return hx_launch(P, n, HxSel{targets, nullptr, nullptr, 0}, m, n, route, out, s);
-}
-
-int launch_halfspace2_external(const double *P, i64 n, const double *Q, i64 m, int route, i64 *out, hipStream_t s) {
-    return hx_launch(P, n, HxSel{nullptr, Q, nullptr, 0}, m, n, route, out, s);
-}
-
-int launch_halfspace2_subsets(const double *P, i64 n, const int *members, i64 nb, int bs, int route, i64 *out,
-                              hipStream_t s) {
-    return hx_launch(P, n, HxSel{nullptr, nullptr, members, bs}, nb, bs, route, out, s);
 }
 
 }  // namespace sd

@@ -18,6 +18,7 @@
 // fixed tree; slices are folded into out[q] strictly in slice order by oja_fold_kernel.  So a target's result does
 // not depend on m, on the other targets of the call, or on how the call is cut into launches.  No atomics.
 #include "sd_common.h"
+#include "point_select.h"
 
 namespace sd {
 
@@ -64,60 +65,15 @@ __device__ static void oja_unrank(u64 r, i64 no, int *idx) {
     }
 }
 
-// Which rows a block's subsets come from and where its target lies (as SxSel in simplex.hip):
-//   default -- the n - 1 rows other than targets[q]; Q -- external point Q[q], all n rows are others;
-//   members -- block q's rows (int32[bs], -1 padded, others first, target LAST).
-struct OjaSel {
-    const i64 *targets;
-    const double *Q;
-    const int *members;
-    int bs;
-};
-
-struct OjaBlock {
-    const double *x;                                                // the target's coordinates
-    const int *mem;
-    i64 tg, no;
-};
-
-__device__ __forceinline__ OjaBlock oja_block(const OjaSel &sel, const double *P, i64 n, int d, i64 q) {
-    OjaBlock b;
-    b.mem = nullptr;
-    if (sel.members) {
-        const int *mem = sel.members + q * sel.bs;
-        int cnt = 0;
-        while (cnt < sel.bs && mem[cnt] >= 0) ++cnt;
-        b.mem = mem;
-        b.no = cnt > 0 ? cnt - 1 : 0;
-        b.tg = cnt > 0 ? mem[cnt - 1] : -1;
-        b.x = cnt > 0 ? P + (i64)b.tg * d : nullptr;
-    } else if (sel.Q) {
-        b.tg = -1;
-        b.no = n;
-        b.x = sel.Q + q * d;
-    } else {
-        b.tg = sel.targets ? sel.targets[q] : q;
-        b.no = n - 1;
-        b.x = P + b.tg * d;
-    }
-    return b;
-}
-
-__device__ __forceinline__ i64 oja_src(const OjaBlock &b, i64 i) {
-    if (b.mem) return b.mem[i];
-    if (b.tg < 0) return i;
-    return i < b.tg ? i : i + 1;                                    // skip the target itself
-}
-
 // translated other i: from LDS, or read and translated here (the same subtraction either way)
 template <int D>
-__device__ __forceinline__ void oja_row(const double *lds, const double *P, const OjaBlock &b, const double *x, i64 i,
+__device__ __forceinline__ void oja_row(const double *lds, const double *P, const PointView &b, const double *x, i64 i,
                                         double (&a)[D]) {
     if (lds) {
 #pragma unroll
         for (int e = 0; e < D; ++e) a[e] = lds[i * D + e];
     } else {
-        const double *p = P + oja_src(b, i) * D;
+        const double *p = P + b.other(i) * D;
 #pragma unroll
         for (int e = 0; e < D; ++e) a[e] = p[e] - x[e];
     }
@@ -210,15 +166,16 @@ __device__ __forceinline__ double oja_block_sum(double v, double *scratch) {
 
 // one workgroup per work unit u = u0 + blockIdx.x = (target q = u / S, slice s = u % S); part[blockIdx.x] = the slice's sum
 template <int D>
-__global__ __launch_bounds__(OJA_THREADS) void oja_kernel(const double *__restrict__ P, i64 n, OjaSel sel, u64 u0, u64 S,
+__global__ __launch_bounds__(OJA_THREADS) void oja_kernel(const double *__restrict__ P, i64 n, PointSel sel, u64 u0, u64 S,
                                                           int use_lds, double *__restrict__ part) {
     extern __shared__ double oja_lds[];
     __shared__ double scratch[OJA_THREADS / 64];
     const u64 u = u0 + blockIdx.x;
     const i64 q = (i64)(u / S);
     const u64 s = u % S;
-    const OjaBlock b = oja_block(sel, P, n, D, q);
-    const u64 total = oja_binom((u64)b.no, D);
+    const PointView b = point_view(sel, P, n, D, q);        // the subsets come from the target's others (point_select.h)
+    const i64 no = b.others();
+    const u64 total = oja_binom((u64)no, D);
     constexpr u64 L = OJA_PER_THREAD;
     if (s >= oja_slices(total)) {                                   // a smaller block of the members form
         if (threadIdx.x == 0) part[blockIdx.x] = 0.0;
@@ -229,8 +186,8 @@ __global__ __launch_bounds__(OJA_THREADS) void oja_kernel(const double *__restri
     for (int e = 0; e < D; ++e) x[e] = b.x[e];
     const double *lds = nullptr;
     if (use_lds) {
-        for (i64 i = threadIdx.x; i < b.no; i += OJA_THREADS) {
-            const double *p = P + oja_src(b, i) * D;
+        for (i64 i = threadIdx.x; i < no; i += OJA_THREADS) {
+            const double *p = P + b.other(i) * D;
 #pragma unroll
             for (int e = 0; e < D; ++e) oja_lds[i * D + e] = p[e] - x[e];
         }
@@ -242,8 +199,7 @@ __global__ __launch_bounds__(OJA_THREADS) void oja_kernel(const double *__restri
     if (first < total) {
         u64 left = total - first < L ? total - first : L;
         int idx[D];
-        oja_unrank<D>(first, b.no, idx);
-        const i64 no = b.no;
+        oja_unrank<D>(first, no, idx);
         for (;;) {
             double c[D];
             if constexpr (D == 1) {
@@ -308,7 +264,8 @@ __global__ __launch_bounds__(256) void oja_fold_kernel(const double *__restrict_
 }
 
 template <int D>
-static int launch_oja_d(const double *P, i64 n, const OjaSel &sel, i64 m, i64 no_max, double *out, hipStream_t s) {
+static int launch_oja_d(const double *P, i64 n, const PointSel &sel, i64 m, double *out, hipStream_t s) {
+    const i64 no_max = sel_others_max(sel, n);
     const u64 total = oja_binom((u64)no_max, D);
     if (total == 0) {                                               // fewer than d others everywhere: empty sums
         SD_HIP(hipMemsetAsync(out, 0, sizeof(double) * m, s));
@@ -345,25 +302,9 @@ static int launch_oja_d(const double *P, i64 n, const OjaSel &sel, i64 m, i64 no
     return SD_OK;
 }
 
-static int launch_oja(const double *P, i64 n, int d, const OjaSel &sel, i64 m, i64 no_max, double *out, hipStream_t s) {
-    switch (d) {
-#define OJA_CASE(D_) case D_: return launch_oja_d<D_>(P, n, sel, m, no_max, out, s);
-        OJA_CASE(1) OJA_CASE(2) OJA_CASE(3) OJA_CASE(4) OJA_CASE(5) OJA_CASE(6) OJA_CASE(7) OJA_CASE(8)
-#undef OJA_CASE
-    }
+int launch_oja(const double *P, i64 n, int d, const PointSel &sel, i64 m, double *out, hipStream_t s) {
+    SD_DISPATCH_D(d, return launch_oja_d<D_>(P, n, sel, m, out, s))
     return fail(SD_ERR_UNSUPPORTED, "oja volume sums cover d in [1,8], got %d", d);
-}
-
-int launch_oja_volume_sums(const double *P, i64 n, int d, const i64 *targets, i64 m, double *out, hipStream_t s) {
-    return launch_oja(P, n, d, OjaSel{targets, nullptr, nullptr, 0}, m, n - 1, out, s);
-}
-
-int launch_oja_external(const double *P, i64 n, int d, const double *Q, i64 m, double *out, hipStream_t s) {
-    return launch_oja(P, n, d, OjaSel{nullptr, Q, nullptr, 0}, m, n, out, s);
-}
-
-int launch_oja_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double *out, hipStream_t s) {
-    return launch_oja(P, n, d, OjaSel{nullptr, nullptr, members, bs}, nb, bs - 1, out, s);
 }
 
 }  // namespace sd

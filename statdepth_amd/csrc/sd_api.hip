@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "sd_common.h"
+#include "point_select.h"
 
 namespace sd {
 
@@ -444,45 +445,67 @@ int sd_bd_strict_counts(const double *X, int64_t T, int64_t n, int64_t st, int64
 }
 
 // ---------------------------------------------------------------------------
+// Point clouds (K4, K5, K7, K10, K11).  Every family has a rows, an external and a blocks entry point: each builds its
+// PointSel (point_select.h) and calls the family's one function below, which holds the family's checks once.
+// ---------------------------------------------------------------------------
+static bool rows_form(const PointSel &sel) { return !sel.Q && !sel.members; }
+
+// the blocks entry points' own arguments, checked ahead of the family's (the external ones only have Q)
+static int check_blocks(const int32_t *members, int bs) {
+    if (!members) return fail(SD_ERR_INVALID, "null pointer");
+    if (bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
+    return SD_OK;
+}
+
+static int check_all_rows(const PointSel &sel, i64 n, i64 m) {
+    if (rows_form(sel) && !sel.targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    return SD_OK;
+}
+
+// ---------------------------------------------------------------------------
 // K5
 // ---------------------------------------------------------------------------
+// (the rows form says "empty point cloud" and has no m < 0 check, the other two say "bad shape": the messages of the
+// former per-form entry points, kept as they were; likewise check_simplex's "bad shape" / "m < 0")
+static int l1_depth(const double *P, i64 n, int d, const PointSel &sel, i64 m, double *out, void *stream) {
+    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n <= 0 || d <= 0 || (m < 0 && !rows_form(sel)))
+        return fail(SD_ERR_INVALID, rows_form(sel) ? "empty point cloud" : "bad shape");
+    if (d > 64) return fail(SD_ERR_UNSUPPORTED, "l1 depth covers d <= 64");
+    int rc = check_all_rows(sel, n, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_l1(P, n, d, sel, m, out, (hipStream_t)stream);
+}
+
 int sd_l1_depth(const double *P, int64_t n, int d, const int64_t *targets, int64_t m,
                 double *out, void *stream) {
-    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
-    if (n <= 0 || d <= 0) return fail(SD_ERR_INVALID, "empty point cloud");
-    if (d > 64) return fail(SD_ERR_UNSUPPORTED, "l1 depth covers d <= 64");
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    if (m == 0) return SD_OK;
-    return launch_l1_depth(P, n, d, targets, m, out, (hipStream_t)stream);
+    return l1_depth(P, n, d, select_rows(targets), m, out, stream);
 }
 
 int sd_l1_external_depth(const double *P, int64_t n, int d, const double *Q, int64_t m, double *out, void *stream) {
-    if (!P || !Q || !out) return fail(SD_ERR_INVALID, "null pointer");
-    if (n <= 0 || d <= 0 || m < 0) return fail(SD_ERR_INVALID, "bad shape");
-    if (d > 64) return fail(SD_ERR_UNSUPPORTED, "l1 depth covers d <= 64");
-    if (m == 0) return SD_OK;
-    return launch_l1_external(P, n, d, Q, m, out, (hipStream_t)stream);
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    return l1_depth(P, n, d, select_external(Q), m, out, stream);
 }
 
 int sd_l1_subset_depth(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs, double *out,
                        void *stream) {
-    if (!P || !members || !out) return fail(SD_ERR_INVALID, "null pointer");
-    if (n <= 0 || d <= 0 || nb < 0 || bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
-    if (d > 64) return fail(SD_ERR_UNSUPPORTED, "l1 depth covers d <= 64");
-    if (nb == 0) return SD_OK;
-    return launch_l1_subsets(P, n, d, members, nb, bs, out, (hipStream_t)stream);
+    int rc = check_blocks(members, bs);
+    return rc ? rc : l1_depth(P, n, d, select_blocks(members, bs), nb, out, stream);
 }
 
 // ---------------------------------------------------------------------------
 // K4
 // ---------------------------------------------------------------------------
-static int check_simplex(const double *P, i64 n, int d, const i64 *targets, i64 m, const void *out, bool exhaustive,
-                         i64 n_others) {
+static int check_simplex(const double *P, i64 n, int d, const PointSel &sel, i64 m, const void *out, bool exhaustive) {
+    if (m < 0 && !rows_form(sel)) return fail(SD_ERR_INVALID, sel.members ? "bad shape" : "m < 0");
     if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (n <= 0) return fail(SD_ERR_INVALID, "empty input");
     if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "simplex containment covers d in [1,8], got %d", d);
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    int rc = check_all_rows(sel, n, m);
+    if (rc) return rc;
     if (exhaustive) {
+        const i64 n_others = sel_others_max(sel, n);
         u64 c;
         if (!binom_u64_checked((u64)n_others, d + 1, &c) || (c >> 62))
             return fail(SD_ERR_OVERFLOW, "C(%lld,%d) subsets per target is not enumerable", (long long)n_others, d + 1);
@@ -490,12 +513,29 @@ static int check_simplex(const double *P, i64 n, int d, const i64 *targets, i64 
     return SD_OK;
 }
 
-int sd_pointcloud_simplex_counts(const double *P, int64_t n, int d, const int64_t *targets, int64_t m,
-                                 double tol, int64_t *out, void *stream) {
-    int rc = check_simplex(P, n, d, targets, m, out, true, n - 1);
+// every (d+1)-subset of the others, in any of the three forms
+static int simplex_counts(const double *P, i64 n, int d, const PointSel &sel, i64 m, double tol, int64_t *out, void *stream) {
+    int rc = check_simplex(P, n, d, sel, m, out, true);
     if (rc) return rc;
     if (m == 0) return SD_OK;
-    return launch_pointcloud_simplex(P, n, d, targets, m, tol, -1, 0, (u64 *)out, (hipStream_t)stream);
+    return launch_pointcloud_simplex(P, n, d, sel, m, tol, -1, 0, (u64 *)out, (hipStream_t)stream);
+}
+
+int sd_pointcloud_simplex_counts(const double *P, int64_t n, int d, const int64_t *targets, int64_t m,
+                                 double tol, int64_t *out, void *stream) {
+    return simplex_counts(P, n, d, select_rows(targets), m, tol, out, stream);
+}
+
+int sd_pointcloud_simplex_external_counts(const double *P, int64_t n, int d, const double *Q, int64_t m, double tol,
+                                          int64_t *out, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    return simplex_counts(P, n, d, select_external(Q), m, tol, out, stream);
+}
+
+int sd_pointcloud_simplex_subset_counts(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs,
+                                        double tol, int64_t *out, void *stream) {
+    int rc = check_blocks(members, bs);
+    return rc ? rc : simplex_counts(P, n, d, select_blocks(members, bs), nb, tol, out, stream);
 }
 
 size_t sd_simplex_sampled_workspace_bytes(int64_t n, int64_t T, int d, int64_t samples) {
@@ -505,37 +545,17 @@ size_t sd_simplex_sampled_workspace_bytes(int64_t n, int64_t T, int d, int64_t s
 int sd_pointcloud_simplex_sampled(const double *P, int64_t n, int d, const int64_t *targets, int64_t m,
                                   double tol, int64_t samples, uint64_t seed, int64_t *out, void *ws, size_t ws_bytes,
                                   void *stream) {
-    int rc = check_simplex(P, n, d, targets, m, out, false, n - 1);
+    int rc = check_simplex(P, n, d, select_rows(targets), m, out, false);
     if (rc) return rc;
     if (samples <= 0) return fail(SD_ERR_INVALID, "samples must be positive");
     if (n - 1 < d + 1) return fail(SD_ERR_INVALID, "need at least d+2 points");
     if (m == 0) return SD_OK;
-    return launch_pointcloud_simplex(P, n, d, targets, m, tol, samples, seed, (u64 *)out, (hipStream_t)stream, ws, ws_bytes);
-}
-
-int sd_pointcloud_simplex_external_counts(const double *P, int64_t n, int d, const double *Q, int64_t m, double tol,
-                                          int64_t *out, void *stream) {
-    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_simplex(P, n, d, (const i64 *)1, m, out, true, n);
-    if (rc) return rc;
-    if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
-    if (m == 0) return SD_OK;
-    return launch_pointcloud_simplex_external(P, n, d, Q, m, tol, (u64 *)out, (hipStream_t)stream);
-}
-
-int sd_pointcloud_simplex_subset_counts(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs,
-                                        double tol, int64_t *out, void *stream) {
-    if (!members) return fail(SD_ERR_INVALID, "null pointer");
-    if (bs <= 0 || nb < 0) return fail(SD_ERR_INVALID, "bad shape");
-    int rc = check_simplex(P, n, d, (const i64 *)1, nb, out, true, bs - 1);
-    if (rc) return rc;
-    if (nb == 0) return SD_OK;
-    return launch_pointcloud_simplex_subsets(P, n, d, members, nb, bs, tol, (u64 *)out, (hipStream_t)stream);
+    return launch_pointcloud_simplex(P, n, d, select_rows(targets), m, tol, samples, seed, (u64 *)out, (hipStream_t)stream, ws, ws_bytes);
 }
 
 int sd_multi_simplex_counts(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m,
                             int relax, double tol, int64_t *out, void *stream) {
-    int rc = check_simplex(P, n, d, targets, m, out, true, n - 1);
+    int rc = check_simplex(P, n, d, select_rows(targets), m, out, true);
     if (rc) return rc;
     if (T <= 0) return fail(SD_ERR_INVALID, "T <= 0");
     if (m == 0) return SD_OK;
@@ -580,7 +600,7 @@ int sd_multi_band_j_counts(const double *P, int64_t n, int64_t T, int d, const i
 int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d, const int64_t *targets, int64_t m,
                              int relax, double tol, int64_t samples, uint64_t seed, int64_t *out, void *ws, size_t ws_bytes,
                              void *stream) {
-    int rc = check_simplex(P, n, d, targets, m, out, false, n - 1);
+    int rc = check_simplex(P, n, d, select_rows(targets), m, out, false);
     if (rc) return rc;
     if (T <= 0) return fail(SD_ERR_INVALID, "T <= 0");
     if (samples <= 0) return fail(SD_ERR_INVALID, "samples must be positive");
@@ -594,7 +614,8 @@ int sd_multi_simplex_sampled(const double *P, int64_t n, int64_t T, int d, const
 // ---------------------------------------------------------------------------
 static constexpr double OJA_MAX_EVALS = 1e14;   // m * C(others, d): beyond this a call would run for hours
 
-static int check_oja(const double *P, i64 n, int d, i64 m, const void *out, i64 n_others) {
+static int oja_volume_sums(const double *P, i64 n, int d, const PointSel &sel, i64 m, double *out, void *stream) {
+    const i64 n_others = sel_others_max(sel, n);
     if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (n <= 0 || m < 0) return fail(SD_ERR_INVALID, "bad shape");
     if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "oja volume sums cover d in [1,8], got %d", d);
@@ -606,33 +627,25 @@ static int check_oja(const double *P, i64 n, int d, i64 m, const void *out, i64 
     if ((double)m * (double)c > OJA_MAX_EVALS)
         return fail(SD_ERR_UNSUPPORTED, "%lld targets x C(%lld,%d) subsets exceeds the cap of %.0e simplex volumes",
                     (long long)m, (long long)n_others, d, OJA_MAX_EVALS);
-    return SD_OK;
+    int rc = check_all_rows(sel, n, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_oja(P, n, d, sel, m, out, (hipStream_t)stream);
 }
 
 int sd_oja_volume_sums(const double *P, int64_t n, int d, const int64_t *targets, int64_t m, double *out, void *stream) {
-    int rc = check_oja(P, n, d, m, out, n - 1);
-    if (rc) return rc;
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    if (m == 0) return SD_OK;
-    return launch_oja_volume_sums(P, n, d, targets, m, out, (hipStream_t)stream);
+    return oja_volume_sums(P, n, d, select_rows(targets), m, out, stream);
 }
 
 int sd_oja_external_volume_sums(const double *P, int64_t n, int d, const double *Q, int64_t m, double *out, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_oja(P, n, d, m, out, n);
-    if (rc) return rc;
-    if (m == 0) return SD_OK;
-    return launch_oja_external(P, n, d, Q, m, out, (hipStream_t)stream);
+    return oja_volume_sums(P, n, d, select_external(Q), m, out, stream);
 }
 
 int sd_oja_subset_volume_sums(const double *P, int64_t n, int d, const int32_t *members, int64_t nb, int bs, double *out,
                               void *stream) {
-    if (!members) return fail(SD_ERR_INVALID, "null pointer");
-    if (bs <= 0 || nb < 0) return fail(SD_ERR_INVALID, "bad shape");
-    int rc = check_oja(P, n, d, nb, out, bs - 1);
-    if (rc) return rc;
-    if (nb == 0) return SD_OK;
-    return launch_oja_subsets(P, n, d, members, nb, bs, out, (hipStream_t)stream);
+    int rc = check_blocks(members, bs);
+    return rc ? rc : oja_volume_sums(P, n, d, select_blocks(members, bs), nb, out, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -730,84 +743,71 @@ int sd_halfspace_counts(const double *P, int64_t n, int d, const double *U, int6
     return launch_halfspace_counts(P, n, d, U, k, targets, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+static int halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, int64_t *out,
+                              void *stream) {
+    int rc = check_halfspace(P, n, d, U, k, m, out, sel_others_max(sel, n) + 1,
+                             (double)m * (double)sel_cnt_max(sel, n) * (double)k * (double)d);
+    if (rc) return rc;
+    if ((rc = check_all_rows(sel, n, m))) return rc;
+    if (m == 0) return SD_OK;
+    return launch_halfspace_pairwise(P, n, d, U, k, sel, m, out, (hipStream_t)stream);
+}
+
 int sd_halfspace_pairwise_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets,
                                  int64_t m, int64_t *out, void *stream) {
-    int rc = check_halfspace(P, n, d, U, k, m, out, n, (double)m * (double)n * (double)k * (double)d);
-    if (rc) return rc;
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    if (m == 0) return SD_OK;
-    return launch_halfspace_pairwise(P, n, d, U, k, targets, m, out, (hipStream_t)stream);
+    return halfspace_pairwise(P, n, d, U, k, select_rows(targets), m, out, stream);
 }
 
 int sd_halfspace_external_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const double *Q, int64_t m,
                                  int64_t *out, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_halfspace(P, n, d, U, k, m, out, n + 1, (double)m * (double)n * (double)k * (double)d);
-    if (rc) return rc;
-    if (m == 0) return SD_OK;
-    return launch_halfspace_external(P, n, d, U, k, Q, m, out, (hipStream_t)stream);
+    return halfspace_pairwise(P, n, d, U, k, select_external(Q), m, out, stream);
 }
 
 int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
                                int64_t nb, int bs, int64_t *out, void *stream) {
-    if (!members) return fail(SD_ERR_INVALID, "null pointer");
-    if (bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
-    int rc = check_halfspace(P, n, d, U, k, nb, out, bs, (double)nb * (double)bs * (double)k * (double)d);
-    if (rc) return rc;
-    if (nb == 0) return SD_OK;
-    return launch_halfspace_subsets(P, n, d, U, k, members, nb, bs, out, (hipStream_t)stream);
+    int rc = check_blocks(members, bs);
+    return rc ? rc : halfspace_pairwise(P, n, d, U, k, select_blocks(members, bs), nb, out, stream);
 }
 
 // ---------------------------------------------------------------------------
 // K11
 // ---------------------------------------------------------------------------
-// shape checks shared by the three entry points; cnt_max = the largest sample in P, others = points a target is counted
-// among; *route = the route that runs (1 sweep, 2 pairwise)
-static int check_halfspace2(const double *P, i64 n, i64 m, int algo, const void *out, i64 cnt_max, i64 others, int *route) {
+static int halfspace2_counts(const double *P, i64 n, const PointSel &sel, i64 m, int algo, int64_t *out, void *stream) {
+    const i64 cnt_max = sel_cnt_max(sel, n);                      // the largest sample in P
     if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (n < 1 || m < 0) return fail(SD_ERR_INVALID, "bad shape (n=%lld, m=%lld)", (long long)n, (long long)m);
     if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (sweep), 2 (pairwise)", algo);
-    if (n >= ((i64)1 << 31) || others >= ((i64)1 << 31))          // counts and indices are 32-bit in the kernels
+    if (n >= ((i64)1 << 31) || sel_others_max(sel, n) + 1 >= ((i64)1 << 31))   // counts and indices are 32-bit in the kernels
         return fail(SD_ERR_UNSUPPORTED, "exact halfspace counts take fewer than 2^31 points, got %lld", (long long)n);
-    *route = halfspace2_route(algo, cnt_max);
-    if (*route == 0)
+    const int route = halfspace2_route(algo, cnt_max);              // the route that runs (1 sweep, 2 pairwise)
+    if (route == 0)
         return fail(SD_ERR_UNSUPPORTED, "the sweep holds samples of up to %lld points, got %lld (algo 0 or 2 takes them)",
                     (long long)HX_SWEEP_CAPACITY, (long long)cnt_max);
-    const double work = halfspace2_work(*route, m, cnt_max);
+    const double work = halfspace2_work(route, m, cnt_max);
     if (work > HS_MAX_WORK)
         return fail(SD_ERR_UNSUPPORTED, "%.3g predicate evaluations exceed the cap of %.0e", work, HS_MAX_WORK);
-    return SD_OK;
+    int rc = check_all_rows(sel, n, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_halfspace2(P, n, sel, m, route, out, (hipStream_t)stream);
 }
 
 int sd_halfspace2_counts(const double *P, int64_t n, const int64_t *targets, int64_t m, int algo, int64_t *out,
                          void *stream) {
-    int route = 0;
-    int rc = check_halfspace2(P, n, m, algo, out, n, n, &route);
-    if (rc) return rc;
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    if (m == 0) return SD_OK;
-    return launch_halfspace2(P, n, targets, m, route, out, (hipStream_t)stream);
+    return halfspace2_counts(P, n, select_rows(targets), m, algo, out, stream);
 }
 
 int sd_halfspace2_external_counts(const double *P, int64_t n, const double *Q, int64_t m, int algo, int64_t *out,
                                   void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int route = 0;
-    int rc = check_halfspace2(P, n, m, algo, out, n, n + 1, &route);
-    if (rc) return rc;
-    if (m == 0) return SD_OK;
-    return launch_halfspace2_external(P, n, Q, m, route, out, (hipStream_t)stream);
+    return halfspace2_counts(P, n, select_external(Q), m, algo, out, stream);
 }
 
 int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
                                 int64_t *out, void *stream) {
-    if (!members) return fail(SD_ERR_INVALID, "null pointer");
-    if (bs <= 0) return fail(SD_ERR_INVALID, "bad shape");
-    int route = 0;
-    int rc = check_halfspace2(P, n, nb, algo, out, bs, bs, &route);
-    if (rc) return rc;
-    if (nb == 0) return SD_OK;
-    return launch_halfspace2_subsets(P, n, members, nb, bs, route, out, (hipStream_t)stream);
+    int rc = check_blocks(members, bs);
+    return rc ? rc : halfspace2_counts(P, n, select_blocks(members, bs), nb, algo, out, stream);
 }
 
 }  // extern "C"

@@ -102,16 +102,13 @@ int launch_bd_strict(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, i
 size_t bd_strict_external_workspace_bytes(i64 T, i64 n, i64 m);
 int launch_bd_strict_external(const double *Y, i64 T, i64 n, const double *Q, i64 m, u64 *out, void *ws, size_t ws_bytes,
                               hipStream_t s);
+// The point-cloud launchers below take the selection of the m targets (rows of P, external points, or blocks of rows)
+// as a PointSel: point_select.h.
+struct PointSel;
 // K5 l1
-int launch_l1_depth(const double *P, i64 n, int d, const i64 *targets, i64 m, double *out, hipStream_t s);
-int launch_l1_external(const double *P, i64 n, int d, const double *Q, i64 m, double *out, hipStream_t s);
-int launch_l1_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double *out, hipStream_t s);
-// K4 simplex
-int launch_pointcloud_simplex_external(const double *P, i64 n, int d, const double *Q, i64 m, double tol, u64 *out,
-                                       hipStream_t s);
-int launch_pointcloud_simplex_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double tol,
-                                      u64 *out, hipStream_t s);
-int launch_pointcloud_simplex(const double *P, i64 n, int d, const i64 *targets, i64 m, double tol,
+int launch_l1(const double *P, i64 n, int d, const PointSel &sel, i64 m, double *out, hipStream_t s);
+// K4 simplex (samples < 0: every subset; the sampled estimator takes the rows form only)
+int launch_pointcloud_simplex(const double *P, i64 n, int d, const PointSel &sel, i64 m, double tol,
                               i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws = nullptr, size_t ws_bytes = 0);
 int launch_multi_simplex(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, int relax,
                          double tol, i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws = nullptr, size_t ws_bytes = 0);
@@ -128,9 +125,7 @@ int launch_multi_band_j(const double *P, i64 n, i64 T, int d, const i64 *targets
                         size_t ws_bytes, hipStream_t s);
 
 // K7 Oja volume sums (oja.hip): out = sum of |det| / d! over the d-subsets of the others
-int launch_oja_volume_sums(const double *P, i64 n, int d, const i64 *targets, i64 m, double *out, hipStream_t s);
-int launch_oja_external(const double *P, i64 n, int d, const double *Q, i64 m, double *out, hipStream_t s);
-int launch_oja_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double *out, hipStream_t s);
+int launch_oja(const double *P, i64 n, int d, const PointSel &sel, i64 m, double *out, hipStream_t s);
 
 // K8 probabilistic depths (prob_depth.hip): unnormalised sums of the reference's normal and Poisson depths
 int launch_prob_normal_sums(const double *mu, const double *sigma, i64 n, const i64 *targets, i64 m, double *out,
@@ -148,21 +143,14 @@ size_t halfspace_workspace_bytes(i64 n, i64 k);
 size_t halfspace_min_workspace_bytes(i64 n);
 int launch_halfspace_counts(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
                             void *ws, size_t ws_bytes, hipStream_t s);
-int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
+int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, i64 *out,
                               hipStream_t s);
-int launch_halfspace_external(const double *P, i64 n, int d, const double *U, i64 k, const double *Q, i64 m, i64 *out,
-                              hipStream_t s);
-int launch_halfspace_subsets(const double *P, i64 n, int d, const double *U, i64 k, const int *members, i64 nb, int bs,
-                             i64 *out, hipStream_t s);
 
 // K11 exact halfspace depth in the plane (halfspace_exact.hip): route 1 = angular sweep in LDS, 2 = pairwise L/R/S/O
 constexpr i64 HX_SWEEP_CAPACITY = 8192;                             // sample points one sweep workgroup holds
 int halfspace2_route(int algo, i64 cnt_max);                       // 0: algo = 1 (sweep) above the capacity
 double halfspace2_work(int route, i64 m, i64 cnt_max);             // predicate evaluations
-int launch_halfspace2(const double *P, i64 n, const i64 *targets, i64 m, int route, i64 *out, hipStream_t s);
-int launch_halfspace2_external(const double *P, i64 n, const double *Q, i64 m, int route, i64 *out, hipStream_t s);
-int launch_halfspace2_subsets(const double *P, i64 n, const int *members, i64 nb, int bs, int route, i64 *out,
-                              hipStream_t s);
+int launch_halfspace2(const double *P, i64 n, const PointSel &sel, i64 m, int route, i64 *out, hipStream_t s);
 
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
@@ -228,6 +216,19 @@ __device__ __forceinline__ void band_counts_add(u32 A, u32 B, u32 N, u64 nm1, u6
         case 7: { constexpr int J_ = 7; __VA_ARGS__; } break; \
         case 8: { constexpr int J_ = 8; __VA_ARGS__; } break; \
         default: return sd::fail(SD_ERR_INVALID, "J=%d outside [2,8]", (int)(J)); \
+    }
+
+// dispatch a runtime d in [1, 8] to a template instantiation; any other d falls through (the caller says what it covers)
+#define SD_DISPATCH_D(d, ...)                         \
+    switch (d) {                                      \
+        case 1: { constexpr int D_ = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int D_ = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int D_ = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int D_ = 4; __VA_ARGS__; } break; \
+        case 5: { constexpr int D_ = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int D_ = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int D_ = 7; __VA_ARGS__; } break; \
+        case 8: { constexpr int D_ = 8; __VA_ARGS__; } break; \
     }
 
 }  // namespace sd

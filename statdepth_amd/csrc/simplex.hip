@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "sd_common.h"
+#include "point_select.h"
 
 namespace sd {
 
@@ -194,71 +195,34 @@ __device__ __forceinline__ u64 block_sum_u64(u64 v, u64 *scratch) {
     return r;
 }
 
-// Which rows of P a block's subsets are drawn from, and where its target lies:
-//   default   -- the n - 1 rows other than targets[q] (the subset loops of _pointwisedepth / _simplex_depth);
-//   members   -- an explicit block of rows per target (int32[nb][bs], -1 padded; the block's OTHERS first, its target
-//                LAST): the K-block sampled estimator (_samplepointwisedepth, _pointcloud.py:107-121) in one launch;
-//   Q         -- EXTERNAL targets (m x d): every row of P is an "other" (the homogeneity coefficients' depth of a
-//                point of G inside F u {g}, homogeneity.py:172-186, for all of G at once).  Point clouds only (T = 0).
-struct SxSel {
-    const int *members;
-    int bs;
-    const double *Q;
-    int d;
-};
-
-struct SxBlock {
-    const int *mem;
-    const double *xq;
-    i64 tg, no;
-    u64 total, key;
-};
-
-__device__ __forceinline__ SxBlock sx_block(const SxSel &sel, const i64 *targets, i64 n, i64 q, int k, u64 total) {
-    SxBlock b;
-    b.mem = nullptr;
-    b.xq = nullptr;
-    if (sel.members) {
-        const int *mem = sel.members + q * sel.bs;
-        int cnt = 0;
-        while (cnt < sel.bs && mem[cnt] >= 0) ++cnt;
-        b.mem = mem;
-        b.no = cnt > 0 ? cnt - 1 : 0;
-        b.tg = cnt > 0 ? mem[cnt - 1] : 0;
-        b.total = cnt > 0 ? binom_dev((u64)b.no, k) : 0;        // exhaustive inside the block
-        b.key = (u64)b.tg;
-    } else if (sel.Q) {
-        b.xq = sel.Q + q * sel.d;
-        b.no = n;
-        b.tg = -1;
-        b.total = total;
-        b.key = (u64)(n + q);
-    } else {
-        b.tg = targets ? targets[q] : q;
-        b.no = n - 1;
-        b.total = total;
-        b.key = (u64)b.tg;
-    }
-    return b;
+// The targets are selected by a PointSel (point_select.h); the subsets are drawn from a target's others.  The external
+// and the block form are for point clouds only (T = 0); a block is enumerated exhaustively whatever `total` says.
+__device__ __forceinline__ u64 sx_total(const PointView &v, int k, u64 total) {
+    return v.mem ? binom_dev((u64)v.others(), k) : total;
 }
 
-__device__ __forceinline__ i64 sx_src(const SxBlock &b, i64 i, bool sampled = false) {
-    if (b.mem) return b.mem[i];
-    if (b.xq || sampled) return i;                               // (a sampled subset holds rows, never the target's)
-    return i < b.tg ? i : i + 1;                                 // skip the target itself
+// row of P behind index i of a subset.  direct (sx_direct, taken once per thread): i is a row already
+__device__ __forceinline__ bool sx_direct(const PointView &v, i64 samples) {
+    return samples >= 0 || v.tg < 0;                             // a sampled subset holds rows, never the target's; no row to skip
+}
+__device__ __forceinline__ i64 sx_src(const PointView &v, bool direct, i64 i) {
+    if (v.mem) return v.mem[i];
+    if (direct) return i;
+    return i < v.tg ? i : i + 1;                                 // skip the target itself
 }
 
 // grid = (chunks, m).  T == 0 selects the pointcloud form (P is n x d);
 // otherwise P is n x T x d and c counts timepoints (relax / strict reduction).
 __global__ __launch_bounds__(SX_THREADS) void simplex_kernel(
-    const double *__restrict__ P, i64 n, i64 T, int d, const i64 *__restrict__ targets, int relax, double tol,
-    u64 total, u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *__restrict__ out, SxSel sel) {
+    const double *__restrict__ P, i64 n, i64 T, int d, PointSel sel, int relax, double tol,
+    u64 total, u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *__restrict__ out) {
     __shared__ u64 scratch[SX_THREADS / 64];
     i64 q = q0 + blockIdx.y;
     int k = d + 1;
-    const SxBlock blk = sx_block(sel, targets, n, q, k, total);
-    const i64 tg = blk.tg, no = blk.no;
-    total = blk.total;
+    const PointView blk = point_view(sel, P, n, d, q);
+    const i64 tg = blk.tg, no = blk.others();
+    const bool direct = sx_direct(blk, samples);
+    total = sx_total(blk, k, total);
     u64 tid = (u64)blockIdx.x * SX_THREADS + threadIdx.x;
     u64 first = tid * per_thread;
     u64 acc = 0;
@@ -276,11 +240,11 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel(
             u64 cnt = 0;
             for (i64 t = 0; t < TT; ++t) {
                 for (int c = 0; c < k; ++c) {
-                    i64 src = sx_src(blk, idx[c], samples >= 0);
+                    i64 src = sx_src(blk, direct, idx[c]);
                     const double *pp = P + (src * TT + t) * d;
                     for (int e = 0; e < d; ++e) pts[c * d + e] = pp[e];
                 }
-                const double *xx = blk.xq ? blk.xq : P + (tg * TT + t) * d;
+                const double *xx = T > 0 ? P + (tg * TT + t) * d : blk.x;  // curves (rows form only): the target at timepoint t
                 for (int e = 0; e < d; ++e) x[e] = xx[e];
                 cnt += point_in_hull(pts, k, d, x, tol);
             }
@@ -400,14 +364,15 @@ __device__ __forceinline__ int hull_full_rank(double (&R)[D + 1][D + 2], double 
 // grid = (chunks, m), the work decomposition of simplex_kernel; D = d known at compile time.
 template <int D>
 __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
-    const double *__restrict__ P, i64 n, i64 T, const i64 *__restrict__ targets, int relax, double tol,
-    u64 total, u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *__restrict__ out, SxSel sel) {
+    const double *__restrict__ P, i64 n, i64 T, PointSel sel, int relax, double tol,
+    u64 total, u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *__restrict__ out) {
     __shared__ u64 scratch[SX_THREADS / 64];
     constexpr int K = D + 1;
     const i64 q = q0 + blockIdx.y;
-    const SxBlock blk = sx_block(sel, targets, n, q, K, total);
-    const i64 tg = blk.tg, no = blk.no;
-    total = blk.total;
+    const PointView blk = point_view(sel, P, n, D, q);
+    const i64 tg = blk.tg, no = blk.others();
+    const bool direct = sx_direct(blk, samples);
+    total = sx_total(blk, K, total);
     const u64 tid = (u64)blockIdx.x * SX_THREADS + threadIdx.x;
     const u64 first = tid * per_thread;
     u64 acc = 0;
@@ -426,10 +391,10 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
                 double R[K][K + 1];
                 double scale = 1.0;
                 bool anynan = false;
-                const double *xx = blk.xq ? blk.xq : P + (tg * TT + t) * D;
+                const double *xx = T > 0 ? P + (tg * TT + t) * D : blk.x;  // curves (rows form only): the target at timepoint t
 #pragma unroll
                 for (int c = 0; c < K; ++c) {
-                    const i64 src = sx_src(blk, idx[c], samples >= 0);
+                    const i64 src = sx_src(blk, direct, idx[c]);
                     const double *pp = P + (src * TT + t) * D;
 #pragma unroll
                     for (int e = 0; e < D; ++e) {
@@ -452,7 +417,7 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
                 if (res == 2) {                                         // degenerate simplex: generic code, from the data
                     double pts[SMAX * 8], x[8];
                     for (int c = 0; c < K; ++c) {
-                        const i64 src = sx_src(blk, idx[c], samples >= 0);
+                        const i64 src = sx_src(blk, direct, idx[c]);
                         const double *pp = P + (src * TT + t) * D;
                         for (int e = 0; e < D; ++e) pts[c * D + e] = pp[e];
                     }
@@ -859,11 +824,7 @@ size_t simplex_sampled_workspace_bytes(i64 n, i64 T, int d, i64 samples) {
     if (d < 1 || d > 8 || samples <= 0) return 0;
     const i64 TT = T > 0 ? T : 1;
     size_t per = 0;
-    switch (d) {
-#define SX_PB(D_) case D_: per = sxw_pair_bytes<D_>(); break;
-        SX_PB(1) SX_PB(2) SX_PB(3) SX_PB(4) SX_PB(5) SX_PB(6) SX_PB(7) SX_PB(8)
-#undef SX_PB
-    }
+    SD_DISPATCH_D(d, per = sxw_pair_bytes<D_>())
     i64 pairs = samples * TT;
     if (pairs > ((i64)1 << 20)) pairs = (i64)1 << 20;                   // batches of up to 2^20 pairs: at most ~1.7 GB at d = 8
     return (size_t)pairs * per + align_up((size_t)n * 4, 256) + 1024;
@@ -903,26 +864,19 @@ static int launch_simplex_ws(const double *P, i64 n, i64 T, const i64 *targets, 
     return SD_OK;
 }
 
-static int launch_simplex_common(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, int relax,
-                                 double tol, i64 samples, u64 seed, u64 *out, hipStream_t s,
-                                 SxSel sel = SxSel{nullptr, 0, nullptr, 0}, void *ws = nullptr, size_t ws_bytes = 0) {
+static int launch_simplex_common(const double *P, i64 n, i64 T, int d, const PointSel &sel, i64 m, int relax,
+                                 double tol, i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws, size_t ws_bytes) {
     SD_HIP(hipMemsetAsync(out, 0, sizeof(u64) * m, s));
     u64 total;
-    // subsets per target: of the n - 1 others / of all n rows (external targets) / of the largest block's others
-    const i64 pool = sel.members ? (i64)sel.bs - 1 : (sel.Q ? n : n - 1);
-    if (samples >= 0) total = (u64)samples;
-    else if (!binom_u64_checked((u64)pool, d + 1, &total)) return fail(SD_ERR_OVERFLOW, "subset count overflow");
+    if (samples >= 0) total = (u64)samples;                      // else the subsets of the most others a target has
+    else if (!binom_u64_checked((u64)sel_others_max(sel, n), d + 1, &total)) return fail(SD_ERR_OVERFLOW, "subset count overflow");
     if (total == 0) return SD_OK;
     // sampled, targets of the set, counts that add over the timepoints (point clouds, relax=True): the shared factorisation
     if (samples > 0 && !sel.members && !sel.Q && (T == 0 || relax) && d >= 1 && d <= 8 && n >= d + 3 && xswitch("SD_SIMPLEX_GENERIC") != 1 &&
         xswitch("SD_SIMPLEX_PERTARGET") != 1) {
         // with a workspace that holds at least a few hundred records: factor into HBM, replay from there (else the per-target kernels)
         if (ws && ws_bytes >= simplex_sampled_workspace_bytes(n, T, d, 256 < samples ? 256 : samples)) {
-            switch (d) {
-#define SX_WS(D_) case D_: return launch_simplex_ws<D_>(P, n, T, targets, m, tol, samples, seed, out, ws, ws_bytes, s);
-                SX_WS(1) SX_WS(2) SX_WS(3) SX_WS(4) SX_WS(5) SX_WS(6) SX_WS(7) SX_WS(8)
-#undef SX_WS
-            }
+            SD_DISPATCH_D(d, return launch_simplex_ws<D_>(P, n, T, sel.targets, m, tol, samples, seed, out, ws, ws_bytes, s))
         }
     }
     // aim for ~2^18 threads over all targets, at least 1 subset per thread
@@ -936,45 +890,26 @@ static int launch_simplex_common(const double *P, i64 n, i64 T, int d, const i64
     for (i64 q0 = 0; q0 < m; q0 += 65535) {   // grid.y limit: fold large m into several launches
         i64 mm = m - q0 < 65535 ? m - q0 : 65535;
         dim3 grid((unsigned)blocks, (unsigned)mm);
-#define SX_FAST(D_) case D_: hipLaunchKernelGGL((simplex_kernel_fast<D_>), grid, dim3(SX_THREADS), 0, s, P, n, T, targets, \
-                                                 relax, tol, total, per_thread, samples, seed, q0, out, sel); break;
-        if (xswitch("SD_SIMPLEX_GENERIC") == 1) {            // cross-check builds: the generic (scratch-memory) kernel
-            hipLaunchKernelGGL(simplex_kernel, grid, dim3(SX_THREADS), 0, s, P, n, T, d, targets, relax, tol, total,
-                               per_thread, samples, seed, q0, out, sel);
-        } else {
-            switch (d) {
-                SX_FAST(1) SX_FAST(2) SX_FAST(3) SX_FAST(4) SX_FAST(5) SX_FAST(6) SX_FAST(7) SX_FAST(8)
-                default:
-                    hipLaunchKernelGGL(simplex_kernel, grid, dim3(SX_THREADS), 0, s, P, n, T, d, targets, relax, tol,
-                                       total, per_thread, samples, seed, q0, out, sel);
-            }
-        }
-#undef SX_FAST
+        // the generic (scratch-memory) kernel where the cross-check builds ask for it
+        if (d < 1 || d > 8 || xswitch("SD_SIMPLEX_GENERIC") == 1)
+            hipLaunchKernelGGL(simplex_kernel, grid, dim3(SX_THREADS), 0, s, P, n, T, d, sel, relax, tol, total, per_thread,
+                               samples, seed, q0, out);
+        else
+            SD_DISPATCH_D(d, hipLaunchKernelGGL((simplex_kernel_fast<D_>), grid, dim3(SX_THREADS), 0, s, P, n, T, sel, relax,
+                                                tol, total, per_thread, samples, seed, q0, out))
     }
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
 
-int launch_pointcloud_simplex(const double *P, i64 n, int d, const i64 *targets, i64 m, double tol,
+int launch_pointcloud_simplex(const double *P, i64 n, int d, const PointSel &sel, i64 m, double tol,
                               i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws, size_t ws_bytes) {
-    return launch_simplex_common(P, n, 0, d, targets, m, 1, tol, samples, seed, out, s, SxSel{nullptr, 0, nullptr, 0}, ws, ws_bytes);
-}
-
-// external targets Q (m x d): out[q] = #{(d+1)-subsets of ALL n rows of P whose simplex contains Q[q]}
-int launch_pointcloud_simplex_external(const double *P, i64 n, int d, const double *Q, i64 m, double tol, u64 *out,
-                                       hipStream_t s) {
-    return launch_simplex_common(P, n, 0, d, nullptr, m, 1, tol, -1, 0, out, s, SxSel{nullptr, 0, Q, d});
-}
-
-// explicit blocks: out[k] = #{(d+1)-subsets of block k's others whose simplex contains the block's target (its last row)}
-int launch_pointcloud_simplex_subsets(const double *P, i64 n, int d, const int *members, i64 nb, int bs, double tol,
-                                      u64 *out, hipStream_t s) {
-    return launch_simplex_common(P, n, 0, d, nullptr, nb, 1, tol, -1, 0, out, s, SxSel{members, bs, nullptr, d});
+    return launch_simplex_common(P, n, 0, d, sel, m, 1, tol, samples, seed, out, s, ws, ws_bytes);
 }
 
 int launch_multi_simplex(const double *P, i64 n, i64 T, int d, const i64 *targets, i64 m, int relax,
                          double tol, i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws, size_t ws_bytes) {
-    return launch_simplex_common(P, n, T, d, targets, m, relax, tol, samples, seed, out, s, SxSel{nullptr, 0, nullptr, 0}, ws, ws_bytes);
+    return launch_simplex_common(P, n, T, d, select_rows(targets), m, relax, tol, samples, seed, out, s, ws, ws_bytes);
 }
 
 }  // namespace sd

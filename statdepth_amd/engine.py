@@ -159,17 +159,25 @@ def _targets_dev(targets, n, dev, dtype=np.int64):
     return td, len(tg), td.data_ptr()
 
 
-def _members_dev(members, dev, n, rows=None):
+def _members_dev(members, dev, n, rows=None, trailing_padding=False):
     """(tensor, nb, bs) of the block members on dev: nb blocks of bs indices, -1 padded.  rows: the number of blocks
-    the caller has targets for."""
+    the caller has targets for.  trailing_padding: the point-cloud block form, whose kernels take a block's members up to
+    its first -1 and its target from the last of them -- a -1 in front of a member is refused."""
     t = torch()
     mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
     if mem.ndim != 2:
         raise ValueError("members must be 2-D (blocks x block size, -1 padded, target last)")
     if rows is not None and mem.shape[0] != rows:
         raise ValueError("members must have one row (block) per target")
-    if mem.size and (int(mem.min()) < -1 or int(mem.max()) >= n):
+    lowest = int(mem.min()) if mem.size else 0
+    if mem.size and (lowest < -1 or int(mem.max()) >= n):
         raise IndexError("block member index out of range (valid: -1 padding, 0 .. n-1)")
+    if trailing_padding and lowest < 0:                              # (an array without padding is not read again)
+        pad = mem.ravel() < 0
+        gap = pad[:-1] > pad[1:]                                      # a -1 with a member behind it ...
+        gap[mem.shape[1] - 1::mem.shape[1]] = False                   # ... in the same block
+        if bool(gap.any()):
+            raise IndexError("block members must come first and the -1 padding last")
     return t.from_numpy(mem).to(dev), mem.shape[0], mem.shape[1]
 
 
@@ -355,29 +363,65 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
                    workspace=lambda: _strict_workspace(lib, dev, M, m, J, workspace_budget))
 
 
-def l1_depth(P, targets=None, device=None):
+# Point clouds.  Every depth of K4, K5, K7, K10 and K11 is asked for in three forms ("Point clouds: the three
+# forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
+# block.  The public functions below name the C entry point and the form; _points does the rest.
+_ROWS, _EXTERNAL, _BLOCKS = "rows", "external", "blocks"
+
+
+def _points(name, dtype, P, device, form, arg, *extra, U=None, plane=False, workspace=None):
+    """lib.<name>(P, n, [d, [U, k,]] selection, *extra, out, [ws, ws_bytes,] stream); out: one value of dtype per target.
+    selection: (targets, m) for the rows targets=arg of P (None: all), (Q, m) for the external points Q=arg, or
+    (members, nb, bs) for the blocks members=arg (-1 padded at the end, others first, target last).  U: K10's k x d
+    directions.  plane: K11 -- P and Q are checked to be planar and exact, d is not passed, and an index outside the
+    sample is a ValueError like K11's other argument checks.  workspace(dev, n, d): (buffer, bytes).
+    `keep` holds the selection's device tensor until the launch has been issued."""
+    assert form in (_ROWS, _EXTERNAL, _BLOCKS)
     t = torch()
     lib = _lib()
     dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    td, m, tp = _targets_dev(targets, n, dev)
-    out = t.empty(m, dtype=t.float64, device=dev)
-    return _launch(dev, lib.sd_l1_depth, out, Pd.data_ptr(), n, d, tp, m)
+    shape = np.shape(P)
+    if len(shape) != 2:
+        raise ValueError("expected a 2-D array")
+    n = shape[0]
+    # the indices first: what would read outside the sample is refused before anything is uploaded
+    try:
+        if form == _ROWS:
+            keep, m, ptr = _targets_dev(arg, n, dev)
+            sel = (ptr, m)
+        elif form == _BLOCKS:
+            keep, m, bs = _members_dev(arg, dev, n, trailing_padding=True)
+            sel = (keep.data_ptr(), m, bs)
+    except IndexError as e:
+        if plane:
+            raise ValueError(str(e)) from e
+        raise
+    Pd = _plane_points(P, dev) if plane else _upload(P, 2, dev)
+    d = Pd.shape[1]
+    head = (Pd.data_ptr(), n) if plane else (Pd.data_ptr(), n, d)
+    if U is not None:
+        Ud = _directions_dev(U, d, dev)
+        head += (Ud.data_ptr(), Ud.shape[0])
+    if form == _EXTERNAL:
+        keep = _plane_points(arg, dev, "Q") if plane else _upload(arg, 2, dev)
+        if keep.shape[1] != d:
+            raise ValueError("Q must have the same number of coordinates as P")
+        m = keep.shape[0]
+        sel = (keep.data_ptr(), m)
+    out = t.empty(m, dtype=dtype, device=dev)
+    ws = (lambda: workspace(dev, n, d)) if workspace is not None else None
+    return _launch(dev, getattr(lib, name), out, *head, *sel, *extra, workspace=ws)
+
+
+def l1_depth(P, targets=None, device=None):
+    return _points("sd_l1_depth", torch().float64, P, device, _ROWS, targets)
 
 
 def pointcloud_simplex_counts(P, targets=None, tol=1e-7, samples=None, seed=0, device=None):
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    td, m, tp = _targets_dev(targets, n, dev)
-    out = t.empty(m, dtype=t.int64, device=dev)
     if samples is None:
-        return _launch(dev, lib.sd_pointcloud_simplex_counts, out, Pd.data_ptr(), n, d, tp, m, tol)
-    return _launch(dev, lib.sd_pointcloud_simplex_sampled, out, Pd.data_ptr(), n, d, tp, m, tol, int(samples), int(seed),
-                   workspace=lambda: _sized(dev, lib.sd_simplex_sampled_workspace_bytes(n, 0, d, int(samples))))
+        return _points("sd_pointcloud_simplex_counts", torch().int64, P, device, _ROWS, targets, tol)
+    return _points("sd_pointcloud_simplex_sampled", torch().int64, P, device, _ROWS, targets, tol, int(samples), int(seed),
+                   workspace=lambda dev, n, d: _sized(dev, _lib().sd_simplex_sampled_workspace_bytes(n, 0, d, int(samples))))
 
 
 def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, seed=0, device=None):
@@ -396,79 +440,41 @@ def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, se
                    workspace=lambda: _sized(dev, lib.sd_simplex_sampled_workspace_bytes(n, T, d, int(samples))))
 
 
-def _external_points(fn, dtype, P, Q, device, *extra):
-    """fn(P, n, d, Q, m, *extra, out, stream) for the m rows of Q against ALL n rows of P; out: (m,) of dtype."""
-    t = torch()
-    dev = _device(device)
-    Pd, Qd = _upload(P, 2, dev), _upload(Q, 2, dev)
-    n, d = Pd.shape
-    if Qd.shape[1] != d:
-        raise ValueError("Q must have the same number of coordinates as P")
-    m = Qd.shape[0]
-    out = t.empty(m, dtype=dtype, device=dev)
-    return _launch(dev, fn, out, Pd.data_ptr(), n, d, Qd.data_ptr(), m, *extra)
-
-
-def _subset_points(fn, dtype, P, members, device, *extra):
-    """fn(P, n, d, members, nb, bs, *extra, out, stream) per block (rows of `members`, -1 padded, others first, target
-    last); out: (nb,) of dtype."""
-    t = torch()
-    dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    md, nb, bs = _members_dev(members, dev, n)
-    out = t.empty(nb, dtype=dtype, device=dev)
-    return _launch(dev, fn, out, Pd.data_ptr(), n, d, md.data_ptr(), nb, bs, *extra)
-
-
 def pointcloud_simplex_external_counts(P, Q, tol=1e-7, device=None):
     """int64[m]: (d+1)-subsets of ALL rows of P whose simplex contains the external point Q[q]."""
-    lib = _lib()
-    return _external_points(lib.sd_pointcloud_simplex_external_counts, torch().int64, P, Q, device, tol)
+    return _points("sd_pointcloud_simplex_external_counts", torch().int64, P, device, _EXTERNAL, Q, tol)
 
 
 def pointcloud_simplex_subset_counts(P, members, tol=1e-7, device=None):
     """int64[nb]: per block (rows of `members`, -1 padded, others first, target last) the (d+1)-subsets of the
     block's others whose simplex contains its target."""
-    lib = _lib()
-    return _subset_points(lib.sd_pointcloud_simplex_subset_counts, torch().int64, P, members, device, tol)
+    return _points("sd_pointcloud_simplex_subset_counts", torch().int64, P, device, _BLOCKS, members, tol)
 
 
 def l1_external_depth(P, Q, device=None):
     """float64[m]: L1 depth of the external point Q[q] inside P u {Q[q]}."""
-    lib = _lib()
-    return _external_points(lib.sd_l1_external_depth, torch().float64, P, Q, device)
+    return _points("sd_l1_external_depth", torch().float64, P, device, _EXTERNAL, Q)
 
 
 def l1_subset_depth(P, members, device=None):
     """float64[nb]: L1 depth of each block's target (last row of the block) inside the block."""
-    lib = _lib()
-    return _subset_points(lib.sd_l1_subset_depth, torch().float64, P, members, device)
+    return _points("sd_l1_subset_depth", torch().float64, P, device, _BLOCKS, members)
 
 
 def oja_volume_sums(P, targets=None, device=None):
     """float64[m]: sum over d-subsets S of the other rows of vol(conv(S u {P[target]})) (sd_oja_volume_sums)."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    td, m, tp = _targets_dev(targets, n, dev)
-    out = t.empty(m, dtype=t.float64, device=dev)
-    return _launch(dev, lib.sd_oja_volume_sums, out, Pd.data_ptr(), n, d, tp, m)
+    return _points("sd_oja_volume_sums", torch().float64, P, device, _ROWS, targets)
 
 
 def oja_external_volume_sums(P, Q, device=None):
     """float64[m]: sum over d-subsets S of ALL rows of P of vol(conv(S u {Q[q]})) (sd_oja_external_volume_sums)."""
-    lib = _lib()
-    return _external_points(lib.sd_oja_external_volume_sums, torch().float64, P, Q, device)
+    return _points("sd_oja_external_volume_sums", torch().float64, P, device, _EXTERNAL, Q)
 
 
 def oja_subset_volume_sums(P, members, device=None):
     """float64[nb]: per block (rows of `members`, -1 padded, others first, target last) the sum over d-subsets S of
     the block's others of vol(conv(S u {target}))."""
-    lib = _lib()
-    return _subset_points(lib.sd_oja_subset_volume_sums, torch().float64, P, members, device)
+    return _points("sd_oja_subset_volume_sums", torch().float64, P, device, _BLOCKS, members)
 
 
 def prob_normal_sums(mu, sigma, targets=None, device=None):
@@ -575,58 +581,29 @@ def halfspace_counts(P, U, targets=None, device=None, workspace_budget=None, alg
     target and every tie counted (sd_halfspace_counts); depth = counts / n.  workspace_budget: upper bound in bytes for
     the scratch buffer (default: the recommended size), never below the floor of one direction per chunk; the counts do
     not depend on it.  algo='pairwise': the same counts from the pairwise kernel (sd_halfspace_pairwise_counts)."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    Ud = _directions_dev(U, d, dev)
-    k = Ud.shape[0]
-    td, m, tp = _targets_dev(targets, n, dev)
-    out = t.empty(m, dtype=t.int64, device=dev)
     if algo == "pairwise":
-        return _launch(dev, lib.sd_halfspace_pairwise_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), k, tp, m)
+        return _points("sd_halfspace_pairwise_counts", torch().int64, P, device, _ROWS, targets, U=U)
     if algo != "rank":
         raise ValueError("algo must be 'rank' or 'pairwise'")
 
-    def sized():
-        want, floor = halfspace_workspace_bytes(n, d, k)
+    def sized(dev, n, d):
+        want, floor = halfspace_workspace_bytes(n, d, np.shape(U)[0])
         if workspace_budget is not None:
             want = max(floor, min(want, int(workspace_budget)))
         return _sized(dev, want)
-    return _launch(dev, lib.sd_halfspace_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), k, tp, m, workspace=sized)
+    return _points("sd_halfspace_counts", torch().int64, P, device, _ROWS, targets, U=U, workspace=sized)
 
 
 def halfspace_external_counts(P, Q, U, device=None):
     """int64[m]: the halfspace counts of the external point Q[q] inside P u {Q[q]} (n + 1 points, Q[q] counted once) over
     the directions U (sd_halfspace_external_counts); depth = counts / (n + 1)."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    Pd, Qd = _upload(P, 2, dev), _upload(Q, 2, dev)
-    n, d = Pd.shape
-    if Qd.shape[1] != d:
-        raise ValueError("Q must have the same number of coordinates as P")
-    Ud = _directions_dev(U, d, dev)
-    m = Qd.shape[0]
-    out = t.empty(m, dtype=t.int64, device=dev)
-    return _launch(dev, lib.sd_halfspace_external_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), Ud.shape[0],
-                   Qd.data_ptr(), m)
+    return _points("sd_halfspace_external_counts", torch().int64, P, device, _EXTERNAL, Q, U=U)
 
 
 def halfspace_subset_counts(P, members, U, device=None):
     """int64[nb]: per block (rows of `members`, -1 padded, target last) the halfspace counts of the block's target inside
     the block over the directions U (sd_halfspace_subset_counts); depth = counts / block size."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    Pd = _upload(P, 2, dev)
-    n, d = Pd.shape
-    Ud = _directions_dev(U, d, dev)
-    md, nb, bs = _members_dev(members, dev, n)
-    out = t.empty(nb, dtype=t.int64, device=dev)
-    return _launch(dev, lib.sd_halfspace_subset_counts, out, Pd.data_ptr(), n, d, Ud.data_ptr(), Ud.shape[0],
-                   md.data_ptr(), nb, bs)
+    return _points("sd_halfspace_subset_counts", torch().int64, P, device, _BLOCKS, members, U=U)
 
 
 HALFSPACE2_ALGOS = {"auto": 0, "sweep": 1, "pairwise": 2}
@@ -650,50 +627,20 @@ def _plane_points(A, dev, what="P"):
     return Ad
 
 
-def _index_as_value_error(fn, *args):
-    """K11's entry points report an index outside the sample as a ValueError, like their other argument checks."""
-    try:
-        return fn(*args)
-    except IndexError as e:
-        raise ValueError(str(e)) from e
-
-
 def halfspace_exact_counts(P, targets=None, device=None, algo="auto"):
     """int64[m]: the exact halfspace (Tukey) counts of x = P[targets[q]] inside the planar sample P (n x 2): the fewest
     sample points in a closed halfplane with x on its boundary, x and its duplicates counted (sd_halfspace2_counts);
     depth = counts / n.  algo: 'auto', 'sweep' (samples of at most 8192 points) or 'pairwise'; the same integers."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    a = _halfspace2_algo(algo)
-    Pd = _plane_points(P, dev)
-    n = Pd.shape[0]
-    td, m, tp = _index_as_value_error(_targets_dev, targets, n, dev)
-    out = t.empty(m, dtype=t.int64, device=dev)
-    return _launch(dev, lib.sd_halfspace2_counts, out, Pd.data_ptr(), n, tp, m, a)
+    return _points("sd_halfspace2_counts", torch().int64, P, device, _ROWS, targets, _halfspace2_algo(algo), plane=True)
 
 
 def halfspace_exact_external_counts(P, Q, device=None, algo="auto"):
     """int64[m]: the exact halfspace counts of the external point Q[q] inside P u {Q[q]} (n + 1 points, Q[q] counted once;
     sd_halfspace2_external_counts); depth = counts / (n + 1)."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    a = _halfspace2_algo(algo)
-    Pd, Qd = _plane_points(P, dev), _plane_points(Q, dev, "Q")
-    m = Qd.shape[0]
-    out = t.empty(m, dtype=t.int64, device=dev)
-    return _launch(dev, lib.sd_halfspace2_external_counts, out, Pd.data_ptr(), Pd.shape[0], Qd.data_ptr(), m, a)
+    return _points("sd_halfspace2_external_counts", torch().int64, P, device, _EXTERNAL, Q, _halfspace2_algo(algo), plane=True)
 
 
 def halfspace_exact_subset_counts(P, members, device=None, algo="auto"):
     """int64[nb]: per block (rows of `members`, -1 padded, target last) the exact halfspace counts of the block's target
     inside the block (sd_halfspace2_subset_counts); depth = counts / block size."""
-    t = torch()
-    lib = _lib()
-    dev = _device(device)
-    a = _halfspace2_algo(algo)
-    Pd = _plane_points(P, dev)
-    md, nb, bs = _index_as_value_error(_members_dev, members, dev, Pd.shape[0])
-    out = t.empty(nb, dtype=t.int64, device=dev)
-    return _launch(dev, lib.sd_halfspace2_subset_counts, out, Pd.data_ptr(), Pd.shape[0], md.data_ptr(), nb, bs, a)
+    return _points("sd_halfspace2_subset_counts", torch().int64, P, device, _BLOCKS, members, _halfspace2_algo(algo), plane=True)

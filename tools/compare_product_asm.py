@@ -8,8 +8,11 @@ For both trees the product build (the Makefile's CXXFLAGS, no -DSD_CROSSCHECK) o
 Kernels are compared by symbol over the union of a tree's files -- one that moved to another product file is still the same
 kernel: its instruction stream (comments dropped, local labels renumbered per kernel) and its .amdhsa_ resource block (VGPRs,
 SGPRs, LDS, scratch, ...) must be identical.  Kernels may disappear from the product only when they are named in
-MOVED_TO_XONLY, and then they must be in one of the new tree's XONLY translation units (the cross-check library).  Needs hipcc
-only, no GPU.  Exit status 0: all of that holds.
+MOVED_TO_XONLY, and then they must be in one of the new tree's XONLY translation units (the cross-check library).  A kernel
+whose argument list this change rewrites has another symbol in the new tree: those named in NEW_ARGUMENTS are paired by their
+demangled name without the arguments, and must keep the PINNED fields of the resource block and of the code object's metadata
+(registers, scratch, LDS, wavefront and workgroup set-up); their SGPR and instruction counts are reported, not judged.  Needs
+hipcc only, no GPU.  Exit status 0: all of that holds.
 """
 import argparse
 import concurrent.futures
@@ -20,6 +23,12 @@ import sys
 import tempfile
 
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
+# short names of kernels that now take the point selector (point_select.h's PointSel, by value) where they took a selector
+# struct of their own file or loose targets / Q / members / bs arguments
+NEW_ARGUMENTS = ("simplex_kernel", "simplex_kernel_fast", "l1_depth_kernel", "oja_kernel", "hs_pairwise_kernel",
+                 "hx_sweep_kernel", "hx_pairwise_kernel")
+PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
+                    r"wavefront|workgroup|workitem")
 
 
 def make_var(makefile, name):
@@ -73,7 +82,18 @@ def kernels(path):
         def local(m):
             return names.setdefault(m.group(0), ".L%d" % len(names))
         body[sym] = [re.sub(r"\.L[A-Za-z_]+\d+(?:_\d+)?", local, ln) for ln in text]
-    return {s: (body[s], res[s]) for s in res}
+    # the code object's metadata of the kernel (.vgpr_count, .agpr_count, .sgpr_count, .max_flat_workgroup_size, ...)
+    meta = {}
+    for entry in re.split(r"\n  - ", open(path).read().split("amdhsa.kernels:")[-1]):
+        nm = re.search(r"^\s*\.name:\s+(\S+)", entry, re.M)
+        if nm and nm.group(1) in res:
+            meta[nm.group(1)] = [f".meta{k} {v}" for k, v in re.findall(r"^\s*(\.(?:[asv]gpr_count|max_flat_workgroup_size|"
+                                                                       r"wavefront_size)):\s+(\S+)", entry, re.M)]
+    return {s: (body[s], res[s] + meta.get(s, [])) for s in res}
+
+
+def short_name(name):
+    return name.split("::")[-1].split("<")[0]
 
 
 def demangle(sym):
@@ -114,10 +134,23 @@ def main():
         old, new = asm.get("parent", {}), asm.get("new", {})
         xonly_names = {demangle(s) for s in asm.get("xonly", {})}
         same = moved = 0
+        renamed = {demangle(s): s for s in set(new) - set(old) if short_name(demangle(s)) in NEW_ARGUMENTS}
         for sym in sorted(old):
             name = demangle(sym)
+            if sym not in new and name in renamed:
+                nsym = renamed.pop(name)
+                pin = lambda res: sorted(ln for ln in res if PINNED.search(ln))
+                was, now = pin(old[sym][1]), pin(new[nsym][1])
+                sg = lambda res: next((ln.split()[-1] for ln in res if ln.startswith(".meta.sgpr_count")), "?")
+                report.append(f"{where['new'][nsym]}: {name}: new arguments, pinned fields {'same' if was == now else 'DIFFER'}; "
+                              f"SGPRs {sg(old[sym][1])} -> {sg(new[nsym][1])}, instructions {len(old[sym][0])} -> "
+                              f"{len(new[nsym][0])}")
+                if was != now:
+                    ok = False
+                    report.extend(f"    {x}  ->  {y}" for x, y in zip(was, now) if x != y)
+                continue
             if sym not in new:
-                short = name.split("::")[-1].split("<")[0]
+                short = short_name(name)
                 allowed = short in MOVED_TO_XONLY and name in xonly_names
                 ok &= allowed
                 report.append(f"{where['parent'][sym]}: {name}: left the product, " +
@@ -134,7 +167,8 @@ def main():
                 ok = False
                 report.append(f"{where['new'][sym]}: {name}: DIFFERS (instructions {'same' if code else 'differ'}, "
                               f"resource block {'same' if resources else 'differs'})")
-        for sym in sorted(set(new) - set(old)):
+        for sym in sorted(s for s in set(new) - set(old) if short_name(demangle(s)) not in NEW_ARGUMENTS
+                          or demangle(s) in renamed):
             ok = False
             report.append(f"{where['new'][sym]}: {demangle(sym)}: NEW in the product")
         insts = sum(len(old[s][0]) for s in old if s in new)
