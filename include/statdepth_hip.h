@@ -430,6 +430,39 @@ int sd_halfspace2_external_counts(const double *P, int64_t n, const double *Q, i
 int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
                                 int64_t *out, void *stream);
 
+/* ---- K12: projection depth (Stahel-Donoho outlyingness) of a point cloud over a fixed direction set ----
+ * No reference code.  P is n x d row-major, U is k x d row-major (both device), d <= 8.  For a sample S of N points:
+ *   z_r(x)    = K10's projection, the same bits (features in increasing order, products and sums rounded separately);
+ *   median(v) = s[(N-1)/2] for N odd, (s[N/2-1] + s[N/2]) * 0.5 for N even (s = v sorted; the sum rounded, then the
+ *               product rounded);
+ *   med_r     = median(z_r(S));  mad_r = median(|z_r(p_i) - med_r|) (one rounded subtraction, the sign cleared; no
+ *               1.4826 factor);
+ *   o_r(q)    = |z_r(q) - med_r| / mad_r, one correctly rounded division; a numerator of 0 gives 0 whatever mad_r is, a
+ *               numerator above 0 with mad_r = 0 gives +inf;
+ *   out[q]    = max over r of o_r(q);   depth = 1 / (1 + out) on the host.
+ * Every step is one correctly rounded fp64 operation or an order statistic: a numpy restatement gives the same bits.
+ * The data and the directions must be finite with magnitudes of at most 2^500 (the host checks), so nothing overflows
+ * on the way to the division and no NaN arises.
+ *   sd_projection_outlyingness:          S = P, targets: m int64 row indices (device), NULL = all (m == n).  Per chunk
+ *       of kc directions: K10's projection and sort, med and MAD by O(log n) selection from the sorted rows, then one
+ *       evaluation per (target, direction).  kc follows from ws_bytes; sd_projection_workspace_bytes recommends a size,
+ *       sd_projection_min_workspace_bytes is the floor (one direction per chunk: about 24 n bytes), SD_ERR_WORKSPACE
+ *       below it.  The result does not depend on the workspace size (the maximum is exact).
+ *   sd_projection_external_outlyingness: m external points Q (m x d, device); S = P u {Q[q]}, N = n + 1: every external
+ *       point has a median and a MAD of its own, selected from P's sorted rows with Q[q]'s projection inserted.
+ *   sd_projection_subset_outlyingness:   blocks of rows, members int32[nb*bs], -1 padded at the end, the block's target
+ *       LAST; S = the block's members.  bs <= 2048 (a block is sorted in LDS).  An empty block gives 0.
+ * SD_ERR_INVALID for NULL pointers or n, d, k, bs < 1; SD_ERR_UNSUPPORTED for d > 8, bs > 2048, 2^31 or more points, or
+ * more than 10^14 projections and comparisons.  All before any device work.  Every launch is bounded in work. */
+size_t sd_projection_workspace_bytes(int64_t n, int d, int64_t k);
+size_t sd_projection_min_workspace_bytes(int64_t n, int d, int64_t k);
+int sd_projection_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets,
+                               int64_t m, double *out, void *ws, size_t ws_bytes, void *stream);
+int sd_projection_external_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const double *Q,
+                                        int64_t m, double *out, void *ws, size_t ws_bytes, void *stream);
+int sd_projection_subset_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
+                                      int64_t nb, int bs, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,27 +35,19 @@
 // LDS budget: tile sort 24 KB (2048 x (8 + 4) bytes), merge 48 KB (input and output images), pairwise 256 x d x 8 bytes
 // (16 KB at d = 8).  256 threads (4 wave64) per workgroup everywhere.  Every launch is bounded: a ranking launch covers at
 // most max(n, 2^25) values, a pairwise launch at most HS_UNITS workgroups of HS_SLICE x 256 projections each.
+//
+// The projection and the sorted rows (hs_proj, launch_hs_sort_chunk) are shared with K12 (projection.hip) through
+// halfspace_sort.h.
 #include "sd_common.h"
 #include "point_select.h"
+#include "halfspace_sort.h"
 
 namespace sd {
 
-constexpr int HS_THREADS = 256;
-constexpr int HS_TILE = 2048;                                      // values per sort / merge tile
-constexpr i64 HS_CHUNK_VALUES = (i64)1 << 25;                      // projected values per chunk (one row when n is larger)
-constexpr i64 HS_REC_VALUES = (i64)1 << 23;                        // ... of the recommended workspace
 constexpr int HS_PTILE = 256;                                      // pairwise: sample points per LDS tile
 constexpr i64 HS_SLICE = 4096;                                     // pairwise: sample points per workgroup
 constexpr u64 HS_UNITS = (u64)1 << 14;                             // pairwise: workgroups per launch
 constexpr size_t HS_ACC_BYTES = (size_t)64 << 20;                  // pairwise: accumulator bytes per batch of targets
-
-template <int D>
-__device__ __forceinline__ double hs_proj(const double (&x)[D], const double (&u)[D]) {
-    double z = __dmul_rn(x[0], u[0]);
-#pragma unroll
-    for (int e = 1; e < D; ++e) z = __dadd_rn(z, __dmul_rn(x[e], u[e]));
-    return z;
-}
 
 // ---------------------------------------------------------------------------------------------- ranking route
 template <int D>
@@ -247,11 +239,9 @@ __global__ __launch_bounds__(HS_THREADS) void hs_gather_kernel(const u32 *__rest
     out[j] = (i64)cnt[targets ? targets[j] : j];
 }
 
-static inline int hs_ntiles(i64 n) { return (int)((n + HS_TILE - 1) / HS_TILE); }
-
 // fixed part (the running minima and the alignment of the six carve-outs) and the part per direction of a chunk
-static inline size_t hs_ws_fixed(i64 n) { return align_up((size_t)n * 4, 256) + 6 * 256; }
-static inline size_t hs_ws_per_direction(i64 n) { return (size_t)n * 24 + (size_t)hs_ntiles(n) * 4; }
+static inline size_t hs_ws_fixed(i64 n) { return align_up((size_t)n * 4, 256) + (1 + HS_SORT_CARVES) * 256; }
+static inline size_t hs_ws_per_direction(i64 n) { return hs_sort_bytes_per_direction(n); }
 
 size_t halfspace_min_workspace_bytes(i64 n) { return hs_ws_fixed(n) + hs_ws_per_direction(n); }
 
@@ -261,51 +251,58 @@ size_t halfspace_workspace_bytes(i64 n, i64 k) {
     return hs_ws_fixed(n) + (size_t)kc * hs_ws_per_direction(n);
 }
 
+// one chunk: projection, tile sort, merge passes; the sorted rows are in b.K[*src] / b.I[*src]
 template <int D>
-static int launch_hs_counts_d(const double *P, i64 n, const double *U, i64 k, const i64 *targets, i64 m, i64 *out, void *ws,
-                              size_t ws_bytes, hipStream_t s) {
+static int hs_sort_chunk_d(const double *P, i64 n, const double *U, int kk, const HsSortBuffers &b, int *src_out,
+                           hipStream_t s) {
+    const int ntiles = hs_ntiles(n);
+    const unsigned gx = (unsigned)((n + HS_THREADS - 1) / HS_THREADS);
+    unsigned gy = gx >= 2048 ? 1 : (2048 + gx - 1) / gx;
+    gy = gy > (unsigned)kk ? (unsigned)kk : gy;
+    hipLaunchKernelGGL((hs_project_kernel<D>), dim3(gx, gy), dim3(HS_THREADS), 0, s, P, n, U, kk, b.K[0]);
+    SD_HIP(hipGetLastError());
+    const i64 tiles = (i64)kk * ntiles;
+    hipLaunchKernelGGL(hs_tile_sort_kernel, dim3((unsigned)tiles), dim3(HS_THREADS), 0, s, b.K[0], b.I[0], n, ntiles);
+    SD_HIP(hipGetLastError());
+    int src = 0;
+    for (i64 w = HS_TILE; w < n; w *= 2) {
+        hipLaunchKernelGGL(hs_partition_kernel, dim3((unsigned)((tiles + HS_THREADS - 1) / HS_THREADS)), dim3(HS_THREADS),
+                           0, s, b.K[src], n, w, ntiles, tiles, b.part);
+        SD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hs_merge_kernel, dim3((unsigned)tiles), dim3(HS_THREADS), 0, s, b.K[src], b.I[src], b.K[src ^ 1],
+                           b.I[src ^ 1], n, w, ntiles, b.part);
+        SD_HIP(hipGetLastError());
+        src ^= 1;
+    }
+    *src_out = src;
+    return SD_OK;
+}
+
+int launch_hs_sort_chunk(const double *P, i64 n, int d, const double *U, int kk, const HsSortBuffers &b, int *src,
+                         hipStream_t s) {
+    SD_DISPATCH_D(d, return hs_sort_chunk_d<D_>(P, n, U, kk, b, src, s))
+    return fail(SD_ERR_UNSUPPORTED, "halfspace projections cover d in [1,8], got %d", d);
+}
+
+static int launch_hs_counts(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
+                            void *ws, size_t ws_bytes, hipStream_t s) {
     if (!ws || ws_bytes < halfspace_min_workspace_bytes(n))
         return fail(SD_ERR_WORKSPACE, "workspace too small for one direction per chunk (sd_halfspace_min_workspace_bytes)");
-    i64 kc = (i64)((ws_bytes - hs_ws_fixed(n)) / hs_ws_per_direction(n));
-    const i64 cap = HS_CHUNK_VALUES / n < 1 ? 1 : HS_CHUNK_VALUES / n;
-    kc = kc > cap ? cap : kc;
-    kc = kc > k ? k : kc;
-    const int ntiles = hs_ntiles(n);
+    const i64 kc = hs_chunk_directions(ws_bytes - hs_ws_fixed(n), hs_ws_per_direction(n), n, k);
     Carver cv(ws, ws_bytes);
     u32 *cnt = (u32 *)cv.take((size_t)n * 4);
-    double *Kb[2];
-    u32 *Ib[2];
-    Kb[0] = (double *)cv.take((size_t)kc * n * 8);
-    Kb[1] = (double *)cv.take((size_t)kc * n * 8);
-    Ib[0] = (u32 *)cv.take((size_t)kc * n * 4);
-    Ib[1] = (u32 *)cv.take((size_t)kc * n * 4);
-    int *part = (int *)cv.take((size_t)kc * ntiles * 4);
-    if (!cnt || !Kb[0] || !Kb[1] || !Ib[0] || !Ib[1] || !part)
+    HsSortBuffers b;
+    if (!hs_sort_carve(cv, n, kc, b) || !cnt)
         return fail(SD_ERR_WORKSPACE, "workspace too small (sd_halfspace_min_workspace_bytes)");
     SD_HIP(hipMemsetAsync(cnt, 0xff, (size_t)n * 4, s));
-    const unsigned gx = (unsigned)((n + HS_THREADS - 1) / HS_THREADS);
     for (i64 c0 = 0; c0 < k; c0 += kc) {
         const int kk = (int)(k - c0 < kc ? k - c0 : kc);
-        unsigned gy = gx >= 2048 ? 1 : (2048 + gx - 1) / gx;
-        gy = gy > (unsigned)kk ? (unsigned)kk : gy;
-        hipLaunchKernelGGL((hs_project_kernel<D>), dim3(gx, gy), dim3(HS_THREADS), 0, s, P, n, U + c0 * D, kk, Kb[0]);
-        SD_HIP(hipGetLastError());
-        const i64 tiles = (i64)kk * ntiles;
-        hipLaunchKernelGGL(hs_tile_sort_kernel, dim3((unsigned)tiles), dim3(HS_THREADS), 0, s, Kb[0], Ib[0], n, ntiles);
-        SD_HIP(hipGetLastError());
         int src = 0;
-        for (i64 w = HS_TILE; w < n; w *= 2) {
-            hipLaunchKernelGGL(hs_partition_kernel, dim3((unsigned)((tiles + HS_THREADS - 1) / HS_THREADS)), dim3(HS_THREADS),
-                               0, s, Kb[src], n, w, ntiles, tiles, part);
-            SD_HIP(hipGetLastError());
-            hipLaunchKernelGGL(hs_merge_kernel, dim3((unsigned)tiles), dim3(HS_THREADS), 0, s, Kb[src], Ib[src], Kb[src ^ 1],
-                               Ib[src ^ 1], n, w, ntiles, part);
-            SD_HIP(hipGetLastError());
-            src ^= 1;
-        }
+        const int rc = launch_hs_sort_chunk(P, n, d, U + c0 * d, kk, b, &src, s);
+        if (rc) return rc;
         const i64 total = (i64)kk * n;
         hipLaunchKernelGGL(hs_rank_kernel, dim3((unsigned)((total + HS_THREADS - 1) / HS_THREADS)), dim3(HS_THREADS), 0, s,
-                           Kb[src], Ib[src], n, total, cnt);
+                           b.K[src], b.I[src], n, total, cnt);
         SD_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(hs_gather_kernel, dim3((unsigned)((m + HS_THREADS - 1) / HS_THREADS)), dim3(HS_THREADS), 0, s, cnt,
@@ -425,8 +422,8 @@ static int launch_hs_pairwise_d(const double *P, i64 n, const double *U, i64 k, 
 
 int launch_halfspace_counts(const double *P, i64 n, int d, const double *U, i64 k, const i64 *targets, i64 m, i64 *out,
                             void *ws, size_t ws_bytes, hipStream_t s) {
-    SD_DISPATCH_D(d, return launch_hs_counts_d<D_>(P, n, U, k, targets, m, out, ws, ws_bytes, s))
-    return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
+    if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "halfspace counts cover d in [1,8], got %d", d);
+    return launch_hs_counts(P, n, d, U, k, targets, m, out, ws, ws_bytes, s);
 }
 
 int launch_halfspace_pairwise(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, i64 *out,

@@ -810,4 +810,75 @@ int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *membe
     return rc ? rc : halfspace2_counts(P, n, select_blocks(members, bs), nb, algo, out, stream);
 }
 
+// ---------------------------------------------------------------------------
+// K12
+// ---------------------------------------------------------------------------
+static double log2_steps(i64 n) {
+    double l = 1.0;
+    for (i64 v = n; v > 1; v >>= 1) l += 1.0;
+    return l;
+}
+
+// shape checks shared by the three entry points; `sample` = the largest sample of the call, work = the call's estimate
+static int check_projection(const double *P, i64 n, int d, const double *U, i64 k, i64 m, const void *out, i64 sample,
+                            double work) {
+    if (!P || !U || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n < 1 || d < 1 || k < 1 || m < 0) return fail(SD_ERR_INVALID, "bad shape (n=%lld, d=%d, k=%lld, m=%lld)", (long long)n,
+                                                       d, (long long)k, (long long)m);
+    if (d > 8) return fail(SD_ERR_UNSUPPORTED, "projection outlyingness covers d in [1,8], got %d", d);
+    if (n >= ((i64)1 << 31) || sample >= ((i64)1 << 31))          // the sort's indices are 32-bit
+        return fail(SD_ERR_UNSUPPORTED, "projection outlyingness takes fewer than 2^31 points, got %lld", (long long)n);
+    if (k >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "projection outlyingness takes fewer than 2^31 directions");
+    if (work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g projections and comparisons exceed the cap of %.0e", work, HS_MAX_WORK);
+    return SD_OK;
+}
+
+size_t sd_projection_workspace_bytes(int64_t n, int d, int64_t k) {
+    if (n < 1 || d < 1 || k < 1 || n >= ((i64)1 << 31)) return 0;
+    return projection_workspace_bytes(n, k);
+}
+
+size_t sd_projection_min_workspace_bytes(int64_t n, int d, int64_t k) {
+    if (n < 1 || d < 1 || k < 1 || n >= ((i64)1 << 31)) return 0;
+    return projection_min_workspace_bytes(n);
+}
+
+// rows and external form: sort per chunk of directions, then m k evaluations (external: with a selection each)
+static int projection_sorted(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, double *out,
+                             void *ws, size_t ws_bytes, void *stream) {
+    const double logn = log2_steps(n);
+    int rc = check_projection(P, n, d, U, k, m, out, sel_others_max(sel, n) + 1,
+                              (double)k * (double)n * ((double)d + logn) +
+                                  (double)m * (double)k * ((double)d + (sel.Q ? 3.0 * logn : 0.0)));
+    if (rc) return rc;
+    if ((rc = check_all_rows(sel, n, m))) return rc;
+    if (m == 0) return SD_OK;
+    return launch_projection_sorted(P, n, d, U, k, sel, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int sd_projection_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets,
+                               int64_t m, double *out, void *ws, size_t ws_bytes, void *stream) {
+    return projection_sorted(P, n, d, U, k, select_rows(targets), m, out, ws, ws_bytes, stream);
+}
+
+int sd_projection_external_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const double *Q,
+                                        int64_t m, double *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    return projection_sorted(P, n, d, U, k, select_external(Q), m, out, ws, ws_bytes, stream);
+}
+
+int sd_projection_subset_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
+                                      int64_t nb, int bs, double *out, void *stream) {
+    int rc = check_blocks(members, bs);
+    if (rc) return rc;
+    const double logb = log2_steps(bs);
+    rc = check_projection(P, n, d, U, k, nb, out, bs, (double)nb * (double)k * (double)bs * ((double)d + logb * logb));
+    if (rc) return rc;
+    if (bs > PD_MAX_BLOCK)
+        return fail(SD_ERR_UNSUPPORTED, "projection outlyingness takes blocks of at most %d members, got %d", PD_MAX_BLOCK, bs);
+    if (nb == 0) return SD_OK;
+    return launch_projection_blocks(P, n, d, U, k, select_blocks(members, bs), nb, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

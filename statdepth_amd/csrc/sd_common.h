@@ -152,6 +152,16 @@ int halfspace2_route(int algo, i64 cnt_max);                       // 0: algo = 
 double halfspace2_work(int route, i64 m, i64 cnt_max);             // predicate evaluations
 int launch_halfspace2(const double *P, i64 n, const PointSel &sel, i64 m, int route, i64 *out, hipStream_t s);
 
+// K12 projection depth (projection.hip): out = max over directions of |z - med| / mad.  launch_projection_sorted serves
+// the rows and the external form (sel), launch_projection_blocks the blocks form (sel.bs <= PD_MAX_BLOCK: the caller checks)
+constexpr int PD_MAX_BLOCK = 2048;                                  // members of a block: what pd_blocks_kernel sorts in LDS
+size_t projection_workspace_bytes(i64 n, i64 k);
+size_t projection_min_workspace_bytes(i64 n);
+int launch_projection_sorted(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 m, double *out,
+                             void *ws, size_t ws_bytes, hipStream_t s);
+int launch_projection_blocks(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 nb, double *out,
+                             hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

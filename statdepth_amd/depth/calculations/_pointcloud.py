@@ -9,6 +9,8 @@ Mahalanobis depth (:152-173) is not provided: the reference's covariance is sing
 Halfspace (Tukey) depth over a fixed direction set (containment='halfspace', sd_halfspace_*) is an extension the
 reference does not have; DESIGN.md §3 K10 states its definition.  directions='exact' asks for the exact halfspace depth
 (d = 2: sd_halfspace2_*; d = 1: the direction (1.0), which is exact already).
+Projection depth (containment='projection', sd_projection_*: 1 / (1 + the Stahel-Donoho outlyingness) over the same kind
+of direction set) is another extension; DESIGN.md §3 K12 states its definition bit for bit.
 """
 from typing import Union
 
@@ -98,6 +100,35 @@ def _halfspace_setup(P: np.ndarray, directions, seed):
     return None
 
 
+_PROJECTION_MAX_BLOCK = 2048                             # members of a K-block: sd_projection_subset_outlyingness sorts it in LDS
+
+
+def _projection_check(P: np.ndarray) -> None:
+    if P.shape[1] > 8:
+        raise NotImplementedError('projection depth is implemented for d <= 8')
+    engine.projection_check('coordinates', P)            # finite, |x| <= 2^500: ValueError otherwise
+
+
+def _projection_setup(P: np.ndarray, directions, seed) -> np.ndarray:
+    """Host checks of containment='projection', then the k x d direction array (as for halfspace: an int with `seed`, or
+    an array used as given)."""
+    _projection_check(P)
+    if isinstance(directions, str):
+        if directions == 'exact':
+            raise NotImplementedError("projection depth has no exact form: directions='exact' belongs to "
+                                      "containment='halfspace'; give a number of directions or a (k x d) array")
+        raise ValueError(f"directions must be a positive number of directions or a (k x {P.shape[1]}) array, "
+                         f"got {directions!r}")
+    U = _halfspace_directions(directions, seed, P.shape[1])   # finite, no all-zero row
+    engine.projection_check('direction entries', U)
+    return U
+
+
+def _projection_depth(outlyingness: np.ndarray) -> np.ndarray:
+    """1 / (1 + O) in numpy; O = inf gives 0.0."""
+    return 1.0 / (1.0 + np.asarray(outlyingness, dtype=np.float64))
+
+
 def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None, containment='simplex',
                     quiet=True, device=None, directions=1000, seed=0) -> pd.Series:
     n, d = data.shape
@@ -139,6 +170,13 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         else:
             counts = engine.halfspace_counts(P, U, _row_positions(data, to_compute), device=device)
         return pd.Series(index=to_compute, data=counts.astype(np.float64) / n)
+    elif containment == 'projection':
+        # An extension (no such string in the reference): 1 / (1 + O), O = max over the directions of
+        # |x.u - med(P.u)| / MAD(P.u), the Stahel-Donoho outlyingness over the direction set
+        P = data.to_numpy(dtype=np.float64)
+        U = _projection_setup(P, directions, seed)
+        out = engine.projection_outlyingness(P, U, _row_positions(data, to_compute), device=device)
+        return pd.Series(index=to_compute, data=_projection_depth(out))
     elif containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     else:
@@ -160,6 +198,8 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directio
         if directions is None:                           # directions='exact' in the plane
             return engine.halfspace_exact_subset_counts(P, mem, device=device).astype(np.float64) / sizes
         return engine.halfspace_subset_counts(P, mem, directions, device=device).astype(np.float64) / sizes
+    if containment == 'projection':                      # med and MAD of the block, its target included
+        return _projection_depth(engine.projection_subset_outlyingness(P, mem, directions, device=device))
     if containment == 'simplex':
         d = P.shape[1]
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
@@ -178,23 +218,30 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     so the reference itself cannot run this path any more).  The draws are made first -- rows by position, from
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
     (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
-    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts / sd_halfspace2_subset_counts) instead
-    of as many `_pointwisedepth` calls.
+    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts / sd_halfspace2_subset_counts /
+    sd_projection_subset_outlyingness) instead of as many `_pointwisedepth` calls.
     Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
     normaliser (the reference's is identically 0).  Halfspace: one direction set (directions, seed) for
-    every block, or none (directions='exact'); neither takes anything from the global RNG.
+    every block, or none (directions='exact'); neither takes anything from the global RNG.  Projection: one direction
+    set as well; blocks of more than 2 048 rows (the n // K drawn rows and the point: n // K + 1 > 2048) are refused
+    before anything is drawn.
     """
     if K == 1:
         return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device,
                                directions=directions, seed=seed)
     if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    if containment not in ('simplex', 'l1', 'oja', 'halfspace'):
+    if containment not in ('simplex', 'l1', 'oja', 'halfspace', 'projection'):
         raise ValueError(f'{containment} is not a valid containment measure. ')
     n, d = data.shape
     U = None
     if containment == 'halfspace':                       # host checks first: bad input never reaches the RNG or the GPU
         U = _halfspace_setup(data.to_numpy(dtype=np.float64), directions, seed)
+    if containment == 'projection':
+        U = _projection_setup(data.to_numpy(dtype=np.float64), directions, seed)
+        if n // K + 1 > _PROJECTION_MAX_BLOCK:           # a block: n // K drawn rows, and the point where the draw missed it
+            raise NotImplementedError(f'K-sampled projection depth takes blocks of at most {_PROJECTION_MAX_BLOCK} rows '
+                                      f'(n // K drawn rows and the point itself), got {n // K + 1}: raise K')
     if to_compute is None:
         to_compute = data.index
     ss = n // K

@@ -1,7 +1,7 @@
 """Public factories and result objects (reference: statdepth/depth/depth.py).
 
 `FunctionalDepth` (:362-402) and `PointcloudDepth` (:347-359) keep the reference's
-signatures; `device=`, `algo=` and, for containment='halfspace', `directions=` and `seed=` are keyword-only additions.  `ProbabilisticDepth` is the
+signatures; `device=`, `algo=` and, for containment='halfspace' and 'projection', `directions=` and `seed=` are keyword-only additions.  `ProbabilisticDepth` is the
 signature the reference documents (docs/index.md §5.1.3) and lists in `__all__` (:11) without
 implementing it, plus `to_compute` and the keyword-only `device=`.  Result classes keep
 the reference's method names and conventions (:14-65,178-185,337-341), including the
@@ -144,10 +144,12 @@ class _PointwiseDepth(_FunctionalDepthSeries):
 
 def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, containment='simplex', quiet=True,
                     *, device=None, directions=1000, seed=0) -> _PointwiseDepth:
-    """`directions` and `seed` belong to containment='halfspace' (every other containment ignores them): an int k asks
-    for k unit directions drawn from `np.random.default_rng(seed)`, a (k x d) array is used as given -- both give the
-    directional depth, an upper bound of the halfspace depth once d >= 2.  'exact' gives the halfspace depth itself for
-    d <= 2 (`seed` is ignored; d >= 3 raises NotImplementedError)."""
+    """`directions` and `seed` belong to containment='halfspace' and containment='projection' (every other containment
+    ignores them): an int k asks for k unit directions drawn from `np.random.default_rng(seed)`, a (k x d) array is used
+    as given.  For 'halfspace' both give the directional depth, an upper bound of the halfspace depth once d >= 2, and
+    'exact' gives the halfspace depth itself for d <= 2 (`seed` is ignored; d >= 3 raises NotImplementedError).  For
+    'projection' they are the directions of the Stahel-Donoho outlyingness O = max |x.u - med| / MAD, depth =
+    1 / (1 + O); there 'exact' raises NotImplementedError."""
     if K is not None:
         depth = _samplepointwisedepth(data=data, to_compute=to_compute, K=K, containment=containment,
                                       device=device, directions=directions, seed=seed)

@@ -363,7 +363,7 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
                    workspace=lambda: _strict_workspace(lib, dev, M, m, J, workspace_budget))
 
 
-# Point clouds.  Every depth of K4, K5, K7, K10 and K11 is asked for in three forms ("Point clouds: the three
+# Point clouds.  Every depth of K4, K5, K7, K10, K11 and K12 is asked for in three forms ("Point clouds: the three
 # forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
 # block.  The public functions below name the C entry point and the form; _points does the rest.
 _ROWS, _EXTERNAL, _BLOCKS = "rows", "external", "blocks"
@@ -372,8 +372,8 @@ _ROWS, _EXTERNAL, _BLOCKS = "rows", "external", "blocks"
 def _points(name, dtype, P, device, form, arg, *extra, U=None, plane=False, workspace=None):
     """lib.<name>(P, n, [d, [U, k,]] selection, *extra, out, [ws, ws_bytes,] stream); out: one value of dtype per target.
     selection: (targets, m) for the rows targets=arg of P (None: all), (Q, m) for the external points Q=arg, or
-    (members, nb, bs) for the blocks members=arg (-1 padded at the end, others first, target last).  U: K10's k x d
-    directions.  plane: K11 -- P and Q are checked to be planar and exact, d is not passed, and an index outside the
+    (members, nb, bs) for the blocks members=arg (-1 padded at the end, others first, target last).  U: the k x d
+    directions of K10 and K12.  plane: K11 -- P and Q are checked to be planar and exact, d is not passed, and an index outside the
     sample is a ValueError like K11's other argument checks.  workspace(dev, n, d): (buffer, bytes).
     `keep` holds the selection's device tensor until the launch has been issued."""
     assert form in (_ROWS, _EXTERNAL, _BLOCKS)
@@ -644,3 +644,58 @@ def halfspace_exact_subset_counts(P, members, device=None, algo="auto"):
     """int64[nb]: per block (rows of `members`, -1 padded, target last) the exact halfspace counts of the block's target
     inside the block (sd_halfspace2_subset_counts); depth = counts / block size."""
     return _points("sd_halfspace2_subset_counts", torch().int64, P, device, _BLOCKS, members, _halfspace2_algo(algo), plane=True)
+
+
+_PROJECTION_MAX_ABS = 2.0 ** 500
+
+
+def projection_workspace_bytes(n, d, k):
+    """(recommended, floor) workspace sizes of sd_projection_outlyingness and sd_projection_external_outlyingness; the
+    floor holds one direction per chunk."""
+    lib = _native.load()
+    return (int(lib.sd_projection_workspace_bytes(int(n), int(d), int(k))),
+            int(lib.sd_projection_min_workspace_bytes(int(n), int(d), int(k))))
+
+
+def projection_check(what, *arrays):
+    """The value check of projection depth, in one place: every entry finite with magnitude at most 2^500, so that no
+    projection, midpoint or deviation overflows and no NaN arises (NaN fails the comparison too).  The callers that
+    take user data (PointcloudDepth, PointcloudHomogeneity) run it once, on the host, before anything else; the
+    projection_* functions below do not repeat it -- like halfspace_counts they take their arrays as they are."""
+    for A in arrays:
+        A = np.asarray(A, dtype=np.float64)
+        if A.size and not bool((np.abs(A) <= _PROJECTION_MAX_ABS).all()):
+            raise ValueError(f"projection depth needs finite {what} of magnitude at most 2^500")
+
+
+def _projection_workspace(U, workspace_budget):
+    def sized(dev, n, d):
+        want, floor = projection_workspace_bytes(n, d, np.shape(U)[0])
+        if workspace_budget is not None:
+            want = max(floor, min(want, int(workspace_budget)))
+        return _sized(dev, want)
+    return sized
+
+
+def projection_outlyingness(P, U, targets=None, device=None, workspace_budget=None):
+    """float64[m]: the Stahel-Donoho outlyingness max over the rows u of U (k x d) of |x.u - med(P.u)| / MAD(P.u) for
+    x = P[targets[q]] inside the sample P (sd_projection_outlyingness; DESIGN §3 K12 states every rounding);
+    depth = 1 / (1 + outlyingness).  +inf where a direction has MAD 0 and x is off its median.  workspace_budget: upper
+    bound in bytes for the scratch buffer (default: the recommended size), never below the floor of one direction per
+    chunk; the result does not depend on it.  P and U: finite, magnitudes of at most 2^500, no all-zero direction
+    (projection_check; the public API checks)."""
+    return _points("sd_projection_outlyingness", torch().float64, P, device, _ROWS, targets, U=U,
+                   workspace=_projection_workspace(U, workspace_budget))
+
+
+def projection_external_outlyingness(P, Q, U, device=None, workspace_budget=None):
+    """float64[m]: the outlyingness of the external point Q[q] inside P u {Q[q]} (n + 1 points: a median and a MAD per
+    external point and direction; sd_projection_external_outlyingness)."""
+    return _points("sd_projection_external_outlyingness", torch().float64, P, device, _EXTERNAL, Q, U=U,
+                   workspace=_projection_workspace(U, workspace_budget))
+
+
+def projection_subset_outlyingness(P, members, U, device=None):
+    """float64[nb]: per block (rows of `members`, -1 padded, target last; at most 2048 members) the outlyingness of the
+    block's target inside the block (sd_projection_subset_outlyingness); an empty block gives 0."""
+    return _points("sd_projection_subset_outlyingness", torch().float64, P, device, _BLOCKS, members, U=U)

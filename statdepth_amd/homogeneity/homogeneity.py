@@ -187,6 +187,11 @@ def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -
         _halfspace_check(Fx)
         _halfspace_check(Qx)
         return engine.halfspace_external_counts(Fx, Qx, _halfspace_directions(1000, 0, d)).astype(np.float64) / (n + 1)
+    if containment == 'projection':                # med and MAD of F u {g} per external point, the default directions
+        from ..depth.calculations._pointcloud import _halfspace_directions, _projection_check, _projection_depth
+        _projection_check(Fx)
+        _projection_check(Qx)
+        return _projection_depth(engine.projection_external_outlyingness(Fx, Qx, _halfspace_directions(1000, 0, d)))
     if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
     raise ValueError(f'{containment} is not a valid containment measure. ')
