@@ -5,12 +5,13 @@
 // barrier-separated phases leave the VALU idle while the LDS works and the other way round (SQ counters: VALU busy 57 %,
 // LDS busy 37 %, together the kernel's whole time).  Here a key is placed by a 31-bit image q(x), non-decreasing in x
 // whatever the data and whatever the map's constants (round 4: a THREE-PIECE map -- a linear core of 14 336 buckets over the
-// row's range, clipped to a central bracket taken from a sample of 1 024 keys when the range is much wider than the bulk
+// row's range, clipped to a central bracket of the bulk (taken from the threads' own minima and maxima) when the range is much wider than it
 // (heavy tails, outlying curves), and below and above the core 1 024 buckets each for a float-like code of the distance to
 // the core's edge, bits(d + c) - bits(c) with c = core width / 448: linear with the core's slope next to the edge, halving
 // per octave, 32 octaves; every piece is monotone and the pieces are ordered): its top 14 bits are the key's bucket, and LDS
 // holds a 31-bit BUCKET-LOCAL image -- q's low 17 bits followed by 14 more bits of the core's fraction, 45 bits of resolution in
-// all (a tail key keeps q's 31: its 14 extra bits are 0) -- so that a row of up to 11 264 curves + its 16 384-bucket
+// all (a tail key keeps q's 31: its 14 extra bits are 0; a core key's 45 bits are the mantissa of ONE fma, v = 2^38 + image,
+// rounded to nearest: see convert4) -- so that a row of up to 11 264 curves + its 16 384-bucket
 // histogram take 77 KiB and two 512-thread workgroups, half a row apart in phase, share a CU: one's compares run under the
 // other's LDS traffic.  Order is decided by the images (within a bucket; buckets are ordered) wherever they differ; keys whose
 // images coincide (two core values within range / 2^45, two tail values within the tail's 31-bit resolution, or equal values)
@@ -43,7 +44,9 @@ constexpr int R32_PAD = 12;                     // sentinel images behind the ke
 constexpr u32 R32_TB = 1024;                    // buckets of each tail
 constexpr int R32_TSH = 30;                     // tail code = (bits(d + c) - bits(c)) >> 30: 2^22 codes = 32 buckets per octave
 constexpr double R32_CDIV = 1.0 / 448.0;        // c = core width / 448: the first octave continues the core's slope (32 * 448 = 14 336)
-constexpr double R32_BETA = 2.0;                // the central bracket of the sample is widened by this many spans on either side
+constexpr double R32_BETA = 2.0;                // the central bracket is widened by this many spans on either side
+constexpr double R32_VBASE = 274877906944.0;    // 2^38: v = 2^38 + u has one ulp = 2^-14 image, its mantissa is the 45-bit image
+constexpr u32 R32_VBASE_HI = 0x42500000u;       // high word of 2^38
 constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the keys (masked off by the member pass: any value would do)
 
 template <int E, int LNB>
@@ -53,6 +56,9 @@ struct R32Cfg {
     static_assert(QW >= 1 && NB / 2 == QW * 4 * NT, "whole quads of histogram words per thread");
     static constexpr int SH = 31 - LNB;
     static constexpr u32 C0 = R32_TB << SH, C1 = ((u32)NB - R32_TB) << SH;   // images of the core: [C0, C1)
+    static constexpr u32 CU0 = 2u << SH, CU1 = ((u32)NB - 2u) << SH;         // ... of a row that is not clipped: [CU0, CU1)
+    static_assert(C0 % (2u << SH) == 0 && C1 % (2u << SH) == 0 && CU0 % (2u << SH) == 0 && CU1 % (2u << SH) == 0,
+                  "the core's bounds are whole steps of the high word of 2^38 + image (2^18 images)");
     static constexpr u32 NANIMG = ((u32)NB + 2u) << SH;         // a NaN's image: its bucket is the dummy counter NB + 2
     static_assert(LNB == 14, "the first tail octave continues the core's slope for 14 336 core buckets");
     static constexpr size_t HDR = 8 * NW * 8 + NW * 4 + 32 + (size_t)R32_LCAP * 8;
@@ -69,10 +75,10 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                                                                  u32 *__restrict__ gate, u32 epoch, u64 *__restrict__ out_zero) {
     using C = R32Cfg<E, LNB>;
     constexpr int NT = C::NT, NW = C::NW, NB = C::NB, QW = C::QW, SH = C::SH;
-    constexpr u32 C0 = C::C0, C1 = C::C1, NANIMG = C::NANIMG;
+    constexpr u32 C0 = C::C0, C1 = C::C1, CU0 = C::CU0, CU1 = C::CU1, NANIMG = C::NANIMG;
     extern __shared__ double Sm[];
     const int n = (int)n64;
-    double *red = Sm;                                                 // [2][NW][4] min / max of the row, central bracket of its sample
+    double *red = Sm;                                                 // [2][NW][4] min / max of the row, central bracket of its keys
     u32 *wtot = reinterpret_cast<u32 *>(red + 8 * NW);                // [NW]
     u32 *misc = wtot + NW;                                            // [0]: set-aside keys so far, [1]: running sum of the ranks
     u32 *lkey = misc + 8, *lbe = lkey + R32_LCAP;                     // (row index << 14 | curve), B0 | E0 << 16
@@ -110,11 +116,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     u32 acc[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] = 0;
-    // the sample of a row: one key per thread at evenly spaced curve indices -- thread t takes position j = 397 t mod 512 of the 512,
-    // so that the 16 lanes of a DPP row hold keys from all over the curve index (curves ordered by level would otherwise make
-    // every group one level).  The innermost of the 32 groups' minima and maxima bracket the bulk (about the quartiles).
-    double smp;
-    auto sample_issue = [&](i64 r) { smp = Y[(row0 + r) * n + (((((u32)t * 397u) & 511u) * (u32)n) >> 9)]; };
     auto row_range = [&](int parity) {
         double mn = INF, mx = -INF;
 #pragma unroll
@@ -122,27 +123,26 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             mn = rb_mm<false>(mn, x[e]);
             mx = rb_mm<true>(mx, x[e]);
         }
+        // the central bracket (it only places the core: the map is monotone whatever it says), from the keys in hand: a thread's
+        // keys are a strided subset of the row, so the minima and maxima of groups of 16 keys or more (one lane from E = 16 on,
+        // 2 or 4 lanes below) are 32 small samples from all over the curve index, and the innermost of them -- the largest
+        // minimum, the smallest maximum -- bracket the bulk.  In float; a group without a value is neutral.
+        float2 wb = rb3_wave_bracket<E, NT>(mn, mx);
+        // Two unrelated keys equal (curves 512 apart, up to ten pairs per thread: 3 584 pairs of a row or more, as many as the
+        // round-4 sample compared; values 0.1 apart over a range of 200 escape 5 120 pairs in 3 rows of 1 000): values on a
+        // grid.  Such a row is ranked in closed form when every bucket holds ONE value, which the tail buckets of a clipped
+        // map -- octaves wide -- would spoil: an inverted bracket switches the clipping off for the row (its tails are no
+        // heavier for being rounded; if they are heavy, the row is crowded and handed over as in round 3).  One clipped tie
+        // row overflows the list and hands all its workgroup's rows over, so the test must not miss.
+        {
+            bool eqs = false;
+#pragma unroll
+            for (int e = 0; e < (E - 1 < 10 ? E - 1 : 10); ++e) eqs = eqs || (x[e] == x[e + 1]);   // (a slot beyond n is NaN: no)
+            if (__ballot(eqs) != 0) { wb.x = __builtin_huge_valf(); wb.y = -__builtin_huge_valf(); }
+        }
+        const float imn = wb.x, imx = wb.y;
         mn = rb_wave_allreduce<false>(mn);
         mx = rb_wave_allreduce<true>(mx);
-        // the sample's central bracket, in float (it only places the core: the map is monotone whatever it says): a NaN drops
-        // out of v_min / v_max, a group without a value keeps +-inf and switches the bracket off
-        const float sf = (float)smp;
-        const float rmn = rb_row_allreduce_f32<false>(sf == sf ? sf : __builtin_huge_valf());
-        const float rmx = rb_row_allreduce_f32<true>(sf == sf ? sf : -__builtin_huge_valf());
-        auto rl = [](float v, int l) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-        float imn = fmaxf(fmaxf(rl(rmn, 0), rl(rmn, 16)), fmaxf(rl(rmn, 32), rl(rmn, 48)));
-        float imx = fminf(fminf(rl(rmx, 0), rl(rmx, 16)), fminf(rl(rmx, 32), rl(rmx, 48)));
-        // Two sample values of a group of 16 equal (positions scattered over the row): values on a grid.  Such a row is ranked in
-        // closed form when every bucket holds ONE value, which the tail buckets of a clipped map -- octaves wide -- would spoil:
-        // an inverted bracket switches the clipping off for the row (its tails are no heavier for being rounded; if they are
-        // heavy, the row is crowded and handed over as in round 3).
-        {
-            bool eqs = false;                                         // every pair of the group of 16 but those 8 lanes apart
-#define R32_NB(k) eqs = eqs || (__int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sf), 0x120 + k, 0xF, 0xF, false)) == sf);   // row_ror:k
-            R32_NB(1) R32_NB(2) R32_NB(3) R32_NB(4) R32_NB(5) R32_NB(6) R32_NB(7)
-#undef R32_NB
-            if (__ballot(eqs) != 0) { imn = __builtin_huge_valf(); imx = -__builtin_huge_valf(); }
-        }
         double *rp = red + parity * 4 * NW;
         if ((t & 63) == 63) {
             double *wp = rp + 4 * (t >> 6);
@@ -166,7 +166,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         // the second launch (gate[1] = epoch << 8 | count; block-uniform scalar load, a few rows stale at worst)
         if (rowidx && t == 0) misc[3] = __hip_atomic_load(gate + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ONE load per workgroup
         __builtin_amdgcn_s_setprio(R32_PRIO_LDS);                     // latency-bound phases go first, the compares of the member
-        sample_issue(r);
         load_row(r);                                                  // pass (the other workgroup's, half a row away) fill in
         row_range(par);
         double *redp = red + par * 4 * NW;
@@ -180,6 +179,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         double mscale, moff, mc;
         u64 mcb;
         u32 mc0, mcw;                                                 // the core's first image and its width in images
+        u32 mh0, mhw;                                                 // ... as high words of v = 2^38 + image: first, and how many
         bool go, bad;
         {
             const double2 p = reinterpret_cast<const double2 *>(redp)[2 * (lane & (NW - 1))];
@@ -192,10 +192,10 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             // overflowing range or all values equal (one bucket) is handed over.
             const bool fin = (hi > lo) && (lo > -INF) && (hi < INF) && ((hi - lo) < INF);
             bad = !fin && (hi >= lo);
-            // the core: the row's range, clipped to the sample's central bracket widened by R32_BETA spans on either side (a
+            // the core: the row's range, clipped to the central bracket widened by R32_BETA spans on either side (a
             // light-tailed row keeps its whole range and never sees the tail code; heavy tails and outlying curves go to the tails)
             const double si = imx - imn;
-            u32 c0 = 256u, c1 = 0x7FFFFE00u;                          // a light-tailed row: the core takes the whole image range
+            u32 c0 = CU0, c1 = CU1;                                   // a light-tailed row: the core takes the whole image range
             if (fin && si > 0.0 && si < INF && (hi - lo) > (1.5 * (1.0 + 2.0 * R32_BETA)) * si) {   // block-uniform: the range is
                 const double lo2 = imn - R32_BETA * si, hi2 = imx + R32_BETA * si;                  // much wider than the bulk
                 lo = lo2 > lo ? lo2 : lo;
@@ -207,56 +207,63 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             mcw = c1 - c0;
             const double wc = hi - lo;
             mscale = ((double)mcw - 64.0) / wc;                       // the largest key of an unclipped row stays inside the core
-            moff = __builtin_fma(-lo, mscale, (double)c0);
+            moff = __builtin_fma(-lo, mscale, R32_VBASE + (double)c0);    // exact sum: lo lands on 2^38 + c0
+            mh0 = R32_VBASE_HI + (c0 >> (SH + 1));
+            mhw = mcw >> (SH + 1);
             mc = wc * R32_CDIV;
             mcb = (u64)__double_as_longlong(mc);
             go = fin && (wc > 0.0) && (mscale < INF) && (mc > 0.0);
             bad = bad || (fin && !go);
         }
-        // images of four keys: core keys cost fma + cvt + the core test + 14 more bits; the tail code is computed only when some
-        // lane of the wave has a key outside the core (or a NaN: cvt gives 0).  Out: the bucket (top 14 bits of the 31-bit image
-        // q) in bk, the bucket-local image in q -- q's low 17 bits, then 14 more bits of the core's fraction (0 in the tails)
+        // images of four keys: a core key costs ONE fp64 instruction.  v = fma(x, mscale, moff) with moff = the core's offset + 2^38
+        // lies in [2^38, 2^39) for a core key, where one ulp is 2^-14: the 52-bit mantissa of v IS the 45-bit image
+        // I = round(2^14 u) (the fma's single rounding; u = the 31-bit image with its fraction), bucket = I >> 31 = bits 31 .. 44
+        // of the two words, local image = the low word's 31 bits.  fma is monotone in x and the mantissa is monotone in v inside
+        // the binade, so the image is non-decreasing in x whatever the constants.  The core's bounds are multiples of 2^18
+        // images = one step of the high word: mh0 <= high word < mh0 + mhw is EXACTLY vlo <= v < vlo + mcw, and a NaN, a negative
+        // v (sign bit: a huge unsigned word) or any other binade fails it.  The tail code is computed only when some lane of the
+        // wave has a key outside the core; which side is read off v itself (monotone in x: v < vlo <=> below the core, also
+        // for the row's minimum when the offset's rounding puts it a hair under the bound).  Out: the bucket in bk, the
+        // bucket-local image in q (a tail key: its 31-bit image's low 17 bits, 14 zero bits behind them)
         auto convert4 = [&](const double (&xv)[4], u32 (&q)[4], u32 (&bk)[4]) {
             bool anyout = false;
-            u32 fr[4];
+            u32 vh[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const double u = __builtin_fma(xv[i], mscale, moff);
-                u32 qi;
-                asm("v_cvt_u32_f64 %0, %1" : "=v"(qi) : "v"(u));      // saturating: below -> 0, above -> 2^32 - 1, NaN -> 0
-                // floor(2^14 frac(u)): exact, and frac(u) = u - qi for a core key (0 < u < 2^31); the 45-bit image is q << 14 | fr
-                const double f = __builtin_amdgcn_fract(u) * 16384.0;
-                asm("v_cvt_u32_f64 %0, %1" : "=v"(fr[i]) : "v"(f));
-                q[i] = qi;
-                anyout = anyout || (qi - mc0 >= mcw);
+                const u64 w = (u64)__double_as_longlong(__builtin_fma(xv[i], mscale, moff));
+                vh[i] = (u32)(w >> 32);
+                q[i] = (u32)w;
+                anyout = anyout || (vh[i] - mh0 >= mhw);
             }
             if (__ballot(anyout) != 0) {
+                const double vlo = __longlong_as_double((long long)((u64)mh0 << 32));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const bool outc = q[i] - mc0 >= mcw, low = q[i] < mc0;
+                    const bool outc = vh[i] - mh0 >= mhw;
+                    const bool low = __longlong_as_double((long long)(((u64)vh[i] << 32) | q[i])) < vlo;
                     double d = low ? lo - xv[i] : xv[i] - hi;
                     d = rb_mm<true>(d, 0.0);                          // a key the rounding put just outside: code 0
                     const u64 tc = ((u64)__double_as_longlong(d + mc) - mcb) >> R32_TSH;
                     // below the core: mc0 - 1 downwards; above: from the core's end upwards; clamped to what is left of the
-                    // image range (a clipped core leaves 1 024 buckets on either side, an unclipped one a few images: only a
+                    // image range (a clipped core leaves 1 024 buckets on either side, an unclipped one two buckets: only a
                     // key the rounding put just outside comes here then)
                     const u32 room = low ? mc0 - 1u : 0x7FFFFEFFu - (mc0 + mcw);
                     const u32 tcc = tc < (u64)room ? (u32)tc : room;
                     u32 qt = low ? (mc0 - 1u) - tcc : (mc0 + mcw) + tcc;
                     qt = (xv[i] == xv[i]) ? qt : NANIMG;
-                    q[i] = outc ? qt : q[i];
-                    fr[i] = outc ? 0u : fr[i];                        // a tail key keeps the 31-bit resolution
+                    vh[i] = outc ? qt >> (SH + 1) : vh[i];            // the words of qt << 14: a tail key keeps the 31-bit resolution
+                    q[i] = outc ? qt << (31 - SH) : q[i];
                 }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                bk[i] = q[i] >> SH;                                   // a NaN's image: the dummy counter NB + 2
-                q[i] = ((q[i] << (31 - SH)) & 0x7FFFFFFFu) | fr[i];
+                bk[i] = __builtin_amdgcn_alignbit(vh[i], q[i], 31) & 0x7FFFu;   // a NaN's image: the dummy counter NB + 2
+                q[i] &= 0x7FFFFFFFu;
             }
         };
         u32 bc[E];                                                    // bucket | slot << 16, then (at the scatter) base | count << 14
         if (go) {
-            // ---- (1) image, bucket, slot: trunc(min(fl(fl(x - lo) * scale), TOP)), negative -> 0, is non-decreasing in x ----
+            // ---- (1) image, bucket, slot ----
 
             // batches of 8 atomics in flight; their return values (the slots) are packed 4 to a register per batch
 #pragma unroll
