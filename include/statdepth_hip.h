@@ -463,6 +463,48 @@ int sd_projection_external_outlyingness(const double *P, int64_t n, int d, const
 int sd_projection_subset_outlyingness(const double *P, int64_t n, int d, const double *U, int64_t k, const int32_t *members,
                                       int64_t nb, int bs, double *out, void *stream);
 
+/* ---- K13: exact simplicial depth of a point cloud in the plane (angular sweep) ---------------
+ * The reference's point-cloud simplex depth (_pointcloud.py:14-66) for d = 2, decided with exact signs instead of K4's
+ * tolerance.  P is n x 2 row-major fp64 (device).  For a target x, over its OTHERS p_i (the sample without the target's
+ * own row: all n rows for an external point, a block's members before the last for a block), m of them:
+ *   v_i   = (fl(p_i0 - x0), fl(p_i1 - x1))   one rounded fp64 subtraction per component, as in K11;
+ *           others with v_i = (0, 0) are duplicates of x: every triple that holds one of them contains x;
+ *   cross(a, b) = a0 b1 - a1 b0,  dot(a, b) = a0 b0 + a1 b1,  of which only the EXACT signs are used (K11's predicate);
+ *   for every nonzero v_j, counting over the nonzero v_k:
+ *     e_j = #{k : cross(v_j, v_k) > 0} + #{k later than j in sample order : cross(v_j, v_k) = 0 and dot(v_j, v_k) > 0};
+ *   out[x] = C(m, 3) - sum over j of C(e_j, 2).
+ * out[x] is the number of triples of others whose closed convex hull (a segment or a point for a degenerate triple)
+ * contains x.  A triple misses x exactly when its three vectors are nonzero and fit in an open half-plane; the sum counts
+ * such triples once each, at their clockwise-most member, members of one direction ordered by position in the sample.  The
+ * sum does not depend on that tie order: over a direction class of size s with common L = #{cross > 0} it is
+ * sum_{r < s} C(L + r, 2), so the sweep may order a class as it likes.
+ * depth = out / C(N, 3) on the host, N the sample size INCLUDING the point (K4's normalisers): n for a row target, n + 1
+ * for an external point, the block size for a block.
+ * Predicate limits as K11: finite data with |coordinate| <= 2^500 (the host layer raises otherwise); nonzero coordinate
+ * differences of at least 2^-500 in magnitude -- NOT checked.
+ * algo: 0 = auto, 1 = sweep, 2 = pairwise; the same integers from both.
+ *   sweep     one workgroup per target: K11's compaction, sort and flag prefix over the nonzero vectors of the others;
+ *             groups are runs of sorted neighbours with cross = 0; the element at position i of group [g0, g1] with flip
+ *             flag f has L = #{positions > g1 with flag f} + #{positions < g0 with flag != f} and rank r among the
+ *             same-flag elements of its group; sum of C(L + r, 2) in 64 bits.  Capacity tiers of 64 / 512 / 2048 / 8192
+ *             others (64 / 256 / 512 / 1024 threads); at most 8192 others.  O(m log^2 m) per target, whatever the ties.
+ *   pairwise  the definition as it stands, O(m^2) predicate pairs per target.
+ *   auto      the sweep up to 8192 others, the pairwise kernel above.
+ *   sd_simplicial2_counts:          targets: m int64 row indices (device), NULL = all (m == n); n - 1 others each.
+ *   sd_simplicial2_external_counts: m external points Q (m x 2, device); n others each.
+ *   sd_simplicial2_subset_counts:   blocks of rows, members int32[nb*bs], -1 padded at the end, the block's target LAST;
+ *       at most bs - 1 others.  An empty block, and any target with fewer than 3 others, gives 0.
+ * SD_ERR_INVALID for NULL pointers, n < 1, bs < 1 or an unknown algo; SD_ERR_UNSUPPORTED for 2^31 or more points, for
+ * algo = 1 with more than 8192 others, where C(others, 3) does not fit int64 (more than 3 810 779 others), or beyond 10^14
+ * predicate evaluations on the route that would run (K11's formulas over the others).  All before any device work.
+ * Every launch is bounded in work. */
+int sd_simplicial2_counts(const double *P, int64_t n, const int64_t *targets, int64_t m, int algo, int64_t *out,
+                          void *stream);
+int sd_simplicial2_external_counts(const double *P, int64_t n, const double *Q, int64_t m, int algo, int64_t *out,
+                                   void *stream);
+int sd_simplicial2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
+                                 int64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

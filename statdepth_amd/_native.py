@@ -82,6 +82,9 @@ SIGNATURES = {
     "sd_halfspace2_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
     "sd_halfspace2_external_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
     "sd_halfspace2_subset_counts": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
+    "sd_simplicial2_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_simplicial2_external_counts": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_simplicial2_subset_counts": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
     "sd_projection_workspace_bytes": (_sz, [_i64, _int, _i64]),
     "sd_projection_min_workspace_bytes": (_sz, [_i64, _int, _i64]),
     "sd_projection_outlyingness": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

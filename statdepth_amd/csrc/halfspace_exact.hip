@@ -8,23 +8,15 @@
 // The four candidates are the open sides of the line through q along v_j turned a hair to either side; the closed-halfplane
 // count is upper semicontinuous in the direction, so its minimum over all closed halfplanes through q is reached there.
 //
-// Predicate.  sign(a b - c d): p1 = fl(a b), p2 = fl(c d); rounding is monotone, so p1 != p2 decides.  Otherwise the
-// products' rounding errors e1 = fma(a, b, -p1), e2 = fma(c, d, -p2) are exact fp64 numbers and a b - c d = e1 - e2, so the
-// comparison of e1 with e2 decides.  Exact while no product overflows or underflows: |coordinates| <= 2^500 (the host
-// checks) and nonzero coordinate differences >= 2^-500 in magnitude (not checked: they are not known before they are formed).
+// The exact predicate, the compaction of the vectors into LDS, the angular sort of their half-plane images and the flag
+// prefix are plane_sweep.h, shared with K13 (simplicial_exact.hip).
 //
 // Two kernels over one selector (PointSel, point_select.h: a row of P against all rows; an external Q[q] against all rows
 // with one added to c0; a block's last member against the block's members), the same integers from both:
 //
 // hx_sweep_kernel<CAP, NT>   one workgroup per target or block, samples of up to CAP = 64 / 512 / 2048 / 8192 points with
-//   NT = 64 / 256 / 512 / 1024 threads.  The sample is streamed once: v formed, the nonzero vectors compacted into LDS (wave
-//   ballot + one LDS atomic per wave) as they are, 16 bytes each in two fp64 arrays (consecutive lanes on consecutive
-//   8-byte slots: no bank conflict in ds_read_b64 / ds_write_b64).  A vector is read through its image in the half-plane
-//   y > 0 or (y = 0, x > 0): negated when the flag f(v) = (y < 0 or (y = 0 and x < 0)) is set -- negation is exact and f is
-//   recomputed wherever it is needed, never stored.  The images are sorted by angle with a bitonic network whose comparator
-//   is the exact cross sign (a total preorder on a half-plane; padding slots hold (0, 0), which no real element is, and sort
-//   last).  rank_sort.h's network was not reused: its comparator is v_min_f64 / v_max_f64 on fp64 keys in registers, and
-//   here the order has no fp64 key.  Cuts lie after the last element and wherever two neighbours have cross != 0; for a cut
+//   NT = 64 / 256 / 512 / 1024 threads.  The nonzero vectors are compacted into LDS and their half-plane images sorted by
+//   angle (plane_sweep.h).  Cuts lie after the last element and wherever two neighbours have cross != 0; for a cut
 //   after position s, A = #{i <= s, f = 0} + #{i > s, f = 1} and B = (number of nonzero vectors) - A.  The flags are prefix-
 //   summed by ballot per run of 64 positions plus one wave scan over the runs; out = c0 + min over cuts of min(A, B).
 //   LDS at CAP = 8192: 128 KiB of vectors + 528 bytes, one workgroup per CU.
@@ -39,6 +31,7 @@
 // pairs or one workgroup (256 x n pairs; the 10^14 cap of the entry points keeps n below 10^7 on that route).
 #include "sd_common.h"
 #include "point_select.h"
+#include "plane_sweep.h"
 
 namespace sd {
 
@@ -46,27 +39,6 @@ constexpr int HX_PT = 256;                                         // pairwise: 
 constexpr double HX_SWEEP_LAUNCH = 17179869184.0;                  // 2^34 comparator evaluations per sweep launch
 constexpr double HX_PAIR_LAUNCH = 68719476736.0;                   // 2^36 predicate pairs per pairwise launch
 constexpr int HX_NONE = 0x7fffffff;
-
-// exact sign of a b - c d (see the header of this file)
-__device__ __forceinline__ int hx_sign_diff(double a, double b, double c, double d) {
-    const double p1 = __dmul_rn(a, b), p2 = __dmul_rn(c, d);
-    if (p1 != p2) return p1 > p2 ? 1 : -1;
-    const double e1 = __fma_rn(a, b, -p1), e2 = __fma_rn(c, d, -p2);
-    return e1 > e2 ? 1 : (e1 < e2 ? -1 : 0);
-}
-__device__ __forceinline__ int hx_cross(double ax, double ay, double bx, double by) { return hx_sign_diff(ax, by, ay, bx); }
-__device__ __forceinline__ int hx_dot(double ax, double ay, double bx, double by) { return hx_sign_diff(ax, bx, -ay, by); }
-
-// the vector lies outside the half-plane y > 0 or (y = 0, x > 0): its image there is -v
-__device__ __forceinline__ bool hx_flip(double x, double y) { return y < 0.0 || (y == 0.0 && x < 0.0); }
-
-// a's image sorts strictly behind b's: by angle in [0, pi), padding (0, 0) behind every real element
-__device__ __forceinline__ bool hx_after(double ax, double ay, double bx, double by) {
-    const bool apad = ax == 0.0 && ay == 0.0, bpad = bx == 0.0 && by == 0.0;
-    if (apad || bpad) return apad && !bpad;
-    const int s = hx_cross(ax, ay, bx, by);
-    return hx_flip(ax, ay) != hx_flip(bx, by) ? s > 0 : s < 0;
-}
 
 __device__ __forceinline__ int hx_wave_min(int v) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -80,7 +52,6 @@ __device__ __forceinline__ int hx_wave_min(int v) {
 template <int CAP, int NT>
 __global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__ P, i64 n, PointSel sel, i64 q0,
                                                       i64 *__restrict__ out) {
-    static_assert(CAP % 64 == 0 && NT % 64 == 0 && CAP / 64 <= 128, "one wave scans the runs of 64, two per lane at most");
     __shared__ double sx[CAP];
     __shared__ double sy[CAP];
     __shared__ int s_run[CAP / 64];                                 // flags set per run of 64 positions, then their prefix
@@ -88,96 +59,17 @@ __global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__
     const int t = threadIdx.x, lane = t & 63;
     const i64 q = q0 + blockIdx.x;
     const PointView w = point_view_coop<NT>(sel, P, n, 2, q, &s_cnt);
-    const double qx = w.x[0], qy = w.x[1];
     const int wcnt = (int)w.cnt;                                    // <= CAP: the launcher chose the tier
-    if (t == 0) {
-        s_nz = 0;
-        s_min = HX_NONE;
-    }
-    __syncthreads();
-    for (int i0 = 0; i0 < wcnt; i0 += NT) {                         // compaction of the nonzero vectors, in any order
-        const int i = i0 + t;
-        double vx = 0.0, vy = 0.0;
-        if (i < wcnt) {
-            const i64 src = w.mem ? (i64)w.mem[i] : (i64)i;
-            vx = __dsub_rn(P[src * 2], qx);
-            vy = __dsub_rn(P[src * 2 + 1], qy);
-        }
-        const bool nz = vx != 0.0 || vy != 0.0;
-        const u64 mask = __ballot(nz);
-        int base = 0;
-        if (lane == 0 && mask) base = atomicAdd(&s_nz, __popcll(mask));
-        base = __shfl(base, 0);
-        if (nz) {
-            const int pos = base + __popcll(mask & (((u64)1 << lane) - 1));
-            sx[pos] = vx;
-            sy[pos] = vy;
-        }
-    }
-    __syncthreads();
-    const int cnt = s_nz;
+    if (t == 0) s_min = HX_NONE;
+    const int cnt = hx_compact<NT, false>(P, w, sx, sy, &s_nz);     // the nonzero vectors, in any order
     const int c0 = wcnt - cnt + w.self();
     if (cnt == 0) {                                                 // (block-uniform) also the empty block: 0
         if (t == 0) out[q] = (i64)c0;
         return;
     }
-    int N2 = 2;
-    while (N2 < cnt) N2 <<= 1;
-    for (int p = cnt + t; p < N2; p += NT) {
-        sx[p] = 0.0;
-        sy[p] = 0.0;
-    }
-    __syncthreads();
-    for (int k = 2; k <= N2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int x = t; x < (N2 >> 1); x += NT) {
-                const int i = ((x & ~(j - 1)) << 1) | (x & (j - 1));
-                const int l = i | j;
-                const bool up = (i & k) == 0;
-                const double ax = sx[i], ay = sy[i], bx = sx[l], by = sy[l];
-                const bool sw = up ? hx_after(ax, ay, bx, by) : hx_after(bx, by, ax, ay);
-                if (sw) {
-                    sx[i] = bx; sy[i] = by;
-                    sx[l] = ax; sy[l] = ay;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    hx_sort<NT>(sx, sy, cnt);
     // F1(s) = #{i <= s : f}: per run of 64 positions by ballot, the runs by one wave
-    for (int i0 = 0; i0 < cnt; i0 += NT) {
-        const int i = i0 + t;
-        const bool f = i < cnt && hx_flip(sx[i], sy[i]);
-        const u64 mask = __ballot(f);
-        if (lane == 0 && i < cnt) s_run[i >> 6] = __popcll(mask);
-    }
-    __syncthreads();
-    if (t < 64) {
-        constexpr int EPL = (CAP / 64 + 63) / 64;                   // runs per lane
-        const int nrun = (cnt + 63) >> 6;
-        int v[EPL], sum = 0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int r = t * EPL + e;
-            v[e] = r < nrun ? s_run[r] : 0;
-            sum += v[e];
-        }
-        int inc = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(inc, o);
-            if (t >= o) inc += y;
-        }
-        int exc = inc - sum;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const int r = t * EPL + e;
-            if (r < nrun) s_run[r] = exc;
-            exc += v[e];
-        }
-        if (t == 63) s_t1 = inc;
-    }
-    __syncthreads();
-    const int T1 = s_t1;
+    const int T1 = hx_flag_prefix<CAP, NT>(sx, sy, cnt, s_run, &s_t1, nullptr);
     int best = HX_NONE;
     for (int i0 = 0; i0 < cnt; i0 += NT) {
         const int i = i0 + t;
@@ -201,14 +93,6 @@ __global__ __launch_bounds__(NT) void hx_sweep_kernel(const double *__restrict__
     __syncthreads();
     if (t == 0) out[q] = (i64)c0 + (i64)s_min;
 }
-
-static inline double hx_sweep_wg_work(int cap) {                    // comparator evaluations of one workgroup at a tier
-    int L = 0;
-    while ((1 << L) < cap) ++L;
-    return (double)(cap / 2) * (double)(L * (L + 1) / 2);
-}
-
-static inline int hx_tier(i64 cnt_max) { return cnt_max <= 64 ? 64 : cnt_max <= 512 ? 512 : cnt_max <= 2048 ? 2048 : 8192; }
 
 template <int CAP, int NT>
 static int hx_launch_sweep(const double *P, i64 n, const PointSel &sel, i64 m, i64 *out, hipStream_t s) {

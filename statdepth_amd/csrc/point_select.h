@@ -1,4 +1,4 @@
-// point_select.h -- which rows of a point cloud a target is set against (internal; K4, K5, K7, K10 pairwise, K11, K12).
+// point_select.h -- which rows of a point cloud a target is set against (internal; K4, K5, K7, K10 pairwise, K11, K12, K13).
 //
 // Every point-cloud depth is asked for in three forms, one launch each:
 //   rows     -- row targets[q] of P (NULL: row q) inside P: the sample is all n rows, the target among them;
@@ -7,7 +7,7 @@
 //   blocks   -- the LAST member of block q (members int32[m][bs], padded with -1 AT THE END) inside that block: the
 //               sample is the block's rows, others first (the K-block sampled estimator, _pointcloud.py:107-121).
 //               A block's members are the entries before its first -1; a block without members has no target.
-// K4, K5 and K7 work on the target's OTHERS (the sample without the target's row); K10 and K11 count the whole sample,
+// K4, K5, K7 and K13 work on the target's OTHERS (the sample without the target's row); K10 and K11 count the whole sample,
 // and an external target counts itself on top (self); K12 takes the median and the MAD of the whole sample, an external
 // target's projection inserted.
 #pragma once

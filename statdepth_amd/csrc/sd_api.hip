@@ -881,4 +881,47 @@ int sd_projection_subset_outlyingness(const double *P, int64_t n, int d, const d
     return launch_projection_blocks(P, n, d, U, k, select_blocks(members, bs), nb, out, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// K13
+// ---------------------------------------------------------------------------
+static int simplicial2_counts(const double *P, i64 n, const PointSel &sel, i64 m, int algo, int64_t *out, void *stream) {
+    const i64 others_max = sel_others_max(sel, n);                // the most vectors a target has
+    if (!P || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (n < 1 || m < 0) return fail(SD_ERR_INVALID, "bad shape (n=%lld, m=%lld)", (long long)n, (long long)m);
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (sweep), 2 (pairwise)", algo);
+    if (n >= ((i64)1 << 31) || others_max + 1 >= ((i64)1 << 31))    // counts and indices are 32-bit in the kernels
+        return fail(SD_ERR_UNSUPPORTED, "exact simplicial counts take fewer than 2^31 points, got %lld", (long long)n);
+    const int route = simplicial2_route(algo, others_max);          // the route that runs (1 sweep, 2 pairwise)
+    if (route == 0)
+        return fail(SD_ERR_UNSUPPORTED, "the sweep holds up to %lld other points, got %lld (algo 0 or 2 takes them)",
+                    (long long)SX_SWEEP_CAPACITY, (long long)others_max);
+    if (others_max > simplicial2_max_others())
+        return fail(SD_ERR_UNSUPPORTED, "C(%lld, 3) triples overflow int64: at most %lld other points", (long long)others_max,
+                    (long long)simplicial2_max_others());
+    const double work = simplicial2_work(route, m, others_max);
+    if (work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g predicate evaluations exceed the cap of %.0e", work, HS_MAX_WORK);
+    int rc = check_all_rows(sel, n, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    return launch_simplicial2(P, n, sel, m, route, out, (hipStream_t)stream);
+}
+
+int sd_simplicial2_counts(const double *P, int64_t n, const int64_t *targets, int64_t m, int algo, int64_t *out,
+                          void *stream) {
+    return simplicial2_counts(P, n, select_rows(targets), m, algo, out, stream);
+}
+
+int sd_simplicial2_external_counts(const double *P, int64_t n, const double *Q, int64_t m, int algo, int64_t *out,
+                                   void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    return simplicial2_counts(P, n, select_external(Q), m, algo, out, stream);
+}
+
+int sd_simplicial2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
+                                 int64_t *out, void *stream) {
+    int rc = check_blocks(members, bs);
+    return rc ? rc : simplicial2_counts(P, n, select_blocks(members, bs), nb, algo, out, stream);
+}
+
 }  // extern "C"

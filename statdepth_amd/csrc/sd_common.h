@@ -152,6 +152,13 @@ int halfspace2_route(int algo, i64 cnt_max);                       // 0: algo = 
 double halfspace2_work(int route, i64 m, i64 cnt_max);             // predicate evaluations
 int launch_halfspace2(const double *P, i64 n, const PointSel &sel, i64 m, int route, i64 *out, hipStream_t s);
 
+// K13 exact simplicial depth in the plane (simplicial_exact.hip): route 1 = angular sweep in LDS, 2 = pairwise e_j
+constexpr i64 SX_SWEEP_CAPACITY = 8192;                             // others one sweep workgroup holds
+int simplicial2_route(int algo, i64 others_max);                   // 0: algo = 1 (sweep) above the capacity
+double simplicial2_work(int route, i64 m, i64 others_max);         // predicate evaluations
+i64 simplicial2_max_others();                                      // the most others whose C(others, 3) fits int64
+int launch_simplicial2(const double *P, i64 n, const PointSel &sel, i64 m, int route, i64 *out, hipStream_t s);
+
 // K12 projection depth (projection.hip): out = max over directions of |z - med| / mad.  launch_projection_sorted serves
 // the rows and the external form (sel), launch_projection_blocks the blocks form (sel.bs <= PD_MAX_BLOCK: the caller checks)
 constexpr int PD_MAX_BLOCK = 2048;                                  // members of a block: what pd_blocks_kernel sorts in LDS

@@ -11,6 +11,8 @@ reference does not have; DESIGN.md §3 K10 states its definition.  directions='e
 (d = 2: sd_halfspace2_*; d = 1: the direction (1.0), which is exact already).
 Projection depth (containment='projection', sd_projection_*: 1 / (1 + the Stahel-Donoho outlyingness) over the same kind
 of direction set) is another extension; DESIGN.md §3 K12 states its definition bit for bit.
+containment='simplex_exact' is the reference's simplex depth of a planar cloud counted by an angular sweep with exact signs
+(sd_simplicial2_*): O(n log^2 n) per point where 'simplex' enumerates C(n - 1, 3) triangles.
 """
 from typing import Union
 
@@ -100,6 +102,18 @@ def _halfspace_setup(P: np.ndarray, directions, seed):
     return None
 
 
+def _simplex_exact_check(P: np.ndarray) -> None:
+    """Host checks of containment='simplex_exact': the plane, finite, |coordinate| <= 2^500."""
+    d = P.shape[1]
+    if d != 2:
+        raise NotImplementedError("exact simplicial depth (containment='simplex_exact') is implemented for the plane "
+                                  f"(d = 2), got d = {d}: use containment='simplex'")
+    if not np.isfinite(P).all():
+        raise ValueError('exact simplicial depth does not accept NaN or infinite values')
+    if P.size and np.abs(P).max() > 2.0 ** 500:          # the exact predicate's products must not overflow
+        raise ValueError('exact simplicial depth needs coordinates of magnitude at most 2^500')
+
+
 _PROJECTION_MAX_BLOCK = 2048                             # members of a K-block: sd_projection_subset_outlyingness sorts it in LDS
 
 
@@ -139,6 +153,12 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         counts = engine.pointcloud_simplex_counts(P, _row_positions(data, to_compute), device=device)
         depths = counts.astype(np.float64) / binom(n, d + 1)     # n INCLUDES the point (:38,56)
         return pd.Series(index=to_compute, data=depths)
+    elif containment == 'simplex_exact':
+        # the same depth for d = 2 with exact signs in place of the tolerance, by angular sweep
+        P = data.to_numpy(dtype=np.float64)
+        _simplex_exact_check(P)
+        counts = engine.simplicial_exact_counts(P, _row_positions(data, to_compute), device=device)
+        return pd.Series(index=to_compute, data=counts.astype(np.float64) / binom(n, 3))
     elif containment == 'l1':
         P = data.to_numpy(dtype=np.float64)
         depths = engine.l1_depth(P, _row_positions(data, to_compute), device=device)
@@ -205,6 +225,9 @@ def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directio
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
         counts = engine.pointcloud_simplex_subset_counts(P, mem, device=device).astype(np.float64)
         return counts / binom(sizes, d + 1)              # (:38,56) on the sample: its size INCLUDES the point
+    if containment == 'simplex_exact':
+        sizes = np.array([len(b) for b in blocks], dtype=np.float64)
+        return engine.simplicial_exact_subset_counts(P, mem, device=device).astype(np.float64) / binom(sizes, 3)
     return engine.l1_subset_depth(P, mem, device=device)  # (:148-150) on the sample
 
 
@@ -219,7 +242,7 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
     (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
     sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts / sd_halfspace2_subset_counts /
-    sd_projection_subset_outlyingness) instead of as many `_pointwisedepth` calls.
+    sd_projection_subset_outlyingness / sd_simplicial2_subset_counts) instead of as many `_pointwisedepth` calls.
     Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
     normaliser (the reference's is identically 0).  Halfspace: one direction set (directions, seed) for
     every block, or none (directions='exact'); neither takes anything from the global RNG.  Projection: one direction
@@ -231,10 +254,12 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
                                directions=directions, seed=seed)
     if containment == 'mahalanobis':
         raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    if containment not in ('simplex', 'l1', 'oja', 'halfspace', 'projection'):
+    if containment not in ('simplex', 'simplex_exact', 'l1', 'oja', 'halfspace', 'projection'):
         raise ValueError(f'{containment} is not a valid containment measure. ')
     n, d = data.shape
     U = None
+    if containment == 'simplex_exact':
+        _simplex_exact_check(data.to_numpy(dtype=np.float64))
     if containment == 'halfspace':                       # host checks first: bad input never reaches the RNG or the GPU
         U = _halfspace_setup(data.to_numpy(dtype=np.float64), directions, seed)
     if containment == 'projection':

@@ -149,7 +149,10 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
     as given.  For 'halfspace' both give the directional depth, an upper bound of the halfspace depth once d >= 2, and
     'exact' gives the halfspace depth itself for d <= 2 (`seed` is ignored; d >= 3 raises NotImplementedError).  For
     'projection' they are the directions of the Stahel-Donoho outlyingness O = max |x.u - med| / MAD, depth =
-    1 / (1 + O); there 'exact' raises NotImplementedError."""
+    1 / (1 + O); there 'exact' raises NotImplementedError.
+    containment='simplex_exact' is 'simplex' for planar data (d = 2; any other d raises NotImplementedError) counted by an
+    angular sweep with exact orientation signs, O(n log^2 n) per point: the closed triangles of the other points that
+    contain the point, over C(n, 3).  'simplex' itself keeps its enumeration and its tolerance."""
     if K is not None:
         depth = _samplepointwisedepth(data=data, to_compute=to_compute, K=K, containment=containment,
                                       device=device, directions=directions, seed=seed)

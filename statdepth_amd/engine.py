@@ -363,7 +363,7 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
                    workspace=lambda: _strict_workspace(lib, dev, M, m, J, workspace_budget))
 
 
-# Point clouds.  Every depth of K4, K5, K7, K10, K11 and K12 is asked for in three forms ("Point clouds: the three
+# Point clouds.  Every depth of K4, K5, K7, K10, K11, K12 and K13 is asked for in three forms ("Point clouds: the three
 # forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
 # block.  The public functions below name the C entry point and the form; _points does the rest.
 _ROWS, _EXTERNAL, _BLOCKS = "rows", "external", "blocks"
@@ -373,7 +373,7 @@ def _points(name, dtype, P, device, form, arg, *extra, U=None, plane=False, work
     """lib.<name>(P, n, [d, [U, k,]] selection, *extra, out, [ws, ws_bytes,] stream); out: one value of dtype per target.
     selection: (targets, m) for the rows targets=arg of P (None: all), (Q, m) for the external points Q=arg, or
     (members, nb, bs) for the blocks members=arg (-1 padded at the end, others first, target last).  U: the k x d
-    directions of K10 and K12.  plane: K11 -- P and Q are checked to be planar and exact, d is not passed, and an index outside the
+    directions of K10 and K12.  plane: K11 and K13 -- P and Q are checked to be planar and exact, d is not passed, and an index outside the
     sample is a ValueError like K11's other argument checks.  workspace(dev, n, d): (buffer, bytes).
     `keep` holds the selection's device tensor until the launch has been issued."""
     assert form in (_ROWS, _EXTERNAL, _BLOCKS)
@@ -621,9 +621,9 @@ def _plane_points(A, dev, what="P"):
     t = torch()
     Ad = _upload(A, 2, dev)
     if Ad.shape[1] != 2:
-        raise ValueError(f"exact halfspace counts are defined for points in the plane: {what} must be n x 2")
+        raise ValueError(f"exact halfspace and simplicial counts are defined for points in the plane: {what} must be n x 2")
     if Ad.numel() and not bool((Ad.abs() <= _HALFSPACE2_MAX_ABS).all()):      # NaN fails the comparison too
-        raise ValueError("exact halfspace counts need finite coordinates of magnitude at most 2^500")
+        raise ValueError("the exact predicate needs finite coordinates of magnitude at most 2^500")
     return Ad
 
 
@@ -644,6 +644,25 @@ def halfspace_exact_subset_counts(P, members, device=None, algo="auto"):
     """int64[nb]: per block (rows of `members`, -1 padded, target last) the exact halfspace counts of the block's target
     inside the block (sd_halfspace2_subset_counts); depth = counts / block size."""
     return _points("sd_halfspace2_subset_counts", torch().int64, P, device, _BLOCKS, members, _halfspace2_algo(algo), plane=True)
+
+
+def simplicial_exact_counts(P, targets=None, device=None, algo="auto"):
+    """int64[m]: the exact simplicial counts of x = P[targets[q]] inside the planar sample P (n x 2): the triples of the
+    other n - 1 rows whose closed triangle contains x, decided with exact signs (sd_simplicial2_counts); depth = counts /
+    C(n, 3).  algo: 'auto', 'sweep' (at most 8192 others) or 'pairwise'; the same integers."""
+    return _points("sd_simplicial2_counts", torch().int64, P, device, _ROWS, targets, _halfspace2_algo(algo), plane=True)
+
+
+def simplicial_exact_external_counts(P, Q, device=None, algo="auto"):
+    """int64[m]: the triples of ALL n rows of P whose closed triangle contains the external point Q[q]
+    (sd_simplicial2_external_counts); depth = counts / C(n + 1, 3)."""
+    return _points("sd_simplicial2_external_counts", torch().int64, P, device, _EXTERNAL, Q, _halfspace2_algo(algo), plane=True)
+
+
+def simplicial_exact_subset_counts(P, members, device=None, algo="auto"):
+    """int64[nb]: per block (rows of `members`, -1 padded, others first, target last) the triples of the block's others whose
+    closed triangle contains its target (sd_simplicial2_subset_counts); depth = counts / C(block size, 3)."""
+    return _points("sd_simplicial2_subset_counts", torch().int64, P, device, _BLOCKS, members, _halfspace2_algo(algo), plane=True)
 
 
 _PROJECTION_MAX_ABS = 2.0 ** 500

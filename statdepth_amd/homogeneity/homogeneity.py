@@ -175,6 +175,11 @@ def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -
     n, d = Fx.shape
     if containment == 'simplex':
         return engine.pointcloud_simplex_external_counts(Fx, Qx).astype(np.float64) / binom(n + 1, d + 1)
+    if containment == 'simplex_exact':             # the same normaliser, the counts by the exact sweep (d = 2)
+        from ..depth.calculations._pointcloud import _simplex_exact_check
+        _simplex_exact_check(Fx)
+        _simplex_exact_check(Qx)
+        return engine.simplicial_exact_external_counts(Fx, Qx).astype(np.float64) / binom(n + 1, 3)
     if containment == 'l1':
         return engine.l1_external_depth(Fx, Qx)
     if containment == 'oja':                       # subsets of F, normaliser the hull of the intact F u {g}
