@@ -505,6 +505,44 @@ int sd_simplicial2_external_counts(const double *P, int64_t n, const double *Q, 
 int sd_simplicial2_subset_counts(const double *P, int64_t n, const int32_t *members, int64_t nb, int bs, int algo,
                                  int64_t *out, void *stream);
 
+/* ---- K14: integrated rank depths of curves (Fraiman-Muniz, MEI / MHI, half-region, univariate halfspace) ----
+ * No reference code (the reference has only band depths for curves).  X is T x n fp64 in either layout, finite or
+ * +-inf.  NaN is NOT supported: the counts of a row that holds one are unspecified (the host layer refuses NaN).
+ * For a target q at timepoint t, over the other n - 1 curves:
+ *   A = #{y : y(t) > x_q(t)},  B = #{y : y(t) < x_q(t)}   (ties in neither; so #{y <= x} = n - A and #{y >= x} = n - B
+ *   with the target counting itself in both);
+ * out[q] is the record of five non-negative int64
+ *   SA = sum_t A,   SB = sum_t B,   SF = sum_t |2 A - n|,   SM = sum_t max(A, B),   MM = max_t max(A, B),
+ * and the depths are formed on the host in fp64, one expression each, the division last:
+ *   Fraiman-Muniz         1 - SF / (2 n T)       mean over t of 1 - |1/2 - F_t(x(t))|, F_t the empirical CDF with "<=":
+ *                                                F = (n - A) / n.  Not symmetric under x -> -x: the published definition;
+ *   modified epigraph     (n T - SB) / (n T)     mean proportion of curves at or above x;
+ *   modified hypograph    (n T - SA) / (n T)     mean proportion of curves at or below x;
+ *   modified half-region  min of the two         (Lopez-Pintado & Romo 2011);
+ *   integrated halfspace  (n T - SM) / (n T)     mean over t of the univariate Tukey depth min(#<=, #>=) / n;
+ *   infimal halfspace     (n - MM) / n           its infimum over t.
+ * Both routes form the same pairs (A, B) of every (row, curve) and one kernel folds them into the records:
+ *   image (algo 1)  n <= 16 384: the rank kernel of K1+K2 in its pair-image mode, a batch of rows at a time (at most
+ *                   2^16 rows and 1 GiB), u32 words B | A << 16, one streaming pass over 4 bytes per (row, curve);
+ *   sort  (algo 2)  any n < 2^31: K10's sort with the curve's index as payload, a chunk of rows at a time; the rank of
+ *                   every sorted position (runs of ties by binary search) stored as u64 B | A << 32 at the curve's
+ *                   place, then the same fold.  O(T n log n).
+ *   auto  (algo 0)  the image route up to 16 384 curves, the sort route above.
+ * The batch and the chunk follow from ws_bytes: sd_rank_depth_workspace_bytes recommends a size,
+ * sd_rank_depth_min_workspace_bytes is the floor (one row per batch: about 4 n bytes on the image route, 24 n on the
+ * sort route, plus 8 T n for the time-major copy of a curve-major X).  sd_rank_depth_rows_per_batch says how many rows a
+ * batch (a chunk) of a call with ws_bytes takes, 0 below the floor or for a shape or algo the call refuses: at the
+ * recommended size all T rows in one batch whenever T is within the route's caps (image: 2^16 rows and a 1 GiB image;
+ * sort: 2^23 values).  The integers do not depend on the workspace size.
+ * targets: m int64 curve indices (device), NULL = all (m == n).  out: m x 5 int64 (device).
+ * SD_ERR_INVALID for NULL X or out, T < 1, n < 2 or an unknown algo; SD_ERR_UNSUPPORTED for algo = 1 with n > 16 384 or
+ * for 2^31 or more curves or timepoints; SD_ERR_WORKSPACE below the floor.  All before any device work. */
+size_t sd_rank_depth_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+size_t sd_rank_depth_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+int64_t sd_rank_depth_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes);
+int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
+                       int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,10 @@ SIGNATURES = {
     "sd_projection_outlyingness": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "sd_projection_external_outlyingness": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "sd_projection_subset_outlyingness": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sd_rank_depth_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_rank_depth_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_rank_depth_rows_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _int, _sz]),
+    "sd_rank_depth_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -37,7 +37,7 @@
 // most max(n, 2^25) values, a pairwise launch at most HS_UNITS workgroups of HS_SLICE x 256 projections each.
 //
 // The projection and the sorted rows (hs_proj, launch_hs_sort_chunk) are shared with K12 (projection.hip) through
-// halfspace_sort.h.
+// halfspace_sort.h; the sort without the projection (launch_hs_sort_rows) serves K14's rows of curves (rank_depths.hip).
 #include "sd_common.h"
 #include "point_select.h"
 #include "halfspace_sort.h"
@@ -251,16 +251,9 @@ size_t halfspace_workspace_bytes(i64 n, i64 k) {
     return hs_ws_fixed(n) + (size_t)kc * hs_ws_per_direction(n);
 }
 
-// one chunk: projection, tile sort, merge passes; the sorted rows are in b.K[*src] / b.I[*src]
-template <int D>
-static int hs_sort_chunk_d(const double *P, i64 n, const double *U, int kk, const HsSortBuffers &b, int *src_out,
-                           hipStream_t s) {
+// kk rows of n values already in b.K[0]: tile sort, merge passes; the sorted rows are in b.K[*src] / b.I[*src]
+int launch_hs_sort_rows(i64 n, int kk, const HsSortBuffers &b, int *src_out, hipStream_t s) {
     const int ntiles = hs_ntiles(n);
-    const unsigned gx = (unsigned)((n + HS_THREADS - 1) / HS_THREADS);
-    unsigned gy = gx >= 2048 ? 1 : (2048 + gx - 1) / gx;
-    gy = gy > (unsigned)kk ? (unsigned)kk : gy;
-    hipLaunchKernelGGL((hs_project_kernel<D>), dim3(gx, gy), dim3(HS_THREADS), 0, s, P, n, U, kk, b.K[0]);
-    SD_HIP(hipGetLastError());
     const i64 tiles = (i64)kk * ntiles;
     hipLaunchKernelGGL(hs_tile_sort_kernel, dim3((unsigned)tiles), dim3(HS_THREADS), 0, s, b.K[0], b.I[0], n, ntiles);
     SD_HIP(hipGetLastError());
@@ -276,6 +269,18 @@ static int hs_sort_chunk_d(const double *P, i64 n, const double *U, int kk, cons
     }
     *src_out = src;
     return SD_OK;
+}
+
+// one chunk: projection into b.K[0], then launch_hs_sort_rows
+template <int D>
+static int hs_sort_chunk_d(const double *P, i64 n, const double *U, int kk, const HsSortBuffers &b, int *src_out,
+                           hipStream_t s) {
+    const unsigned gx = (unsigned)((n + HS_THREADS - 1) / HS_THREADS);
+    unsigned gy = gx >= 2048 ? 1 : (2048 + gx - 1) / gx;
+    gy = gy > (unsigned)kk ? (unsigned)kk : gy;
+    hipLaunchKernelGGL((hs_project_kernel<D>), dim3(gx, gy), dim3(HS_THREADS), 0, s, P, n, U, kk, b.K[0]);
+    SD_HIP(hipGetLastError());
+    return launch_hs_sort_rows(n, kk, b, src_out, s);
 }
 
 int launch_hs_sort_chunk(const double *P, i64 n, int d, const double *U, int kk, const HsSortBuffers &b, int *src,

@@ -2,7 +2,8 @@
 //
 // launch_hs_sort_chunk (halfspace.hip) projects the sample on a chunk of directions and sorts every direction's
 // projections: hs_project_kernel, hs_tile_sort_kernel, then hs_partition_kernel / hs_merge_kernel passes between two
-// buffers.  K10 ranks the sorted rows (halfspace.hip), K12 selects medians from them (projection.hip).
+// buffers.  K10 ranks the sorted rows (halfspace.hip), K12 selects medians from them (projection.hip), K14 sorts rows
+// of curves with launch_hs_sort_rows and ranks them into a pair image (rank_depths.hip).
 #pragma once
 #include "sd_common.h"
 
@@ -44,6 +45,8 @@ static inline i64 hs_chunk_directions(size_t bytes, size_t per_direction, i64 n,
 // b.K[*src] (kk x n), the values' sample rows beside them in b.I[*src].  d in [1, 8].
 int launch_hs_sort_chunk(const double *P, i64 n, int d, const double *U, int kk, const HsSortBuffers &b, int *src,
                          hipStream_t s);
+// The same sort of kk rows of n values that the caller has put into b.K[0] (the second half of launch_hs_sort_chunk).
+int launch_hs_sort_rows(i64 n, int kk, const HsSortBuffers &b, int *src, hipStream_t s);
 
 #ifdef __HIPCC__
 template <int D>

@@ -924,4 +924,56 @@ int sd_simplicial2_subset_counts(const double *P, int64_t n, const int32_t *memb
     return rc ? rc : simplicial2_counts(P, n, select_blocks(members, bs), nb, algo, out, stream);
 }
 
+// ---------------------------------------------------------------------------
+// K14
+// ---------------------------------------------------------------------------
+// the route that runs (1 pair image of the bucket kernel, 2 sort), 0 where the shape or algo has none
+static int rank_depth_route(int algo, i64 T, i64 n) {
+    if (T < 1 || n < 2 || n >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
+    if (algo == 1) return n <= RD_IMAGE_MAX_N ? 1 : 0;
+    return algo == 2 || n > RD_IMAGE_MAX_N ? 2 : 1;
+}
+
+size_t sd_rank_depth_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    (void)m;
+    const int route = rank_depth_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + rank_depth_workspace_bytes(T, n, route) : 0;
+}
+
+size_t sd_rank_depth_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    (void)m;
+    const int route = rank_depth_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + rank_depth_min_workspace_bytes(n, route) : 0;
+}
+
+int64_t sd_rank_depth_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes) {
+    (void)m;
+    const int route = rank_depth_route(algo, T, n);
+    const size_t tm = route ? time_major_bytes(T, n, st, sn) : 0;
+    return route && ws_bytes >= tm ? rank_depth_rows_per_batch(T, n, route, ws_bytes - tm) : 0;
+}
+
+int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
+                       int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1 || n < 2) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint and two curves",
+                                    (long long)T, (long long)n);
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (image), 2 (sort)", algo);
+    if (n >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "rank depths take fewer than 2^31 curves, got %lld", (long long)n);
+    if (algo == 1 && n > RD_IMAGE_MAX_N)
+        return fail(SD_ERR_UNSUPPORTED, "the image route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
+                    (long long)RD_IMAGE_MAX_N, (long long)n);
+    int rc = check_matrix(X, T, n, st, sn, targets, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    if (!ws || ws_bytes < sd_rank_depth_min_workspace_bytes(T, n, st, sn, m, algo))
+        return fail(SD_ERR_WORKSPACE, "workspace below sd_rank_depth_min_workspace_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes);
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
+    const size_t rest = cv.rest();
+    return launch_rank_depth_sums(Y, T, n, targets, m, rank_depth_route(algo, T, n), out, cv.take(rest), rest, s);
+}
+
 }  // extern "C"

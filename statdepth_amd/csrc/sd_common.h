@@ -169,6 +169,16 @@ int launch_projection_sorted(const double *P, i64 n, int d, const double *U, i64
 int launch_projection_blocks(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 nb, double *out,
                              hipStream_t s);
 
+// K14 integrated rank depths of curves (rank_depths.hip): out[q] = (SA, SB, SF, SM, MM).  route 1 = pair image of the
+// bucket kernel (n <= RD_IMAGE_MAX_N), 2 = K10's sort and a u64 pair image (any n); the workspace sizes are those of the
+// route alone, behind the time-major copy
+constexpr i64 RD_IMAGE_MAX_N = 16384;
+size_t rank_depth_workspace_bytes(i64 T, i64 n, int route);
+size_t rank_depth_min_workspace_bytes(i64 n, int route);
+i64 rank_depth_rows_per_batch(i64 T, i64 n, int route, size_t bytes);   // rows a batch / chunk takes with `bytes`; 0 below the floor
+int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
+                           size_t ws_bytes, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

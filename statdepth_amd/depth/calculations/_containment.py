@@ -5,22 +5,31 @@ HIP kernels.  A user-supplied callable keeps the reference's plug-in protocol
 `containment(data=<T x j DataFrame>, curve=<Series>, relax=<bool>) -> float`
 (docs/index.md:124-148) and is evaluated by the generic enumerator in _functional.py,
 on the host, because arbitrary Python cannot run on the GPU.
+
+RANK_DEPTHS names the integrated rank depths of univariate curves (_rank.py): not band containments, but selected through
+the same argument.
 """
 from inspect import signature
 
 BUILTIN = ('r2', 'r2_enum', 'simplex')
+RANK_DEPTHS = ('fm', 'mei', 'mhi', 'half_region', 'integrated_halfspace', 'infimal_halfspace')
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'] or a pass a custom containment function.')
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS)}, '
+                         f'or a pass a custom containment function.')
     params = signature(containment).parameters
     if len(params) != 3:   # only the arity is enforced (:37-41)
         raise ValueError('Custom containment method has incorrect number of parameters. '
                          'Expected 3, recieved {}'.format(len(params)))
     return containment
+
+
+def _is_rank_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in RANK_DEPTHS
 
 
 def _select_containment(containment):

@@ -7,6 +7,7 @@ calls into libstatdepth_hip (statdepth_amd.engine); the float normalisers stay h
 in fp64, written as the reference writes them.
 """
 import math
+import numbers
 from itertools import combinations
 from typing import List, Union
 
@@ -16,8 +17,9 @@ from scipy.special import binom
 
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
-from ._containment import _select_containment
-from ._helper import DepthDegeneracy, _handle_depth_errors
+from ._containment import _is_rank_depth, _select_containment
+from ._helper import DepthDegeneracy, _deep_check, _handle_depth_errors
+from ._rank import _rank_depth_values
 
 __all__ = ['_functionaldepth', '_samplefunctionaldepth']
 
@@ -135,8 +137,44 @@ def _componentwise_band_depth(data: List[pd.DataFrame], to_compute, J: int, rela
     return pd.Series(index=f, data=depth)
 
 
+def _rank_depths(data, to_compute, J, containment: str, deep_check=False, device=None) -> pd.Series:
+    """An integrated rank depth (containment in _containment.RANK_DEPTHS: 'fm', 'mei', 'mhi', 'half_region',
+    'integrated_halfspace', 'infimal_halfspace') of the columns `to_compute` of the single frame in `data`: one device
+    call for the integer records (sd_rank_depth_sums), the normalisation of _rank.py on the host.  Labels, `to_compute`
+    and the result's order are those of 'r2'.  What cannot be computed is refused here, before anything is uploaded.
+    The band-depth rule that J be below the number of timepoints does not apply: these depths have no J."""
+    def refuse(reason):
+        raise ValueError(f'containment \'{containment}\' {reason}')
+
+    if not isinstance(data, list):
+        raise ValueError('data must be passed as a list.')
+    if len(data) == 0:
+        raise ValueError('No data passed.')
+    if len(data) != 1:
+        refuse('is defined for univariate data only (a list of one DataFrame whose columns are the curves).')
+    if not isinstance(J, numbers.Integral) or isinstance(J, bool) or J != 2:
+        refuse(f'has no band size: J must be left at its default 2, got {J!r}.')
+    if deep_check:
+        _deep_check(data)
+    df = data[0]
+    _require_unique_labels(df)
+    X = df.to_numpy(dtype=np.float64, copy=False)      # keeps the frame's memory layout
+    T, n = X.shape
+    if n < 2:
+        refuse(f'needs at least 2 curves, got {n}.')
+    if T < 1:
+        refuse('needs at least one timepoint.')
+    if np.isnan(X).any():
+        refuse('does not take NaN (a missing value has no rank): drop or fill them first.')
+    cols = df.columns if to_compute is None else to_compute
+    records = engine.rank_depth_sums(X, _positions(df, cols), device=device)
+    return pd.Series(index=cols, data=_rank_depth_values(records, n, T, containment))
+
+
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
                      relax=False, deep_check=False, quiet=True, device=None, algo='auto') -> pd.Series:
+    if _is_rank_depth(containment):                      # not a band depth: `relax` and `algo` have nothing to select
+        return _rank_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)
 
@@ -196,6 +234,8 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     reference's blocks; each block's depth is one device call.
     """
     samples = []
+    if _is_rank_depth(containment):
+        raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)
     if len(data) != 1:

@@ -164,6 +164,17 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
 
 def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, containment='r2', relax=False,
                     deep_check=False, quiet=True, *, device=None, algo='auto'):
+    """Band depth of curves ('r2', 'r2_enum', 'simplex' or a callable), as in the reference.
+
+    For univariate data (`data` a list of one frame whose columns are the curves) `containment` also names the integrated
+    rank depths, all computed from the per-timepoint counts of curves strictly above and strictly below:
+    'fm' (Fraiman-Muniz, 1 - |1/2 - F_t(x(t))| averaged over t with the "<=" empirical CDF, hence not symmetric under
+    x -> -x), 'mei' and 'mhi' (modified epigraph and hypograph index: the mean proportion of curves at or above, resp. at
+    or below the curve), 'half_region' (their minimum, the modified half-region depth), 'integrated_halfspace' and
+    'infimal_halfspace' (mean and infimum over t of the univariate Tukey depth).  Labels, `to_compute` and the result
+    object are those of 'r2'.  These are the integrated ("modified") forms, so `relax` is accepted and ignored -- there
+    is no strict form to select -- and `algo` is ignored too.  ValueError for multivariate data, `K` other than None, `J`
+    other than 2, NaN anywhere in the frame, or fewer than 2 curves."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)

@@ -363,6 +363,52 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
                    workspace=lambda: _strict_workspace(lib, dev, M, m, J, workspace_budget))
 
 
+RANK_DEPTH_ALGOS = {"auto": 0, "image": 1, "sort": 2}
+
+
+def _rank_depth_algo(algo):
+    if isinstance(algo, str) and algo not in RANK_DEPTH_ALGOS:
+        raise ValueError(f"algo must be one of {sorted(RANK_DEPTH_ALGOS)}, got {algo!r}")
+    return RANK_DEPTH_ALGOS[algo] if isinstance(algo, str) else int(algo)
+
+
+def rank_depth_workspace_bytes(T, n, algo="auto", curve_major=False):
+    """(recommended, floor) workspace sizes of sd_rank_depth_sums for a T x n matrix; the floor holds one row per batch.
+    curve_major: the matrix is F-contiguous and takes a time-major copy in the workspace as well."""
+    lib = _native.load()
+    T, n, a = int(T), int(n), _rank_depth_algo(algo)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return (int(lib.sd_rank_depth_workspace_bytes(T, n, st, sn, n, a)),
+            int(lib.sd_rank_depth_min_workspace_bytes(T, n, st, sn, n, a)))
+
+
+def rank_depth_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False):
+    """Rows of the matrix a batch (image route) or a chunk (sort route) of sd_rank_depth_sums takes with ws_bytes of
+    workspace; 0 below the floor.  At the recommended size this is all T rows whenever T is within the route's caps."""
+    lib = _native.load()
+    T, n, a = int(T), int(n), _rank_depth_algo(algo)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return int(lib.sd_rank_depth_rows_per_batch(T, n, st, sn, n, a, int(ws_bytes)))
+
+
+def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
+    """int64[m, 5]: the records (SA, SB, SF, SM, MM) of the integrated rank depths (sd_rank_depth_sums) -- per target the
+    sums over t of A (others strictly above), of B (strictly below), of |2A - n| and of max(A, B), and the maximum over t
+    of max(A, B).  X must not hold NaN (the depth layer checks; this function takes its array as it is).  algo: 'auto',
+    'image' (n <= 16 384) or 'sort', or their numbers 0, 1, 2.  ws_bytes: the workspace size to run with (default: the
+    recommended one); the records do not depend on it, below the floor the library refuses."""
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    a = _rank_depth_algo(algo)
+    td, m, tp = _targets_dev(targets, M.n, dev)
+    out = t.empty((m, 5), dtype=t.int64, device=dev)
+    size = (lambda: lib.sd_rank_depth_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
+    return _launch(dev, lib.sd_rank_depth_sums, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a,
+                   workspace=lambda: _sized(dev, size()))
+
+
 # Point clouds.  Every depth of K4, K5, K7, K10, K11, K12 and K13 is asked for in three forms (DESIGN.md, "Point clouds: the three
 # forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
 # block.  The public functions below name the C entry point and the form; _points does the rest.
