@@ -6,6 +6,7 @@ import pandas as pd
 import pytest
 
 from conftest import assert_depths_close, depths_of, frame_df, golden_names, load_golden
+from test_oja_host import oja2_rowwise_targets as _oja2_rowwise_targets
 from test_oja_host import oja_depths, oja_external, oja_sampled, oja_sums
 
 pytestmark = pytest.mark.gpu
@@ -154,17 +155,6 @@ def test_target_beyond_4096_slices_split_across_launches(eng):
     assert np.array_equal(alone, three[[2]])
     want = _oja2_rowwise_targets(P, [5])
     assert np.all(np.abs(alone - want) <= 1e-10 * want)
-
-
-def _oja2_rowwise_targets(P, targets):
-    out = []
-    for t in targets:
-        a = np.delete(P, t, axis=0) - P[t]
-        s = 0.0
-        for i in range(len(a)):                                         # row by row: the n^2 table does not fit
-            s += np.abs(a[i, 0] * a[i + 1:, 1] - a[i, 1] * a[i + 1:, 0]).sum()
-        out.append(s / 2.0)
-    return np.array(out)
 
 
 # ---------------------------------------------------------------- sampled (K) and external forms

@@ -37,6 +37,18 @@ def oja_sums(P, targets=None):
     return np.array([_volume_sum(np.delete(P, t, axis=0), P[t]) for t in targets])
 
 
+def oja2_rowwise_targets(P, targets):
+    """oja_sums at d = 2 for clouds whose n^2 table of cross products does not fit: one row of it at a time."""
+    out = []
+    for t in targets:
+        a = np.delete(P, t, axis=0) - P[t]
+        s = 0.0
+        for i in range(len(a)):
+            s += np.abs(a[i, 0] * a[i + 1:, 1] - a[i, 1] * a[i + 1:, 0]).sum()
+        out.append(s / 2.0)
+    return np.array(out)
+
+
 def oja_depths(P, targets=None):
     return oja_sums(P, targets) / ConvexHull(P).volume
 
