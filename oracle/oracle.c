@@ -18,6 +18,7 @@
  * layouts (C-contiguous T x n: st=n,sn=1; F-contiguous: st=1,sn=T) are read in
  * place.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -387,6 +388,14 @@ int oracle_bd_strict_counts(const double *X, long T, long n, long st, long sn,
  * affinely independent points among them: enumerate column subsets of size rank
  * in the pivoted row space.  Tolerances: rank threshold and consistency are
  * relative to the data scale; `tol` bounds l from below (l is scale free).
+ * The data scale is the simplex's own: after the NaN / infinity checks the
+ * members and x are centred on the first member, and the coordinate rows, right-
+ * hand side included, are multiplied by 2^-e, e = ilogb(largest centred |entry| of
+ * the MEMBERS) (all members coincide: of the centred x), so the members end in
+ * [1, 2) and scale = max(that, scaled |x|).  Both steps are exact where the
+ * subtractions are: the decision is the same bit for bit for 2^k P, and for P + t
+ * while P + t is exact.  An infinity made by either step: outside.  (Before, scale
+ * was max(1, max |raw entry|): absolute thresholds below 1, swamped ones above.)
  * kpts = number of points (d+1 for a simplex), d = dimension.  kpts, d+1 <= 12.
  * -------------------------------------------------------------------------- */
 #define SMAX 12
@@ -426,23 +435,39 @@ static int solve_subset(const double R[SMAX][SMAX + 1], int rank, const int *col
 int oracle_point_in_hull(const double *P, int kpts, int d, const double *x, double tol) {
     if (kpts > SMAX || d + 1 > SMAX || kpts < 1) return -1;
     int rows = d + 1;
-    /* R = [M | b], rhs kept in column SMAX */
+    /* R = [M | b], rhs kept in column SMAX.  A NaN or an infinity anywhere: outside. */
+    for (int c = 0; c < kpts * d; ++c)
+        if (!(fabs(P[c]) <= DBL_MAX)) return 0;
+    for (int r = 0; r < d; ++r)
+        if (!(fabs(x[r]) <= DBL_MAX)) return 0;
     double R[SMAX][SMAX + 1];
+    /* centre on the first member; m, mx: the largest centred |entry| of the members, of x */
+    double m = 0.0, mx = 0.0;
+    for (int r = 0; r < d; ++r) {
+        for (int c = 0; c < kpts; ++c) {
+            double v = P[c * d + r] - P[r];
+            R[r][c] = v;
+            if (fabs(v) > m) m = fabs(v);
+        }
+        double v = x[r] - P[r];
+        R[r][SMAX] = v;
+        if (fabs(v) > mx) mx = fabs(v);
+    }
+    if (isinf(m) || isinf(mx)) return 0;           /* the subtraction overflowed */
+    /* the exponent of the members alone (of x where they all coincide) goes: exact, and the members end in [1, 2) */
+    int e = m > 0.0 ? ilogb(m) : mx > 0.0 ? ilogb(mx) : 0;
     double scale = 1.0;
     for (int r = 0; r < d; ++r) {
         for (int c = 0; c < kpts; ++c) {
-            double v = P[c * d + r];
-            if (v != v) return 0;
-            R[r][c] = v;
-            if (fabs(v) > scale) scale = fabs(v);
+            R[r][c] = ldexp(R[r][c], -e);
+            if (fabs(R[r][c]) > scale) scale = fabs(R[r][c]);
         }
-        if (x[r] != x[r]) return 0;
-        R[r][SMAX] = x[r];
-        if (fabs(x[r]) > scale) scale = fabs(x[r]);
+        R[r][SMAX] = ldexp(R[r][SMAX], -e);
+        if (fabs(R[r][SMAX]) > scale) scale = fabs(R[r][SMAX]);
     }
     for (int c = 0; c < kpts; ++c) R[d][c] = 1.0;
     R[d][SMAX] = 1.0;
-    if (isinf(scale)) return 0;
+    if (isinf(scale)) return 0;                    /* x that many extents away */
     double rank_eps = 1e-10 * scale;
     int colperm[SMAX];
     for (int c = 0; c < kpts; ++c) colperm[c] = c;

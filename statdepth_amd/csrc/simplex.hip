@@ -56,25 +56,47 @@ __device__ static bool solve_subset(const double (*R)[SMAX + 1], int rank, const
     return true;
 }
 
+// The system every site eliminates is NORMALISED: after the NaN / infinity checks the members and x are
+// centred on the first member, and the coordinate rows, right-hand side included, are multiplied by 2^-e, e = ilogb of the
+// largest centred |entry| of the MEMBERS (of x where they all coincide).  Both steps are exact for data that the subtraction
+// does not round, so the decision is the same bit for bit under P -> 2^k P and under exact translations, and rank_eps and the
+// consistency threshold are relative to the simplex's own extent.  An infinity that the subtraction or the scaling makes:
+// outside.  The same statements, in the same order, as oracle_point_in_hull.
+__device__ __forceinline__ bool sx_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for a NaN
+
 // pts: kpts x d (row-major, local), x: d
 __device__ static bool point_in_hull(const double *pts, int kpts, int d, const double *x, double tol) {
     int rows = d + 1;
+    for (int c = 0; c < kpts * d; ++c)
+        if (!sx_finite(pts[c])) return false;
+    for (int r = 0; r < d; ++r)
+        if (!sx_finite(x[r])) return false;
     double R[SMAX][SMAX + 1];
+    double m = 0.0, mx = 0.0;                                    // the largest centred |entry| of the members, of x
+    for (int r = 0; r < d; ++r) {
+        for (int c = 0; c < kpts; ++c) {
+            double v = pts[c * d + r] - pts[r];
+            R[r][c] = v;
+            if (fabs(v) > m) m = fabs(v);
+        }
+        double v = x[r] - pts[r];
+        R[r][SMAX] = v;
+        if (fabs(v) > mx) mx = fabs(v);
+    }
+    if (isinf(m) || isinf(mx)) return false;                     // the subtraction overflowed
+    int e = m > 0.0 ? ilogb(m) : mx > 0.0 ? ilogb(mx) : 0;
     double scale = 1.0;
     for (int r = 0; r < d; ++r) {
         for (int c = 0; c < kpts; ++c) {
-            double v = pts[c * d + r];
-            if (v != v) return false;
-            R[r][c] = v;
-            if (fabs(v) > scale) scale = fabs(v);
+            R[r][c] = ldexp(R[r][c], -e);
+            if (fabs(R[r][c]) > scale) scale = fabs(R[r][c]);
         }
-        if (x[r] != x[r]) return false;
-        R[r][SMAX] = x[r];
-        if (fabs(x[r]) > scale) scale = fabs(x[r]);
+        R[r][SMAX] = ldexp(R[r][SMAX], -e);
+        if (fabs(R[r][SMAX]) > scale) scale = fabs(R[r][SMAX]);
     }
     for (int c = 0; c < kpts; ++c) R[d][c] = 1.0;
     R[d][SMAX] = 1.0;
-    if (isinf(scale)) return false;
+    if (isinf(scale)) return false;                              // x that many extents away
     double rank_eps = 1e-10 * scale;
     int rank = 0;
     int lim = rows < kpts ? rows : kpts;
@@ -256,6 +278,57 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel(
     if (threadIdx.x == 0 && tot) atomicAdd(&out[q], tot);
 }
 
+// The loaders of the register-resident forms.  sx_members: columns 0 .. D of R from the members row(0) .. row(D), centred on
+// row(0) (kept in p0) and scaled by 2^-e; `scale` = the scaled member maximum, in [1, 2), or 1 where all members coincide
+// (then e = 0: the system is rank deficient and point_in_hull decides it from the data).  False: a NaN or an infinity.
+// sx_target: the last column of R from x with the same p0 and e, `scale` raised to its largest |entry|; an infinity there
+// is hull_full_rank's to refuse.  e depends on the members alone, which keeps the shared factorisation replayable.
+template <int D, int W, typename Row>
+__device__ __forceinline__ bool sx_members(double (&R)[D + 1][W], Row row, double (&p0)[D], int &e, double &scale) {
+    bool ok = true;
+    double m = 0.0;
+    const double *q0 = row(0);
+#pragma unroll
+    for (int r = 0; r < D; ++r) p0[r] = q0[r];
+#pragma unroll
+    for (int c = 0; c <= D; ++c) {
+        const double *pp = row(c);
+#pragma unroll
+        for (int r = 0; r < D; ++r) {
+            const double v = pp[r];
+            ok &= sx_finite(v);
+            const double w = v - p0[r];
+            R[r][c] = w;
+            m = fabs(w) > m ? fabs(w) : m;
+        }
+        R[D][c] = 1.0;
+    }
+    ok = ok && sx_finite(m);
+    e = ok && m > 0.0 ? ilogb(m) : 0;
+#pragma unroll
+    for (int c = 0; c <= D; ++c)
+#pragma unroll
+        for (int r = 0; r < D; ++r) R[r][c] = ldexp(R[r][c], -e);
+    const double ms = ldexp(m, -e);                                     // exact and monotone: the maximum of the scaled entries
+    scale = ms > 1.0 ? ms : 1.0;
+    return ok;
+}
+
+template <int D, int W>
+__device__ __forceinline__ bool sx_target(double (&R)[D + 1][W], const double *xx, const double (&p0)[D], int e, double &scale) {
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+        const double v = xx[r];
+        ok &= sx_finite(v);
+        const double w = ldexp(v - p0[r], -e);
+        R[r][W - 1] = w;
+        scale = fabs(w) > scale ? fabs(w) : scale;
+    }
+    R[D][W - 1] = 1.0;
+    return ok;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Register-resident form of the same test for a compile-time dimension D and a NON-degenerate simplex
 // (D + 1 points of full rank -- every simplex of continuous data).  The (D+1) x (D+2) system lives in VGPRs:
@@ -388,32 +461,13 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
             if (samples >= 0) sample_next_valid(seed, tg, &snext, K, n, idx);
             u64 cnt = 0;
             for (i64 t = 0; t < TT; ++t) {
-                double R[K][K + 1];
-                double scale = 1.0;
-                bool anynan = false;
+                double R[K][K + 1], p0[D];
+                double scale;
+                int e;
                 const double *xx = T > 0 ? P + (tg * TT + t) * D : blk.x;  // curves (rows form only): the target at timepoint t
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    const i64 src = sx_src(blk, direct, idx[c]);
-                    const double *pp = P + (src * TT + t) * D;
-#pragma unroll
-                    for (int e = 0; e < D; ++e) {
-                        const double v = pp[e];
-                        anynan |= v != v;
-                        R[e][c] = v;
-                        scale = fabs(v) > scale ? fabs(v) : scale;
-                    }
-                    R[D][c] = 1.0;
-                }
-#pragma unroll
-                for (int e = 0; e < D; ++e) {
-                    const double v = xx[e];
-                    anynan |= v != v;
-                    R[e][K] = v;
-                    scale = fabs(v) > scale ? fabs(v) : scale;
-                }
-                R[D][K] = 1.0;
-                int res = anynan ? 0 : hull_full_rank<D>(R, scale, tol);
+                bool ok = sx_members<D>(R, [&](int c) { return P + (sx_src(blk, direct, idx[c]) * TT + t) * D; }, p0, e, scale);
+                ok &= sx_target<D>(R, xx, p0, e, scale);
+                int res = ok ? hull_full_rank<D>(R, scale, tol) : 0;
                 if (res == 2) {                                         // degenerate simplex: generic code, from the data
                     double pts[SMAX * 8], x[8];
                     for (int c = 0; c < K; ++c) {
@@ -444,7 +498,9 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
 // substitution -- so replaying that sequence gives the barycentric coordinates of the per-target elimination BIT FOR BIT,
 // at about 2 K^2 multiply-subtracts + K divisions per test instead of a K x K elimination (d = 8: ~400 instructions
 // against ~7 500; d = 3: ~90 against ~700, and no random gathers: the members are read once per subset).
-// What depends on the target besides the right-hand side is `scale` (it includes |x|) through rank_eps = 1e-10 scale: a
+// The system is the normalised one (above): the record carries the subset's first member p0 (in final row order) and its exponent e,
+// functions of the subset alone, and a target's right-hand side for this subset is 2^-e (x - p0).
+// What depends on the target besides the right-hand side is `scale` (it includes that |x|) through rank_eps = 1e-10 scale: a
 // target whose own scale would put the smallest pivot at or below rank_eps, and a subset that is rank deficient, holds a NaN
 // or an infinity, or exchanges rows in the second elimination, take the per-target code (point_in_hull), decision for decision
 // the old kernel's.  A target that is a MEMBER of the subset skips it and takes a spare shared subset instead (the first
@@ -477,8 +533,8 @@ __device__ __noinline__ int sxw_special(const double *P, i64 TT, i64 t, const in
 
 template <int D> struct SxwCfg {
     static constexpr int K = D + 1, NL = K * (K - 1) / 2, NU = K * (K + 1) / 2;
-    static constexpr int DW = 2 * NL + NU + 2;                          // doubles: f1, f2, u, scale, minpiv
-    static constexpr int IW = ((2 * K + 1 + 3) / 4) * 4;                // ints: perm, members, status; padded to 16 bytes
+    static constexpr int DW = 2 * NL + NU + 2 + K;                      // doubles: f1, f2, u, scale, minpiv, p0 (the first member) by final row
+    static constexpr int IW = ((2 * K + 2 + 3) / 4) * 4;                // ints: perm, members, status, e; padded to 16 bytes
     static constexpr size_t REC = (size_t)DW * 8 + (size_t)IW * 4;      // bytes of a record
     static constexpr int TPT = D >= 5 ? 2 : 4;                          // targets per thread of the replay
 };
@@ -498,25 +554,14 @@ __global__ __launch_bounds__(64) void sxw_factor_kernel(const double *__restrict
     double *rd = recd + (size_t)v * DW;
     int *ri = reci + (size_t)v * IW;
     double *m1l = m1g + (size_t)v * (K * (K - 1));                      // the first elimination's multipliers by ORIGINAL row
-    double R[K][K];
+    double R[K][K], p0[D];
     int rowid[K];
-    double scale = 1.0;
-    bool irregular = false;
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        const double *pp = P + (idx[c] * TT + t) * D;
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-            const double x = pp[e];
-            irregular |= x != x;
-            R[e][c] = x;
-            scale = fabs(x) > scale ? fabs(x) : scale;
-        }
-        R[D][c] = 1.0;
-    }
+    double scale;
+    int e;
+    // the normalised matrix: p0, e and scale are functions of the subset alone
+    bool irregular = !sx_members<D>(R, [&](int c) { return P + (idx[c] * TT + t) * D; }, p0, e, scale);
 #pragma unroll
     for (int i = 0; i < K; ++i) rowid[i] = i;
-    irregular |= isinf(scale);
     const double rank_eps = 1e-10 * scale;
     double minpiv = __builtin_huge_val();
 #pragma unroll
@@ -599,8 +644,16 @@ __global__ __launch_bounds__(64) void sxw_factor_kernel(const double *__restrict
     rd[2 * NL + NU] = scale;
     rd[2 * NL + NU + 1] = minpiv;
 #pragma unroll
+    for (int i = 0; i < K; ++i) {                                       // p0 in the final row order (the row of ones: 0), as the replay gathers b
+        double v = 0.0;
+#pragma unroll
+        for (int r = 0; r < D; ++r) v = rowid[i] == r ? p0[r] : v;
+        rd[2 * NL + NU + 2 + i] = v;
+    }
+#pragma unroll
     for (int i = 0; i < K; ++i) { ri[i] = rowid[i]; ri[K + i] = (int)idx[i]; }
     ri[2 * K] = irregular ? 1 : 0;
+    ri[2 * K + 1] = e;
 }
 
 // replay of pairs [w0, w0 + cnt) on a tile of targets: grid = (tiles, splits); counts leave as one atomic per target
@@ -628,7 +681,8 @@ __global__ __launch_bounds__(256) void sxw_apply_kernel(const double *__restrict
     const i64 per = (cnt + gridDim.y - 1) / gridDim.y;
     const i64 vbeg = (i64)blockIdx.y * per, vend = vbeg + per < cnt ? vbeg + per : cnt;
     i64 tcur = -1;
-    double xx[TPT][K], sx[TPT];
+    double xx[TPT][K];
+    bool xnan[TPT];
     // A record travels as ONE coalesced load per wave (lane L holds doubles L and 64 + L, and int L), prefetched a pair ahead;
     // its values reach the arithmetic through v_readlane with compile-time lane numbers: wave-uniform operands in SGPRs without
     // the scalar cache's latency per value (a scalar load per value, waited for one by one, was ten times slower) and without LDS.
@@ -660,17 +714,10 @@ __global__ __launch_bounds__(256) void sxw_apply_kernel(const double *__restrict
 #pragma unroll
             for (int p = 0; p < TPT; ++p) {
                 const double *xp = P + (tg[p] * TT + t) * D;
-                double sc = 1.0;
-                bool isn = false;
+                xnan[p] = false;
 #pragma unroll
-                for (int e = 0; e < D; ++e) {
-                    const double x = xp[e];
-                    xx[p][e] = x;
-                    isn |= x != x;
-                    sc = fabs(x) > sc ? fabs(x) : sc;
-                }
+                for (int e = 0; e < D; ++e) { xx[p][e] = xp[e]; xnan[p] |= xp[e] != xp[e]; }
                 xx[p][D] = 1.0;
-                sx[p] = isn ? __builtin_nan("") : sc;
             }
         }
         const double scaleS = RD(2 * NL + NU), minpiv = RD(2 * NL + NU + 1);
@@ -678,20 +725,38 @@ __global__ __launch_bounds__(256) void sxw_apply_kernel(const double *__restrict
         int perm[K], mem[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) { perm[i] = RI(i); mem[i] = RI(K + i); }
+        const int ex = RI(2 * K + 1);
         bool special[TPT], in[TPT], skip[TPT];
-        double b[TPT][K], l[TPT][K];
+        double b[TPT][K], l[TPT][K], sc[TPT];
 #pragma unroll
         for (int p = 0; p < TPT; ++p) {
             bool member = false;
 #pragma unroll
             for (int i = 0; i < K; ++i) member |= (i64)mem[i] == tg[p];
-            const double sc = sx[p] > scaleS ? sx[p] : scaleS;          // NaN x: sc = scaleS, and the per-target code says no
-            special[p] = status != 0 || !(sx[p] == sx[p]) || !(minpiv > 1e-10 * sc) || isinf(sc);
             skip[p] = member;                                           // this target takes a spare subset instead (sxw_spare_kernel)
             in[p] = true;
+            sc[p] = scaleS;
+        }
+        // the right-hand side of this subset's normalised system, in its final row order: x centred on the subset's first member
+        // and scaled by its 2^-e; the row of ones (p0 = 0 there, and no scaling) stays 1.  Unconditional arithmetic: no branches.
+#pragma unroll
+        for (int p = 0; p < TPT; ++p)
 #pragma unroll
             for (int i = 0; i < K; ++i) b[p][i] = xx[p][perm[i]];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const double p0i = RD(2 * NL + NU + 2 + i);
+            const int exi = perm[i] == D ? 0 : -ex;                      // block-uniform
+#pragma unroll
+            for (int p = 0; p < TPT; ++p) {
+                const double w = ldexp(b[p][i] - p0i, exi);
+                b[p][i] = w;
+                sc[p] = fmax(sc[p], fabs(w));                           // w is a NaN only where x is: xnan
+            }
         }
+        // a NaN, or an infinity in x or made by the subtraction or the scaling: the per-target code says no
+#pragma unroll
+        for (int p = 0; p < TPT; ++p) special[p] = status != 0 || xnan[p] || !(minpiv > 1e-10 * sc[p]) || isinf(sc[p]);
         if (status == 0) {                                              // block-uniform
             int w = 0;
 #pragma unroll
@@ -780,30 +845,12 @@ __global__ __launch_bounds__(256) void sxw_spare_kernel(const double *__restrict
     for (int got = 0; got < need; ++got) {
         i64 idx[K];
         sample_next_valid(seed, tg, &snext, K, n, idx);
-        double R[K][K + 1];
-        double scale = 1.0;
-        bool anynan = false;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const double *pp = P + (idx[c] * TT + t) * D;
-#pragma unroll
-            for (int e = 0; e < D; ++e) {
-                const double v = pp[e];
-                anynan |= v != v;
-                R[e][c] = v;
-                scale = fabs(v) > scale ? fabs(v) : scale;
-            }
-            R[D][c] = 1.0;
-        }
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-            const double v = xx[e];
-            anynan |= v != v;
-            R[e][K] = v;
-            scale = fabs(v) > scale ? fabs(v) : scale;
-        }
-        R[D][K] = 1.0;
-        int res = anynan ? 0 : hull_full_rank<D>(R, scale, tol);
+        double R[K][K + 1], p0[D];
+        double scale;
+        int e;
+        bool ok = sx_members<D>(R, [&](int c) { return P + (idx[c] * TT + t) * D; }, p0, e, scale);
+        ok &= sx_target<D>(R, xx, p0, e, scale);
+        int res = ok ? hull_full_rank<D>(R, scale, tol) : 0;
         if (res == 2) {                                                 // degenerate simplex: generic code, from the data
             double pts[SMAX * 8], x[8];
             for (int c = 0; c < K; ++c) {
