@@ -543,6 +543,38 @@ int64_t sd_rank_depth_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t s
 int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
                        int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K15: extremal depth of curves (Narisetty & Nair, JASA 2016) ----
+ * No reference code.  X is T x n fp64 in either layout, finite or +-inf; NaN is NOT supported (the host layer refuses
+ * it).  For curve q at timepoint t, with K14's A and B over the other n - 1 curves (ties in neither):
+ *   pointwise extremity  e_q(t) = |A - B|  in [0, n - 1]      (the paper's pointwise depth is 1 - e / n);
+ *   v_q = the T values e_q(.) sorted in descending order;
+ *   curve f is more extreme than or equal to g  iff  v_f >= v_g lexicographically.
+ * This is the paper's ordering of the depth CDFs: compare Phi from the lowest depth level upward, and at the first
+ * difference the larger Phi belongs to the more extreme curve.  The device returns one int64 per target,
+ *   G_q = #{ i in the sample : v_i >=lex v_q }   (q itself and every curve with an identical vector are counted),
+ * and the host forms ED = G / n in fp64 with one division: 1 for the deepest curve, equal depths for equal vectors.
+ * Example: rows [1,2,3,4], [2,1,3,3], [1,3,2,4] (T = 3, n = 4) have e = (3,1,1,3), (1,3,2,2), (3,1,1,3), so
+ * v = (3,3,1), (3,1,1), (2,1,1), (3,3,2), G = [2, 3, 4, 1], ED = [0.5, 0.75, 1, 0.25].
+ * Stages: (1) the pair image of a batch of rows by K14's two routes -- algo 0 auto, 1 image (n <= 16 384), 2 sort, the
+ * same boundary; (2) a transposing transform writes |A - B| of all n curves into the u32 matrix E, curve-major;
+ * (3) every curve's row of E is sorted descending in LDS (padded with 0 to a power of two; at most 16 384 timepoints =
+ * 64 KiB of keys) and its head packed into one u64: the first P = min(T, 64 / b) entries in fields of b bits, most
+ * significant first, missing fields 0, b = max(16, bit width of n - 1), so P = 4 up to 65 536 curves, 3 up to 2^21,
+ * 2 beyond; (4) each target counts the curves with a larger head and, where the heads are equal, compares the entries
+ * P .. T - 1 to the first difference (equal to the end counts).
+ * Workspace, in this order: the time-major copy of a curve-major X (8 T n bytes), E (4 T n), the heads (8 n), each
+ * padded to 256 bytes, then stage 1's batch exactly as K14 sizes it (sd_rank_depth_rows_per_batch of what is left).
+ * sd_extremal_workspace_bytes recommends a size, sd_extremal_min_workspace_bytes is the floor (one row per batch); both
+ * are 0 for a shape or algo the call refuses.  The integers do not depend on the workspace size.
+ * targets: m int64 indices of sample curves (device), NULL = all (m == n).  out: m int64 (device).
+ * SD_ERR_INVALID for NULL X or out, T < 1, n < 2 or an unknown algo; SD_ERR_UNSUPPORTED for T > 16 384, for 2^31 or more
+ * curves, for algo = 1 with n > 16 384, or where the worst-case walk n m T exceeds 10^14 entry comparisons;
+ * SD_ERR_WORKSPACE below the floor.  All before any device work.  Every launch is bounded in work. */
+size_t sd_extremal_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+size_t sd_extremal_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
+                       int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

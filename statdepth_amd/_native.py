@@ -94,6 +94,9 @@ SIGNATURES = {
     "sd_rank_depth_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
     "sd_rank_depth_rows_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _int, _sz]),
     "sd_rank_depth_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "sd_extremal_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_extremal_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_extremal_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
 }
 
 

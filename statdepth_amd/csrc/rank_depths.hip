@@ -27,6 +27,9 @@
 // over the image, as rank_accumulate_kernel), LDS tree over the slices.  The first batch writes out =, later batches
 // add to the four sums and take the maximum for MM.  A (target, slice) pair has one owner and the batches follow each
 // other on the stream: no atomics, and integer sums and maxima do not depend on the batch size.  40 KB of LDS.
+//
+// The routes hand each batch's image to a RankImageConsumer (launch_rank_pair_images): the fold here, K15's transform
+// into the extremity matrix in extremal.hip.
 #include "sd_common.h"
 #include "rank_routes.h"
 #include "halfspace_sort.h"
@@ -180,8 +183,8 @@ i64 rank_depth_rows_per_batch(i64 T, i64 n, int route, size_t bytes) {
 }
 
 // ---------------------------------------------------------------------------------------------- the two routes
-static int rank_depth_image_route(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, u64 *out, void *ws,
-                                  size_t ws_bytes, hipStream_t s) {
+// Each route hands the pair image of a batch (rows [row0, row0 + rows) of Y) to `use`; the image is overwritten by the next batch.
+static int rank_depth_image_route(const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws, size_t ws_bytes, hipStream_t s) {
     const i64 rpb = rank_depth_rows_per_batch(T, n, 1, ws_bytes);
     if (!ws || rpb < 1) return fail(SD_ERR_WORKSPACE, "workspace too small for one row per batch (sd_rank_depth_min_workspace_bytes)");
     Carver cv(ws, ws_bytes);
@@ -191,13 +194,12 @@ static int rank_depth_image_route(const double *Y, i64 T, i64 n, const i64 *targ
     for (i64 row0 = 0; row0 < T; row0 += rpb) {
         const i64 rows = T - row0 < rpb ? T - row0 : rpb;
         int rc = launch_rank_bucket_image(Y, n, row0, rows, AB, nnan, s);
-        if (rc || (rc = launch_rank_depth_fold<u32>(AB, rows, n, targets, m, out, row0 == 0, s))) return rc;
+        if (rc || (rc = use.image32(AB, row0, rows, s))) return rc;
     }
     return SD_OK;
 }
 
-static int rank_depth_sort_route(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, u64 *out, void *ws,
-                                 size_t ws_bytes, hipStream_t s) {
+static int rank_depth_sort_route(const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws, size_t ws_bytes, hipStream_t s) {
     const i64 kc = rank_depth_rows_per_batch(T, n, 2, ws_bytes);
     if (!ws || kc < 1) return fail(SD_ERR_WORKSPACE, "workspace too small for one row per chunk (sd_rank_depth_min_workspace_bytes)");
     Carver cv(ws, ws_bytes);
@@ -214,15 +216,35 @@ static int rank_depth_sort_route(const double *Y, i64 T, i64 n, const i64 *targe
         hipLaunchKernelGGL(rd_rank_scatter_kernel, dim3((unsigned)((total + HS_THREADS - 1) / HS_THREADS)), dim3(HS_THREADS), 0,
                            s, b.K[src], b.I[src], n, total, img);
         SD_HIP(hipGetLastError());
-        if ((rc = launch_rank_depth_fold<u64>(img, kk, n, targets, m, out, c0 == 0, s))) return rc;
+        if ((rc = use.image64(img, c0, kk, s))) return rc;
     }
     return SD_OK;
 }
 
+int launch_rank_pair_images(const double *Y, i64 T, i64 n, int route, RankImageConsumer &use, void *ws, size_t ws_bytes,
+                            hipStream_t s) {
+    if (route == 1) return rank_depth_image_route(Y, T, n, use, ws, ws_bytes, s);
+    return rank_depth_sort_route(Y, T, n, use, ws, ws_bytes, s);
+}
+
+// K14's consumer: the fold into the records
+struct RankDepthFold final : RankImageConsumer {
+    i64 n, m;
+    const i64 *targets;
+    u64 *out;
+    RankDepthFold(i64 n_, const i64 *targets_, i64 m_, u64 *out_) : n(n_), m(m_), targets(targets_), out(out_) {}
+    int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) override {
+        return launch_rank_depth_fold<u32>(img, rows, n, targets, m, out, row0 == 0, s);
+    }
+    int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) override {
+        return launch_rank_depth_fold<u64>(img, rows, n, targets, m, out, row0 == 0, s);
+    }
+};
+
 int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
                            size_t ws_bytes, hipStream_t s) {
-    if (route == 1) return rank_depth_image_route(Y, T, n, targets, m, (u64 *)out, ws, ws_bytes, s);
-    return rank_depth_sort_route(Y, T, n, targets, m, (u64 *)out, ws, ws_bytes, s);
+    RankDepthFold fold(n, targets, m, (u64 *)out);
+    return launch_rank_pair_images(Y, T, n, route, fold, ws, ws_bytes, s);
 }
 
 }  // namespace sd

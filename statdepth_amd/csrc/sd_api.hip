@@ -976,4 +976,51 @@ int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_
     return launch_rank_depth_sums(Y, T, n, targets, m, rank_depth_route(algo, T, n), out, cv.take(rest), rest, s);
 }
 
+// ---------------------------------------------------------------------------
+// K15
+// ---------------------------------------------------------------------------
+// K14's route for a shape the extremal depth takes, 0 otherwise
+static int extremal_route(int algo, i64 T, i64 n) { return T > EX_MAX_T ? 0 : rank_depth_route(algo, T, n); }
+
+size_t sd_extremal_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    (void)m;
+    const int route = extremal_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + extremal_fixed_workspace_bytes(T, n) + rank_depth_workspace_bytes(T, n, route) : 0;
+}
+
+size_t sd_extremal_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    (void)m;
+    const int route = extremal_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + extremal_fixed_workspace_bytes(T, n) + rank_depth_min_workspace_bytes(n, route) : 0;
+}
+
+int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
+                       int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1 || n < 2) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint and two curves",
+                                    (long long)T, (long long)n);
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (image), 2 (sort)", algo);
+    if (T > EX_MAX_T)
+        return fail(SD_ERR_UNSUPPORTED, "extremal depth sorts up to %lld timepoints per curve, got %lld", (long long)EX_MAX_T,
+                    (long long)T);
+    if (n >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "extremal depth takes fewer than 2^31 curves, got %lld", (long long)n);
+    if (algo == 1 && n > RD_IMAGE_MAX_N)
+        return fail(SD_ERR_UNSUPPORTED, "the image route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
+                    (long long)RD_IMAGE_MAX_N, (long long)n);
+    const double walk = (double)n * (double)m * (double)T;         // every pair undecided by its head, to the last entry
+    if (walk > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g entry comparisons in the worst case exceed the cap of %.0e", walk, HS_MAX_WORK);
+    int rc = check_matrix(X, T, n, st, sn, targets, m);
+    if (rc) return rc;
+    if (m == 0) return SD_OK;
+    if (!ws || ws_bytes < sd_extremal_min_workspace_bytes(T, n, st, sn, m, algo))
+        return fail(SD_ERR_WORKSPACE, "workspace below sd_extremal_min_workspace_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes);
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
+    const size_t rest = cv.rest();
+    return launch_extremal_counts(Y, T, n, targets, m, extremal_route(algo, T, n), out, cv.take(rest), rest, s);
+}
+
 }  // extern "C"

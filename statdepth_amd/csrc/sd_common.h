@@ -178,6 +178,23 @@ size_t rank_depth_min_workspace_bytes(i64 n, int route);
 i64 rank_depth_rows_per_batch(i64 T, i64 n, int route, size_t bytes);   // rows a batch / chunk takes with `bytes`; 0 below the floor
 int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
                            size_t ws_bytes, hipStream_t s);
+// What takes the pair image of one batch of rows [row0, row0 + rows) of Y, img[r][i] of row row0 + r and curve i: B | A << 16
+// in u32 on route 1, B | A << 32 in u64 on route 2.  It enqueues on s; the next batch overwrites the image.
+struct RankImageConsumer {
+    virtual int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) = 0;
+    virtual int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) = 0;
+    virtual ~RankImageConsumer() = default;
+};
+// the two routes of K14, batch by batch, with `ws` sized as for launch_rank_depth_sums
+int launch_rank_pair_images(const double *Y, i64 T, i64 n, int route, RankImageConsumer &use, void *ws, size_t ws_bytes,
+                            hipStream_t s);
+
+// K15 extremal depth of curves (extremal.hip): out[q] = #{curves i : v_i >=lex v_q}, v the descending sort of |A - B| over
+// time.  `route` and the workspace behind the time-major copy as in K14, plus the extremity matrix and the heads
+constexpr i64 EX_MAX_T = 16384;                                     // keys one sort workgroup holds in LDS (64 KiB)
+size_t extremal_fixed_workspace_bytes(i64 T, i64 n);                // E and H; stage 1 takes the rest
+int launch_extremal_counts(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
+                           size_t ws_bytes, hipStream_t s);
 
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);

@@ -7,19 +7,21 @@ HIP kernels.  A user-supplied callable keeps the reference's plug-in protocol
 on the host, because arbitrary Python cannot run on the GPU.
 
 RANK_DEPTHS names the integrated rank depths of univariate curves (_rank.py): not band containments, but selected through
-the same argument.
+the same argument.  ORDER_DEPTHS names the depths that order the curves instead of averaging over time (the extremal
+depth, _functional._extremal_depth), selected the same way.
 """
 from inspect import signature
 
 BUILTIN = ('r2', 'r2_enum', 'simplex')
 RANK_DEPTHS = ('fm', 'mei', 'mhi', 'half_region', 'integrated_halfspace', 'infimal_halfspace')
+ORDER_DEPTHS = ('extremal',)
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
     if len(params) != 3:   # only the arity is enforced (:37-41)
@@ -30,6 +32,10 @@ def _is_valid_containment(containment):
 
 def _is_rank_depth(containment) -> bool:
     return isinstance(containment, str) and containment in RANK_DEPTHS
+
+
+def _is_order_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in ORDER_DEPTHS
 
 
 def _select_containment(containment):

@@ -17,7 +17,7 @@ from scipy.special import binom
 
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
-from ._containment import _is_rank_depth, _select_containment
+from ._containment import _is_order_depth, _is_rank_depth, _select_containment
 from ._helper import DepthDegeneracy, _deep_check, _handle_depth_errors
 from ._rank import _rank_depth_values
 
@@ -137,12 +137,10 @@ def _componentwise_band_depth(data: List[pd.DataFrame], to_compute, J: int, rela
     return pd.Series(index=f, data=depth)
 
 
-def _rank_depths(data, to_compute, J, containment: str, deep_check=False, device=None) -> pd.Series:
-    """An integrated rank depth (containment in _containment.RANK_DEPTHS: 'fm', 'mei', 'mhi', 'half_region',
-    'integrated_halfspace', 'infimal_halfspace') of the columns `to_compute` of the single frame in `data`: one device
-    call for the integer records (sd_rank_depth_sums), the normalisation of _rank.py on the host.  Labels, `to_compute`
-    and the result's order are those of 'r2'.  What cannot be computed is refused here, before anything is uploaded.
-    The band-depth rule that J be below the number of timepoints does not apply: these depths have no J."""
+def _ranked_frame(data, J, containment: str, deep_check=False):
+    """(frame, its T x n fp64 matrix) for a depth built on the pointwise ranks of univariate curves (the rank depths and
+    the extremal depth), or the refusal they share, raised before anything is uploaded: one frame, J at its default,
+    unique labels, at least 2 curves and 1 timepoint, no NaN."""
     def refuse(reason):
         raise ValueError(f'containment \'{containment}\' {reason}')
 
@@ -166,15 +164,46 @@ def _rank_depths(data, to_compute, J, containment: str, deep_check=False, device
         refuse('needs at least one timepoint.')
     if np.isnan(X).any():
         refuse('does not take NaN (a missing value has no rank): drop or fill them first.')
+    return df, X
+
+
+def _rank_depths(data, to_compute, J, containment: str, deep_check=False, device=None) -> pd.Series:
+    """An integrated rank depth (containment in _containment.RANK_DEPTHS: 'fm', 'mei', 'mhi', 'half_region',
+    'integrated_halfspace', 'infimal_halfspace') of the columns `to_compute` of the single frame in `data`: one device
+    call for the integer records (sd_rank_depth_sums), the normalisation of _rank.py on the host.  Labels, `to_compute`
+    and the result's order are those of 'r2'.  What cannot be computed is refused here, before anything is uploaded.
+    The band-depth rule that J be below the number of timepoints does not apply: these depths have no J."""
+    df, X = _ranked_frame(data, J, containment, deep_check)
+    T, n = X.shape
     cols = df.columns if to_compute is None else to_compute
     records = engine.rank_depth_sums(X, _positions(df, cols), device=device)
     return pd.Series(index=cols, data=_rank_depth_values(records, n, T, containment))
+
+
+EXTREMAL_MAX_T = 16384             # timepoints a curve's sort holds on the device (sd_extremal_counts)
+
+
+def _extremal_depth(data, to_compute, J, containment: str, deep_check=False, device=None) -> pd.Series:
+    """The extremal depth (Narisetty & Nair 2016; containment 'extremal') of the columns `to_compute` of the single frame
+    in `data`: G / n, G the number of sample curves at least as extreme as the curve (sd_extremal_counts: the curve itself
+    and its ties included), so the deepest curve has depth 1.  Labels, `to_compute` and the result's order are those of
+    'r2'; the refusals are those of the rank depths, and more than 16 384 timepoints are not implemented."""
+    df, X = _ranked_frame(data, J, containment, deep_check)
+    T, n = X.shape
+    if T > EXTREMAL_MAX_T:
+        raise NotImplementedError(f'containment \'{containment}\' is implemented for up to {EXTREMAL_MAX_T} timepoints, '
+                                  f'got {T}.')
+    cols = df.columns if to_compute is None else to_compute
+    G = engine.extremal_counts(X, _positions(df, cols), device=device)
+    return pd.Series(index=cols, data=np.asarray(G, dtype=np.float64) / n)
 
 
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
                      relax=False, deep_check=False, quiet=True, device=None, algo='auto') -> pd.Series:
     if _is_rank_depth(containment):                      # not a band depth: `relax` and `algo` have nothing to select
         return _rank_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
+    if _is_order_depth(containment):
+        return _extremal_depth(data, to_compute, J, containment, deep_check=deep_check, device=device)
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)
 
@@ -234,7 +263,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     reference's blocks; each block's depth is one device call.
     """
     samples = []
-    if _is_rank_depth(containment):
+    if _is_rank_depth(containment) or _is_order_depth(containment):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

@@ -409,6 +409,34 @@ def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
                    workspace=lambda: _sized(dev, size()))
 
 
+def extremal_workspace_bytes(T, n, algo="auto", curve_major=False):
+    """(recommended, floor) workspace sizes of sd_extremal_counts for a T x n matrix: the extremity matrix (4 T n bytes)
+    and the heads (8 n) in front of the batch of sd_rank_depth_sums; the floor holds one row per batch.  (0, 0) for a
+    shape or algo the call refuses.  curve_major: the matrix is F-contiguous and takes a time-major copy as well."""
+    lib = _native.load()
+    T, n, a = int(T), int(n), _rank_depth_algo(algo)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return (int(lib.sd_extremal_workspace_bytes(T, n, st, sn, n, a)),
+            int(lib.sd_extremal_min_workspace_bytes(T, n, st, sn, n, a)))
+
+
+def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
+    """int64[m]: G of the extremal depth (sd_extremal_counts) -- per target the number of sample curves, itself included,
+    whose descending-sorted vector of pointwise extremities |A - B| is lexicographically at least the target's; the depth
+    is G / n.  X must not hold NaN (the depth layer checks; this function takes its array as it is).  targets: indices of
+    sample curves (None: all).  algo and ws_bytes as for rank_depth_sums; the counts do not depend on ws_bytes."""
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    a = _rank_depth_algo(algo)
+    td, m, tp = _targets_dev(targets, M.n, dev)
+    out = t.empty((m,), dtype=t.int64, device=dev)
+    size = (lambda: lib.sd_extremal_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
+    return _launch(dev, lib.sd_extremal_counts, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a,
+                   workspace=lambda: _sized(dev, size()))
+
+
 # Point clouds.  Every depth of K4, K5, K7, K10, K11, K12 and K13 is asked for in three forms (DESIGN.md, "Point clouds: the three
 # forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
 # block.  The public functions below name the C entry point and the form; _points does the rest.
