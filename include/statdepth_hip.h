@@ -575,6 +575,48 @@ size_t sd_extremal_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t
 int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
                        int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K16: central regions, fence, outside counts and whiskers of the functional boxplot ----
+ * (Sun & Genton, JCGS 2011, from the modified band depth; Narisetty & Nair 2016 from the extremal depth.)  No reference
+ * code.  X is T x n fp64 in either layout, finite or +-inf; NaN is NOT supported (the host layer refuses it).
+ * Levels.  level: n bytes (device), level[i] in 0 .. L, 1 <= L <= 8.  Region l is { i : level[i] <= l }, l = 0 .. L - 1,
+ * so regions are nested; level[i] >= L means "in no region".  The host derives the bytes from a depth vector and ascending
+ * fractions alphas[0 .. L): curves ranked by descending depth (ties: the earlier column is deeper), region l the first
+ * min(n, max(1, ceil(alphas[l] n))) of them, level[i] the smallest l whose region holds i.
+ * Every output is an input value, an integer, or one of four rounded fp64 operations:
+ *   env[l][0][t] = min, env[l][1][t] = max of X[t][i] over region l            (+inf / -inf for an empty region);
+ *   fence of the region `box` with the factor F >= 0, per t, each line ONE rounded operation (no contraction):
+ *       r = upper - lower;  w = F * r;  lf = lower - w;  uf = upper + w;     fence[0][t] = lf, fence[1][t] = uf
+ *     (plain IEEE: a row whose box region is all +inf has a NaN fence, and a NaN fence flags nobody);
+ *   outside[i][0] = #{ t : X[t][i] < lf[t] },  outside[i][1] = #{ t : X[t][i] > uf[t] }   (int32; a curve is an outlier
+ *     iff either is nonzero; a member of the box region never is);
+ *   whisker[0][t] / whisker[1][t] = min / max of X[t][i] over the curves that are not outliers.
+ * The sign of a zero among equal values is not specified.
+ * Example: rows [1,2,3,4,9], [2,2,2,2,-7], [0,5,1,3,2] (T = 3, n = 5), level = [1,0,0,1,2], L = 2, box = 0, F = 1.5:
+ *   env[0] = (2,2,1) .. (3,2,5), env[1] = (1,2,0) .. (4,2,5), fence = (0.5,2,-5) .. (4.5,2,11),
+ *   outside = [0 0; 0 0; 0 0; 0 0; 1 1] (9 > 4.5, -7 < 2), whisker = (1,2,0) .. (4,2,5).
+ * Routes.  Up to sd_central_regions_row_capacity() (16 384) curves a workgroup holds whole rows in registers: per row and
+ * exact level the min / max are reduced over the thread, the wave and the workgroup, one thread accumulates the levels,
+ * writes env and the fence, the fence goes back through LDS and every thread compares the values it still holds; the
+ * counts stay in registers over the workgroup's rows and meet in integer atomic adds (exact in any order), so X is read
+ * once for regions, fence and counts.  Above the capacity, for any n < 2^31: blocks of 8192 curves write their min / max per
+ * (row, level) to the workspace, a second kernel folds them into env and the fence, a third reads X again for the counts.
+ * The whiskers are a further launch of the envelope code with one level, outside == (0, 0).  Dependencies between passes
+ * are kernel boundaries; every loop is bounded by T or n.  A curve-major X takes a time-major copy first.
+ * Workspace, in this order, each padded to 256 bytes: the time-major copy of a curve-major X (8 T n bytes), a fence
+ * (16 T), the counts (8 n: used where whisker is asked for without outside), and above the capacity the blocks' min / max
+ * (16 T L ceil(n / 8192)).  sd_central_regions_workspace_bytes is the size the call needs (0 for a shape or L it refuses).
+ * box = -1: envelopes only; fence, outside and whisker must be NULL.  box in [0, L): any of the three may be NULL.
+ * env: L x 2 x T doubles; fence, whisker: 2 x T doubles; outside: n x 2 int32 (all device).
+ * SD_ERR_INVALID for NULL X, level or env, T < 1, n < 1, strides that are neither layout, L outside [1, 8], box outside
+ * [-1, L), a negative, NaN or infinite factor, or fence / outside / whisker with box = -1; SD_ERR_UNSUPPORTED for 2^31 or
+ * more curves or timepoints; SD_ERR_WORKSPACE when ws_bytes is below sd_central_regions_workspace_bytes.  All before any
+ * device work. */
+int64_t sd_central_regions_row_capacity(void);
+size_t sd_central_regions_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int L);
+int sd_central_regions(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const uint8_t *level, int L, int box,
+                       double factor, double *env, double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,9 @@ SIGNATURES = {
     "sd_extremal_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
     "sd_extremal_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
     "sd_extremal_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "sd_central_regions_row_capacity": (_i64, []),
+    "sd_central_regions_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
+    "sd_central_regions": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -1023,4 +1023,38 @@ int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_
     return launch_extremal_counts(Y, T, n, targets, m, extremal_route(algo, T, n), out, cv.take(rest), rest, s);
 }
 
+// ---------------------------------------------------------------------------
+// K16
+// ---------------------------------------------------------------------------
+int64_t sd_central_regions_row_capacity(void) { return CR_ROW_CAPACITY; }
+
+size_t sd_central_regions_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int L) {
+    if (T < 1 || n < 1 || T >= ((i64)1 << 31) || n >= ((i64)1 << 31) || L < 1 || L > 8) return 0;
+    return time_major_bytes(T, n, st, sn) + central_regions_workspace_bytes(T, n, L);
+}
+
+int sd_central_regions(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const uint8_t *level, int L, int box,
+                       double factor, double *env, double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes,
+                       void *stream) {
+    if (!X || !level || !env) return fail(SD_ERR_INVALID, "null pointer (X, level and env are required)");
+    if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint and one curve",
+                                    (long long)T, (long long)n);
+    if (L < 1 || L > 8) return fail(SD_ERR_INVALID, "L=%d outside [1,8]", L);
+    if (box < -1 || box >= L) return fail(SD_ERR_INVALID, "box=%d outside [-1,%d)", box, L);
+    if (!(factor >= 0.0) || factor > 1.79769313486231570815e308)
+        return fail(SD_ERR_INVALID, "the fence factor must be finite and not negative, got %g", factor);
+    if (box < 0 && (fence || outside || whisker))
+        return fail(SD_ERR_INVALID, "box=-1 asks for the envelopes only: fence, outside and whisker must be null");
+    int rc = check_matrix(X, T, n, st, sn, nullptr, n);
+    if (rc) return rc;
+    if (!ws || ws_bytes < sd_central_regions_workspace_bytes(T, n, st, sn, L))
+        return fail(SD_ERR_WORKSPACE, "workspace below sd_central_regions_workspace_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes);
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
+    const size_t rest = cv.rest();
+    return launch_central_regions(Y, T, n, level, L, box, factor, env, fence, outside, whisker, cv.take(rest), rest, s);
+}
+
 }  // extern "C"

@@ -196,6 +196,14 @@ size_t extremal_fixed_workspace_bytes(i64 T, i64 n);                // E and H; 
 int launch_extremal_counts(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
                            size_t ws_bytes, hipStream_t s);
 
+// K16 central regions, fence, outside counts and whiskers of the functional boxplot (central_regions.hip).  Y time-major;
+// fence, outside and whisker may be null (all three are with box = -1).  The workspace behind the time-major copy: a
+// fence (16 T bytes), the counts (8 n) and, above the row capacity, the column blocks' min / max (16 T L per block)
+constexpr i64 CR_ROW_CAPACITY = 16384;                              // curves of one row a workgroup holds in registers
+size_t central_regions_workspace_bytes(i64 T, i64 n, int L);
+int launch_central_regions(const double *Y, i64 T, i64 n, const uint8_t *level, int L, int box, double factor, double *env,
+                           double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

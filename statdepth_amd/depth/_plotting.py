@@ -39,6 +39,31 @@ def curves_figure(frame: pd.DataFrame, marked, title=None, xaxis_title=None, yax
     return _finish(go.Figure(data=traces, layout=layout), return_plot, showlegend)
 
 
+def boxplot_figure(result, title=None, xaxis_title=None, yaxis_title=None, return_plot=False, showlegend=False):
+    """The functional boxplot of a FunctionalBoxplotResult: every region as a filled band (the widest first, so the
+    box lies on top), the whiskers as thin lines, the median curve in black, the outliers in red."""
+    go = _go()
+    x = result.envelope.index
+    traces = []
+    for a in sorted(result.regions, reverse=True):
+        band = result.regions[a]
+        shade = 'rgba(110,168,255,0.55)' if a == result.alpha else 'rgba(110,168,255,0.25)'
+        traces.append(go.Scatter(x=x, y=band['lower'], mode='lines', line=dict(color='#6ea8ff', width=.5),
+                                 name=f'region {a:g} lower', showlegend=False))
+        traces.append(go.Scatter(x=x, y=band['upper'], mode='lines', line=dict(color='#6ea8ff', width=.5), fill='tonexty',
+                                 fillcolor=shade, name=f'region {a:g}'))
+    for side in ('lower', 'upper'):
+        traces.append(go.Scatter(x=x, y=result.whiskers[side], mode='lines', line=dict(color='#1f3b73', width=1),
+                                 name=f'whisker {side}'))
+    traces.append(go.Scatter(x=x, y=result.data[result.median], mode='lines', line=dict(color='Black', width=1.5),
+                             name=f'median {result.median}'))
+    for c in result.outliers:
+        traces.append(go.Scatter(x=x, y=result.data[c], mode='lines', name=str(c), line=_MARKED))
+    layout = go.Layout(title=dict(text=title, y=0.9, x=0.5, xanchor='center', yanchor='top'),
+                       xaxis=dict(title=xaxis_title), yaxis=dict(title=yaxis_title))
+    return _finish(go.Figure(data=traces, layout=layout), return_plot, showlegend)
+
+
 def _scatter(go, frame: pd.DataFrame, **marker_kw):
     """2-D or 3-D marker trace of a point cloud; other dimensions have no picture in the reference either (:215-216,307-308)."""
     cols = list(frame.columns)

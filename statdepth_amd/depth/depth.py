@@ -16,9 +16,11 @@ from .calculations._functional import _functionaldepth, _samplefunctionaldepth
 from .calculations._helper import DepthDegeneracy   # noqa: F401
 from .calculations._pointcloud import _pointwisedepth, _samplepointwisedepth
 from .calculations._uncertainty import _probabilistic_band_depth
+from .calculations import _boxplot
+from .calculations._boxplot import FunctionalBoxplotResult
 from . import _plotting
 
-__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth']
+__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot']
 
 
 class AbstractDepth(ABC):
@@ -111,6 +113,15 @@ class _FunctionalDepthUnivariate(_FunctionalDepthSeries):
         return _plotting.curves_figure(self._orig_data, self.outlying(n=n).index, title, xaxis_title, yaxis_title,
                                        return_plot, showlegend)
 
+    def central_region(self, alpha=0.5, device=None) -> pd.DataFrame:
+        '''The envelope ('lower' and 'upper' on the time index) of the deepest fraction `alpha` of the curves by these
+        depths.  ValueError unless every column of the data has a depth (a result of `to_compute` or `K` has not).'''
+        return _boxplot._central_region(self._orig_data, self._depths, alpha=alpha, device=device)
+
+    def boxplot(self, alpha=0.5, factor=1.5, levels=(), device=None) -> FunctionalBoxplotResult:
+        '''The functional boxplot of the data by these depths: FunctionalBoxplot(data, depths=self, ...).'''
+        return FunctionalBoxplot(self._orig_data, self._depths, alpha=alpha, factor=factor, levels=levels, device=device)
+
 
 class _PointwiseDepth(_FunctionalDepthSeries):
     '''Points are the ROWS of the frame (:337-341).'''
@@ -184,6 +195,32 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     if len(data) == 1:                                   # univariate by assumption (:399-400)
         return _FunctionalDepthUnivariate(df=data[0], depths=depth)
     return _FunctionalDepthSeries(df=data[0], depths=depth)   # multivariate (:401-402)
+
+
+def FunctionalBoxplot(data, depths=None, *, alpha=0.5, factor=1.5, levels=(), device=None,
+                      **depth_kwargs) -> FunctionalBoxplotResult:
+    """The functional boxplot of univariate curves (Sun & Genton 2011): the envelope of the deepest fraction `alpha` of
+    the curves, the fence `factor` times its pointwise width beyond it, the curves that leave the fence somewhere (the
+    outliers) and the envelope of the others (the whiskers), all in one device call.
+
+    data: a DataFrame whose columns are the curves, or a list of one.  depths: a Series or a depth result indexed by the
+    column labels -- any depth, the user's own or a K-sampled one included.  depths=None computes
+    FunctionalDepth([data], **depth_kwargs) with relax=True unless given: the modified band depth, the paper's choice;
+    containment='extremal' gives the regions of Narisetty & Nair (2016) without their simultaneous-coverage calibration.
+    levels: further fractions whose regions are returned (and drawn) beside `alpha`.  Curves of equal depth are ranked in
+    column order.
+    ValueError, before anything is uploaded: more than one frame, duplicate labels, NaN in the data or the depths, depths
+    that do not cover every column exactly once, a fraction outside (0, 1], more than 8 distinct fractions, a negative or
+    non-finite factor."""
+    df, X, fr, box = _boxplot._check_boxplot(data, alpha, factor, levels)
+    if depths is None:
+        depth_kwargs.setdefault('relax', True)
+        depths = FunctionalDepth([df], device=device, **depth_kwargs)
+    else:
+        if depth_kwargs:
+            raise ValueError(f'depths are given: {sorted(depth_kwargs)} would have no effect.')
+        depths = _boxplot._aligned_depths(df, depths)
+    return _boxplot._functional_boxplot(df, X, fr, box, depths, factor, device=device)
 
 
 def ProbabilisticDepth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compute=None, K=None, J=2, relax=False, *,

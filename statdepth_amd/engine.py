@@ -437,6 +437,67 @@ def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
                    workspace=lambda: _sized(dev, size()))
 
 
+def central_regions_row_capacity():
+    """The most curves of the row-resident route of sd_central_regions (whole rows in one workgroup's registers); above
+    it the call goes through column blocks.  (torch first, as in _lib: a test may ask this before any device call.)"""
+    torch()
+    return int(_native.load().sd_central_regions_row_capacity())
+
+
+def central_regions_workspace_bytes(T, n, L, curve_major=False):
+    """The workspace sd_central_regions needs for a T x n matrix and L levels: a fence (16 T bytes), the counts (8 n) and,
+    above the row capacity, the column blocks' min / max; 0 for a shape or L the call refuses.  curve_major: the matrix is
+    F-contiguous and takes a time-major copy (8 T n) as well."""
+    torch()
+    lib = _native.load()
+    T, n = int(T), int(n)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return int(lib.sd_central_regions_workspace_bytes(T, n, st, sn, int(L)))
+
+
+def central_regions(X, level, L=None, box=None, factor=1.5, whiskers=True, device=None, outside=True, fence=True):
+    """(env, fence, outside, whisker) of the functional boxplot (sd_central_regions); the entries not asked for are None.
+    X: T x n, NaN-free (the depth layer checks; this function takes its array as it is).  level: n bytes in 0 .. L, region l
+    = { i : level[i] <= l }, a level >= L in no region.  L: the number of regions (default: min(8, max(level) + 1), so that every
+    level present names a region).
+    env: float64 [L, 2, T], min and max of every region per timepoint.  box=None: envelopes only.  box in [0, L): fence
+    float64 [2, T] = lower - factor * (upper - lower), upper + factor * (upper - lower) of region `box`; outside int32
+    [n, 2], the timepoints at which a curve lies below / above the fence; whisker float64 [2, T], min and max over the
+    curves with no such timepoint.  whiskers=False, outside=False, fence=False leave the output out (whiskers without
+    outside keep the counts on the device); the others do not change."""
+    t = torch()
+    lv = np.ascontiguousarray(np.asarray(level, dtype=np.uint8))
+    if lv.ndim != 1 or lv.shape[0] != np.shape(X)[1]:
+        raise ValueError("level must hold one byte per curve")
+    L = min(8, int(lv.max()) + 1) if L is None else int(L)
+    if not 1 <= L <= 8:
+        raise ValueError(f"L must be in [1, 8], got {L}")
+    b = -1 if box is None else int(box)
+    if not (box is None or 0 <= b < L):
+        raise ValueError("box must be None (envelopes only) or the index of a region")
+    if not (np.isfinite(factor) and factor >= 0):
+        raise ValueError("the fence factor must be finite and not negative")
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    lvd = t.from_numpy(lv).to(dev)
+    fenced = b >= 0
+    env = t.empty((L, 2, M.T), dtype=t.float64, device=dev)
+    fen = t.empty((2, M.T), dtype=t.float64, device=dev) if fenced and fence else None
+    cnt = t.empty((M.n, 2), dtype=t.int32, device=dev) if fenced and outside else None
+    whi = t.empty((2, M.T), dtype=t.float64, device=dev) if fenced and whiskers else None
+    ptr = lambda x: x.data_ptr() if x is not None else None
+
+    def call(X_, T_, n_, st_, sn_, level_, L_, box_, factor_, fence_, outside_, whisker_, env_, ws_, ws_bytes_, stream_):
+        return lib.sd_central_regions(X_, T_, n_, st_, sn_, level_, L_, box_, factor_, env_, fence_, outside_, whisker_, ws_,
+                                      ws_bytes_, stream_)
+
+    _launch(dev, call, env, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, lvd.data_ptr(), L, b, float(factor), ptr(fen), ptr(cnt),
+            ptr(whi), workspace=lambda: _sized(dev, lib.sd_central_regions_workspace_bytes(M.T, M.n, M.st, M.sn, L)),
+            return_tensor=True)
+    return tuple(x.cpu().numpy() if x is not None else None for x in (env, fen, cnt, whi))
+
+
 # Point clouds.  Every depth of K4, K5, K7, K10, K11, K12 and K13 is asked for in three forms (DESIGN.md, "Point clouds: the three
 # forms"): row targets[q] of P inside P, the external point Q[q] inside P u {Q[q]}, the last member of block q inside the
 # block.  The public functions below name the C entry point and the form; _points does the rest.
