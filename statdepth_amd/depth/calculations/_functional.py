@@ -18,7 +18,7 @@ from scipy.special import binom
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
 from ._containment import _is_order_depth, _is_rank_depth, _select_containment
-from ._helper import DepthDegeneracy, _deep_check, _handle_depth_errors
+from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._rank import _rank_depth_values
 
 __all__ = ['_functionaldepth', '_samplefunctionaldepth']
@@ -74,10 +74,7 @@ def _univariate_depths(df: pd.DataFrame, cols, J: int, relax: bool, device=None,
         if J > 4:
             raise NotImplementedError('strict band depth (relax=False) is implemented for J <= 4')
         counts = engine.bd_strict_counts(X, tg, J=J, device=device).astype(np.float64)
-    depth = np.zeros(len(tg), dtype=np.float64)
-    for j in range(2, J + 1):
-        depth += counts[:, j - 2] / binom(n, j)        # (:253)
-    return depth
+    return _band_depth_sum(counts, n, J)               # (:253)
 
 
 def _callable_band_depth(data: pd.DataFrame, curve, relax: bool, containment, J: int) -> float:
@@ -117,24 +114,19 @@ def _componentwise_band_depth(data: List[pd.DataFrame], to_compute, J: int, rela
     P = _curves_tensor(data)
     n, T, d = P.shape
     tg = np.asarray(list(f), dtype=np.int64)
-    depth = np.zeros(len(tg), dtype=np.float64)
     if relax:
         if J > 4:
             raise NotImplementedError("'r2_enum' with relax=True is implemented for J <= 4")
         if J == 2:
-            depth += engine.multi_band_counts(P, tg, device=device).astype(np.float64) / T / binom(n, 2)
+            counts = engine.multi_band_counts(P, tg, device=device).astype(np.float64)[:, None] / T
         else:
             counts = engine.multi_band_j_counts(P, tg, J=J, device=device).astype(np.float64) / T
-            for j in range(2, J + 1):
-                depth += counts[:, j - 2] / binom(n, j)
     else:
         if J > 4:
             raise NotImplementedError('strict band depth (relax=False) is implemented for J <= 4')
         X = P.reshape(n, T * d).T                        # rows = (timepoint, feature), columns = curves; no copy
         counts = engine.bd_strict_counts(X, tg, J=J, device=device).astype(np.float64)
-        for j in range(2, J + 1):
-            depth += counts[:, j - 2] / binom(n, j)
-    return pd.Series(index=f, data=depth)
+    return pd.Series(index=f, data=_band_depth_sum(counts, n, J))
 
 
 def _ranked_frame(data, J, containment: str, deep_check=False):
@@ -306,10 +298,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
         df = orig                                        # (:183) the pool the reference's loop leaves behind
     if batched:
         # every (target, block) pair of the estimator in ONE launch
-        width = max(len(b) for b in blocks)
-        mem = np.full((len(blocks), width), -1, dtype=np.int32)
-        for i, b in enumerate(blocks):
-            mem[i, :len(b)] = b
+        mem = _padded_members(blocks)
         X = full.to_numpy(dtype=np.float64)
         T = X.shape[0]
         if relax:
@@ -319,8 +308,6 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
             counts = engine.bd_strict_subset_counts(X, mem, np.asarray(block_targets, dtype=np.int32),
                                                     device=device).astype(np.float64)[:, None]
         sizes = np.array([len(b) for b in blocks], dtype=np.float64)
-        depth = np.zeros(len(blocks))
-        for j in range(2, J + 1):
-            depth += counts[:, j - 2] / binom(sizes, j)  # (:253) n = block size including the target
+        depth = _band_depth_sum(counts, sizes, J)        # (:253) n = block size including the target
         samples = [np.mean(depth[i * K:(i + 1) * K]) for i in range(len(orig.columns))]
     return pd.Series(index=df.columns, data=samples)     # (:186)

@@ -8,10 +8,28 @@ so callers' try/except blocks and message matching keep working.  The checks are
 from typing import Callable
 
 import numpy as np
+from scipy.special import binom
 
 
 class DepthDegeneracy(Exception):
     """Depth is not well defined for this input (degenerate simplices, empty sample blocks ...)."""
+
+
+def _padded_members(blocks) -> np.ndarray:
+    """The int32 member matrix of the subset kernels: row i holds the indices of blocks[i], then -1 up to the longest."""
+    mem = np.full((len(blocks), max(len(b) for b in blocks)), -1, dtype=np.int32)
+    for i, b in enumerate(blocks):
+        mem[i, :len(b)] = b
+    return mem
+
+
+def _band_depth_sum(counts: np.ndarray, n, J: int) -> np.ndarray:
+    """sum_{j=2..J} counts[:, j-2] / binom(n, j), the band-depth normalisation (_functional.py:253): n counts the target,
+    a Python int or the float array of block sizes; the caller has divided by T where the counts are over timepoints."""
+    depth = np.zeros(counts.shape[0], dtype=np.float64)
+    for j in range(2, J + 1):
+        depth += counts[:, j - 2] / binom(n, j)
+    return depth
 
 
 def _n_observations_too_few(data, J):

@@ -14,14 +14,15 @@ of direction set) is another extension; DESIGN.md §3 K12 states its definition 
 containment='simplex_exact' is the reference's simplex depth of a planar cloud counted by an angular sweep with exact signs
 (sd_simplicial2_*): O(n log^2 n) per point where 'simplex' enumerates C(n - 1, 3) triangles.
 """
-from typing import Union
+from dataclasses import dataclass
+from typing import Callable, Optional, Union
 
 import numpy as np
 import pandas as pd
 from scipy.special import binom
 
 from ... import engine
-from ._helper import DepthDegeneracy
+from ._helper import DepthDegeneracy, _padded_members
 
 __all__ = ['_pointwisedepth', '_samplepointwisedepth']
 
@@ -48,8 +49,8 @@ def _hull_volume(P: np.ndarray) -> float:
         raise DepthDegeneracy(_OJA_HULL_MESSAGE) from e
 
 
-def _oja_check_dim(d: int) -> None:
-    if d > 8:
+def _oja_check(P: np.ndarray) -> None:
+    if P.shape[1] > 8:
         raise NotImplementedError('oja depth is implemented for d <= 8')
 
 
@@ -83,9 +84,8 @@ def _halfspace_check(P: np.ndarray) -> None:
 
 
 def _halfspace_setup(P: np.ndarray, directions, seed):
-    """Host checks of containment='halfspace', then the k x d direction array -- or None for the exact depth of a planar
+    """The k x d direction array of containment='halfspace' for a checked cloud -- or None for the exact depth of a planar
     cloud (directions='exact', d = 2: no direction set, K11)."""
-    _halfspace_check(P)
     d = P.shape[1]
     if not isinstance(directions, str):
         return _halfspace_directions(directions, seed, d)
@@ -124,9 +124,8 @@ def _projection_check(P: np.ndarray) -> None:
 
 
 def _projection_setup(P: np.ndarray, directions, seed) -> np.ndarray:
-    """Host checks of containment='projection', then the k x d direction array (as for halfspace: an int with `seed`, or
+    """The k x d direction array of containment='projection' for a checked cloud (as for halfspace: an int with `seed`, or
     an array used as given)."""
-    _projection_check(P)
     if isinstance(directions, str):
         if directions == 'exact':
             raise NotImplementedError("projection depth has no exact form: directions='exact' belongs to "
@@ -138,9 +137,92 @@ def _projection_setup(P: np.ndarray, directions, seed) -> np.ndarray:
     return U
 
 
-def _projection_depth(outlyingness: np.ndarray) -> np.ndarray:
-    """1 / (1 + O) in numpy; O = inf gives 0.0."""
-    return 1.0 / (1.0 + np.asarray(outlyingness, dtype=np.float64))
+@dataclass(frozen=True)
+class _Family:
+    """One point-cloud depth family.  rows / blocks / external: the engine function of each form, by name (looked up on
+    `engine` when it is called).  depth(raw, N, d, vols): its raw output to depths; N is the size of each target's sample,
+    the target included (n, the block lengths as a float array, n + 1 for an external point), vols the samples' hull
+    volumes where `hull` asks for them.  check(P): the host check of a point array.  setup(P, directions, seed): the
+    direction array of a checked cloud, or None for the `exact` kind.  max_block: the largest K-block the blocks form takes."""
+    rows: str
+    blocks: str
+    external: Optional[str]
+    depth: Callable
+    check: Optional[Callable] = None
+    setup: Optional[Callable] = None
+    hull: bool = False
+    max_block: Optional[int] = None
+    exact: Optional['_Family'] = None
+
+
+# the halfspace depth itself for d <= 2 (DESIGN §3 K11), seed unused; no external form
+_HALFSPACE_EXACT = _Family('halfspace_exact_counts', 'halfspace_exact_subset_counts', None,
+                           depth=lambda raw, N, d, vols: raw.astype(np.float64) / N)
+
+_FAMILIES = {
+    # (d+1)-subsets of the others whose simplex contains the point, over binom(N, d + 1): N INCLUDES the point (:38,56)
+    'simplex': _Family('pointcloud_simplex_counts', 'pointcloud_simplex_subset_counts',
+                       'pointcloud_simplex_external_counts',
+                       depth=lambda raw, N, d, vols: raw.astype(np.float64) / binom(N, d + 1)),
+    # the same depth for d = 2 with exact signs in place of the tolerance, by angular sweep (DESIGN §3 K13)
+    'simplex_exact': _Family('simplicial_exact_counts', 'simplicial_exact_subset_counts',
+                             'simplicial_exact_external_counts',
+                             depth=lambda raw, N, d, vols: raw.astype(np.float64) / binom(N, 3),
+                             check=_simplex_exact_check),
+    'l1': _Family('l1_depth', 'l1_subset_depth', 'l1_external_depth',
+                  depth=lambda raw, N, d, vols: raw),    # (:148-150)
+    # (:175-205) with every other row of the sample in the subsets, also for a to_compute subset; the normaliser is the
+    # hull of the sample the depth refers to: P, the block, or the intact F u {g} (DESIGN §4)
+    'oja': _Family('oja_volume_sums', 'oja_subset_volume_sums', 'oja_external_volume_sums',
+                   depth=lambda raw, N, d, vols: raw / vols, check=_oja_check, hull=True),
+    # An extension (no such string in the reference): min over the directions of min(#{p.u <= x.u}, #{p.u >= x.u}),
+    # the point itself and ties counted, over N -- the random Tukey depth, an upper bound of the exact halfspace
+    # depth for d >= 2 and exact for d = 1 (DESIGN §3 K10).  The sample, its target included, is what is counted.
+    'halfspace': _Family('halfspace_counts', 'halfspace_subset_counts', 'halfspace_external_counts',
+                         depth=_HALFSPACE_EXACT.depth, check=_halfspace_check, setup=_halfspace_setup,
+                         exact=_HALFSPACE_EXACT),
+    # An extension (no such string in the reference): 1 / (1 + O), O = max over the directions of
+    # |x.u - med(S.u)| / MAD(S.u), the Stahel-Donoho outlyingness over the direction set (DESIGN §3 K12); med and MAD
+    # of the sample S, its target included; O = inf gives 0.0
+    'projection': _Family('projection_outlyingness', 'projection_subset_outlyingness',
+                          'projection_external_outlyingness',
+                          depth=lambda raw, N, d, vols: 1.0 / (1.0 + np.asarray(raw, dtype=np.float64)),
+                          check=_projection_check,
+                          setup=_projection_setup, max_block=_PROJECTION_MAX_BLOCK),
+}
+
+
+def _family(containment) -> _Family:
+    if containment == 'mahalanobis':
+        raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
+    if not isinstance(containment, str) or containment not in _FAMILIES:
+        raise ValueError(f'{containment} is not a valid containment measure. ')   # (:63-64)
+    return _FAMILIES[containment]
+
+
+def _host_side(fam: _Family, directions, seed, *arrays):
+    """Everything a family refuses on the host: its check of every array, in order, then its directions from the first.
+    Returns (the family -- its exact kind where the set-up gave no direction set --, the direction array or None)."""
+    if fam.check is not None:
+        for A in arrays:
+            fam.check(A)
+    U = None if fam.setup is None else fam.setup(arrays[0], directions, seed)
+    return (fam.exact if U is None and fam.exact is not None else fam), U
+
+
+def _hulls(fam: _Family, samples) -> Optional[np.ndarray]:
+    """Hull volume of each target's sample (`samples()` yields them), on the host: a degenerate sample never reaches the
+    GPU.  None for a family that does not ask for it."""
+    return np.array([_hull_volume(S) for S in samples()], dtype=np.float64) if fam.hull else None
+
+
+def _engine_call(fam: _Family, form: str, P, sel, U, **kw) -> np.ndarray:
+    """The family's engine function of `form` ('rows', 'blocks', 'external') on the selector `sel` (row positions, the
+    padded member matrix, the external points)."""
+    f = getattr(engine, getattr(fam, form))
+    if U is None:
+        return f(P, sel, **kw)
+    return f(P, U, sel, **kw) if form == 'rows' else f(P, sel, U, **kw)
 
 
 def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None, containment='simplex',
@@ -148,22 +230,7 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
     n, d = data.shape
     if to_compute is None:
         to_compute = data.index                          # (:41-42)
-    if containment == 'simplex':
-        P = data.to_numpy(dtype=np.float64)
-        counts = engine.pointcloud_simplex_counts(P, _row_positions(data, to_compute), device=device)
-        depths = counts.astype(np.float64) / binom(n, d + 1)     # n INCLUDES the point (:38,56)
-        return pd.Series(index=to_compute, data=depths)
-    elif containment == 'simplex_exact':
-        # the same depth for d = 2 with exact signs in place of the tolerance, by angular sweep
-        P = data.to_numpy(dtype=np.float64)
-        _simplex_exact_check(P)
-        counts = engine.simplicial_exact_counts(P, _row_positions(data, to_compute), device=device)
-        return pd.Series(index=to_compute, data=counts.astype(np.float64) / binom(n, 3))
-    elif containment == 'l1':
-        P = data.to_numpy(dtype=np.float64)
-        depths = engine.l1_depth(P, _row_positions(data, to_compute), device=device)
-        return pd.Series(index=to_compute, data=depths)          # (:150)
-    elif containment in ('linf', 'linf_relax'):
+    if containment in ('linf', 'linf_relax'):
         # An extension (the reference knows no such string and raises ValueError, :63-64): the L-infinity / box
         # containment SURVEY 8 P4 spells out with reference semantics -- the band depth of the points read as curves over
         # their coordinates, FunctionalDepth([data.T]).  'linf': the share of pairs of other points whose bounding box
@@ -171,64 +238,32 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
         from ._functional import _univariate_depths
         depths = _univariate_depths(data.T, list(to_compute), 2, containment == 'linf_relax', device=device)
         return pd.Series(index=to_compute, data=depths)
-    elif containment == 'oja':
-        # (:175-205) with every other row in the subsets, also for a to_compute subset
-        _oja_check_dim(d)
-        P = data.to_numpy(dtype=np.float64)
-        vol = _hull_volume(P)                                    # host first: a degenerate sample never reaches the GPU
-        sums = engine.oja_volume_sums(P, _row_positions(data, to_compute), device=device)
-        return pd.Series(index=to_compute, data=sums / vol)
-    elif containment == 'halfspace':
-        # An extension (no such string in the reference): min over the directions of min(#{p.u <= x.u}, #{p.u >= x.u}),
-        # the point itself and ties counted, over n -- the random Tukey depth, an upper bound of the exact halfspace
-        # depth for d >= 2 and exact for d = 1
-        # directions='exact': the halfspace depth itself for d <= 2, seed unused
-        P = data.to_numpy(dtype=np.float64)
-        U = _halfspace_setup(P, directions, seed)
-        if U is None:
-            counts = engine.halfspace_exact_counts(P, _row_positions(data, to_compute), device=device)
-        else:
-            counts = engine.halfspace_counts(P, U, _row_positions(data, to_compute), device=device)
-        return pd.Series(index=to_compute, data=counts.astype(np.float64) / n)
-    elif containment == 'projection':
-        # An extension (no such string in the reference): 1 / (1 + O), O = max over the directions of
-        # |x.u - med(P.u)| / MAD(P.u), the Stahel-Donoho outlyingness over the direction set
-        P = data.to_numpy(dtype=np.float64)
-        U = _projection_setup(P, directions, seed)
-        out = engine.projection_outlyingness(P, U, _row_positions(data, to_compute), device=device)
-        return pd.Series(index=to_compute, data=_projection_depth(out))
-    elif containment == 'mahalanobis':
-        raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    else:
-        raise ValueError(f'{containment} is not a valid containment measure. ')   # (:63-64)
+    P = data.to_numpy(dtype=np.float64)
+    fam, U = _host_side(_family(containment), directions, seed, P)
+    vols = _hulls(fam, lambda: [P])
+    raw = _engine_call(fam, 'rows', P, _row_positions(data, to_compute), U, device=device)
+    return pd.Series(index=to_compute, data=fam.depth(raw, n, d, vols))
 
 
 def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directions=None) -> np.ndarray:
-    """Depth of each block's target (its LAST row) inside the block, every block in one launch."""
-    width = max(len(b) for b in blocks)
-    mem = np.full((len(blocks), width), -1, dtype=np.int32)
-    for i, b in enumerate(blocks):
-        mem[i, :len(b)] = b
-    if containment == 'oja':                             # (:187-205) on the sample: the block's own hull
-        _oja_check_dim(P.shape[1])
-        vols = np.array([_hull_volume(P[np.asarray(b)]) for b in blocks], dtype=np.float64)
-        return engine.oja_subset_volume_sums(P, mem, device=device) / vols
-    if containment == 'halfspace':                       # the block, its target included, is the sample
-        sizes = np.array([len(b) for b in blocks], dtype=np.float64)
-        if directions is None:                           # directions='exact' in the plane
-            return engine.halfspace_exact_subset_counts(P, mem, device=device).astype(np.float64) / sizes
-        return engine.halfspace_subset_counts(P, mem, directions, device=device).astype(np.float64) / sizes
-    if containment == 'projection':                      # med and MAD of the block, its target included
-        return _projection_depth(engine.projection_subset_outlyingness(P, mem, directions, device=device))
-    if containment == 'simplex':
-        d = P.shape[1]
-        sizes = np.array([len(b) for b in blocks], dtype=np.float64)
-        counts = engine.pointcloud_simplex_subset_counts(P, mem, device=device).astype(np.float64)
-        return counts / binom(sizes, d + 1)              # (:38,56) on the sample: its size INCLUDES the point
-    if containment == 'simplex_exact':
-        sizes = np.array([len(b) for b in blocks], dtype=np.float64)
-        return engine.simplicial_exact_subset_counts(P, mem, device=device).astype(np.float64) / binom(sizes, 3)
-    return engine.l1_subset_depth(P, mem, device=device)  # (:148-150) on the sample
+    """Depth of each block's target (its LAST row) inside the block, every block in one launch.  `directions`: the
+    direction array of a family that has one; None there asks for its exact kind."""
+    fam = _family(containment)
+    if directions is None and fam.exact is not None:
+        fam = fam.exact
+    mem = _padded_members(blocks)
+    sizes = np.array([len(b) for b in blocks], dtype=np.float64)
+    vols = _hulls(fam, lambda: (P[np.asarray(b)] for b in blocks))
+    return fam.depth(_engine_call(fam, 'blocks', P, mem, directions, device=device), sizes, P.shape[1], vols)
+
+
+def _external_depths(F: np.ndarray, Q: np.ndarray, containment, directions=1000, seed=0) -> np.ndarray:
+    """Depth of every external point Q[q] inside F u {Q[q]} (n + 1 points), one launch; `directions` and `seed` default
+    to PointcloudDepth's."""
+    n, d = F.shape
+    fam, U = _host_side(_family(containment), directions, seed, F, Q)
+    vols = _hulls(fam, lambda: (np.vstack([F, Q[[r]]]) for r in range(Q.shape[0])))
+    return fam.depth(_engine_call(fam, 'external', F, Q, U), n + 1, d, vols)
 
 
 def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, containment='simplex',
@@ -240,9 +275,7 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     appended when the draw missed it (:117-118; the reference's `DataFrame.append` is gone from pandas >= 2,
     so the reference itself cannot run this path any more).  The draws are made first -- rows by position, from
     the global numpy RNG exactly as `DataFrame.sample` consumes it -- and all len(to_compute) * ss
-    (point, sample) pairs are evaluated in ONE launch (sd_pointcloud_simplex_subset_counts /
-    sd_l1_subset_depth / sd_oja_subset_volume_sums / sd_halfspace_subset_counts / sd_halfspace2_subset_counts /
-    sd_projection_subset_outlyingness / sd_simplicial2_subset_counts) instead of as many `_pointwisedepth` calls.
+    (point, sample) pairs are evaluated in ONE launch (the family's blocks form) instead of as many `_pointwisedepth` calls.
     Oja: the depth of the point inside its block -- the block's other rows in the subsets, the block's hull as the
     normaliser (the reference's is identically 0).  Halfspace: one direction set (directions, seed) for
     every block, or none (directions='exact'); neither takes anything from the global RNG.  Projection: one direction
@@ -252,21 +285,14 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
     if K == 1:
         return _pointwisedepth(data=data, to_compute=to_compute, containment=containment, device=device,
                                directions=directions, seed=seed)
-    if containment == 'mahalanobis':
-        raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    if containment not in ('simplex', 'simplex_exact', 'l1', 'oja', 'halfspace', 'projection'):
-        raise ValueError(f'{containment} is not a valid containment measure. ')
-    n, d = data.shape
-    U = None
-    if containment == 'simplex_exact':
-        _simplex_exact_check(data.to_numpy(dtype=np.float64))
-    if containment == 'halfspace':                       # host checks first: bad input never reaches the RNG or the GPU
-        U = _halfspace_setup(data.to_numpy(dtype=np.float64), directions, seed)
-    if containment == 'projection':
-        U = _projection_setup(data.to_numpy(dtype=np.float64), directions, seed)
-        if n // K + 1 > _PROJECTION_MAX_BLOCK:           # a block: n // K drawn rows, and the point where the draw missed it
-            raise NotImplementedError(f'K-sampled projection depth takes blocks of at most {_PROJECTION_MAX_BLOCK} rows '
-                                      f'(n // K drawn rows and the point itself), got {n // K + 1}: raise K')
+    fam = _family(containment)
+    n = data.shape[0]
+    P = data.to_numpy(dtype=np.float64)
+    fam, U = _host_side(fam, directions, seed, P)        # host checks first: bad input never reaches the RNG or the GPU
+    # a block: n // K drawn rows, and the point where the draw missed it
+    if fam.max_block is not None and n // K + 1 > fam.max_block:
+        raise NotImplementedError(f'K-sampled {containment} depth takes blocks of at most {fam.max_block} rows '
+                                  f'(n // K drawn rows and the point itself), got {n // K + 1}: raise K')
     if to_compute is None:
         to_compute = data.index
     ss = n // K
@@ -279,5 +305,5 @@ def _samplepointwisedepth(data: pd.DataFrame, to_compute: pd.Index = None, K=2, 
         for _ in range(ss):
             drawn = rows.sample(n=ss).to_numpy()
             blocks.append(np.append(drawn[drawn != tp], tp))          # others in draw order, the point last
-    depth = _block_depths(data.to_numpy(dtype=np.float64), blocks, containment, device=device, directions=U)
+    depth = _block_depths(P, blocks, containment, device=device, directions=U)
     return pd.Series(index=to_compute, data=depth.reshape(len(targets), ss).mean(axis=1))

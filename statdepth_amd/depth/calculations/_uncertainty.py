@@ -19,12 +19,11 @@ from itertools import combinations
 import numpy as np
 import pandas as pd
 from scipy.integrate import quad
-from scipy.special import binom
 from scipy.stats import norm
 
 from ... import engine
 from ._functional import _positions, _require_unique_labels, _sample_blocks
-from ._helper import DepthDegeneracy, _handle_depth_errors
+from ._helper import DepthDegeneracy, _band_depth_sum, _handle_depth_errors, _padded_members
 
 __all__ = ['probabilistic_normal_depth', 'probabilistic_poisson_depth']
 
@@ -133,9 +132,7 @@ def _probabilistic_band_depth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compu
         tg = _positions(data, cols)
         sums = engine.prob_band_sums(mu, var, relax, tg, device=device)
         counts = sums / T if relax else sums             # as _univariate_depths normalises its counts
-        depth = np.zeros(len(tg), dtype=np.float64)
-        depth += counts / binom(n, 2)
-        return pd.Series(index=cols, data=depth)
+        return pd.Series(index=cols, data=_band_depth_sum(counts[:, None], n, 2))
 
     orig = data.loc[:, cols]
     ss = n // K
@@ -147,13 +144,9 @@ def _probabilistic_band_depth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compu
         block_targets.append(data.columns.get_loc(col))
     if not blocks:
         return pd.Series(index=orig.columns, data=[], dtype=np.float64)
-    width = max(len(b) for b in blocks)
-    mem = np.full((len(blocks), width), -1, dtype=np.int32)
-    for i, b in enumerate(blocks):
-        mem[i, :len(b)] = b
+    mem = _padded_members(blocks)
     sums = engine.prob_band_sums(mu, var, relax, np.asarray(block_targets, dtype=np.int64), mem, device=device)
     counts = sums / T if relax else sums
     sizes = np.array([len(b) for b in blocks], dtype=np.float64)
-    depth = np.zeros(len(blocks))
-    depth += counts / binom(sizes, 2)                    # n = block size including the target
+    depth = _band_depth_sum(counts[:, None], sizes, 2)   # n = block size including the target
     return pd.Series(index=orig.columns, data=[np.mean(depth[i * K:(i + 1) * K]) for i in range(len(orig.columns))])

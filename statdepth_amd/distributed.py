@@ -9,6 +9,7 @@ ranks.  The only other communication is the optional gather of the (tiny) result
 import numpy as np
 
 from . import engine
+from .depth.calculations._helper import _band_depth_sum
 
 # Pieces the exchanges are cut into so that one piece travels (RCCL's stream) while the one before it is computed on (the
 # current stream): sub-slices of every rank's time slice in mode "time", row chunks of the all-gather in mode "targets".
@@ -423,7 +424,6 @@ def sharded_functional_depth(df_local, J=2, relax=True, algo="auto", group=None,
     """
     import pandas as pd
     import torch
-    from scipy.special import binom
     X = np.ascontiguousarray(df_local.to_numpy(dtype=np.float64))
     hooks = (_compute, _compute_all, _compute_strict)
     dev = engine._device() if all(h is None for h in hooks) else torch.device("cpu")
@@ -436,7 +436,4 @@ def sharded_functional_depth(df_local, J=2, relax=True, algo="auto", group=None,
     else:
         counts = sharded_bd_strict_counts(X_loc, J=J, group=group, sizes=sizes,
                                           _compute=_compute_strict).cpu().numpy().astype(np.float64)
-    depth = np.zeros(X.shape[1])
-    for j in range(2, J + 1):
-        depth += counts[:, j - 2] / binom(n, j)
-    return pd.Series(index=df_local.columns, data=depth)
+    return pd.Series(index=df_local.columns, data=_band_depth_sum(counts, n, J))

@@ -15,10 +15,11 @@ from typing import List
 
 import numpy as np
 import pandas as pd
-from scipy.special import binom
 
 from .. import engine
+from ..depth.calculations import _pointcloud
 from ..depth.calculations._containment import _is_order_depth, _is_rank_depth
+from ..depth.calculations._helper import _band_depth_sum
 from ..depth.depth import FunctionalDepth, PointcloudDepth
 
 
@@ -81,10 +82,7 @@ def _depths_of_external(F: pd.DataFrame, Gcols: pd.DataFrame, J: int, relax: boo
         counts = engine.mbd_external_counts(Fx, Gx, J=J).astype(np.float64) / T
     else:
         counts = engine.bd_strict_external_counts(Fx, Gx).astype(np.float64)[:, None]      # `c // T`: every timepoint
-    depth = np.zeros(Gx.shape[1])
-    for j in range(2, J + 1):
-        depth += counts[:, j - 2] / binom(nF + 1, j)
-    return depth
+    return _band_depth_sum(counts, nF + 1, J)
 
 
 def _fresh_label(frame_labels, stem):
@@ -164,7 +162,7 @@ def _functionalhomogeneity(F: List[pd.DataFrame], G: List[pd.DataFrame], K=None,
 # ---- point clouds (:155-200) -------------------------------------------------------------------------------------
 # The reference appends one point of G to F, asks for that point's depth, and drops it again -- once for G's deepest
 # point and, for P3, once per point of G.  Here the points of G are EXTERNAL targets of one launch against F
-# (sd_pointcloud_simplex_external_counts / sd_l1_external_depth); the sample the depth refers to is F u {g}
+# (the external form of the family, _pointcloud._external_depths); the sample the depth refers to is F u {g}
 # (n_F + 1 points), as in the reference's temporary frame.  With K (block sampling) the estimator draws from the
 # global RNG per call, so the calls stay separate -- each is itself one launch (_samplepointwisedepth).
 def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -> np.ndarray:
@@ -175,35 +173,8 @@ def _external_point_depths(F: pd.DataFrame, pts: pd.DataFrame, K, containment) -
             Fg = pd.concat([F, pts.iloc[[r], :].set_axis([lab], axis=0)])
             out.append(PointcloudDepth(Fg, to_compute=[lab], K=K, containment=containment).loc[lab])
         return np.asarray(out, dtype=np.float64)
-    Fx, Qx = F.to_numpy(dtype=np.float64), pts.to_numpy(dtype=np.float64)
-    n, d = Fx.shape
-    if containment == 'simplex':
-        return engine.pointcloud_simplex_external_counts(Fx, Qx).astype(np.float64) / binom(n + 1, d + 1)
-    if containment == 'simplex_exact':             # the same normaliser, the counts by the exact sweep (d = 2)
-        from ..depth.calculations._pointcloud import _simplex_exact_check
-        _simplex_exact_check(Fx)
-        _simplex_exact_check(Qx)
-        return engine.simplicial_exact_external_counts(Fx, Qx).astype(np.float64) / binom(n + 1, 3)
-    if containment == 'l1':
-        return engine.l1_external_depth(Fx, Qx)
-    if containment == 'oja':                       # subsets of F, normaliser the hull of the intact F u {g}
-        from ..depth.calculations._pointcloud import _hull_volume, _oja_check_dim
-        _oja_check_dim(d)
-        vols = np.array([_hull_volume(np.vstack([Fx, Qx[[r]]])) for r in range(Qx.shape[0])], dtype=np.float64)
-        return engine.oja_external_volume_sums(Fx, Qx) / vols
-    if containment == 'halfspace':                 # counted inside F u {g}: n + 1 points, PointcloudDepth's default directions
-        from ..depth.calculations._pointcloud import _halfspace_check, _halfspace_directions
-        _halfspace_check(Fx)
-        _halfspace_check(Qx)
-        return engine.halfspace_external_counts(Fx, Qx, _halfspace_directions(1000, 0, d)).astype(np.float64) / (n + 1)
-    if containment == 'projection':                # med and MAD of F u {g} per external point, the default directions
-        from ..depth.calculations._pointcloud import _halfspace_directions, _projection_check, _projection_depth
-        _projection_check(Fx)
-        _projection_check(Qx)
-        return _projection_depth(engine.projection_external_outlyingness(Fx, Qx, _halfspace_directions(1000, 0, d)))
-    if containment == 'mahalanobis':
-        raise NotImplementedError(f'{containment} depth is outside the band-depth hot path this engine covers')
-    raise ValueError(f'{containment} is not a valid containment measure. ')
+    # Oja: subsets of F, the hull of the intact F u {g}; direction sets: PointcloudDepth's default
+    return _pointcloud._external_depths(F.to_numpy(dtype=np.float64), pts.to_numpy(dtype=np.float64), containment)
 
 
 def _pointcloudhomogeneity(F: pd.DataFrame, G: pd.DataFrame, K=None, containment='simplex', method='p1'):
