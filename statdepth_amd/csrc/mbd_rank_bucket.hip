@@ -1024,20 +1024,8 @@ __global__ __launch_bounds__(256) void rank_finalize4_kernel(const u32 *__restri
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-bool mbd_rank_bucket_supported(i64 T, i64 n, int J) {
-    (void)T;
-    return n > 1 && n <= 16384 && J >= 2 && J <= 3;       // measured faster than the sort kernels from n = 600 to 16384
-}
-
-// upper bound of the grid the launcher will use (the partial totals are sized by it)
-int mbd_rank_bucket_max_grid() { return 2 * device_cus(); }
-
-// the workgroups' partial totals: all this path keeps in HBM
-size_t mbd_rank_bucket_partial_bytes(i64 n, int J) { return align_up((size_t)mbd_rank_bucket_max_grid() * (J - 1) * n * 8, 256); }
-size_t mbd_rank_bucket_workspace_bytes(i64 rows, i64 n, int J) {
-    (void)rows;
-    return mbd_rank_bucket_partial_bytes(n, J) + 512;
-}
+// the workgroups' partial totals: all this path keeps in HBM (2 * CUs: the upper bound of the grid the launchers use)
+size_t mbd_rank_bucket_partial_bytes(i64 n, int J) { return align_up((size_t)2 * device_cus() * (J - 1) * n * 8, 256); }
 
 constexpr int RB_CAP = 127;
 template <int NT, int E, int LNB, int J, int U2>
@@ -1046,7 +1034,7 @@ static int launch_bucket_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *pa
     using C = RBCfg<NT, E, LNB, U2>;
     auto kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2>;
     if constexpr (J == 2) {
-        if (p32 == 2) kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, true>;
+        if (p32 == RB_PARTIAL_ACC32) kf = rank_bucket_kernel<NT, E, LNB, J, RB_CAP, U2, true>;
     }
     const size_t lds = C::lds_bytes((int)n);
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
@@ -1086,39 +1074,28 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
         if (masked) kspin = 1;
         if (kspin < 1) kspin = 1;
     }
-    hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, partial, 2, (u32 *)nullptr, rowflag, gate, epoch, out, Gsum, fblocks,
-                       done, kspin);
+    hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, partial, RB_PARTIAL_ACC32, (u32 *)nullptr, rowflag, gate, epoch, out,
+                       Gsum, fblocks, done, kspin);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
 
+// log2 of the buckets for E = ceil(n / 1024) keys per thread, J = 2, 3 or 0 (the pair-image mode): 8192 buckets up to n = 4096,
+// 16384 above while keys + histogram fit the 160 KiB of LDS (8192 at E = 16), 32768 at E = 10, 11 for J = 2 and the pair-image
+// mode (measured: -2..-3.5 % on continuous rows, -7 % with outlying curves, +6 % on tie-heavy rows whose closed form only
+// pays the longer prefix sum; J = 3 stays at 16384: the wider prefix arrays push it further into scratch)
+constexpr int rb_lnb(int E, int J) { return (E <= 4 || E == 16) ? 13 : ((E == 10 || E == 11) && J != 3) ? 15 : 14; }
+
+// fold (J = 2, 3) and image mode (J = 0, partial = the image, nnan_img = its NaN counts); first member pass: 3 x 16 bytes
 template <int J>
-static int launch_bucket_j(const double *Y, i64 n, i64 row0, i64 rows, u64 *partial, int p32, int G, hipStream_t s) {
-    // E = ceil(n / 1024); 8192 buckets up to n = 4096, 16384 above while keys + histogram fit the 160 KiB of LDS
-    // (8192 at E = 16), 32768 at E = 10, 11 for J = 2 and the pair-image mode (measured: -2..-3.5 % on continuous
-    // rows, -7 % with outlying curves, +6 % on tie-heavy rows whose closed form only pays the longer prefix sum;
-    // J = 3 stays at 16384: the wider prefix arrays push it further into scratch); first member pass: 3 x 16 bytes
-#define RB_ARGS Y, n, row0, rows, partial, p32, G, s
-    const int E = (int)((n + 1023) / 1024);
-    switch (E) {
-        case 1: return launch_bucket_cfg<1024, 1, 13, J, 3>(RB_ARGS);
-        case 2: return launch_bucket_cfg<1024, 2, 13, J, 3>(RB_ARGS);
-        case 3: return launch_bucket_cfg<1024, 3, 13, J, 3>(RB_ARGS);
-        case 4: return launch_bucket_cfg<1024, 4, 13, J, 3>(RB_ARGS);
-        case 5: return launch_bucket_cfg<1024, 5, 14, J, 3>(RB_ARGS);
-        case 6: return launch_bucket_cfg<1024, 6, 14, J, 3>(RB_ARGS);
-        case 7: return launch_bucket_cfg<1024, 7, 14, J, 3>(RB_ARGS);
-        case 8: return launch_bucket_cfg<1024, 8, 14, J, 3>(RB_ARGS);
-        case 9: return launch_bucket_cfg<1024, 9, 14, J, 3>(RB_ARGS);
-        case 10: return launch_bucket_cfg<1024, 10, (J == 3 ? 14 : 15), J, 3>(RB_ARGS);
-        case 11: return launch_bucket_cfg<1024, 11, (J == 3 ? 14 : 15), J, 3>(RB_ARGS);
-        case 12: return launch_bucket_cfg<1024, 12, 14, J, 3>(RB_ARGS);
-        case 13: return launch_bucket_cfg<1024, 13, 14, J, 3>(RB_ARGS);
-        case 14: return launch_bucket_cfg<1024, 14, 14, J, 3>(RB_ARGS);
-        case 15: return launch_bucket_cfg<1024, 15, 14, J, 3>(RB_ARGS);
-        case 16: return launch_bucket_cfg<1024, 16, 13, J, 3>(RB_ARGS);
+static int launch_bucket_e(const double *Y, i64 n, i64 row0, i64 rows, u64 *partial, int p32, int G, hipStream_t s,
+                           u32 *nnan_img = nullptr) {
+#define RB_E(E_) case E_: return launch_bucket_cfg<1024, E_, rb_lnb(E_, J), J, 3>(Y, n, row0, rows, partial, p32, G, s, nnan_img);
+    switch ((int)((n + 1023) / 1024)) {
+        RB_E(1) RB_E(2) RB_E(3) RB_E(4) RB_E(5) RB_E(6) RB_E(7) RB_E(8) RB_E(9) RB_E(10) RB_E(11) RB_E(12) RB_E(13) RB_E(14)
+        RB_E(15) RB_E(16)
     }
-#undef RB_ARGS
+#undef RB_E
     return fail(SD_ERR_UNSUPPORTED, "bucket kernel covers n <= 16384");
 }
 
@@ -1127,14 +1104,7 @@ int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB
     const int cus = device_cus();
     const int G = (int)(rows < cus ? rows : cus);
     if (rows > (i64)G * 2048) return fail(SD_ERR_INVALID, "bucket kernel: more than 2048 rows per workgroup in one launch");
-    u64 *img = reinterpret_cast<u64 *>(AB);
-#define RB_IM(E_, L_) case E_: return launch_bucket_cfg<1024, E_, L_, 0, 3>(Y, n, row0, rows, img, 0, G, s, nnan);
-    switch ((int)((n + 1023) / 1024)) {
-        RB_IM(1, 13) RB_IM(2, 13) RB_IM(3, 13) RB_IM(4, 13) RB_IM(5, 14) RB_IM(6, 14) RB_IM(7, 14) RB_IM(8, 14)
-        RB_IM(9, 14) RB_IM(10, 15) RB_IM(11, 15) RB_IM(12, 14) RB_IM(13, 14) RB_IM(14, 14) RB_IM(15, 14) RB_IM(16, 13)
-    }
-#undef RB_IM
-    return fail(SD_ERR_UNSUPPORTED, "bucket kernel covers n <= 16384");
+    return launch_bucket_e<0>(Y, n, row0, rows, reinterpret_cast<u64 *>(AB), RB_PARTIAL_U64, G, s, nnan);
 }
 
 // J = 2, 4096 < n <= 11264, every curve a target: rank_bucket32_kernel (two workgroups per CU; zeroes out when `first`) + the
@@ -1180,6 +1150,7 @@ int launch_rank_bucket_two_level(const double *Y, i64 n, i64 row0, i64 rows, u64
     int rc = launch_rank_bucket32(Y, n, row0, rows, P32, rowflag, gate, epoch, first ? out : nullptr, G, s);
     if (rc) return rc;
     const int G2 = G < cus ? G : cus;
+    // a table of its own, not rb_lnb: the SEL form takes 16384 buckets at E = 3, 4 and 11 too (32768 at E = 10 only)
 #define RB_SEL(E_) case E_: return launch_bucket_sel_cfg<E_, 14>(Y, n, row0, rows, partial, G2, rowflag, gate, epoch, out, G, fblocks, gate + 2, s);
     switch ((int)((n + 1023) / 1024)) {
         RB_SEL(3) RB_SEL(4) RB_SEL(5) RB_SEL(6) RB_SEL(7) RB_SEL(8) RB_SEL(9) RB_SEL(11)
@@ -1199,12 +1170,12 @@ int launch_rank_bucket(const double *Y, i64 n, i64 row0, i64 rows, int J, u64 *p
     if (rows > (i64)G * 2048) return fail(SD_ERR_INVALID, "bucket kernel: more than 2048 rows per workgroup in one launch");
     // J = 2: a workgroup's total is at most ceil(rows / G) * C(n-1, 2); below 2^32 the partials travel as u32
     const u64 per_wg = (u64)((rows + G - 1) / G) * ((u64)(n - 1) * (u64)(n - 2) / 2);
-    int p32 = (J == 2 && per_wg < ((u64)1 << 32)) ? 1 : 0;
+    int p32 = (J == 2 && per_wg < ((u64)1 << 32)) ? RB_PARTIAL_U32 : RB_PARTIAL_U64;
     // ... and 2 * total stays below 2^32 too (2 * C(v,2) + 2 N v < n^2 per row): the kernel accumulates in 32 bits
-    if (p32 && (u64)((rows + G - 1) / G) * (u64)n * (u64)n < ((u64)1 << 32) && xswitch("SD_RB_ACC64") == 0) p32 = 2;
+    if (p32 && (u64)((rows + G - 1) / G) * (u64)n * (u64)n < ((u64)1 << 32) && xswitch("SD_RB_ACC64") == 0) p32 = RB_PARTIAL_ACC32;
     *p32_out = p32;
-    if (J == 2) return launch_bucket_j<2>(Y, n, row0, rows, partial, p32, G, s);
-    if (J == 3) return launch_bucket_j<3>(Y, n, row0, rows, partial, p32, G, s);
+    if (J == 2) return launch_bucket_e<2>(Y, n, row0, rows, partial, p32, G, s);
+    if (J == 3) return launch_bucket_e<3>(Y, n, row0, rows, partial, p32, G, s);
     return fail(SD_ERR_UNSUPPORTED, "bucket kernel covers J in [2,3]");
 }
 

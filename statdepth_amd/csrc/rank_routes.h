@@ -1,6 +1,5 @@
-// rank_routes.h -- what the translation units of the rank routes call in each other, and what the strict path calls of them
-// (internal; the launchers sd_api.hip dispatches to are in sd_common.h; the strict path's own routes: strict_routes.h).  One
-// declaration per signature.
+// rank_routes.h -- the route plan of a K1+K2 call, what the translation units of the rank routes call in each other, and what
+// the strict path calls of them (internal; the strict path's own routes: strict_routes.h).  One declaration per signature.
 #pragma once
 #include "sd_common.h"
 #include "strict_routes.h"
@@ -9,11 +8,45 @@ namespace sd {
 
 constexpr u32 AB_SPECIAL = 0xFFFFFFFFu;      // u16-pair image (n <= 40 960): the curve is NaN at this timepoint
 
+// ---- the route plan of one K1+K2 call (mbd_rank_ab.hip: mbd_plan) ----
+// Every decision the size functions and the launcher take, made in one place from the shape and -- cross-check builds only --
+// the SD_RANK_IMPL, SD_RANK_ROWS_PER_BATCH, SD_MEDIUM_WIDE and SD_BIG_NOMEDIUM switches (the product's xswitch() is 0).
+// Computed per call: the tests change the environment between calls.
+enum class MbdRoute {
+    Pairwise,      // the pairwise kernel: algo says so, or auto below the thresholds
+    BucketFold,    // n <= 16 384, J <= 3: the bucket kernel folds in registers, partial totals per workgroup
+    PairImage,     // n <= 16 384 and J >= 4, or a retired sort generation: 16-bit pair image + fold
+    MediumImage,   // 16 384 < n <= 32 768, T >= 96: column blocks through one workgroup, pair image + fold
+    LargeN,        // any other n > 16 384: the chunked route (mbd_rank_big.hip)
+    RetiredV1,     // SD_RANK_IMPL = 1, J <= 3: the first-generation kernel, the whole call
+    None           // algo = rank for a shape no rank route covers (n = 1): SD_ERR_UNSUPPORTED
+};
+struct MbdPlan {
+    MbdRoute route;
+    int sorts;             // PairImage: 0 = the bucket kernel's image mode, else the retired generation (SD_RANK_IMPL) that ranks
+    i64 rpb;               // rows of a pair image (PairImage, MediumImage)
+    i64 step;              // BucketFold: rows per batch ...
+    bool tl_full, tl_last; // ... and whether a batch of `step` rows / the last batch takes the two-launch path (32-bit keys)
+    bool gather;           // ... into the totals of ALL curves inside the workspace; the call's subset is gathered at the end
+    size_t partial_bytes;  // BucketFold: the workgroups' partial totals
+    size_t ws_bytes;       // what the route's launcher gets (the caller carves it)
+};
+// all_targets: every curve is a target, in order (targets == NULL, tbegin == 0, m == n)
+MbdPlan mbd_plan(i64 T, i64 n, i64 m, int J, int algo, bool all_targets);
+// what sd_mbd_workspace_bytes reserves for algo = rank and auto: the sum over the rank routes of the shape (see there)
+size_t mbd_rank_routes_workspace_bytes(i64 T, i64 n, int J);
+// runs plan.route (any but Pairwise) with plan.ws_bytes at ws
+int launch_mbd_rank(const MbdPlan &plan, const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out,
+                    void *ws, hipStream_t s);
+
 // ---- mbd_rank_bucket.hip: the bucket kernel of n <= 16 384 and its column-block form up to 40 960 ----
-bool mbd_rank_bucket_supported(i64 T, i64 n, int J);
-int mbd_rank_bucket_max_grid();
+// the kernel's `p32` argument: how a workgroup's partial totals travel (J = 2 only above 0)
+enum : int {
+    RB_PARTIAL_U64 = 0,    // u64 blocks
+    RB_PARTIAL_U32 = 1,    // u32 blocks: ceil(rows / G) * C(n-1, 2) < 2^32
+    RB_PARTIAL_ACC32 = 2   // ... and 32-bit accumulators in the kernel: ceil(rows / G) * n^2 < 2^32
+};
 size_t mbd_rank_bucket_partial_bytes(i64 n, int J);
-size_t mbd_rank_bucket_workspace_bytes(i64 rows, i64 n, int J);
 int launch_rank_bucket(const double *Y, i64 n, i64 row0, i64 rows, int J, u64 *partial, int *p32_out, int *G_out,
                        hipStream_t s);
 int launch_rank_bucket_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s);
@@ -34,7 +67,10 @@ int launch_rank_bucket32(const double *Y, i64 n, i64 row0, i64 rows, u32 *partia
                          u64 *out_zero, int G, hipStream_t s);
 u32 rank_bucket32_epoch();
 
-// ---- mbd_rank_big.hip: the B words of every (row, curve) to img[T][n], the rows' NaN counts to nnan[T] ----
+// ---- mbd_rank_big.hip: the large-n route; its image form: the B words of every (row, curve) to img[T][n], the rows' NaN
+// counts to nnan[T] (mbd_rank_big_supported, mbd_rank_big_workspace_bytes: sd_common.h, the strict path sizes by them) ----
+int launch_mbd_rank_big(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J,
+                        u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
 int launch_rank_big_image(const double *Y, i64 T, i64 n, u32 *img, u32 *nnan, void *ws, size_t ws_bytes, hipStream_t s);
 
 // ---- the retired generations, one hook per point where a cross-check switch diverts a product route ----

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "sd_common.h"
+#include "rank_routes.h"
 #include "point_select.h"
 
 namespace sd {
@@ -87,6 +88,13 @@ static int check_matrix(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64
     if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
     if (targets == nullptr && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
     return SD_OK;
+}
+
+// 1 + floor(log2 n): the sorts' steps per key in the work estimates of K10 and K12
+static double log2_steps(i64 n) {
+    double l = 1.0;
+    for (i64 v = n; v > 1; v >>= 1) l += 1.0;
+    return l;
 }
 
 static bool is_time_major_dense(i64 n, i64 st, i64 sn) { return sn == 1 && st == n; }
@@ -188,30 +196,23 @@ int sd_stream_synchronize(void *stream) {
 // ---------------------------------------------------------------------------
 // K1+K2
 // ---------------------------------------------------------------------------
-static int resolve_mbd_algo(int algo, i64 T, i64 n, i64 m, int J) {
-    if (algo == SD_MBD_PAIRWISE || algo == SD_MBD_RANK) return algo;
-    // rank costs ~n log n per timepoint whatever m is; pairwise costs m*n.
-    if (mbd_rank_supported(T, n, J) && m >= 32) return SD_MBD_RANK;
-    // chunked rank: work ~ (n/C) sorts + (n/C)^2 searches per row whatever m is; pairwise costs m*n
-    if (mbd_rank_big_supported(T, n, J) && m >= 2048) return SD_MBD_RANK;
-    return SD_MBD_PAIRWISE;
-}
-
 size_t sd_mbd_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int J, int algo) {
     if (T <= 0 || n <= 0) return 0;
     size_t b = time_major_bytes(T, n, st, sn);
     b += align_up((size_t)T * 4, 256);   // nan_cnt
-    int a = resolve_mbd_algo(algo, T, n, m, J);
-    if (a == SD_MBD_RANK || algo == SD_MBD_AUTO)
-        b += align_up(mbd_rank_workspace_bytes(T, n, J) + mbd_rank_big_workspace_bytes(T, n, J) +
-                      mbd_rank_medium_workspace_bytes(T, n, J), 256) + 256;
+    // The sum over the rank routes of the shape, not the planned route's own size: sd_mbd_counts_wide sizes its inner workspace
+    // once, for Tc rows, and calls mbd_counts_impl on the last chunk with fewer rows, which may take another route (below 96
+    // rows the medium route hands over to the large-n route)
+    if (algo == SD_MBD_AUTO || mbd_plan(T, n, m, J, algo, true).route != MbdRoute::Pairwise)
+        b += align_up(mbd_rank_routes_workspace_bytes(T, n, J), 256) + 256;
     return b + 1024;
 }
 
+// block: the targets are the curves [tbegin, tbegin + m) (sd_mbd_counts_range), whatever m is
 static int mbd_counts_impl(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn,
-                           const int64_t *targets, int64_t tbegin, int64_t m, int J, int algo,
+                           const int64_t *targets, bool block, int64_t tbegin, int64_t m, int J, int algo,
                            int64_t *out, void *ws, size_t ws_bytes, void *stream) {
-    int rc = check_matrix(X, T, n, st, sn, targets ? targets : (const i64 *)1, m);
+    int rc = check_matrix(X, T, n, st, sn, block ? (const i64 *)1 : targets, m);
     if (rc) return rc;
     if (!targets && (tbegin < 0 || tbegin + m > n))
         return fail(SD_ERR_INVALID, "target block [%lld, %lld) outside [0, %lld)", (long long)tbegin,
@@ -224,26 +225,11 @@ static int mbd_counts_impl(const double *X, int64_t T, int64_t n, int64_t st, in
     Carver cv(ws, ws_bytes);
     const double *Y;
     if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
-    int a = resolve_mbd_algo(algo, T, n, m, J);
-    if (a == SD_MBD_RANK && mbd_rank_medium_supported(T, n, J)) {
-        size_t need = mbd_rank_medium_workspace_bytes(T, n, J);
-        void *rws = cv.take(need);
-        if (!rws) return fail(SD_ERR_WORKSPACE, "workspace too small for the medium rank route");
-        return launch_mbd_rank_medium(Y, T, n, targets, tbegin, m, J, (u64 *)out, rws, need, s);
-    }
-    if (a == SD_MBD_RANK && mbd_rank_big_supported(T, n, J)) {
-        size_t need = mbd_rank_big_workspace_bytes(T, n, J);
-        void *rws = cv.take(need);
-        if (!rws) return fail(SD_ERR_WORKSPACE, "workspace too small for the chunked rank kernel");
-        return launch_mbd_rank_big(Y, T, n, targets, tbegin, m, J, (u64 *)out, rws, need, s);
-    }
-    if (a == SD_MBD_RANK) {
-        if (!mbd_rank_supported(T, n, J))
-            return fail(SD_ERR_UNSUPPORTED, "rank kernel does not cover T=%lld n=%lld J=%d", (long long)T, (long long)n, J);
-        size_t need = mbd_rank_workspace_bytes(T, n, J);
-        void *rws = cv.take(need);
-        if (need && !rws) return fail(SD_ERR_WORKSPACE, "workspace too small for the rank kernel");
-        return launch_mbd_rank(Y, T, n, targets, tbegin, m, J, (u64 *)out, rws, need, s);
+    const MbdPlan plan = mbd_plan(T, n, m, J, algo, !targets && tbegin == 0 && m == n);
+    if (plan.route != MbdRoute::Pairwise) {
+        void *rws = cv.take(plan.ws_bytes);
+        if (plan.ws_bytes && !rws) return fail(SD_ERR_WORKSPACE, "workspace too small for the rank kernels");
+        return launch_mbd_rank(plan, Y, T, n, targets, tbegin, m, J, (u64 *)out, rws, s);
     }
     u32 *nan_cnt = (u32 *)cv.take((size_t)T * 4);
     if (!nan_cnt) return fail(SD_ERR_WORKSPACE, "workspace too small (nan counts)");
@@ -254,14 +240,13 @@ static int mbd_counts_impl(const double *X, int64_t T, int64_t n, int64_t st, in
 int sd_mbd_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn,
                   const int64_t *targets, int64_t m, int J, int algo,
                   int64_t *out, void *ws, size_t ws_bytes, void *stream) {
-    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    return mbd_counts_impl(X, T, n, st, sn, targets, 0, m, J, algo, out, ws, ws_bytes, stream);
+    return mbd_counts_impl(X, T, n, st, sn, targets, false, 0, m, J, algo, out, ws, ws_bytes, stream);
 }
 
 int sd_mbd_counts_range(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn,
                         int64_t target_begin, int64_t m, int J, int algo,
                         int64_t *out, void *ws, size_t ws_bytes, void *stream) {
-    return mbd_counts_impl(X, T, n, st, sn, nullptr, target_begin, m, J, algo, out, ws, ws_bytes, stream);
+    return mbd_counts_impl(X, T, n, st, sn, nullptr, true, target_begin, m, J, algo, out, ws, ws_bytes, stream);
 }
 
 // ---- two-limb totals: T * C(n-1, J) beyond int64 (J >= 4 at n = 10^5) -------------------------------------------
@@ -302,7 +287,7 @@ int sd_mbd_counts_wide(const double *X, int64_t T, int64_t n, int64_t st, int64_
     for (i64 t0 = 0; t0 < T; t0 += Tc) {
         const i64 rows = T - t0 < Tc ? T - t0 : Tc;
         // rows [t0, t0 + rows) of either layout: x(t, i) = X[t*st + i*sn]; a curve-major block keeps its curve stride
-        if ((rc = mbd_counts_impl(X + t0 * st, rows, n, st, sn, targets, 0, m, J, algo, (int64_t *)part, iws, inner, stream)))
+        if ((rc = mbd_counts_impl(X + t0 * st, rows, n, st, sn, targets, false, 0, m, J, algo, (int64_t *)part, iws, inner, stream)))
             return rc;
         hipLaunchKernelGGL(wide_add_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part, count,
                            (u64 *)out, t0 == 0 ? 1 : 0);
@@ -734,8 +719,7 @@ size_t sd_halfspace_min_workspace_bytes(int64_t n, int d, int64_t k) {
 
 int sd_halfspace_counts(const double *P, int64_t n, int d, const double *U, int64_t k, const int64_t *targets, int64_t m,
                         int64_t *out, void *ws, size_t ws_bytes, void *stream) {
-    double logn = 1.0;
-    for (i64 v = n; v > 1; v >>= 1) logn += 1.0;
+    const double logn = log2_steps(n);
     int rc = check_halfspace(P, n, d, U, k, m, out, n, (double)k * (double)n * ((double)d + logn));
     if (rc) return rc;
     if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
@@ -813,12 +797,6 @@ int sd_halfspace2_subset_counts(const double *P, int64_t n, const int32_t *membe
 // ---------------------------------------------------------------------------
 // K12
 // ---------------------------------------------------------------------------
-static double log2_steps(i64 n) {
-    double l = 1.0;
-    for (i64 v = n; v > 1; v >>= 1) l += 1.0;
-    return l;
-}
-
 // shape checks shared by the three entry points; `sample` = the largest sample of the call, work = the call's estimate
 static int check_projection(const double *P, i64 n, int d, const double *U, i64 k, i64 m, const void *out, i64 sample,
                             double work) {

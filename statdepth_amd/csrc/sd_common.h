@@ -72,26 +72,15 @@ bool bd_strict_subsets_supported(i64 T, int bs);
 size_t bd_strict_subsets_workspace_bytes(i64 T, i64 nb, int bs);
 int launch_bd_strict_subsets(const double *Y, i64 T, i64 n, const int *members, i64 nb, int bs, const int *target, u64 *out,
                              void *ws, size_t ws_bytes, hipStream_t s);
-// K1+K2 rank formulation
-size_t mbd_rank_workspace_bytes(i64 T, i64 n, int J);
-bool mbd_rank_supported(i64 T, i64 n, int J);
-int launch_mbd_rank(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J,
-                    u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
+// K1+K2 rank formulation: the route plan and its launcher are in rank_routes.h
 // external targets through the bucket structure (n <= 16384, J <= 3)
 bool mbd_rank_external_supported(i64 T, i64 n, i64 m, int J);
 size_t mbd_rank_external_workspace_bytes(i64 T, i64 n, i64 m, int J);
 int launch_mbd_external_rank(const double *Y, i64 T, i64 n, const double *Q, i64 m, int J, u64 *out, void *ws,
                              size_t ws_bytes, hipStream_t s);
-// K1+K2 rank formulation for n > 16384 (chunked)
+// K1+K2 rank formulation for n > 16384 (chunked): what the strict path and the route plan size its scratch by
 bool mbd_rank_big_supported(i64 T, i64 n, int J);
-// medium sizes (16 384 < n <= 40 960, T >= 96): 2 or 3 column blocks per workgroup, pair image + fold
-bool mbd_rank_medium_supported(i64 T, i64 n, int J);
-size_t mbd_rank_medium_workspace_bytes(i64 T, i64 n, int J);
-int launch_mbd_rank_medium(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out, void *ws,
-                           size_t ws_bytes, hipStream_t s);
 size_t mbd_rank_big_workspace_bytes(i64 T, i64 n, int J);
-int launch_mbd_rank_big(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J,
-                        u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
 // K3 strict
 size_t bd_strict_workspace_bytes(i64 T, i64 n, i64 m, int J);
 size_t bd_strict_min_workspace_bytes(i64 T, i64 n, i64 m, int J);

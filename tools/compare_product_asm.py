@@ -23,10 +23,7 @@ import sys
 import tempfile
 
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
-# short names of kernels that now take the point selector (point_select.h's PointSel, by value) where they took a selector
-# struct of their own file or loose targets / Q / members / bs arguments
-NEW_ARGUMENTS = ("simplex_kernel", "simplex_kernel_fast", "l1_depth_kernel", "oja_kernel", "hs_pairwise_kernel",
-                 "hx_sweep_kernel", "hx_pairwise_kernel")
+NEW_ARGUMENTS = ()             # short names of kernels whose argument list this change rewrites
 PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
                     r"wavefront|workgroup|workitem")
 
