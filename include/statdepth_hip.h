@@ -617,6 +617,48 @@ int sd_central_regions(const double *X, int64_t T, int64_t n, int64_t st, int64_
                        double factor, double *env, double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes,
                        void *stream);
 
+/* ---- K17: total variation depth and modified shape similarity of curves (Huang & Sun 2019) ----
+ * No reference code.  X is T x n fp64 in either layout; NaN is NOT supported (the host layer refuses it).  Infinities are
+ * ranked like any value; they make SN and SW non-finite under IEEE rules (the host layer refuses them for 'mss').
+ * For a target q the whole sample counts, q included:
+ *   a_t = #{j : X[t][j] <= X[t][q]}                                   (n - A of K14: 1 <= a_t <= n);
+ *   c_t = #{j : X[s][j] <= X[s][q] and X[t][j] <= X[t][q]},  s = t - 1, for t >= 1.
+ * Total variation depth: TVD(q) = (1/T) sum_{t=0..T-1} a_t (n - a_t) / n^2, at most 1/4.  The device returns the integer
+ *   SD = sum_t a_t (n - a_t)  (<= T n^2 / 4, fits int64) and the host forms SD / (n^2 T) with one fp64 division.
+ * Shape similarity at step t >= 1:  S_t = (n c_t - a_s a_t)^2 / (a_s (n - a_s) a_t (n - a_t)), the squared phi coefficient
+ *   of the 2 x 2 table of the indicators at s and t; it equals Var(E[R_t | R_s]) / Var(R_t) of the paper and lies in [0, 1].
+ *   Where the denominator is 0 (a_s = n or a_t = n) the numerator is 0 as well and S_t = 1: our convention.
+ *   In fp64: e = (double)(n c_t - a_s a_t), exact since |e| <= n^2 < 2^53, then
+ *   S_t = (e * e) / ((double)(a_s (n - a_s)) * (double)(a_t (n - a_t))), the integer products formed in 64-bit integers:
+ *   three rounded operations.
+ * Modified shape similarity: MSS(q) = sum_{t>=1} v_t S_t, v_t = |X[t][q] - X[t-1][q]| / sum_{u>=1} |X[u][q] - X[u-1][q]|.
+ *   The device returns three doubles per target, SS = sum S_t, SN = sum |D_t| S_t, SW = sum |D_t|; the host returns SN / SW
+ *   when SW > 0 and SS / (T - 1) for a constant curve.  MSS = 1 for a family of parallel curves.
+ * Example: rows [1,2,2,4], [2,1,3,3], [1,3,2,4] (T = 3, n = 4): a = (1,3,3,4), (2,1,4,4), (1,3,2,4); c = (1,1,3,4), (1,1,2,4);
+ *   SD = [10, 9, 7, 0]; S_1 = (1/3, 1/9, 1, 1), S_2 = (1/3, 1/9, 1, 1).
+ * Routes: algo 1, n <= 16 384: K14's pair image (B | A << 16 per row and curve), then one workgroup per pair of consecutive
+ *   rows counts c of all n curves in LDS -- a weak 2-D dominance count of the points (B(s), B(t)): a counting scatter per
+ *   row, a block histogram over strips of 128 positions with a 2-D prefix sum, two strip scans per curve -- and stores c - 1
+ *   as u16; a fold with one owner per (target, row slice) forms the sums.  algo 2, any n < 2^31: a pairwise kernel over the
+ *   doubles alone counts a_s, a_t and c_t by comparison, O(T n m) (SD_ERR_UNSUPPORTED above 10^14 comparisons), and feeds
+ *   the same arithmetic.  algo 0 (auto): algo 1 up to 16 384 curves, algo 2 above.
+ * Workspace, in this order, each padded to 256 bytes: the time-major copy of a curve-major X (8 T n bytes), the row slices'
+ * records (512 m), and on algo 1 the last image row of the batch before (4 n), c - 1 of a batch (2 n per row) and stage 1's
+ * batch as K14 sizes it.  sd_tvd_workspace_bytes recommends a size, sd_tvd_min_workspace_bytes is the floor (one row per
+ * batch), sd_tvd_rows_per_batch says how many rows a batch of a call with ws_bytes takes (T on algo 2); all are 0 for a shape
+ * or algo the call refuses or below the floor.  A pair of rows straddles every batch boundary; each pair is counted exactly
+ * once, and neither the integers nor the doubles depend on the workspace size.
+ * targets: m int64 curve indices (device), NULL = all (m == n).  sd_sum: m int64.  shape: m x 3 doubles (SS, SN, SW).
+ * counts: NULL, or (T - 1) x m uint32, counts[t - 1][q] = c_t of target q (all device).  T = 1 gives SD only: shape is
+ * zeroed and counts is untouched.
+ * SD_ERR_INVALID for NULL X, sd_sum or shape, T < 1, n < 1 or an unknown algo; SD_ERR_UNSUPPORTED for n < 2, for algo = 1
+ * with n > 16 384, or for 2^31 or more curves or timepoints; SD_ERR_WORKSPACE below the floor.  All before any device work. */
+size_t sd_tvd_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+size_t sd_tvd_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo);
+int64_t sd_tvd_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes);
+int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, int algo,
+                int64_t *sd_sum, double *shape, uint32_t *counts, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

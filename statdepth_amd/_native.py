@@ -100,6 +100,10 @@ SIGNATURES = {
     "sd_central_regions_row_capacity": (_i64, []),
     "sd_central_regions_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
     "sd_central_regions": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sd_tvd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_tvd_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_tvd_rows_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _int, _sz]),
+    "sd_tvd_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -1035,4 +1035,58 @@ int sd_central_regions(const double *X, int64_t T, int64_t n, int64_t st, int64_
     return launch_central_regions(Y, T, n, level, L, box, factor, env, fence, outside, whisker, cv.take(rest), rest, s);
 }
 
+// ---------------------------------------------------------------------------
+// K17
+// ---------------------------------------------------------------------------
+// the route that runs (1 LDS, 2 pairwise), 0 where the shape or algo has none
+static int tvd_route(int algo, i64 T, i64 n, i64 m) {
+    if (T < 1 || n < 2 || m < 0 || n >= ((i64)1 << 31) || T >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
+    if (algo == 1) return n <= RD_IMAGE_MAX_N ? 1 : 0;
+    return algo == 2 || n > RD_IMAGE_MAX_N ? 2 : 1;
+}
+
+size_t sd_tvd_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    const int route = tvd_route(algo, T, n, m);
+    return route ? time_major_bytes(T, n, st, sn) + tvd_workspace_bytes(T, n, m, route) : 0;
+}
+
+size_t sd_tvd_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
+    const int route = tvd_route(algo, T, n, m);
+    return route ? time_major_bytes(T, n, st, sn) + tvd_min_workspace_bytes(T, n, m, route) : 0;
+}
+
+int64_t sd_tvd_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes) {
+    const int route = tvd_route(algo, T, n, m);
+    const size_t tm = route ? time_major_bytes(T, n, st, sn) : 0;
+    if (!route || ws_bytes < tm) return 0;
+    if (route == 2) return ws_bytes - tm >= tvd_min_workspace_bytes(T, n, m, 2) ? T : 0;
+    return tvd_rows_per_batch(T, n, m, ws_bytes - tm);
+}
+
+int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, int algo,
+                int64_t *sd_sum, double *shape, uint32_t *counts, void *ws, size_t ws_bytes, void *stream) {
+    if (!X || !sd_sum || !shape) return fail(SD_ERR_INVALID, "null pointer (X, sd_sum and shape are required)");
+    if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (LDS), 2 (pairwise)", algo);
+    if (n < 2) return fail(SD_ERR_UNSUPPORTED, "the total variation depth needs at least two curves, got %lld", (long long)n);
+    if (algo == 1 && n > RD_IMAGE_MAX_N)
+        return fail(SD_ERR_UNSUPPORTED, "the LDS route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
+                    (long long)RD_IMAGE_MAX_N, (long long)n);
+    int rc = check_matrix(X, T, n, st, sn, targets, m);
+    if (rc) return rc;
+    const int route = tvd_route(algo, T, n, m);
+    const double work = (double)n * (double)m * (double)T;         // comparisons of the pairwise route
+    if (route == 2 && work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g comparisons of the pairwise route exceed the cap of %.0e", work, HS_MAX_WORK);
+    if (m == 0) return SD_OK;
+    if (!ws || ws_bytes < sd_tvd_min_workspace_bytes(T, n, st, sn, m, algo))
+        return fail(SD_ERR_WORKSPACE, "workspace below sd_tvd_min_workspace_bytes");
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes);
+    const double *Y;
+    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
+    const size_t rest = cv.rest();
+    return launch_tvd_sums(Y, T, n, targets, m, route, sd_sum, shape, counts, cv.take(rest), rest, s);
+}
+
 }  // extern "C"

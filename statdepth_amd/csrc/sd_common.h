@@ -193,6 +193,15 @@ size_t central_regions_workspace_bytes(i64 T, i64 n, int L);
 int launch_central_regions(const double *Y, i64 T, i64 n, const uint8_t *level, int L, int box, double factor, double *env,
                            double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes, hipStream_t s);
 
+// K17 total variation depth and shape similarity of curves (tvd.hip): sd_sum[q] = SD, shape[q] = (SS, SN, SW), counts
+// (null or [T - 1][m]) = c_t.  route 1 = K14's pair image and the dominance kernel in LDS (n <= RD_IMAGE_MAX_N), 2 =
+// pairwise over the doubles (any n); the workspace sizes are those behind the time-major copy
+size_t tvd_workspace_bytes(i64 T, i64 n, i64 m, int route);
+size_t tvd_min_workspace_bytes(i64 T, i64 n, i64 m, int route);
+i64 tvd_rows_per_batch(i64 T, i64 n, i64 m, size_t bytes);          // route 1: rows a batch takes with `bytes`; 0 below the floor
+int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
+                    u32 *counts, void *ws, size_t ws_bytes, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

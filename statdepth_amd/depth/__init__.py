@@ -1,2 +1,2 @@
-from .depth import FunctionalDepth, PointcloudDepth, ProbabilisticDepth, FunctionalBoxplot   # noqa: F401  (reference: statdepth/depth/__init__.py:1)
+from .depth import FunctionalDepth, PointcloudDepth, ProbabilisticDepth, FunctionalBoxplot, TotalVariationOutliers   # noqa: F401  (reference: statdepth/depth/__init__.py:1)
 from .calculations._helper import DepthDegeneracy     # noqa: F401

@@ -8,20 +8,22 @@ on the host, because arbitrary Python cannot run on the GPU.
 
 RANK_DEPTHS names the integrated rank depths of univariate curves (_rank.py): not band containments, but selected through
 the same argument.  ORDER_DEPTHS names the depths that order the curves instead of averaging over time (the extremal
-depth, _functional._extremal_depth), selected the same way.
+depth, _functional._extremal_depth), selected the same way.  SHAPE_DEPTHS names the depths built on the joint ranks at two
+consecutive timepoints (the total variation depth and the modified shape similarity, _shape.py), selected the same way.
 """
 from inspect import signature
 
 BUILTIN = ('r2', 'r2_enum', 'simplex')
 RANK_DEPTHS = ('fm', 'mei', 'mhi', 'half_region', 'integrated_halfspace', 'infimal_halfspace')
 ORDER_DEPTHS = ('extremal',)
+SHAPE_DEPTHS = ('tvd', 'mss')
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
     if len(params) != 3:   # only the arity is enforced (:37-41)
@@ -36,6 +38,10 @@ def _is_rank_depth(containment) -> bool:
 
 def _is_order_depth(containment) -> bool:
     return isinstance(containment, str) and containment in ORDER_DEPTHS
+
+
+def _is_shape_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in SHAPE_DEPTHS
 
 
 def _select_containment(containment):

@@ -17,9 +17,10 @@ from scipy.special import binom
 
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
-from ._containment import _is_order_depth, _is_rank_depth, _select_containment
+from ._containment import _is_order_depth, _is_rank_depth, _is_shape_depth, _select_containment
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._rank import _rank_depth_values
+from ._shape import _shape_depth_values
 
 __all__ = ['_functionaldepth', '_samplefunctionaldepth']
 
@@ -190,12 +191,32 @@ def _extremal_depth(data, to_compute, J, containment: str, deep_check=False, dev
     return pd.Series(index=cols, data=np.asarray(G, dtype=np.float64) / n)
 
 
+def _shape_depths(data, to_compute, J, containment: str, deep_check=False, device=None) -> pd.Series:
+    """The total variation depth ('tvd') or the modified shape similarity ('mss') of the columns `to_compute` of the single
+    frame in `data` (Huang & Sun 2019; _shape.py): one device call for the sums (sd_tvd_sums), one division on the host.
+    Labels, `to_compute` and the result's order are those of 'r2'; the refusals are those of the rank depths, and 'mss'
+    also needs 2 timepoints and finite values (an infinite step has no weight).  All raised before anything is uploaded."""
+    df, X = _ranked_frame(data, J, containment, deep_check)
+    T, n = X.shape
+    if containment == 'mss':
+        if T < 2:
+            raise ValueError(f'containment \'{containment}\' needs at least 2 timepoints, got {T}.')
+        if not np.isfinite(X).all():
+            raise ValueError(f'containment \'{containment}\' does not take infinite values (a step of infinite length '
+                             'has no weight).')
+    cols = df.columns if to_compute is None else to_compute
+    sd_sum, shape = engine.tvd_sums(X, _positions(df, cols), device=device)
+    return pd.Series(index=cols, data=_shape_depth_values(sd_sum, shape, n, T, containment))
+
+
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
                      relax=False, deep_check=False, quiet=True, device=None, algo='auto') -> pd.Series:
     if _is_rank_depth(containment):                      # not a band depth: `relax` and `algo` have nothing to select
         return _rank_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
     if _is_order_depth(containment):
         return _extremal_depth(data, to_compute, J, containment, deep_check=deep_check, device=device)
+    if _is_shape_depth(containment):
+        return _shape_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)
 
@@ -255,7 +276,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     reference's blocks; each block's depth is one device call.
     """
     samples = []
-    if _is_rank_depth(containment) or _is_order_depth(containment):
+    if _is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

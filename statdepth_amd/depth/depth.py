@@ -7,8 +7,10 @@ implementing it, plus `to_compute` and the keyword-only `device=`.  Result class
 the reference's method names and conventions (:14-65,178-185,337-341), including the
 plotly views (:91-175,193-335; `_plotting.py`, host-side visualisation outside the hot path).
 """
+import math
 from typing import List
 
+import numpy as np
 import pandas as pd
 
 from abc import ABC, abstractmethod
@@ -20,7 +22,7 @@ from .calculations import _boxplot
 from .calculations._boxplot import FunctionalBoxplotResult
 from . import _plotting
 
-__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot']
+__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot', 'TotalVariationOutliers']
 
 
 class AbstractDepth(ABC):
@@ -185,7 +187,14 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     'infimal_halfspace' (mean and infimum over t of the univariate Tukey depth).  Labels, `to_compute` and the result
     object are those of 'r2'.  These are the integrated ("modified") forms, so `relax` is accepted and ignored -- there
     is no strict form to select -- and `algo` is ignored too.  ValueError for multivariate data, `K` other than None, `J`
-    other than 2, NaN anywhere in the frame, or fewer than 2 curves."""
+    other than 2, NaN anywhere in the frame, or fewer than 2 curves.
+
+    Under the same rules `containment` names the two depths of Huang & Sun (2019), which look at two consecutive timepoints
+    at once: 'tvd', the total variation depth (mean over t of a (n - a) / n^2, a the number of curves at or below the curve,
+    at most 1/4), and 'mss', the modified shape similarity (the squared phi coefficient of "at or below at t - 1" and "at or
+    below at t" over the sample, averaged over the steps with the curve's own |increments| as weights; 1 where the curve is
+    the highest at either timepoint).  'mss' also needs 2 timepoints and finite values.  `.boxplot()` and
+    `.central_region()` of a 'tvd' result work as for any depth; TotalVariationOutliers runs the paper's outlier rule."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)
@@ -221,6 +230,60 @@ def FunctionalBoxplot(data, depths=None, *, alpha=0.5, factor=1.5, levels=(), de
             raise ValueError(f'depths are given: {sorted(depth_kwargs)} would have no effect.')
         depths = _boxplot._aligned_depths(df, depths)
     return _boxplot._functional_boxplot(df, X, fr, box, depths, factor, device=device)
+
+
+class TotalVariationOutlierResult:
+    """What the two-step outlier detection of Huang & Sun (2019) returns.
+
+    mss                 Series: the modified shape similarity of every curve, in column order
+    tvd                 Series: the total variation depth of the curves that are not shape outliers, among themselves
+    shape_fence         Q1 - shape_factor * (Q3 - Q1) of mss
+    shape_outliers      Index of the labels with mss below the fence, in column order
+    boxplot             the FunctionalBoxplotResult of the other curves by tvd
+    magnitude_outliers  its outliers
+    outliers            the union, in column order
+    """
+
+    def __init__(self, mss, tvd, shape_fence, shape_outliers, boxplot, magnitude_outliers, outliers):
+        self.mss, self.tvd, self.shape_fence, self.shape_outliers = mss, tvd, shape_fence, shape_outliers
+        self.boxplot, self.magnitude_outliers, self.outliers = boxplot, magnitude_outliers, outliers
+
+    def __repr__(self):
+        return (f'TotalVariationOutlierResult(shape_outliers={list(self.shape_outliers)!r}, '
+                f'magnitude_outliers={list(self.magnitude_outliers)!r})')
+
+
+def TotalVariationOutliers(data, *, shape_factor=3.0, factor=1.5, alpha=0.5, device=None) -> TotalVariationOutlierResult:
+    """Shape and magnitude outliers among univariate curves by the two-step procedure of Huang & Sun (2019).
+
+    Step 1: the modified shape similarity of every curve (FunctionalDepth(containment='mss')); with Q1 and Q3 its quartiles
+    (np.quantile), the curves with MSS < Q1 - shape_factor * (Q3 - Q1) are the shape outliers -- curves that stay inside
+    the bulk but oscillate or cross the others the wrong way, which no pointwise depth and no fence sees.
+    Step 2: FunctionalBoxplot of the remaining curves by their total variation depth (containment='tvd', `alpha` and
+    `factor` as there); its outliers are the magnitude outliers.
+    data: a DataFrame whose columns are the curves, or a list of one.  ValueError for what FunctionalBoxplot or 'mss'
+    refuse (NaN, infinities, fewer than 2 timepoints, duplicate labels, ...), a negative or non-finite shape_factor, or
+    fewer than 2 curves left after step 1."""
+    df, _, _, _ = _boxplot._check_boxplot(data, alpha, factor, ())
+    try:
+        ok = math.isfinite(shape_factor) and shape_factor >= 0
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f'shape_factor must be a finite number >= 0, got {shape_factor!r}.')
+    mss = pd.Series(FunctionalDepth([df], containment='mss', device=device).get_depths())
+    q1, q3 = np.quantile(mss.to_numpy(), [0.25, 0.75])
+    shape_fence = float(q1 - shape_factor * (q3 - q1))
+    is_shape = (mss < shape_fence).to_numpy()
+    shape_outliers = df.columns[is_shape]
+    rest = df.loc[:, ~is_shape]
+    if rest.shape[1] < 2:
+        raise ValueError(f'{rest.shape[1]} curve(s) left after the shape outliers: the boxplot needs at least 2.')
+    tvd = pd.Series(FunctionalDepth([rest], containment='tvd', device=device).get_depths())
+    box = FunctionalBoxplot(rest, tvd, alpha=alpha, factor=factor, device=device)
+    flagged = is_shape | df.columns.isin(box.outliers)
+    return TotalVariationOutlierResult(mss=mss, tvd=tvd, shape_fence=shape_fence, shape_outliers=shape_outliers, boxplot=box,
+                                       magnitude_outliers=box.outliers, outliers=df.columns[flagged])
 
 
 def ProbabilisticDepth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compute=None, K=None, J=2, relax=False, *,

@@ -437,6 +437,66 @@ def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
                    workspace=lambda: _sized(dev, size()))
 
 
+TVD_ALGOS = {"auto": 0, "lds": 1, "pairwise": 2}
+
+
+def _tvd_algo(algo):
+    if isinstance(algo, str) and algo not in TVD_ALGOS:
+        raise ValueError(f"algo must be one of {sorted(TVD_ALGOS)}, got {algo!r}")
+    return TVD_ALGOS[algo] if isinstance(algo, str) else int(algo)
+
+
+def tvd_workspace_bytes(T, n, algo="auto", curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of sd_tvd_sums for a T x n matrix and m targets (default: all n); the floor holds
+    one row per batch.  (0, 0) for a shape or algo the call refuses.  curve_major: the matrix is F-contiguous and takes a
+    time-major copy in the workspace as well."""
+    lib = _native.load()
+    T, n, a = int(T), int(n), _tvd_algo(algo)
+    m = n if m is None else int(m)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return (int(lib.sd_tvd_workspace_bytes(T, n, st, sn, m, a)), int(lib.sd_tvd_min_workspace_bytes(T, n, st, sn, m, a)))
+
+
+def tvd_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False, m=None):
+    """Rows of the matrix a batch of sd_tvd_sums takes with ws_bytes of workspace (all T on the pairwise route); 0 below
+    the floor."""
+    lib = _native.load()
+    T, n, a = int(T), int(n), _tvd_algo(algo)
+    m = n if m is None else int(m)
+    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    return int(lib.sd_tvd_rows_per_batch(T, n, st, sn, m, a, int(ws_bytes)))
+
+
+def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=False):
+    """(sd_sum int64[m], shape float64[m, 3]) of the total variation depth and the shape similarity (sd_tvd_sums), and with
+    counts=True a third entry, uint32[T - 1, m].  Per target q, with a_t = #{j : X[t][j] <= X[t][q]} and c_t = #{j : X[t-1][j]
+    <= X[t-1][q] and X[t][j] <= X[t][q]} over the whole sample: sd_sum = sum_t a_t (n - a_t); shape = (SS, SN, SW), the sums over
+    t >= 1 of S_t, |D_t| S_t and |D_t|, S_t the squared phi coefficient of (a_s, a_t, c_t) (depth/calculations/_shape.py) and
+    D_t = X[t][q] - X[t-1][q]; counts[t - 1][q] = c_t.  X must not hold NaN (the depth layer checks; this function takes its
+    array as it is).  algo: 'auto', 'lds' (n <= 16 384) or 'pairwise', or their numbers 0, 1, 2.  ws_bytes: the workspace
+    size to run with (default: the recommended one); the results do not depend on it, below the floor the library
+    refuses."""
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    a = _tvd_algo(algo)
+    td, m, tp = _targets_dev(targets, M.n, dev)
+    sd = t.empty((m,), dtype=t.int64, device=dev)
+    shape = t.empty((m, 3), dtype=t.float64, device=dev)
+    cnt = t.empty((max(M.T - 1, 0), m), dtype=t.int32, device=dev) if counts else None
+    size = (lambda: lib.sd_tvd_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
+
+    def call(X_, T_, n_, st_, sn_, targets_, m_, algo_, shape_, counts_, sd_, ws_, ws_bytes_, stream_):
+        return lib.sd_tvd_sums(X_, T_, n_, st_, sn_, targets_, m_, algo_, sd_, shape_, counts_, ws_, ws_bytes_, stream_)
+
+    _launch(dev, call, sd, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a, shape.data_ptr(),
+            cnt.data_ptr() if cnt is not None and cnt.numel() else None, workspace=lambda: _sized(dev, size()),
+            return_tensor=True)
+    out = (sd.cpu().numpy(), shape.cpu().numpy())
+    return out + (cnt.cpu().numpy().view(np.uint32),) if counts else out
+
+
 def central_regions_row_capacity():
     """The most curves of the row-resident route of sd_central_regions (whole rows in one workgroup's registers); above
     it the call goes through column blocks.  (torch first, as in _lib: a test may ask this before any device call.)"""
