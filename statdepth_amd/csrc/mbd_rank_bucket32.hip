@@ -76,7 +76,12 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     using C = R32Cfg<E, LNB>;
     constexpr int NT = C::NT, NW = C::NW, NB = C::NB, QW = C::QW, SH = C::SH;
     constexpr u32 C0 = C::C0, C1 = C::C1, CU0 = C::CU0, CU1 = C::CU1, NANIMG = C::NANIMG;
-    extern __shared__ double Sm[];
+    // A static block sized for the class's largest n (E * NT curves): every LDS address is a compile-time offset plus an
+    // index, not the run-time base of a dynamic segment added to each of them.  The layout is the one lds_bytes(n) describes;
+    // the run-time n only decides where the sentinels and the dummy lie inside it.
+    constexpr size_t LDS = C::lds_bytes(E * NT);
+    static_assert(2 * LDS <= 160 * 1024, "two workgroups per CU");
+    __shared__ __attribute__((aligned(16))) double Sm[(LDS + 7) / 8];
     const int n = (int)n64;
     double *red = Sm;                                                 // [2][NW][4] min / max of the row, central bracket of its keys
     u32 *wtot = reinterpret_cast<u32 *>(red + 8 * NW);                // [NW]
@@ -138,7 +143,12 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             bool eqs = false;
 #pragma unroll
             for (int e = 0; e < (E - 1 < 10 ? E - 1 : 10); ++e) eqs = eqs || (x[e] == x[e + 1]);   // (a slot beyond n is NaN: no)
-            if (__ballot(eqs) != 0) { wb.x = __builtin_huge_valf(); wb.y = -__builtin_huge_valf(); }
+            if (__ballot(eqs) != 0) {
+                float finf = __builtin_huge_valf();
+                asm volatile("" : "+v"(finf));                        // (set here: not a constant held in a register for the row loop)
+                wb.x = finf;
+                wb.y = -finf;
+            }
         }
         const float imn = wb.x, imx = wb.y;
         mn = rb_wave_allreduce<false>(mn);
@@ -224,8 +234,10 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         // v (sign bit: a huge unsigned word) or any other binade fails it.  The tail code is computed only when some lane of the
         // wave has a key outside the core; which side is read off v itself (monotone in x: v < vlo <=> below the core, also
         // for the row's minimum when the offset's rounding puts it a hair under the bound).  Out: the bucket in bk, the
-        // bucket-local image in q (a tail key: its 31-bit image's low 17 bits, 14 zero bits behind them)
-        auto convert4 = [&](const double (&xv)[4], u32 (&q)[4], u32 (&bk)[4]) {
+        // bucket-local image in q (a tail key: its 31-bit image's low 17 bits, 14 zero bits behind them).  A slot that holds no
+        // curve (!isk: its x is the NaN of load_row) is given the NaN's image directly and does not send its wave through the
+        // tail code: at n = 10 000 half the waves of a workgroup have such a slot in every row.
+        auto convert4 = [&](const double (&xv)[4], const bool (&isk)[4], u32 (&q)[4], u32 (&bk)[4]) {
             bool anyout = false;
             u32 vh[4];
 #pragma unroll
@@ -233,16 +245,18 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 const u64 w = (u64)__double_as_longlong(__builtin_fma(xv[i], mscale, moff));
                 vh[i] = (u32)(w >> 32);
                 q[i] = (u32)w;
-                anyout = anyout || (vh[i] - mh0 >= mhw);
+                anyout = anyout || (isk[i] && vh[i] - mh0 >= mhw);
             }
             if (__ballot(anyout) != 0) {
                 const double vlo = __longlong_as_double((long long)((u64)mh0 << 32));
+                double zero = 0.0;
+                asm volatile("" : "+v"(zero));                        // set here, where it is used: not a register pair held for the row loop
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool outc = vh[i] - mh0 >= mhw;
                     const bool low = __longlong_as_double((long long)(((u64)vh[i] << 32) | q[i])) < vlo;
                     double d = low ? lo - xv[i] : xv[i] - hi;
-                    d = rb_mm<true>(d, 0.0);                          // a key the rounding put just outside: code 0
+                    d = rb_mm<true>(d, zero);                         // a key the rounding put just outside: code 0
                     const u64 tc = ((u64)__double_as_longlong(d + mc) - mcb) >> R32_TSH;
                     // below the core: mc0 - 1 downwards; above: from the core's end upwards; clamped to what is left of the
                     // image range (a clipped core leaves 1 024 buckets on either side, an unclipped one two buckets: only a
@@ -257,6 +271,8 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
+                vh[i] = isk[i] ? vh[i] : NANIMG >> (SH + 1);          // the words of NANIMG << 14, as the tail code gives a NaN
+                q[i] = isk[i] ? q[i] : NANIMG << (31 - SH);
                 bk[i] = __builtin_amdgcn_alignbit(vh[i], q[i], 31) & 0x7FFFu;   // a NaN's image: the dummy counter NB + 2
                 q[i] &= 0x7FFFFFFFu;
             }
@@ -274,9 +290,14 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     if (e0 + h < E) {
                         double xv[4];
                         u32 q[4], bk[4];
+                        bool isk[4];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) xv[i] = e0 + h + i < E ? x[e0 + h + i] : x[e0 + h];
-                        convert4(xv, q, bk);
+                        for (int i = 0; i < 4; ++i) {
+                            const int e = e0 + h + i < E ? e0 + h + i : e0 + h;
+                            xv[i] = x[e];
+                            isk[i] = e < E - 2 || t + e * NT < n;
+                        }
+                        convert4(xv, isk, q, bk);
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (e0 + h + i < E) { kb[e0 + h + i] = q[i]; bc[e0 + h + i] = bk[i]; }
@@ -665,12 +686,10 @@ size_t rank_bucket32_extra_bytes(i64 rows) { return align_up((size_t)rows + 64, 
 template <int E>
 static int launch32_cfg(const double *Y, i64 n, i64 row0, i64 rows, u32 *partial, unsigned char *rowflag, u32 *gate, u32 epoch,
                         u64 *out_zero, int G, hipStream_t s) {
-    using C = R32Cfg<E, R32_LNB>;
     auto kf = rank_bucket32_kernel<E, R32_LNB>;
-    const size_t lds = C::lds_bytes((int)n);
-    if (lds > 81920) return fail(SD_ERR_UNSUPPORTED, "bucket32 kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
-    SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kf, dim3(G), dim3(R32_NT), lds, s, Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero);
+    if (n > (i64)E * R32_NT || n <= (i64)(E - 2) * R32_NT)            // the kernel's static LDS block holds E * NT keys
+        return fail(SD_ERR_UNSUPPORTED, "bucket32 kernel: n=%lld is not of the class E=%d", (long long)n, E);
+    hipLaunchKernelGGL(kf, dim3(G), dim3(R32_NT), 0, s, Y, n, row0, rows, partial, rowflag, gate, epoch, out_zero);
     SD_HIP(hipGetLastError());
     return SD_OK;
 }
