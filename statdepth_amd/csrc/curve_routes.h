@@ -1,0 +1,72 @@
+// curve_routes.h -- the curve depths on K14's pair image (K14 rank depths, K15 extremal depth, K17 total variation depth):
+// their one route rule, the plan of stage 1 that the size functions and the launchers read, and each family's own plan
+// built on it (internal; the K1+K2 rank routes: rank_routes.h, the strict path's: strict_routes.h).
+#pragma once
+#include "sd_common.h"
+
+namespace sd {
+
+constexpr i64 RD_IMAGE_MAX_N = 16384;                               // curves of a row the bucket kernel's image holds
+
+// The route of a call (rank_depths.hip): 1 = the u32 pair image of the bucket kernel (K14, K15: "image", K17: "LDS";
+// n <= RD_IMAGE_MAX_N), 2 = K10's sort and a u64 pair image (K14, K15: "sort") or K17's pairwise kernel, any n < 2^31;
+// 0 where the shape (T < 1, n < 2, n >= 2^31) or the algo (0 auto, 1, 2) has none.
+int curve_route(int algo, i64 T, i64 n);
+
+// What a plan is sized by: the bytes at hand behind the time-major copy, or a number of rows per batch -- all T for the
+// recommended size, which the route's caps cut down, one row for the floor.
+struct PlanSize {
+    size_t bytes;
+    i64 rows;                                                       // 0: by bytes
+    static PlanSize of_bytes(size_t b) { return {b, 0}; }
+    static PlanSize of_rows(i64 r) { return {0, r}; }
+};
+
+// ---- stage 1 (rank_depths.hip): the pair image of Y, batch by batch ----
+struct PairImagePlan {
+    int route;
+    i64 rows;                                                       // per batch (route 1) or per chunk (route 2); 0: below the floor
+    size_t bytes;                                                   // what stage 1 carves for them
+};
+// By bytes: the most rows they hold within the route's caps.  By rows: the size for them, and the rows that size holds
+// -- more than asked for where the 256-byte padding of a small image leaves room (32 rows at n = 2).
+PairImagePlan pair_image_plan(i64 T, i64 n, int route, PlanSize size);
+
+// What takes the pair image of one batch of rows [row0, row0 + rows) of Y, img[r][i] of row row0 + r and curve i: B | A << 16
+// in u32 on route 1, B | A << 32 in u64 on route 2.  It enqueues on s; the next batch overwrites the image.
+struct RankImageConsumer {
+    virtual int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) = 0;
+    virtual int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) = 0;
+    virtual ~RankImageConsumer() = default;
+};
+// runs plan.route in batches of plan.rows rows, with plan.bytes at ws
+int launch_rank_pair_images(const PairImagePlan &plan, const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws,
+                            hipStream_t s);
+
+// ---- K14 integrated rank depths of curves (rank_depths.hip): out[q] = (SA, SB, SF, SM, MM).  Its plan is stage 1's. ----
+int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
+                           size_t ws_bytes, hipStream_t s);
+
+// ---- K15 extremal depth of curves (extremal.hip): out[q] = #{curves i : v_i >=lex v_q}, v the descending sort of |A - B|
+// over time.  The extremity matrix E and the heads H, then stage 1. ----
+constexpr i64 EX_MAX_T = 16384;                                     // keys one sort workgroup holds in LDS (64 KiB): the caller checks
+struct ExtremalPlan {
+    PairImagePlan stage1;
+    size_t bytes;                                                   // E, H and stage 1
+};
+ExtremalPlan extremal_plan(i64 T, i64 n, int route, PlanSize size);
+int launch_extremal_counts(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
+                           size_t ws_bytes, hipStream_t s);
+
+// ---- K17 total variation depth and shape similarity of curves (tvd.hip): sd_sum[q] = SD, shape[q] = (SS, SN, SW), counts
+// (null or [T - 1][m]) = c_t.  The slices' records; on route 1 then the carried row, C for stage1.rows rows and stage 1. ----
+struct TvdPlan {
+    PairImagePlan stage1;                                           // route 1
+    i64 rows;                                                       // per batch: stage1.rows, or all T on route 2; 0: below the floor
+    size_t bytes;                                                   // the whole of it
+};
+TvdPlan tvd_plan(i64 T, i64 n, i64 m, int route, PlanSize size);
+int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
+                    u32 *counts, void *ws, size_t ws_bytes, hipStream_t s);
+
+}  // namespace sd

@@ -28,7 +28,7 @@
 //      one after the other, 64 entries of both rows at a time.
 //      The sample range is split over grid.y so that few targets still fill the machine; the parts meet in integer
 //      atomic adds on the zeroed result, which are exact in any order.
-#include "sd_common.h"
+#include "curve_routes.h"
 
 namespace sd {
 
@@ -220,8 +220,6 @@ static inline int ex_field_bits(i64 n) {
     return b < 16 ? 16 : b;
 }
 
-size_t extremal_fixed_workspace_bytes(i64 T, i64 n) { return align_up((size_t)n * T * 4, 256) + align_up((size_t)n * 8, 256); }
-
 // stage 2 as the consumer of stage 1's batches
 struct ExtremityTransform final : RankImageConsumer {
     i64 n, T;
@@ -231,16 +229,23 @@ struct ExtremityTransform final : RankImageConsumer {
     int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) override { return launch_ex_transform<u64>(img, row0, rows, n, T, E, s); }
 };
 
+// E and H in front of stage 1, which takes the bytes they leave or is sized by its rows
+ExtremalPlan extremal_plan(i64 T, i64 n, int route, PlanSize size) {
+    const size_t fixed = align_up((size_t)n * T * 4, 256) + align_up((size_t)n * 8, 256);
+    if (!size.rows) size.bytes = size.bytes > fixed ? size.bytes - fixed : 0;
+    const PairImagePlan stage1 = pair_image_plan(T, n, route, size);
+    return {stage1, fixed + stage1.bytes};
+}
+
 int launch_extremal_counts(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
                            size_t ws_bytes, hipStream_t s) {
-    if (T > EX_MAX_T) return fail(SD_ERR_UNSUPPORTED, "extremal depth sorts up to %lld timepoints, got %lld", (long long)EX_MAX_T, (long long)T);
+    const ExtremalPlan plan = extremal_plan(T, n, route, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);
     u32 *E = (u32 *)cv.take((size_t)n * T * 4);
     u64 *H = (u64 *)cv.take((size_t)n * 8);
     if (!E || !H) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_extremal_min_workspace_bytes)");
-    const size_t rest = cv.rest();
     ExtremityTransform transform(n, T, E);
-    int rc = launch_rank_pair_images(Y, T, n, route, transform, cv.take(rest), rest, s);
+    int rc = launch_rank_pair_images(plan.stage1, Y, T, n, transform, cv.take(plan.stage1.bytes), s);
     if (rc) return rc;
 
     int Tp = 2;

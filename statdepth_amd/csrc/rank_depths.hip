@@ -10,7 +10,7 @@
 //
 // Image route (n <= 16 384), per batch of rows: launch_rank_bucket_image (mbd_rank_bucket.hip, the J >= 4 path of
 //   launch_mbd_rank) writes u32[rows][n] = B | A << 16; rank_depth_fold_kernel<u32> folds it.  The batch is what the
-//   workspace holds (rank_depth_rows_per_batch): at most 2^16 rows, at most a 1 GiB image, one row at the floor, and the
+//   workspace holds (pair_image_plan): at most 2^16 rows, at most a 1 GiB image, one row at the floor, and the
 //   whole of T in one batch at the recommended size whenever T is within those caps.
 //
 // Sort route (any n < 2^31), per chunk of kc rows:
@@ -29,8 +29,10 @@
 // other on the stream: no atomics, and integer sums and maxima do not depend on the batch size.  40 KB of LDS.
 //
 // The routes hand each batch's image to a RankImageConsumer (launch_rank_pair_images): the fold here, K15's transform
-// into the extremity matrix in extremal.hip.
-#include "sd_common.h"
+// into the extremity matrix in extremal.hip, K17's dominance kernel and fold in tvd.hip.  The route rule of the three and
+// the plan of this stage -- rows per batch and the bytes carved for them, which the size functions and the launchers of
+// all three read -- are curve_route and pair_image_plan below (curve_routes.h).
+#include "curve_routes.h"
 #include "rank_routes.h"
 #include "halfspace_sort.h"
 
@@ -145,49 +147,48 @@ __global__ __launch_bounds__(HS_THREADS) void rd_rank_scatter_kernel(const doubl
     if (col < n) img[r * n + col] = (u64)lt | (u64)(n - le) << 32;  // (a padding index can surface only among NaN keys)
 }
 
-// ---------------------------------------------------------------------------------------------- workspaces
+// ---------------------------------------------------------------------------------------------- the plan of stage 1
+int curve_route(int algo, i64 T, i64 n) {
+    if (T < 1 || n < 2 || n >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
+    if (algo == 1) return n <= RD_IMAGE_MAX_N ? 1 : 0;
+    return algo == 2 || n > RD_IMAGE_MAX_N ? 2 : 1;
+}
+
 static inline size_t rd_image_bytes(i64 rows, i64 n) { return align_up((size_t)rows * n * 4, 256) + align_up((size_t)rows * 4, 256); }
-static inline i64 rd_image_rows_cap(i64 T, i64 n) {
-    i64 r = (i64)(RD_IMAGE_BYTES / ((size_t)n * 4));
-    r = r > RD_IMAGE_ROWS ? RD_IMAGE_ROWS : r;
-    return r > T ? T : r;
+// What a route carves for `rows` rows.  Sort route: a fixed part (the alignment of the sort buffers' carve-outs) and a part
+// per row of a chunk; the u64 image lies in the key buffer the sort has finished with.
+static inline size_t rd_bytes(int route, i64 rows, i64 n) {
+    return route == 1 ? rd_image_bytes(rows, n) : (size_t)HS_SORT_CARVES * 256 + (size_t)rows * hs_sort_bytes_per_direction(n);
 }
-// fixed part (the alignment of the sort buffers' carve-outs) and the part per row of a chunk; the u64 image lies in the
-// key buffer the sort has finished with
-static inline size_t rd_sort_fixed() { return (size_t)HS_SORT_CARVES * 256; }
-
-size_t rank_depth_min_workspace_bytes(i64 n, int route) {
-    return route == 1 ? rd_image_bytes(1, n) : rd_sort_fixed() + hs_sort_bytes_per_direction(n);
-}
-
-size_t rank_depth_workspace_bytes(i64 T, i64 n, int route) {
-    if (route == 1) return rd_image_bytes(rd_image_rows_cap(T, n), n);
-    i64 kc = HS_REC_VALUES / n;
-    kc = kc < 1 ? 1 : kc > T ? T : kc;
-    return rd_sort_fixed() + (size_t)kc * hs_sort_bytes_per_direction(n);
+// the rows the recommended size is made for: the image's caps, or K10's recommended chunk
+static inline i64 rd_rows_cap(int route, i64 T, i64 n) {
+    i64 r = route == 1 ? (i64)(RD_IMAGE_BYTES / ((size_t)n * 4)) : HS_REC_VALUES / n;
+    r = route == 1 && r > RD_IMAGE_ROWS ? RD_IMAGE_ROWS : r;
+    return r < 1 ? 1 : r > T ? T : r;
 }
 
-// Rows per batch (image route) or per chunk (sort route) of a call with `bytes` of workspace behind the time-major copy:
-// the most whose buffers fit -- by the size functions above, so the recommended size holds exactly the batch it was sized
-// for -- within the route's caps; 0 below the floor.
-i64 rank_depth_rows_per_batch(i64 T, i64 n, int route, size_t bytes) {
-    if (bytes < rank_depth_min_workspace_bytes(n, route)) return 0;
-    if (route != 1) return hs_chunk_directions(bytes - rd_sort_fixed(), hs_sort_bytes_per_direction(n), n, T);
-    // the caps above and the bucket kernel's 2048 rows per workgroup of a launch
-    const i64 cap = rd_image_rows_cap(T, n), grid_cap = (i64)device_cus() * 2048;
-    i64 rpb = (i64)(bytes / ((size_t)n * 4 + 4));                   // an upper bound: rd_image_bytes(r, n) >= r (4 n + 4)
+// A size by rows is rd_bytes of them; the rows are the most whose buffers fit the size by rd_bytes again, so a size made
+// for r rows holds r of them, or more.
+PairImagePlan pair_image_plan(i64 T, i64 n, int route, PlanSize size) {
+    const i64 cap = rd_rows_cap(route, T, n);
+    PairImagePlan p{route, 0, size.rows ? rd_bytes(route, size.rows < cap ? size.rows : cap, n) : size.bytes};
+    if (p.bytes < rd_bytes(route, 1, n)) return p;
+    if (route != 1) {
+        p.rows = hs_chunk_directions(p.bytes - rd_bytes(route, 0, n), hs_sort_bytes_per_direction(n), n, T);
+        return p;
+    }
+    const i64 grid_cap = (i64)device_cus() * 2048;                  // the bucket kernel's 2048 rows per workgroup of a launch
+    i64 rpb = (i64)(p.bytes / ((size_t)n * 4 + 4));                 // an upper bound: rd_image_bytes(r, n) >= r (4 n + 4)
     rpb = rpb > cap ? cap : rpb;
     rpb = rpb > grid_cap ? grid_cap : rpb;
-    while (rpb > 1 && rd_image_bytes(rpb, n) > bytes) --rpb;        // the two paddings: at most 510 bytes
-    return rpb;
+    while (rpb > 1 && rd_image_bytes(rpb, n) > p.bytes) --rpb;      // the two paddings: at most 510 bytes
+    p.rows = rpb;
+    return p;
 }
 
 // ---------------------------------------------------------------------------------------------- the two routes
 // Each route hands the pair image of a batch (rows [row0, row0 + rows) of Y) to `use`; the image is overwritten by the next batch.
-static int rank_depth_image_route(const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws, size_t ws_bytes, hipStream_t s) {
-    const i64 rpb = rank_depth_rows_per_batch(T, n, 1, ws_bytes);
-    if (!ws || rpb < 1) return fail(SD_ERR_WORKSPACE, "workspace too small for one row per batch (sd_rank_depth_min_workspace_bytes)");
-    Carver cv(ws, ws_bytes);
+static int rank_depth_image_route(i64 rpb, const double *Y, i64 T, i64 n, RankImageConsumer &use, Carver &cv, hipStream_t s) {
     u32 *AB = (u32 *)cv.take((size_t)rpb * n * 4);
     u32 *nnan = (u32 *)cv.take((size_t)rpb * 4);
     if (!AB || !nnan) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_rank_depth_min_workspace_bytes)");
@@ -199,10 +200,7 @@ static int rank_depth_image_route(const double *Y, i64 T, i64 n, RankImageConsum
     return SD_OK;
 }
 
-static int rank_depth_sort_route(const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws, size_t ws_bytes, hipStream_t s) {
-    const i64 kc = rank_depth_rows_per_batch(T, n, 2, ws_bytes);
-    if (!ws || kc < 1) return fail(SD_ERR_WORKSPACE, "workspace too small for one row per chunk (sd_rank_depth_min_workspace_bytes)");
-    Carver cv(ws, ws_bytes);
+static int rank_depth_sort_route(i64 kc, const double *Y, i64 T, i64 n, RankImageConsumer &use, Carver &cv, hipStream_t s) {
     HsSortBuffers b;
     if (!hs_sort_carve(cv, n, kc, b)) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_rank_depth_min_workspace_bytes)");
     for (i64 c0 = 0; c0 < T; c0 += kc) {
@@ -221,10 +219,14 @@ static int rank_depth_sort_route(const double *Y, i64 T, i64 n, RankImageConsume
     return SD_OK;
 }
 
-int launch_rank_pair_images(const double *Y, i64 T, i64 n, int route, RankImageConsumer &use, void *ws, size_t ws_bytes,
+int launch_rank_pair_images(const PairImagePlan &plan, const double *Y, i64 T, i64 n, RankImageConsumer &use, void *ws,
                             hipStream_t s) {
-    if (route == 1) return rank_depth_image_route(Y, T, n, use, ws, ws_bytes, s);
-    return rank_depth_sort_route(Y, T, n, use, ws, ws_bytes, s);
+    if (!ws || plan.rows < 1)
+        return fail(SD_ERR_WORKSPACE, "workspace too small for one row per %s (sd_rank_depth_min_workspace_bytes)",
+                    plan.route == 1 ? "batch" : "chunk");
+    Carver cv(ws, plan.bytes);
+    return plan.route == 1 ? rank_depth_image_route(plan.rows, Y, T, n, use, cv, s)
+                           : rank_depth_sort_route(plan.rows, Y, T, n, use, cv, s);
 }
 
 // K14's consumer: the fold into the records
@@ -244,7 +246,7 @@ struct RankDepthFold final : RankImageConsumer {
 int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
                            size_t ws_bytes, hipStream_t s) {
     RankDepthFold fold(n, targets, m, (u64 *)out);
-    return launch_rank_pair_images(Y, T, n, route, fold, ws, ws_bytes, s);
+    return launch_rank_pair_images(pair_image_plan(T, n, route, PlanSize::of_bytes(ws_bytes)), Y, T, n, fold, ws, s);
 }
 
 }  // namespace sd

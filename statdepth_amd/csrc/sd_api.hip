@@ -6,6 +6,7 @@
 
 #include "sd_common.h"
 #include "rank_routes.h"
+#include "curve_routes.h"
 #include "point_select.h"
 
 namespace sd {
@@ -114,6 +115,21 @@ static int time_major(const double *X, i64 T, i64 n, i64 st, i64 sn, Carver &cv,
     if (rc) return rc;
     *Y = Yw;
     return SD_OK;
+}
+
+// The tail of an entry point of K14 to K17: a workspace below `floor` (named by `floor_name`) is refused; then the time-major
+// copy, and launch(Y, ws, ws_bytes, s) with what lies behind it.
+template <typename Launch>
+static int launch_time_major(const double *X, i64 T, i64 n, i64 st, i64 sn, void *ws, size_t ws_bytes, size_t floor,
+                             const char *floor_name, void *stream, Launch launch) {
+    if (!ws || ws_bytes < floor) return fail(SD_ERR_WORKSPACE, "workspace below %s", floor_name);
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes);
+    const double *Y;
+    int rc = time_major(X, T, n, st, sn, cv, s, &Y);
+    if (rc) return rc;
+    const size_t rest = cv.rest();
+    return launch(Y, cv.take(rest), rest, s);
 }
 
 // wide[i] (two 64-bit limbs) (+)= part[i]: the chunk totals of sd_mbd_counts_wide
@@ -903,32 +919,43 @@ int sd_simplicial2_subset_counts(const double *P, int64_t n, const int32_t *memb
 }
 
 // ---------------------------------------------------------------------------
-// K14
+// K14, K15, K17: the curve depths on the pair image (curve_routes.h), and K16
 // ---------------------------------------------------------------------------
-// the route that runs (1 pair image of the bucket kernel, 2 sort), 0 where the shape or algo has none
-static int rank_depth_route(int algo, i64 T, i64 n) {
-    if (T < 1 || n < 2 || n >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
-    if (algo == 1) return n <= RD_IMAGE_MAX_N ? 1 : 0;
-    return algo == 2 || n > RD_IMAGE_MAX_N ? 2 : 1;
+// The refusals that restate curve_route, in the family's words.  Each family keeps its own order of checks.
+static const char *const RD_ALGO_NAMES = "0 (auto), 1 (image), 2 (sort)", *const TVD_ALGO_NAMES = "0 (auto), 1 (LDS), 2 (pairwise)";
+
+static int refuse_algo(int algo, const char *names) {
+    return algo < 0 || algo > 2 ? fail(SD_ERR_INVALID, "algo=%d outside %s", algo, names) : SD_OK;
 }
 
+static int refuse_curves(i64 n, const char *family_takes) {
+    return n >= ((i64)1 << 31) ? fail(SD_ERR_UNSUPPORTED, "%s fewer than 2^31 curves, got %lld", family_takes, (long long)n) : SD_OK;
+}
+
+static int refuse_route1(int algo, i64 n, const char *route1) {
+    if (algo != 1 || n <= RD_IMAGE_MAX_N) return SD_OK;
+    return fail(SD_ERR_UNSUPPORTED, "the %s route holds up to %lld curves, got %lld (algo 0 or 2 takes them)", route1,
+                (long long)RD_IMAGE_MAX_N, (long long)n);
+}
+
+// ---- K14 ----
 size_t sd_rank_depth_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
     (void)m;
-    const int route = rank_depth_route(algo, T, n);
-    return route ? time_major_bytes(T, n, st, sn) + rank_depth_workspace_bytes(T, n, route) : 0;
+    const int route = curve_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + pair_image_plan(T, n, route, PlanSize::of_rows(T)).bytes : 0;
 }
 
 size_t sd_rank_depth_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
     (void)m;
-    const int route = rank_depth_route(algo, T, n);
-    return route ? time_major_bytes(T, n, st, sn) + rank_depth_min_workspace_bytes(n, route) : 0;
+    const int route = curve_route(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + pair_image_plan(T, n, route, PlanSize::of_rows(1)).bytes : 0;
 }
 
 int64_t sd_rank_depth_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes) {
     (void)m;
-    const int route = rank_depth_route(algo, T, n);
+    const int route = curve_route(algo, T, n);
     const size_t tm = route ? time_major_bytes(T, n, st, sn) : 0;
-    return route && ws_bytes >= tm ? rank_depth_rows_per_batch(T, n, route, ws_bytes - tm) : 0;
+    return route && ws_bytes >= tm ? pair_image_plan(T, n, route, PlanSize::of_bytes(ws_bytes - tm)).rows : 0;
 }
 
 int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
@@ -936,40 +963,32 @@ int sd_rank_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_
     if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (T < 1 || n < 2) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint and two curves",
                                     (long long)T, (long long)n);
-    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (image), 2 (sort)", algo);
-    if (n >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "rank depths take fewer than 2^31 curves, got %lld", (long long)n);
-    if (algo == 1 && n > RD_IMAGE_MAX_N)
-        return fail(SD_ERR_UNSUPPORTED, "the image route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
-                    (long long)RD_IMAGE_MAX_N, (long long)n);
-    int rc = check_matrix(X, T, n, st, sn, targets, m);
-    if (rc) return rc;
+    int rc;
+    if ((rc = refuse_algo(algo, RD_ALGO_NAMES)) || (rc = refuse_curves(n, "rank depths take")) ||
+        (rc = refuse_route1(algo, n, "image")) || (rc = check_matrix(X, T, n, st, sn, targets, m)))
+        return rc;
     if (m == 0) return SD_OK;
-    if (!ws || ws_bytes < sd_rank_depth_min_workspace_bytes(T, n, st, sn, m, algo))
-        return fail(SD_ERR_WORKSPACE, "workspace below sd_rank_depth_min_workspace_bytes");
-    hipStream_t s = (hipStream_t)stream;
-    Carver cv(ws, ws_bytes);
-    const double *Y;
-    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
-    const size_t rest = cv.rest();
-    return launch_rank_depth_sums(Y, T, n, targets, m, rank_depth_route(algo, T, n), out, cv.take(rest), rest, s);
+    const int route = curve_route(algo, T, n);
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_rank_depth_min_workspace_bytes(T, n, st, sn, m, algo),
+                             "sd_rank_depth_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_rank_depth_sums(Y, T, n, targets, m, route, out, w, bytes, s);
+                             });
 }
 
-// ---------------------------------------------------------------------------
-// K15
-// ---------------------------------------------------------------------------
-// K14's route for a shape the extremal depth takes, 0 otherwise
-static int extremal_route(int algo, i64 T, i64 n) { return T > EX_MAX_T ? 0 : rank_depth_route(algo, T, n); }
+// ---- K15 ----
+// the route of a shape the extremal depth takes, 0 otherwise
+static int curve_route_k15(int algo, i64 T, i64 n) { return T > EX_MAX_T ? 0 : curve_route(algo, T, n); }
 
 size_t sd_extremal_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
     (void)m;
-    const int route = extremal_route(algo, T, n);
-    return route ? time_major_bytes(T, n, st, sn) + extremal_fixed_workspace_bytes(T, n) + rank_depth_workspace_bytes(T, n, route) : 0;
+    const int route = curve_route_k15(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + extremal_plan(T, n, route, PlanSize::of_rows(T)).bytes : 0;
 }
 
 size_t sd_extremal_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
     (void)m;
-    const int route = extremal_route(algo, T, n);
-    return route ? time_major_bytes(T, n, st, sn) + extremal_fixed_workspace_bytes(T, n) + rank_depth_min_workspace_bytes(n, route) : 0;
+    const int route = curve_route_k15(algo, T, n);
+    return route ? time_major_bytes(T, n, st, sn) + extremal_plan(T, n, route, PlanSize::of_rows(1)).bytes : 0;
 }
 
 int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m,
@@ -977,33 +996,25 @@ int sd_extremal_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_
     if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (T < 1 || n < 2) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint and two curves",
                                     (long long)T, (long long)n);
-    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (image), 2 (sort)", algo);
+    int rc = refuse_algo(algo, RD_ALGO_NAMES);
+    if (rc) return rc;
     if (T > EX_MAX_T)
         return fail(SD_ERR_UNSUPPORTED, "extremal depth sorts up to %lld timepoints per curve, got %lld", (long long)EX_MAX_T,
                     (long long)T);
-    if (n >= ((i64)1 << 31)) return fail(SD_ERR_UNSUPPORTED, "extremal depth takes fewer than 2^31 curves, got %lld", (long long)n);
-    if (algo == 1 && n > RD_IMAGE_MAX_N)
-        return fail(SD_ERR_UNSUPPORTED, "the image route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
-                    (long long)RD_IMAGE_MAX_N, (long long)n);
+    if ((rc = refuse_curves(n, "extremal depth takes")) || (rc = refuse_route1(algo, n, "image"))) return rc;
     const double walk = (double)n * (double)m * (double)T;         // every pair undecided by its head, to the last entry
     if (walk > HS_MAX_WORK)
         return fail(SD_ERR_UNSUPPORTED, "%.3g entry comparisons in the worst case exceed the cap of %.0e", walk, HS_MAX_WORK);
-    int rc = check_matrix(X, T, n, st, sn, targets, m);
-    if (rc) return rc;
+    if ((rc = check_matrix(X, T, n, st, sn, targets, m))) return rc;
     if (m == 0) return SD_OK;
-    if (!ws || ws_bytes < sd_extremal_min_workspace_bytes(T, n, st, sn, m, algo))
-        return fail(SD_ERR_WORKSPACE, "workspace below sd_extremal_min_workspace_bytes");
-    hipStream_t s = (hipStream_t)stream;
-    Carver cv(ws, ws_bytes);
-    const double *Y;
-    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
-    const size_t rest = cv.rest();
-    return launch_extremal_counts(Y, T, n, targets, m, extremal_route(algo, T, n), out, cv.take(rest), rest, s);
+    const int route = curve_route_k15(algo, T, n);
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_extremal_min_workspace_bytes(T, n, st, sn, m, algo),
+                             "sd_extremal_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_extremal_counts(Y, T, n, targets, m, route, out, w, bytes, s);
+                             });
 }
 
-// ---------------------------------------------------------------------------
-// K16
-// ---------------------------------------------------------------------------
+// ---- K16 ----
 int64_t sd_central_regions_row_capacity(void) { return CR_ROW_CAPACITY; }
 
 size_t sd_central_regions_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int L) {
@@ -1025,68 +1036,49 @@ int sd_central_regions(const double *X, int64_t T, int64_t n, int64_t st, int64_
         return fail(SD_ERR_INVALID, "box=-1 asks for the envelopes only: fence, outside and whisker must be null");
     int rc = check_matrix(X, T, n, st, sn, nullptr, n);
     if (rc) return rc;
-    if (!ws || ws_bytes < sd_central_regions_workspace_bytes(T, n, st, sn, L))
-        return fail(SD_ERR_WORKSPACE, "workspace below sd_central_regions_workspace_bytes");
-    hipStream_t s = (hipStream_t)stream;
-    Carver cv(ws, ws_bytes);
-    const double *Y;
-    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
-    const size_t rest = cv.rest();
-    return launch_central_regions(Y, T, n, level, L, box, factor, env, fence, outside, whisker, cv.take(rest), rest, s);
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_central_regions_workspace_bytes(T, n, st, sn, L),
+                             "sd_central_regions_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_central_regions(Y, T, n, level, L, box, factor, env, fence, outside, whisker, w, bytes, s);
+                             });
 }
 
-// ---------------------------------------------------------------------------
-// K17
-// ---------------------------------------------------------------------------
-// the route that runs (1 LDS, 2 pairwise), 0 where the shape or algo has none
-static int tvd_route(int algo, i64 T, i64 n, i64 m) {
-    if (T < 1 || n < 2 || m < 0 || n >= ((i64)1 << 31) || T >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
-    if (algo == 1) return n <= RD_IMAGE_MAX_N ? 1 : 0;
-    return algo == 2 || n > RD_IMAGE_MAX_N ? 2 : 1;
-}
+// ---- K17 ----
+// the route (1 LDS, 2 pairwise) of a shape and a number of targets the total variation depth takes, 0 otherwise
+static int curve_route_k17(int algo, i64 T, i64 n, i64 m) { return m < 0 || T >= ((i64)1 << 31) ? 0 : curve_route(algo, T, n); }
 
 size_t sd_tvd_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
-    const int route = tvd_route(algo, T, n, m);
-    return route ? time_major_bytes(T, n, st, sn) + tvd_workspace_bytes(T, n, m, route) : 0;
+    const int route = curve_route_k17(algo, T, n, m);
+    return route ? time_major_bytes(T, n, st, sn) + tvd_plan(T, n, m, route, PlanSize::of_rows(T)).bytes : 0;
 }
 
 size_t sd_tvd_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo) {
-    const int route = tvd_route(algo, T, n, m);
-    return route ? time_major_bytes(T, n, st, sn) + tvd_min_workspace_bytes(T, n, m, route) : 0;
+    const int route = curve_route_k17(algo, T, n, m);
+    return route ? time_major_bytes(T, n, st, sn) + tvd_plan(T, n, m, route, PlanSize::of_rows(1)).bytes : 0;
 }
 
 int64_t sd_tvd_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int algo, size_t ws_bytes) {
-    const int route = tvd_route(algo, T, n, m);
+    const int route = curve_route_k17(algo, T, n, m);
     const size_t tm = route ? time_major_bytes(T, n, st, sn) : 0;
-    if (!route || ws_bytes < tm) return 0;
-    if (route == 2) return ws_bytes - tm >= tvd_min_workspace_bytes(T, n, m, 2) ? T : 0;
-    return tvd_rows_per_batch(T, n, m, ws_bytes - tm);
+    return route && ws_bytes >= tm ? tvd_plan(T, n, m, route, PlanSize::of_bytes(ws_bytes - tm)).rows : 0;
 }
 
 int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, int algo,
                 int64_t *sd_sum, double *shape, uint32_t *counts, void *ws, size_t ws_bytes, void *stream) {
     if (!X || !sd_sum || !shape) return fail(SD_ERR_INVALID, "null pointer (X, sd_sum and shape are required)");
     if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
-    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (LDS), 2 (pairwise)", algo);
-    if (n < 2) return fail(SD_ERR_UNSUPPORTED, "the total variation depth needs at least two curves, got %lld", (long long)n);
-    if (algo == 1 && n > RD_IMAGE_MAX_N)
-        return fail(SD_ERR_UNSUPPORTED, "the LDS route holds up to %lld curves, got %lld (algo 0 or 2 takes them)",
-                    (long long)RD_IMAGE_MAX_N, (long long)n);
-    int rc = check_matrix(X, T, n, st, sn, targets, m);
+    int rc = refuse_algo(algo, TVD_ALGO_NAMES);
     if (rc) return rc;
-    const int route = tvd_route(algo, T, n, m);
+    if (n < 2) return fail(SD_ERR_UNSUPPORTED, "the total variation depth needs at least two curves, got %lld", (long long)n);
+    if ((rc = refuse_route1(algo, n, "LDS")) || (rc = check_matrix(X, T, n, st, sn, targets, m))) return rc;
+    const int route = curve_route_k17(algo, T, n, m);
     const double work = (double)n * (double)m * (double)T;         // comparisons of the pairwise route
     if (route == 2 && work > HS_MAX_WORK)
         return fail(SD_ERR_UNSUPPORTED, "%.3g comparisons of the pairwise route exceed the cap of %.0e", work, HS_MAX_WORK);
     if (m == 0) return SD_OK;
-    if (!ws || ws_bytes < sd_tvd_min_workspace_bytes(T, n, st, sn, m, algo))
-        return fail(SD_ERR_WORKSPACE, "workspace below sd_tvd_min_workspace_bytes");
-    hipStream_t s = (hipStream_t)stream;
-    Carver cv(ws, ws_bytes);
-    const double *Y;
-    if ((rc = time_major(X, T, n, st, sn, cv, s, &Y))) return rc;
-    const size_t rest = cv.rest();
-    return launch_tvd_sums(Y, T, n, targets, m, route, sd_sum, shape, counts, cv.take(rest), rest, s);
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_tvd_min_workspace_bytes(T, n, st, sn, m, algo),
+                             "sd_tvd_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_tvd_sums(Y, T, n, targets, m, route, sd_sum, shape, counts, w, bytes, s);
+                             });
 }
 
 }  // extern "C"

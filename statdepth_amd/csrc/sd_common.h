@@ -158,32 +158,8 @@ int launch_projection_sorted(const double *P, i64 n, int d, const double *U, i64
 int launch_projection_blocks(const double *P, i64 n, int d, const double *U, i64 k, const PointSel &sel, i64 nb, double *out,
                              hipStream_t s);
 
-// K14 integrated rank depths of curves (rank_depths.hip): out[q] = (SA, SB, SF, SM, MM).  route 1 = pair image of the
-// bucket kernel (n <= RD_IMAGE_MAX_N), 2 = K10's sort and a u64 pair image (any n); the workspace sizes are those of the
-// route alone, behind the time-major copy
-constexpr i64 RD_IMAGE_MAX_N = 16384;
-size_t rank_depth_workspace_bytes(i64 T, i64 n, int route);
-size_t rank_depth_min_workspace_bytes(i64 n, int route);
-i64 rank_depth_rows_per_batch(i64 T, i64 n, int route, size_t bytes);   // rows a batch / chunk takes with `bytes`; 0 below the floor
-int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
-                           size_t ws_bytes, hipStream_t s);
-// What takes the pair image of one batch of rows [row0, row0 + rows) of Y, img[r][i] of row row0 + r and curve i: B | A << 16
-// in u32 on route 1, B | A << 32 in u64 on route 2.  It enqueues on s; the next batch overwrites the image.
-struct RankImageConsumer {
-    virtual int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) = 0;
-    virtual int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) = 0;
-    virtual ~RankImageConsumer() = default;
-};
-// the two routes of K14, batch by batch, with `ws` sized as for launch_rank_depth_sums
-int launch_rank_pair_images(const double *Y, i64 T, i64 n, int route, RankImageConsumer &use, void *ws, size_t ws_bytes,
-                            hipStream_t s);
-
-// K15 extremal depth of curves (extremal.hip): out[q] = #{curves i : v_i >=lex v_q}, v the descending sort of |A - B| over
-// time.  `route` and the workspace behind the time-major copy as in K14, plus the extremity matrix and the heads
-constexpr i64 EX_MAX_T = 16384;                                     // keys one sort workgroup holds in LDS (64 KiB)
-size_t extremal_fixed_workspace_bytes(i64 T, i64 n);                // E and H; stage 1 takes the rest
-int launch_extremal_counts(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
-                           size_t ws_bytes, hipStream_t s);
+// K14 rank depths, K15 extremal depth and K17 total variation depth of curves: the pair-image plan and the launchers are in
+// curve_routes.h
 
 // K16 central regions, fence, outside counts and whiskers of the functional boxplot (central_regions.hip).  Y time-major;
 // fence, outside and whisker may be null (all three are with box = -1).  The workspace behind the time-major copy: a
@@ -192,15 +168,6 @@ constexpr i64 CR_ROW_CAPACITY = 16384;                              // curves of
 size_t central_regions_workspace_bytes(i64 T, i64 n, int L);
 int launch_central_regions(const double *Y, i64 T, i64 n, const uint8_t *level, int L, int box, double factor, double *env,
                            double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes, hipStream_t s);
-
-// K17 total variation depth and shape similarity of curves (tvd.hip): sd_sum[q] = SD, shape[q] = (SS, SN, SW), counts
-// (null or [T - 1][m]) = c_t.  route 1 = K14's pair image and the dominance kernel in LDS (n <= RD_IMAGE_MAX_N), 2 =
-// pairwise over the doubles (any n); the workspace sizes are those behind the time-major copy
-size_t tvd_workspace_bytes(i64 T, i64 n, i64 m, int route);
-size_t tvd_min_workspace_bytes(i64 T, i64 n, i64 m, int route);
-i64 tvd_rows_per_batch(i64 T, i64 n, i64 m, size_t bytes);          // route 1: rows a batch takes with `bytes`; 0 below the floor
-int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
-                    u32 *counts, void *ws, size_t ws_bytes, hipStream_t s);
 
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);

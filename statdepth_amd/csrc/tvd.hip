@@ -60,7 +60,7 @@
 // reads only the doubles.  256 targets a block against LDS tiles of 1024 curves of the rows s and t; a_s, a_t and c_t are
 // counted by comparison and fed to the same arithmetic, the same 16 slices and the same finish.  O(T n m).  A merge route
 // in global memory for large n is out of scope.
-#include "sd_common.h"
+#include "curve_routes.h"
 
 namespace sd {
 
@@ -323,54 +323,41 @@ __global__ __launch_bounds__(256) void tvd_finish_kernel(const double *__restric
 // ---------------------------------------------------------------------------------------------- workspaces
 // behind the time-major copy: the slices' records, then on the LDS route the carried row, C and stage 1's batch
 static inline size_t tvd_part_bytes(i64 m) { return align_up((size_t)m * TVD_SLICES * TVD_REC * 8, 256); }
-static inline size_t tvd_fixed_bytes(i64 n, i64 m) { return tvd_part_bytes(m) + align_up((size_t)n * 4, 256); }
-// the most rows stage 1 takes in a batch of this shape
-static inline i64 tvd_rows_cap(i64 T, i64 n) { return rank_depth_rows_per_batch(T, n, 1, (size_t)1 << 60); }
-// Stage 1 is handed the size K14 recommends for r rows and takes as many rows as that holds: r, or more where the padding
-// of a small image leaves room.  C is sized for what it takes.
-static inline i64 tvd_batch_rows(i64 T, i64 r, i64 n) { return rank_depth_rows_per_batch(T, n, 1, rank_depth_workspace_bytes(r, n, 1)); }
-static inline size_t tvd_batch_bytes(i64 T, i64 r, i64 n) {
-    return align_up((size_t)tvd_batch_rows(T, r, n) * n * 2, 256) + rank_depth_workspace_bytes(r, n, 1);
-}
-
-size_t tvd_min_workspace_bytes(i64 T, i64 n, i64 m, int route) {
-    return route == 1 ? tvd_fixed_bytes(n, m) + tvd_batch_bytes(T, 1, n) : tvd_part_bytes(m);
-}
-
-size_t tvd_workspace_bytes(i64 T, i64 n, i64 m, int route) {
-    return route == 1 ? tvd_fixed_bytes(n, m) + tvd_batch_bytes(T, tvd_rows_cap(T, n), n) : tvd_part_bytes(m);
-}
-
-// The r stage 1 is sized for with `bytes` behind the time-major copy: the most whose image and C fit; 0 below the floor.
-static i64 tvd_sized_rows(i64 T, i64 n, i64 m, size_t bytes) {
-    if (bytes < tvd_min_workspace_bytes(T, n, m, 1)) return 0;
-    const size_t room = bytes - tvd_fixed_bytes(n, m);
-    i64 lo = 1, hi = tvd_rows_cap(T, n);                            // tvd_batch_bytes does not fall as r grows
+// Stage 1 sized for r rows takes as many rows as that size holds -- r, or more where the padding of a small image leaves
+// room -- and C is sized for what it takes: both from the one PairImagePlan.  By bytes, r is the most whose C and stage 1
+// fit (their sum does not fall as r grows); the recommended size is for the most rows stage 1 takes in a batch.
+TvdPlan tvd_plan(i64 T, i64 n, i64 m, int route, PlanSize size) {
+    TvdPlan p{{route, 0, 0}, 0, tvd_part_bytes(m)};
+    if (route != 1) {
+        p.rows = size.rows || size.bytes >= p.bytes ? T : 0;
+        return p;
+    }
+    const size_t fixed = p.bytes + align_up((size_t)n * 4, 256);
+    auto batch = [&](i64 r) {
+        const PairImagePlan s1 = pair_image_plan(T, n, 1, PlanSize::of_rows(r));
+        return TvdPlan{s1, s1.rows, fixed + align_up((size_t)s1.rows * n * 2, 256) + s1.bytes};
+    };
+    i64 lo = 1, hi = pair_image_plan(T, n, 1, PlanSize::of_rows(T)).rows;
+    if (size.rows) return batch(size.rows < hi ? size.rows : hi);
+    if (size.bytes < batch(1).bytes) return p;
     while (lo < hi) {
         const i64 mid = (lo + hi + 1) >> 1;
-        if (tvd_batch_bytes(T, mid, n) <= room) lo = mid;
+        if (batch(mid).bytes <= size.bytes) lo = mid;
         else hi = mid - 1;
     }
-    return lo;
-}
-
-// rows per batch of the LDS route with `bytes` behind the time-major copy; 0 below the floor
-i64 tvd_rows_per_batch(i64 T, i64 n, i64 m, size_t bytes) {
-    const i64 r = tvd_sized_rows(T, n, m, bytes);
-    return r > 0 ? tvd_batch_rows(T, r, n) : 0;
+    return batch(lo);
 }
 
 // ---------------------------------------------------------------------------------------------- host
 struct TvdImageFold final : RankImageConsumer {
     const double *Y;
-    i64 T, n, m, crows;
+    i64 T, n, m;
     const i64 *targets;
     u32 *carry;
     unsigned short *C;
     double *part;
     u32 *counts;
     int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) override {
-        if (rows > crows) return fail(SD_ERR_WORKSPACE, "a batch of %lld rows, C holds %lld", (long long)rows, (long long)crows);
         const int first_local = row0 == 0 ? 1 : 0;
         const i64 pairs = rows - first_local;
         if (pairs > 0) {
@@ -401,20 +388,19 @@ struct TvdImageFold final : RankImageConsumer {
 
 int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
                     u32 *counts, void *ws, size_t ws_bytes, hipStream_t s) {
+    const TvdPlan plan = tvd_plan(T, n, m, route, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);
     double *part = (double *)cv.take((size_t)m * TVD_SLICES * TVD_REC * 8);
-    if (!part) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_tvd_min_workspace_bytes)");
+    if (!part || plan.rows < 1) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_tvd_min_workspace_bytes)");
     if (route == 1) {
-        const i64 sized = tvd_sized_rows(T, n, m, ws_bytes), rpb = sized > 0 ? tvd_batch_rows(T, sized, n) : 0;
         u32 *carry = (u32 *)cv.take((size_t)n * 4);
-        unsigned short *C = rpb > 0 ? (unsigned short *)cv.take((size_t)rpb * n * 2) : nullptr;
-        const size_t stage1 = rpb > 0 ? rank_depth_workspace_bytes(sized, n, 1) : 0;   // the batch C was sized for, exactly
-        void *w1 = rpb > 0 ? cv.take(stage1) : nullptr;
+        unsigned short *C = (unsigned short *)cv.take((size_t)plan.rows * n * 2);
+        void *w1 = cv.take(plan.stage1.bytes);
         if (!carry || !C || !w1) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_tvd_min_workspace_bytes)");
         TvdImageFold fold;
-        fold.Y = Y, fold.T = T, fold.n = n, fold.m = m, fold.crows = rpb, fold.targets = targets, fold.carry = carry, fold.C = C;
+        fold.Y = Y, fold.T = T, fold.n = n, fold.m = m, fold.targets = targets, fold.carry = carry, fold.C = C;
         fold.part = part, fold.counts = counts;
-        int rc = launch_rank_pair_images(Y, T, n, 1, fold, w1, stage1, s);
+        int rc = launch_rank_pair_images(plan.stage1, Y, T, n, fold, w1, s);
         if (rc) return rc;
     } else {
         const dim3 grid((unsigned)((m + TVD_PW_THREADS - 1) / TVD_PW_THREADS), TVD_SLICES);

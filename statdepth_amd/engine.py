@@ -186,16 +186,20 @@ def _sized(dev, nbytes):
     return _workspace(dev, nbytes), int(nbytes)
 
 
+_OUT = object()                                                      # the place of `out` among _launch's args, unless it is the last
+
+
 def _launch(dev, fn, out, *args, workspace=None, return_tensor=False):
-    """fn(*args, out, [ws, ws_bytes,] stream) on dev's current stream; returns out as an ndarray, or the tensor itself
-    with return_tensor.  Nothing is launched when out has no rows.  workspace: None, or a function of no arguments
-    returning (buffer, bytes), asked for only when there is something to launch."""
+    """fn(*args, out, [ws, ws_bytes,] stream) on dev's current stream, out at the place of _OUT where args name one; returns
+    out as an ndarray, or the tensor itself with return_tensor.  Nothing is launched when out has no rows.  workspace:
+    None, or a function of no arguments returning (buffer, bytes), asked for only when there is something to launch."""
     t = torch()
     if out.shape[0]:
         ws = workspace() if workspace is not None else None
         tail = (ws[0].data_ptr(), ws[1]) if ws is not None else ()
+        head = args if any(a is _OUT for a in args) else (*args, _OUT)
         with t.cuda.device(dev):
-            check(fn(*args, out.data_ptr(), *tail, _stream_ptr(dev)))
+            check(fn(*(out.data_ptr() if a is _OUT else a for a in head), *tail, _stream_ptr(dev)))
     return out if return_tensor else out.cpu().numpy()
 
 
@@ -372,12 +376,36 @@ def _rank_depth_algo(algo):
     return RANK_DEPTH_ALGOS[algo] if isinstance(algo, str) else int(algo)
 
 
+def _strides(T, n, curve_major):
+    """(st, sn) of a T x n matrix: curve-major (F-contiguous), or time-major, which a single row or column always is."""
+    return (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+
+
+def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs):
+    """lib.sd_<family>_<what>(X, T, n, st, sn, targets, m, algo, *outputs, ws, ws_bytes, stream) with ws_bytes of workspace
+    (None: what sd_<family>_workspace_bytes recommends).  outputs(t, dev, M, m): the output tensors in the order of the C
+    signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays."""
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    a = algo_of(algo)
+    td, m, tp = _targets_dev(targets, M.n, dev)
+    outs = outputs(t, dev, M, m)
+    size = getattr(lib, f"sd_{family}_workspace_bytes")
+    _launch(dev, getattr(lib, f"sd_{family}_{what}"), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a, _OUT,
+            *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
+            workspace=lambda: _sized(dev, size(M.T, M.n, M.st, M.sn, m, a) if ws_bytes is None else ws_bytes),
+            return_tensor=True)
+    return [o.cpu().numpy() if o is not None else None for o in outs]
+
+
 def rank_depth_workspace_bytes(T, n, algo="auto", curve_major=False):
     """(recommended, floor) workspace sizes of sd_rank_depth_sums for a T x n matrix; the floor holds one row per batch.
     curve_major: the matrix is F-contiguous and takes a time-major copy in the workspace as well."""
     lib = _native.load()
     T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    st, sn = _strides(T, n, curve_major)
     return (int(lib.sd_rank_depth_workspace_bytes(T, n, st, sn, n, a)),
             int(lib.sd_rank_depth_min_workspace_bytes(T, n, st, sn, n, a)))
 
@@ -387,8 +415,7 @@ def rank_depth_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False):
     workspace; 0 below the floor.  At the recommended size this is all T rows whenever T is within the route's caps."""
     lib = _native.load()
     T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
-    return int(lib.sd_rank_depth_rows_per_batch(T, n, st, sn, n, a, int(ws_bytes)))
+    return int(lib.sd_rank_depth_rows_per_batch(T, n, *_strides(T, n, curve_major), n, a, int(ws_bytes)))
 
 
 def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
@@ -397,16 +424,8 @@ def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
     of max(A, B).  X must not hold NaN (the depth layer checks; this function takes its array as it is).  algo: 'auto',
     'image' (n <= 16 384) or 'sort', or their numbers 0, 1, 2.  ws_bytes: the workspace size to run with (default: the
     recommended one); the records do not depend on it, below the floor the library refuses."""
-    t = torch()
-    lib = _lib()
-    M = to_device_matrix(X, device)
-    dev = M.device
-    a = _rank_depth_algo(algo)
-    td, m, tp = _targets_dev(targets, M.n, dev)
-    out = t.empty((m, 5), dtype=t.int64, device=dev)
-    size = (lambda: lib.sd_rank_depth_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
-    return _launch(dev, lib.sd_rank_depth_sums, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a,
-                   workspace=lambda: _sized(dev, size()))
+    return _curves("rank_depth", "sums", _rank_depth_algo, X, targets, device, algo, ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m, 5), dtype=t.int64, device=dev)])[0]
 
 
 def extremal_workspace_bytes(T, n, algo="auto", curve_major=False):
@@ -415,7 +434,7 @@ def extremal_workspace_bytes(T, n, algo="auto", curve_major=False):
     shape or algo the call refuses.  curve_major: the matrix is F-contiguous and takes a time-major copy as well."""
     lib = _native.load()
     T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    st, sn = _strides(T, n, curve_major)
     return (int(lib.sd_extremal_workspace_bytes(T, n, st, sn, n, a)),
             int(lib.sd_extremal_min_workspace_bytes(T, n, st, sn, n, a)))
 
@@ -425,16 +444,8 @@ def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
     whose descending-sorted vector of pointwise extremities |A - B| is lexicographically at least the target's; the depth
     is G / n.  X must not hold NaN (the depth layer checks; this function takes its array as it is).  targets: indices of
     sample curves (None: all).  algo and ws_bytes as for rank_depth_sums; the counts do not depend on ws_bytes."""
-    t = torch()
-    lib = _lib()
-    M = to_device_matrix(X, device)
-    dev = M.device
-    a = _rank_depth_algo(algo)
-    td, m, tp = _targets_dev(targets, M.n, dev)
-    out = t.empty((m,), dtype=t.int64, device=dev)
-    size = (lambda: lib.sd_extremal_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
-    return _launch(dev, lib.sd_extremal_counts, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a,
-                   workspace=lambda: _sized(dev, size()))
+    return _curves("extremal", "counts", _rank_depth_algo, X, targets, device, algo, ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m,), dtype=t.int64, device=dev)])[0]
 
 
 TVD_ALGOS = {"auto": 0, "lds": 1, "pairwise": 2}
@@ -453,7 +464,7 @@ def tvd_workspace_bytes(T, n, algo="auto", curve_major=False, m=None):
     lib = _native.load()
     T, n, a = int(T), int(n), _tvd_algo(algo)
     m = n if m is None else int(m)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
+    st, sn = _strides(T, n, curve_major)
     return (int(lib.sd_tvd_workspace_bytes(T, n, st, sn, m, a)), int(lib.sd_tvd_min_workspace_bytes(T, n, st, sn, m, a)))
 
 
@@ -463,8 +474,7 @@ def tvd_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False, m=None):
     lib = _native.load()
     T, n, a = int(T), int(n), _tvd_algo(algo)
     m = n if m is None else int(m)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
-    return int(lib.sd_tvd_rows_per_batch(T, n, st, sn, m, a, int(ws_bytes)))
+    return int(lib.sd_tvd_rows_per_batch(T, n, *_strides(T, n, curve_major), m, a, int(ws_bytes)))
 
 
 def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=False):
@@ -476,25 +486,10 @@ def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=Fa
     array as it is).  algo: 'auto', 'lds' (n <= 16 384) or 'pairwise', or their numbers 0, 1, 2.  ws_bytes: the workspace
     size to run with (default: the recommended one); the results do not depend on it, below the floor the library
     refuses."""
-    t = torch()
-    lib = _lib()
-    M = to_device_matrix(X, device)
-    dev = M.device
-    a = _tvd_algo(algo)
-    td, m, tp = _targets_dev(targets, M.n, dev)
-    sd = t.empty((m,), dtype=t.int64, device=dev)
-    shape = t.empty((m, 3), dtype=t.float64, device=dev)
-    cnt = t.empty((max(M.T - 1, 0), m), dtype=t.int32, device=dev) if counts else None
-    size = (lambda: lib.sd_tvd_workspace_bytes(M.T, M.n, M.st, M.sn, m, a)) if ws_bytes is None else (lambda: ws_bytes)
-
-    def call(X_, T_, n_, st_, sn_, targets_, m_, algo_, shape_, counts_, sd_, ws_, ws_bytes_, stream_):
-        return lib.sd_tvd_sums(X_, T_, n_, st_, sn_, targets_, m_, algo_, sd_, shape_, counts_, ws_, ws_bytes_, stream_)
-
-    _launch(dev, call, sd, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a, shape.data_ptr(),
-            cnt.data_ptr() if cnt is not None and cnt.numel() else None, workspace=lambda: _sized(dev, size()),
-            return_tensor=True)
-    out = (sd.cpu().numpy(), shape.cpu().numpy())
-    return out + (cnt.cpu().numpy().view(np.uint32),) if counts else out
+    sd, shape, cnt = _curves("tvd", "sums", _tvd_algo, X, targets, device, algo, ws_bytes, lambda t, dev, M, m: [
+        t.empty((m,), dtype=t.int64, device=dev), t.empty((m, 3), dtype=t.float64, device=dev),
+        t.empty((max(M.T - 1, 0), m), dtype=t.int32, device=dev) if counts else None])
+    return (sd, shape, cnt.view(np.uint32)) if counts else (sd, shape)
 
 
 def central_regions_row_capacity():
@@ -511,8 +506,7 @@ def central_regions_workspace_bytes(T, n, L, curve_major=False):
     torch()
     lib = _native.load()
     T, n = int(T), int(n)
-    st, sn = (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
-    return int(lib.sd_central_regions_workspace_bytes(T, n, st, sn, int(L)))
+    return int(lib.sd_central_regions_workspace_bytes(T, n, *_strides(T, n, curve_major), int(L)))
 
 
 def central_regions(X, level, L=None, box=None, factor=1.5, whiskers=True, device=None, outside=True, fence=True):
@@ -547,14 +541,9 @@ def central_regions(X, level, L=None, box=None, factor=1.5, whiskers=True, devic
     cnt = t.empty((M.n, 2), dtype=t.int32, device=dev) if fenced and outside else None
     whi = t.empty((2, M.T), dtype=t.float64, device=dev) if fenced and whiskers else None
     ptr = lambda x: x.data_ptr() if x is not None else None
-
-    def call(X_, T_, n_, st_, sn_, level_, L_, box_, factor_, fence_, outside_, whisker_, env_, ws_, ws_bytes_, stream_):
-        return lib.sd_central_regions(X_, T_, n_, st_, sn_, level_, L_, box_, factor_, env_, fence_, outside_, whisker_, ws_,
-                                      ws_bytes_, stream_)
-
-    _launch(dev, call, env, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, lvd.data_ptr(), L, b, float(factor), ptr(fen), ptr(cnt),
-            ptr(whi), workspace=lambda: _sized(dev, lib.sd_central_regions_workspace_bytes(M.T, M.n, M.st, M.sn, L)),
-            return_tensor=True)
+    _launch(dev, lib.sd_central_regions, env, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, lvd.data_ptr(), L, b, float(factor),
+            _OUT, ptr(fen), ptr(cnt), ptr(whi),
+            workspace=lambda: _sized(dev, lib.sd_central_regions_workspace_bytes(M.T, M.n, M.st, M.sn, L)), return_tensor=True)
     return tuple(x.cpu().numpy() if x is not None else None for x in (env, fen, cnt, whi))
 
 

@@ -134,6 +134,27 @@ def test_batch_boundaries(curve_major):
         engine.tvd_sums(M, algo='lds', ws_bytes=floor - 1)
 
 
+@pytest.mark.parametrize('curve_major', [False, True])
+@pytest.mark.parametrize('n,floor_rows', [(2, 32), (5, 12)])
+def test_floor_whose_image_holds_several_rows(n, floor_rows, curve_major):
+    """T = 70 with so few curves that the 256-byte padding of the floor's image leaves room for more than the one row it
+    is sized for (64 / n of them): stage 1 takes them all, and C has to hold what stage 1 takes.  At the floor, half-way to
+    the recommended size and at it, the integers equal the model and the doubles those of the recommended size."""
+    T = 70
+    X = curves(T, n, 'rounded', seed=4)
+    M = np.asfortranarray(X) if curve_major else X
+    a, c = tvd_counts_np(X)
+    shape0 = engine.tvd_sums(M, algo='lds')[1]                       # the recommended size
+    rec, floor = engine.tvd_workspace_bytes(T, n, algo='lds', curve_major=curve_major)
+    sizes = (floor, (floor + rec) // 2, rec)
+    rows = [engine.tvd_rows_per_batch(T, n, ws, algo='lds', curve_major=curve_major) for ws in sizes]
+    assert rows[0] == floor_rows > 1 and rows[0] < rows[1] <= rows[2] == T, rows
+    for ws in sizes:
+        sd, shape, counts = engine.tvd_sums(M, algo='lds', counts=True, ws_bytes=ws)
+        assert np.array_equal(counts, c) and np.array_equal(sd, sd_of(a, n)), ws
+        assert np.array_equal(shape, shape0), ws
+
+
 def test_one_timepoint_gives_sd_only():
     X = curves(1, 300, 'rounded')
     a, _ = tvd_counts_np(X)
