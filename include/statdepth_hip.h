@@ -659,6 +659,48 @@ int64_t sd_tvd_rows_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int6
 int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, int algo,
                 int64_t *sd_sum, double *shape, uint32_t *counts, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K18: halfspace and projection depth of multivariate curves, integrated over time ----------
+ * No reference code (the multivariate functional halfspace depth of Claeskens, Hubert, Slaets & Vakili 2014 and its
+ * projection-depth sibling, over a fixed direction set).  P is n x T x d row-major fp64, P[i][t][e] (device), d <= 8; U is
+ * k x d row-major (device), shared by all timepoints.  The cloud at t is C_t = {P[i][t][:]}: n points, the target among them.
+ *   h_t(i) = K10's count of point i in C_t (min over the directions of min(ge, le), the point and every tie counted);
+ *   O_t(i) = K12's outlyingness of point i in C_t (median rule, MAD without factor, one correctly rounded division, a
+ *            numerator of 0 gives 0, a positive one with MAD = 0 gives +inf);
+ * both on K10's projection bits.  The records per target:
+ *   sd_multi_halfspace_sums:   out[q] = (SH, MH) = (sum_t h_t, min_t h_t), int64.  Host: mean depth = SH / (n T), infimal
+ *                              depth = MH / n.
+ *   sd_multi_projection_sums:  out[q] = (PS, OM) = (sum_t 1 / (1 + O_t), max_t O_t), doubles.  A term of PS is one rounded
+ *                              addition and one correctly rounded division (O = inf: 0.0); the terms are added in ascending
+ *                              t from 0.0, one rounded addition per timepoint (the order of np.cumsum).  Host: mean depth =
+ *                              PS / T, infimal depth = 1 / (1 + OM).
+ * A numpy restatement gives the same bits, and nothing depends on algo, on the workspace size or on how directions and
+ * timepoints are split: integer min and sum and the maximum of non-negative doubles are order-free, and PS is added by one
+ * owner per target in ascending t, carried across the batches of timepoints in stream order.
+ * Routes: algo 1 (lds), n <= sd_multi_cloud_lds_capacity() = 8192: a batch of timepoints is copied feature-major into the
+ *   workspace; one workgroup per (timepoint, 32 directions) projects the cloud, sorts the n keys in its LDS (64 KB) and
+ *   ranks every point in them (halfspace: a lower and an upper bound per point; projection: K12's selection of the median
+ *   and the MAD); slices of a timepoint meet through atomicMin / atomicMax on the bit pattern.  algo 2 (global), any n: per
+ *   timepoint the cloud is gathered and sd_halfspace_counts' / sd_projection_outlyingness' own launchers run on it.
+ *   algo 0 (auto): algo 1 up to the capacity, algo 2 above.
+ * Workspace: algo 1 holds per timepoint of a batch the copy (8 n d bytes) and every curve's value (4 n or 8 n); algo 2 the
+ * cloud (8 n d), the values (8 n) and K10's / K12's workspace.  sd_multi_*_workspace_bytes recommends a size,
+ * sd_multi_*_min_workspace_bytes is the floor (one timepoint per batch; one direction per chunk); both are 0 for a shape or
+ * algo the call refuses.
+ * targets: m int64 curve indices (device), NULL = all (m == n); repeated and permuted entries are allowed; every curve is
+ * ranked whatever m is.
+ * SD_ERR_INVALID for NULL pointers, n, T, d, k < 1 or an unknown algo; SD_ERR_UNSUPPORTED for d > 8, 2^31 or more curves,
+ * more than 10^14 projections and comparisons (T k n (d + log2 n)), or algo 1 above the capacity; SD_ERR_WORKSPACE below the
+ * floor.  All before any device work.  Every launch is bounded in work. */
+int64_t sd_multi_cloud_lds_capacity(void);
+size_t sd_multi_halfspace_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+size_t sd_multi_halfspace_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+int sd_multi_halfspace_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
+                            int64_t m, int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
+size_t sd_multi_projection_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+size_t sd_multi_projection_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+int sd_multi_projection_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
+                             int64_t m, int algo, double *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

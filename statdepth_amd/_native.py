@@ -104,6 +104,13 @@ SIGNATURES = {
     "sd_tvd_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
     "sd_tvd_rows_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _int, _sz]),
     "sd_tvd_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sd_multi_cloud_lds_capacity": (_i64, []),
+    "sd_multi_halfspace_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_halfspace_min_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_halfspace_sums": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "sd_multi_projection_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_projection_min_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_projection_sums": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
 }
 
 

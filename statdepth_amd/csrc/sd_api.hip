@@ -1081,4 +1081,66 @@ int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, c
                              });
 }
 
+// ---------------------------------------------------------------------------
+// K18
+// ---------------------------------------------------------------------------
+int64_t sd_multi_cloud_lds_capacity(void) { return MC_LDS_CAPACITY; }
+
+// the route of a call the size functions answer for (0: none)
+static int multi_cloud_sized_route(i64 n, i64 T, int d, i64 k, i64 m, int algo) {
+    if (n < 1 || T < 1 || d < 1 || d > 8 || k < 1 || m < 0 || n >= ((i64)1 << 31) || algo < 0 || algo > 2) return 0;
+    return multi_cloud_route(algo, n);
+}
+
+// K10's / K12's checks in their order and wording, with T clouds of n points; then algo, the targets and the route
+static int multi_cloud_sums(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets, i64 m,
+                            int algo, void *out, void *ws, size_t ws_bytes, void *stream) {
+    const double work = (double)T * (double)k * (double)n * ((double)d + log2_steps(n));
+    if (!P || !U || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld): at least one timepoint", (long long)T);
+    int rc = proj ? check_projection(P, n, d, U, k, m, out, n, work) : check_halfspace(P, n, d, U, k, m, out, n, work);
+    if (rc) return rc;
+    if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (lds), 2 (global)", algo);
+    if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
+    const int route = multi_cloud_route(algo, n);
+    if (route == 0)
+        return fail(SD_ERR_UNSUPPORTED, "the LDS route holds clouds of up to %lld curves, got %lld (algo 0 or 2 takes them)",
+                    (long long)MC_LDS_CAPACITY, (long long)n);
+    if (!ws || ws_bytes < multi_cloud_min_workspace_bytes(route, proj, n, d))
+        return fail(SD_ERR_WORKSPACE, "workspace too small for one timepoint per batch (sd_multi_%s_min_workspace_bytes)",
+                    proj ? "projection" : "halfspace");
+    if (m == 0) return SD_OK;
+    return launch_multi_cloud(proj, route, P, n, T, d, U, k, targets, m, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t sd_multi_halfspace_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_workspace_bytes(route, false, n, T, d, k) : 0;
+}
+
+size_t sd_multi_halfspace_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_min_workspace_bytes(route, false, n, d) : 0;
+}
+
+int sd_multi_halfspace_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
+                            int64_t m, int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    return multi_cloud_sums(false, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, stream);
+}
+
+size_t sd_multi_projection_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_workspace_bytes(route, true, n, T, d, k) : 0;
+}
+
+size_t sd_multi_projection_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_min_workspace_bytes(route, true, n, d) : 0;
+}
+
+int sd_multi_projection_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
+                             int64_t m, int algo, double *out, void *ws, size_t ws_bytes, void *stream) {
+    return multi_cloud_sums(true, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, stream);
+}
+
 }  // extern "C"

@@ -169,6 +169,16 @@ size_t central_regions_workspace_bytes(i64 T, i64 n, int L);
 int launch_central_regions(const double *Y, i64 T, i64 n, const uint8_t *level, int L, int box, double factor, double *env,
                            double *fence, int32_t *outside, double *whisker, void *ws, size_t ws_bytes, hipStream_t s);
 
+// K18 halfspace and projection depth of multivariate curves over time (multi_cloud.hip): out = m x 2 records, (SH, MH)
+// int64 or (PS, OM) double.  route 1 = a cloud's projections ranked in one workgroup's LDS, 2 = K10's / K12's launchers
+// per timepoint
+constexpr i64 MC_LDS_CAPACITY = 8192;                               // curves whose projections one workgroup sorts in LDS
+int multi_cloud_route(int algo, i64 n);                            // 0: algo = 1 (lds) above the capacity
+size_t multi_cloud_workspace_bytes(int route, bool proj, i64 n, i64 T, int d, i64 k);
+size_t multi_cloud_min_workspace_bytes(int route, bool proj, i64 n, int d);
+int launch_multi_cloud(bool proj, int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets,
+                       i64 m, void *out, void *ws, size_t ws_bytes, hipStream_t s);
+
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);
 

@@ -10,6 +10,9 @@ RANK_DEPTHS names the integrated rank depths of univariate curves (_rank.py): no
 the same argument.  ORDER_DEPTHS names the depths that order the curves instead of averaging over time (the extremal
 depth, _functional._extremal_depth), selected the same way.  SHAPE_DEPTHS names the depths built on the joint ranks at two
 consecutive timepoints (the total variation depth and the modified shape similarity, _shape.py), selected the same way.
+CLOUD_DEPTHS names the depths of the point X(t) inside the cloud of all curves' points at t, aggregated over time (the
+multivariate functional halfspace depth and its projection-depth sibling, _functional._cloud_depths): the only names of
+these four tuples that take multivariate curves.
 """
 from inspect import signature
 
@@ -17,6 +20,7 @@ BUILTIN = ('r2', 'r2_enum', 'simplex')
 RANK_DEPTHS = ('fm', 'mei', 'mhi', 'half_region', 'integrated_halfspace', 'infimal_halfspace')
 ORDER_DEPTHS = ('extremal',)
 SHAPE_DEPTHS = ('tvd', 'mss')
+CLOUD_DEPTHS = ('halfspace', 'projection')
 
 
 def _is_valid_containment(containment):
@@ -24,6 +28,7 @@ def _is_valid_containment(containment):
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
                          f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS)}, '
+                         f'for univariate or multivariate data one of {list(CLOUD_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
     if len(params) != 3:   # only the arity is enforced (:37-41)
@@ -42,6 +47,10 @@ def _is_order_depth(containment) -> bool:
 
 def _is_shape_depth(containment) -> bool:
     return isinstance(containment, str) and containment in SHAPE_DEPTHS
+
+
+def _is_cloud_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in CLOUD_DEPTHS
 
 
 def _select_containment(containment):

@@ -17,8 +17,9 @@ from scipy.special import binom
 
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
-from ._containment import _is_order_depth, _is_rank_depth, _is_shape_depth, _select_containment
+from ._containment import _is_cloud_depth, _is_order_depth, _is_rank_depth, _is_shape_depth, _select_containment
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
+from ._pointcloud import _halfspace_directions
 from ._rank import _rank_depth_values
 from ._shape import _shape_depth_values
 
@@ -209,8 +210,91 @@ def _shape_depths(data, to_compute, J, containment: str, deep_check=False, devic
     return pd.Series(index=cols, data=_shape_depth_values(sd_sum, shape, n, T, containment))
 
 
+def _cloud_depth_values(records, n: int, T: int, containment: str, aggregate: str) -> np.ndarray:
+    """The records [m, 2] of engine.multi_halfspace_sums (SH, MH: int64) or engine.multi_projection_sums (PS, OM: fp64) of
+    curves among n at T timepoints -> the fp64 depths: one division each ('projection', 'inf': one addition as well)."""
+    if containment == 'halfspace':
+        R = np.asarray(records, dtype=np.int64).reshape(-1, 2)
+        if aggregate == 'mean':
+            return R[:, 0].astype(np.float64) / np.float64(np.int64(n) * np.int64(T))
+        return R[:, 1].astype(np.float64) / np.float64(n)
+    R = np.asarray(records, dtype=np.float64).reshape(-1, 2)
+    if aggregate == 'mean':
+        return R[:, 0] / np.float64(T)
+    return 1.0 / (1.0 + R[:, 1])                         # OM = inf: 0.0
+
+
+def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, device=None, directions=1000, seed=0,
+                  aggregate='mean') -> pd.Series:
+    """The halfspace or the projection depth of curves over time (containment in _containment.CLOUD_DEPTHS): the depth of
+    the point X(t) inside the cloud of all curves' points at t -- PointcloudDepth's 'halfspace' / 'projection' over the
+    direction set (`directions`, `seed`), the same for every t -- averaged over t (aggregate='mean': the multivariate
+    functional halfspace depth of Claeskens et al. 2014, resp. the mean of 1 / (1 + O_t)) or its infimum over t ('inf').
+    One device call for the records (sd_multi_halfspace_sums / sd_multi_projection_sums), the normalisation on the host.
+    A list of n >= 2 frames (T x d each): the curves are the frames, `to_compute` and the result's index are list
+    positions, as for 'simplex'.  A list of one frame: its columns are the curves (d = 1, the direction [[1.0]]), labels
+    and `to_compute` as for 'r2'.  What cannot be computed is refused here, before anything is uploaded."""
+    def refuse(reason):
+        raise ValueError(f'containment \'{containment}\' {reason}')
+
+    if not isinstance(data, list):
+        raise ValueError('data must be passed as a list.')
+    if len(data) == 0:
+        raise ValueError('No data passed.')
+    if not isinstance(J, numbers.Integral) or isinstance(J, bool) or J != 2:
+        refuse(f'has no band size: J must be left at its default 2, got {J!r}.')
+    if aggregate not in ('mean', 'inf'):
+        refuse(f"takes aggregate='mean' (the average over the timepoints) or 'inf' (their infimum), got {aggregate!r}.")
+    if deep_check:
+        _deep_check(data)
+    if len(data) == 1:                                   # univariate: the columns are the curves
+        df = data[0]
+        _require_unique_labels(df)
+        P = np.ascontiguousarray(df.to_numpy(dtype=np.float64).T)[:, :, None]
+        index = df.columns if to_compute is None else to_compute
+        targets = _positions(df, index)
+    else:
+        shape = np.shape(data[0])
+        if len(shape) != 2 or any(np.shape(f) != shape for f in data):
+            refuse(f'needs frames of one shape (timepoints x features), got {sorted(set(np.shape(f) for f in data))}.')
+        P = _curves_tensor(data)
+        index = [i for i in range(len(data))] if to_compute is None else to_compute
+        targets = np.asarray(list(index), dtype=np.int64)
+    n, T, d = P.shape
+    if n < 2:
+        refuse(f'needs at least 2 curves, got {n}.')
+    if T < 1:
+        refuse('needs at least one timepoint.')
+    if d < 1:
+        refuse('needs at least one feature.')
+    if d > 8:
+        refuse(f'is implemented for at most 8 features, got {d}.')
+    if not np.isfinite(P).all():
+        refuse('does not take NaN or infinite values: drop or fill them first.')
+    if containment == 'projection':
+        engine.projection_check('coordinates', P)        # |x| <= 2^500: no projection or midpoint overflows
+    if isinstance(directions, str):
+        if directions != 'exact':
+            refuse(f"takes a positive number of directions, a (k x {d}) array or 'exact', got directions={directions!r}.")
+        if d != 1:
+            raise NotImplementedError(f"containment '{containment}' of curves with directions='exact' is implemented for "
+                                      f"one feature (where the direction (1.0) is exact), got d = {d}")
+        U = np.ones((1, 1), dtype=np.float64)
+    else:
+        U = _halfspace_directions(directions, seed, d)   # finite, no all-zero row
+    if containment == 'projection':
+        engine.projection_check('direction entries', U)
+    sums = engine.multi_halfspace_sums if containment == 'halfspace' else engine.multi_projection_sums
+    records = sums(P, U, targets, device=device)
+    return pd.Series(index=index, data=_cloud_depth_values(records, n, T, containment, aggregate))
+
+
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
-                     relax=False, deep_check=False, quiet=True, device=None, algo='auto') -> pd.Series:
+                     relax=False, deep_check=False, quiet=True, device=None, algo='auto', directions=1000, seed=0,
+                     aggregate='mean') -> pd.Series:
+    if _is_cloud_depth(containment):                     # multivariate too; `relax` and `algo` have nothing to select
+        return _cloud_depths(data, to_compute, J, containment, deep_check=deep_check, device=device,
+                             directions=directions, seed=seed, aggregate=aggregate)
     if _is_rank_depth(containment):                      # not a band depth: `relax` and `algo` have nothing to select
         return _rank_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
     if _is_order_depth(containment):
@@ -276,7 +360,8 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     reference's blocks; each block's depth is one device call.
     """
     samples = []
-    if _is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment):
+    if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
+            or _is_cloud_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

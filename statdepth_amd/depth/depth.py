@@ -176,7 +176,7 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
 
 
 def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, containment='r2', relax=False,
-                    deep_check=False, quiet=True, *, device=None, algo='auto'):
+                    deep_check=False, quiet=True, *, device=None, algo='auto', directions=1000, seed=0, aggregate='mean'):
     """Band depth of curves ('r2', 'r2_enum', 'simplex' or a callable), as in the reference.
 
     For univariate data (`data` a list of one frame whose columns are the curves) `containment` also names the integrated
@@ -194,13 +194,23 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     at most 1/4), and 'mss', the modified shape similarity (the squared phi coefficient of "at or below at t - 1" and "at or
     below at t" over the sample, averaged over the steps with the curve's own |increments| as weights; 1 where the curve is
     the highest at either timepoint).  'mss' also needs 2 timepoints and finite values.  `.boxplot()` and
-    `.central_region()` of a 'tvd' result work as for any depth; TotalVariationOutliers runs the paper's outlier rule."""
+    `.central_region()` of a 'tvd' result work as for any depth; TotalVariationOutliers runs the paper's outlier rule.
+
+    containment='halfspace' and 'projection' take multivariate curves as well: a list of n >= 2 frames, each T x d with d <= 8
+    (`to_compute` and the result's index are list positions, as for 'simplex'), or a list of one frame whose columns are the
+    curves (d = 1).  The depth of a curve is PointcloudDepth's depth of its point X(t) inside the cloud of all curves' points
+    at t, over one direction set for every t -- `directions` and `seed` mean what they mean there; 'exact' only for d = 1 --
+    aggregated over t: aggregate='mean' averages (for 'halfspace' the multivariate functional halfspace depth of Claeskens,
+    Hubert, Slaets & Vakili 2014), aggregate='inf' takes the infimum.  Every other containment ignores the three arguments.
+    `relax` and `algo` are ignored; ValueError for `K` other than None, `J` other than 2, frames of unequal shape, NaN or
+    infinite values, fewer than 2 curves, no timepoint or more than 8 features."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)
     else:
         depth = _functionaldepth(data=data, to_compute=to_compute, J=J, containment=containment, relax=relax,
-                                 deep_check=deep_check, quiet=quiet, device=device, algo=algo)
+                                 deep_check=deep_check, quiet=quiet, device=device, algo=algo, directions=directions,
+                                 seed=seed, aggregate=aggregate)
     if len(data) == 1:                                   # univariate by assumption (:399-400)
         return _FunctionalDepthUnivariate(df=data[0], depths=depth)
     return _FunctionalDepthSeries(df=data[0], depths=depth)   # multivariate (:401-402)

@@ -753,6 +753,81 @@ def _directions_dev(U, d, dev):
     return Ud
 
 
+MULTI_CLOUD_ALGOS = {"auto": 0, "lds": 1, "global": 2}
+
+
+def _multi_cloud_algo(algo):
+    if isinstance(algo, str) and algo not in MULTI_CLOUD_ALGOS:
+        raise ValueError(f"algo must be one of {sorted(MULTI_CLOUD_ALGOS)}, got {algo!r}")
+    return MULTI_CLOUD_ALGOS[algo] if isinstance(algo, str) else int(algo)
+
+
+def multi_cloud_lds_capacity():
+    """The most curves of the LDS route of sd_multi_halfspace_sums / sd_multi_projection_sums (a cloud's projections sorted
+    in one workgroup's LDS); above it 'auto' takes the global route.  (torch first, as in _lib.)"""
+    torch()
+    return int(_native.load().sd_multi_cloud_lds_capacity())
+
+
+def _multi_cloud_workspace_bytes(family, n, T, d, k, m, algo):
+    lib = _native.load()
+    n, T, d, k, a = int(n), int(T), int(d), int(k), _multi_cloud_algo(algo)
+    m = n if m is None else int(m)
+    return (int(getattr(lib, f"sd_multi_{family}_workspace_bytes")(n, T, d, k, m, a)),
+            int(getattr(lib, f"sd_multi_{family}_min_workspace_bytes")(n, T, d, k, m, a)))
+
+
+def multi_halfspace_workspace_bytes(n, T, d, k, m=None, algo="auto"):
+    """(recommended, floor) workspace sizes of sd_multi_halfspace_sums for n curves x T timepoints x d features, k directions
+    and m targets (default: all n); the floor holds one timepoint per batch.  (0, 0) for a shape or algo the call refuses."""
+    return _multi_cloud_workspace_bytes("halfspace", n, T, d, k, m, algo)
+
+
+def multi_projection_workspace_bytes(n, T, d, k, m=None, algo="auto"):
+    """(recommended, floor) workspace sizes of sd_multi_projection_sums; as multi_halfspace_workspace_bytes."""
+    return _multi_cloud_workspace_bytes("projection", n, T, d, k, m, algo)
+
+
+def _multi_cloud_sums(family, dtype, P, U, targets, device, algo, ws_bytes):
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    a = _multi_cloud_algo(algo)
+    shape = np.shape(P)
+    if len(shape) != 3:
+        raise ValueError("expected a 3-D array (curves x timepoints x features)")
+    n, T, d = shape
+    td, m, tp = _targets_dev(targets, n, dev)                        # the indices first: refused before anything is uploaded
+    Pd = _upload(P, 3, dev)
+    Ud = _directions_dev(U, d, dev)
+    k = Ud.shape[0]
+    out = t.empty((m, 2), dtype=dtype, device=dev)
+    size = getattr(lib, f"sd_multi_{family}_workspace_bytes")
+    return _launch(dev, getattr(lib, f"sd_multi_{family}_sums"), out, Pd.data_ptr(), n, T, d, Ud.data_ptr(), k, tp, m, a,
+                   workspace=lambda: _sized(dev, size(n, T, d, k, m, a) if ws_bytes is None else ws_bytes))
+
+
+def multi_halfspace_sums(P, U, targets=None, device=None, algo="auto", ws_bytes=None):
+    """int64[m, 2]: the records (SH, MH) of the halfspace depth of multivariate curves over time (sd_multi_halfspace_sums).
+    P: (n, T, d) curves, U: k x d directions shared by all timepoints.  With h_t the halfspace count of the curve's point
+    inside the cloud of all curves' points at t (halfspace_counts on P[:, t, :]): SH = sum_t h_t, MH = min_t h_t; the mean
+    depth is SH / (n T), the infimal depth MH / n.  P must be finite (the depth layer checks; this function takes its array
+    as it is).  algo: 'auto', 'lds' (n <= multi_cloud_lds_capacity()) or 'global', or their numbers 0, 1, 2.  ws_bytes: the
+    workspace size to run with (default: the recommended one); the records do not depend on it or on algo, below the floor
+    the library refuses."""
+    return _multi_cloud_sums("halfspace", torch().int64, P, U, targets, device, algo, ws_bytes)
+
+
+def multi_projection_sums(P, U, targets=None, device=None, algo="auto", ws_bytes=None):
+    """float64[m, 2]: the records (PS, OM) of the projection depth of multivariate curves over time
+    (sd_multi_projection_sums).  With O_t the Stahel-Donoho outlyingness of the curve's point inside the cloud at t
+    (projection_outlyingness on P[:, t, :]): PS = sum_t 1 / (1 + O_t), added in ascending t (the last entry of np.cumsum),
+    OM = max_t O_t; the mean depth is PS / T, the infimal depth 1 / (1 + OM).  P and U: finite, magnitudes of at most 2^500
+    (projection_check; the depth layer checks).  algo and ws_bytes as for multi_halfspace_sums; the same bits whatever
+    they are."""
+    return _multi_cloud_sums("projection", torch().float64, P, U, targets, device, algo, ws_bytes)
+
+
 def halfspace_workspace_bytes(n, d, k):
     """(recommended, floor) workspace sizes of sd_halfspace_counts; the floor holds one direction per chunk."""
     lib = _native.load()

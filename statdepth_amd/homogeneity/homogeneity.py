@@ -18,7 +18,7 @@ import pandas as pd
 
 from .. import engine
 from ..depth.calculations import _pointcloud
-from ..depth.calculations._containment import _is_order_depth, _is_rank_depth, _is_shape_depth
+from ..depth.calculations._containment import _is_cloud_depth, _is_order_depth, _is_rank_depth, _is_shape_depth
 from ..depth.calculations._helper import _band_depth_sum
 from ..depth.depth import FunctionalDepth, PointcloudDepth
 
@@ -106,7 +106,8 @@ def _depth_of_one_external(Fd: pd.DataFrame, g: np.ndarray, kw) -> float:
 
 def _functionalhomogeneity(F: List[pd.DataFrame], G: List[pd.DataFrame], K=None, J=2, containment='r2', method='p1',
                            relax=False, deep_check=False, quiet=False):
-    if _is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment):
+    if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
+            or _is_cloud_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no homogeneity coefficient: they are defined on band depths '
                          f'(\'r2\', \'r2_enum\', \'simplex\' or a callable).')
     _handle_errors(F, G, method)
