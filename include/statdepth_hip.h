@@ -701,6 +701,38 @@ size_t sd_multi_projection_min_workspace_bytes(int64_t n, int64_t T, int d, int6
 int sd_multi_projection_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
                              int64_t m, int algo, double *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K19: directional outlyingness of multivariate curves (the records of the MS-plot) ---------
+ * No reference code (Dai & Genton 2018, 2019: the Stahel-Donoho outlyingness with a direction; its mean over time shows a
+ * magnitude outlier, its variation over time a shape outlier).  P, U, targets, algo as for K18.  Per timepoint t:
+ *   o_t(i) = K18's O_t(i), on the same bits;
+ *   c_t    = the LOWEST curve index among those minimising o_t over ALL n curves (whatever the targets are): the sample point
+ *            of largest projection depth, the median of the cloud over the direction set;
+ *   diff_e = P[i][t][e] - P[c_t][t][e];  s = sum_e diff_e^2, added in ascending e, each term one rounded multiplication and
+ *            one rounded addition (no fma);  r = sqrt(s), correctly rounded;
+ *   O_t(i)_e = o_t(i) * (diff_e / r): one rounded division and one rounded multiplication.
+ *   r == 0: O_t(i) is the zero vector -- the centre itself, its duplicates, and differences so small that their squares
+ *            underflow.  o_t(i) = +inf (a direction's MAD is 0) is NOT special-cased: the products follow IEEE, +-inf, or NaN
+ *            where diff_e = 0.
+ * Per target, over ascending t, a Welford record of d running means M_e and one running sum Q, both from 0.0: at timepoint
+ * t, with c = (double)(t + 1), for e ascending
+ *   delta_e = O_e - M_e;   M_e = M_e + delta_e / c;   Q = Q + delta_e * (O_e - M_e(new))       every operation rounded once.
+ * out[q] = (M_0 .. M_(d-1), Q), d + 1 doubles.  Host: MO = M, VO = Q / T, FO = sum_e M_e^2 + VO.
+ * centres (NULL or T int64, device): c_t.  curves (NULL or m x T x d doubles, device): O_t of every target; both cost nothing
+ * when NULL, and neither is written when m == 0.
+ * A numpy restatement gives the same bits, and nothing depends on algo, on the workspace size or on how directions and
+ * timepoints are split: o_t is order-free, c_t is an argmin with a fixed tie rule, and the record has one owner per target
+ * in ascending t, carried in out[] across the batches of timepoints in stream order.
+ * The project-sort-select stage is K18's, launch for launch; per batch of timepoints one workgroup per timepoint then
+ * reduces every curve's value to c_t, and a thread per target folds the batch into its record.
+ * Workspace: sd_multi_projection_*'s layout plus 8 bytes per timepoint of a batch (the centres, padded to 256 bytes as a
+ * whole); recommended size, floor and the value 0 as for K18.
+ * The refusals are sd_multi_projection_sums', in its order, all before any device work.  Every launch is bounded in work. */
+size_t sd_multi_outlyingness_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+size_t sd_multi_outlyingness_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo);
+int sd_multi_outlyingness_moments(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k,
+                                  const int64_t *targets, int64_t m, int algo, double *out, int64_t *centres, double *curves,
+                                  void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ SIGNATURES = {
     "sd_multi_projection_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
     "sd_multi_projection_min_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
     "sd_multi_projection_sums": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "sd_multi_outlyingness_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_outlyingness_min_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
+    "sd_multi_outlyingness_moments": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

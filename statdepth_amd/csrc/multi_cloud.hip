@@ -14,8 +14,10 @@
 // depends on the route, the workspace size or how directions and timepoints are split.
 //
 // The timepoints are taken in batches of Tb (what the workspace holds).  Per batch both routes leave V[tb][i], the value
-// of EVERY curve i at timepoint t0 + tb, in the workspace, and mc_fold_kernel (a thread per target) adds the batch's
-// timepoints to out[] in ascending t.
+// of EVERY curve i at timepoint t0 + tb, in the workspace, and hand the batch to a consumer (McBatch, McConsumer) once every
+// slice of it has been launched.  K18's consumer is mc_fold_kernel (a thread per target), which adds the batch's timepoints
+// to out[] in ascending t; K19's (directional_out.hip) takes the centre of each cloud and folds the directional
+// outlyingness.  There is one batch loop per route, whoever consumes.
 //
 // LDS route (n <= MC_LDS_CAPACITY = 8192):
 //   the batch is copied feature-major, Y[tb][e][i] (launch_to_time_major, a tiled transpose): the input's point stride is
@@ -38,6 +40,7 @@
 // 8192 keys; the global route's launches are K10's and K12's.  No kernel waits on another workgroup.
 #include <type_traits>
 #include "sd_common.h"
+#include "multi_cloud_batches.h"
 #include "point_select.h"
 #include "projection_select.h"
 
@@ -231,37 +234,42 @@ int multi_cloud_route(int algo, i64 n) {
     return algo == 0 ? 2 : 0;
 }
 
-// LDS route: Y (8 n d bytes per timepoint) and V (4 or 8 n), each padded to 256 bytes
-static inline size_t mc_lds_per_timepoint(bool proj, i64 n, int d) { return (size_t)n * ((size_t)d * 8 + (proj ? 8 : 4)); }
-static inline size_t mc_lds_fixed() { return 2 * 256; }
-// global route: the cloud (8 n d) and V (8 n), each padded to 256 bytes, in front of K10's or K12's own workspace
-static inline size_t mc_global_fixed(i64 n, int d) { return align_up((size_t)n * d * 8, 256) + align_up((size_t)n * 8, 256) + 256; }
-
-size_t multi_cloud_min_workspace_bytes(int route, bool proj, i64 n, int d) {
-    if (route == 1) return mc_lds_fixed() + mc_lds_per_timepoint(proj, n, d);
-    return mc_global_fixed(n, d) + (proj ? projection_min_workspace_bytes(n) : halfspace_min_workspace_bytes(n));
+// LDS route: Y (8 n d bytes per timepoint), V (4 or 8 n) and the consumer's extra bytes, each padded to 256 bytes
+static inline size_t mc_lds_per_timepoint(bool proj, i64 n, int d, size_t extra) {
+    return (size_t)n * ((size_t)d * 8 + (proj ? 8 : 4)) + extra;
+}
+static inline size_t mc_lds_fixed(size_t extra) { return (extra ? 3 : 2) * 256; }
+// global route: the cloud (8 n d), V (8 n) and the extra bytes, each padded to 256 bytes, in front of K10's or K12's own workspace
+static inline size_t mc_global_fixed(i64 n, int d, size_t extra) {
+    return align_up((size_t)n * d * 8, 256) + align_up((size_t)n * 8, 256) + align_up(extra, 256) + 256;
 }
 
-size_t multi_cloud_workspace_bytes(int route, bool proj, i64 n, i64 T, int d, i64 k) {
+size_t multi_cloud_min_workspace_bytes(int route, bool proj, i64 n, int d, size_t extra) {
+    if (route == 1) return mc_lds_fixed(extra) + mc_lds_per_timepoint(proj, n, d, extra);
+    return mc_global_fixed(n, d, extra) + (proj ? projection_min_workspace_bytes(n) : halfspace_min_workspace_bytes(n));
+}
+
+size_t multi_cloud_workspace_bytes(int route, bool proj, i64 n, i64 T, int d, i64 k, size_t extra) {
     if (route == 1) {
         i64 Tb = MC_REC_VALUES / (n * d);
         Tb = Tb < 1 ? 1 : Tb > T ? T : Tb;
-        return mc_lds_fixed() + (size_t)Tb * mc_lds_per_timepoint(proj, n, d);
+        return mc_lds_fixed(extra) + (size_t)Tb * mc_lds_per_timepoint(proj, n, d, extra);
     }
-    return mc_global_fixed(n, d) + (proj ? projection_workspace_bytes(n, k) : halfspace_workspace_bytes(n, k));
+    return mc_global_fixed(n, d, extra) + (proj ? projection_workspace_bytes(n, k) : halfspace_workspace_bytes(n, k));
 }
 
 template <int D, bool PROJ>
-static int launch_mc_lds_d(const double *P, i64 n, i64 T, const double *U, i64 k, const i64 *targets, i64 m, void *out,
+static int launch_mc_lds_d(const double *P, i64 n, i64 T, const double *U, i64 k, size_t extra, const McConsumer &consume,
                            void *ws, size_t ws_bytes, hipStream_t s) {
-    const size_t per = mc_lds_per_timepoint(PROJ, n, D);
-    i64 Tb = (i64)((ws_bytes - mc_lds_fixed()) / per);              // (the caller has checked the floor)
+    const size_t per = mc_lds_per_timepoint(PROJ, n, D, extra);
+    i64 Tb = (i64)((ws_bytes - mc_lds_fixed(extra)) / per);         // (the caller has checked the floor)
     Tb = Tb > T ? T : Tb > MC_MAX_BATCH ? MC_MAX_BATCH : Tb;
     const size_t vbytes = PROJ ? 8 : 4;
     Carver cv(ws, ws_bytes);
     double *Y = (double *)cv.take((size_t)Tb * n * D * 8);
     void *V = cv.take((size_t)Tb * n * vbytes);
-    if (Tb < 1 || !Y || !V) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_multi_*_min_workspace_bytes)");
+    void *X = extra ? cv.take((size_t)Tb * extra) : nullptr;
+    if (Tb < 1 || !Y || !V || (extra && !X)) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_multi_*_min_workspace_bytes)");
     const u64 S = (u64)((k + MC_SLICE - 1) / MC_SLICE);
     for (i64 t0 = 0; t0 < T; t0 += Tb) {
         const i64 tb = T - t0 < Tb ? T - t0 : Tb;
@@ -275,50 +283,54 @@ static int launch_mc_lds_d(const double *P, i64 n, i64 T, const double *U, i64 k
             hipLaunchKernelGGL((mc_lds_kernel<D, PROJ>), dim3((unsigned)g), dim3(MC_THREADS), 0, s, Y, (int)n, U, k, S, u0, V);
             SD_HIP(hipGetLastError());
         }
-        if (PROJ) rc = launch_mc_fold((const double *)V, n, tb, targets, m, t0 == 0, out, s);
-        else rc = launch_mc_fold((const u32 *)V, n, tb, targets, m, t0 == 0, out, s);
-        if (rc) return rc;
+        if ((rc = consume(McBatch{V, Y, true, X, t0, tb}, s))) return rc;   // V is final: every slice has met in it
     }
     return SD_OK;
 }
 
-static int launch_mc_global(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets,
-                            i64 m, void *out, void *ws, size_t ws_bytes, hipStream_t s) {
+static int launch_mc_global(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, size_t extra,
+                            const McConsumer &consume, void *ws, size_t ws_bytes, hipStream_t s) {
     Carver cv(ws, ws_bytes);
     double *C = (double *)cv.take((size_t)n * d * 8);
     void *V = cv.take((size_t)n * 8);
+    void *X = extra ? cv.take(extra) : nullptr;
     const size_t inner_bytes = cv.rest();
     void *inner = cv.take(inner_bytes);
-    if (!C || !V || !inner) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_multi_*_min_workspace_bytes)");
+    if (!C || !V || !inner || (extra && !X)) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_multi_*_min_workspace_bytes)");
     for (i64 t = 0; t < T; ++t) {
         hipLaunchKernelGGL(mc_gather_kernel, dim3((unsigned)((n * d + MC_FOLD_THREADS - 1) / MC_FOLD_THREADS)),
                            dim3(MC_FOLD_THREADS), 0, s, P, n, T, d, t, C);
         SD_HIP(hipGetLastError());
         int rc;
-        if (proj) {
-            rc = launch_projection_sorted(C, n, d, U, k, select_rows(nullptr), n, (double *)V, inner, inner_bytes, s);
-            if (!rc) rc = launch_mc_fold((const double *)V, n, 1, targets, m, t == 0, out, s);
-        } else {
-            rc = launch_halfspace_counts(C, n, d, U, k, nullptr, n, (i64 *)V, inner, inner_bytes, s);
-            if (!rc) rc = launch_mc_fold((const i64 *)V, n, 1, targets, m, t == 0, out, s);
-        }
+        if (proj) rc = launch_projection_sorted(C, n, d, U, k, select_rows(nullptr), n, (double *)V, inner, inner_bytes, s);
+        else rc = launch_halfspace_counts(C, n, d, U, k, nullptr, n, (i64 *)V, inner, inner_bytes, s);
+        if (!rc) rc = consume(McBatch{V, C, false, X, t, 1}, s);
         if (rc) return rc;
     }
     return SD_OK;
 }
 
-int launch_multi_cloud(bool proj, int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets,
-                       i64 m, void *out, void *ws, size_t ws_bytes, hipStream_t s) {
-    if (!ws || ws_bytes < multi_cloud_min_workspace_bytes(route, proj, n, d))
-        return fail(SD_ERR_WORKSPACE, "workspace too small for one timepoint per batch (sd_multi_%s_min_workspace_bytes)",
-                    proj ? "projection" : "halfspace");
-    if (route == 2) return launch_mc_global(proj, P, n, T, d, U, k, targets, m, out, ws, ws_bytes, s);
+int launch_multi_cloud_batches(bool proj, int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, size_t extra,
+                               const McConsumer &consume, void *ws, size_t ws_bytes, hipStream_t s) {
+    if (!ws || ws_bytes < multi_cloud_min_workspace_bytes(route, proj, n, d, extra))
+        return fail(SD_ERR_WORKSPACE, "workspace too small for one timepoint per batch (sd_multi_*_min_workspace_bytes)");
+    if (route == 2) return launch_mc_global(proj, P, n, T, d, U, k, extra, consume, ws, ws_bytes, s);
     if (proj) {
-        SD_DISPATCH_D(d, return (launch_mc_lds_d<D_, true>(P, n, T, U, k, targets, m, out, ws, ws_bytes, s)))
+        SD_DISPATCH_D(d, return (launch_mc_lds_d<D_, true>(P, n, T, U, k, extra, consume, ws, ws_bytes, s)))
     } else {
-        SD_DISPATCH_D(d, return (launch_mc_lds_d<D_, false>(P, n, T, U, k, targets, m, out, ws, ws_bytes, s)))
+        SD_DISPATCH_D(d, return (launch_mc_lds_d<D_, false>(P, n, T, U, k, extra, consume, ws, ws_bytes, s)))
     }
     return fail(SD_ERR_UNSUPPORTED, "multivariate curve depths cover d in [1,8], got %d", d);
+}
+
+// K18's own consumer: the fold of the batch into the records (SH, MH) / (PS, OM)
+int launch_multi_cloud(bool proj, int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets,
+                       i64 m, void *out, void *ws, size_t ws_bytes, hipStream_t s) {
+    return launch_multi_cloud_batches(proj, route, P, n, T, d, U, k, 0, [=](const McBatch &b, hipStream_t st) {
+        if (proj) return launch_mc_fold((const double *)b.V, n, b.tb, targets, m, b.t0 == 0, out, st);
+        if (b.feature_major) return launch_mc_fold((const u32 *)b.V, n, b.tb, targets, m, b.t0 == 0, out, st);
+        return launch_mc_fold((const i64 *)b.V, n, b.tb, targets, m, b.t0 == 0, out, st);
+    }, ws, ws_bytes, s);
 }
 
 }  // namespace sd

@@ -1092,9 +1092,10 @@ static int multi_cloud_sized_route(i64 n, i64 T, int d, i64 k, i64 m, int algo) 
     return multi_cloud_route(algo, n);
 }
 
-// K10's / K12's checks in their order and wording, with T clouds of n points; then algo, the targets and the route
-static int multi_cloud_sums(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets, i64 m,
-                            int algo, void *out, void *ws, size_t ws_bytes, void *stream) {
+// K10's / K12's checks in their order and wording, with T clouds of n points; then algo, the targets, the route and the
+// floor of the workspace (extra: the batch consumer's own bytes per timepoint; family: the name in the size functions)
+static int multi_cloud_checked(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets, i64 m,
+                               int algo, void *out, void *ws, size_t ws_bytes, size_t extra, const char *family, int &route) {
     const double work = (double)T * (double)k * (double)n * ((double)d + log2_steps(n));
     if (!P || !U || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (T < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld): at least one timepoint", (long long)T);
@@ -1102,14 +1103,21 @@ static int multi_cloud_sums(bool proj, const double *P, i64 n, i64 T, int d, con
     if (rc) return rc;
     if (algo < 0 || algo > 2) return fail(SD_ERR_INVALID, "algo=%d outside 0 (auto), 1 (lds), 2 (global)", algo);
     if (!targets && m != n) return fail(SD_ERR_INVALID, "targets=NULL requires m == n");
-    const int route = multi_cloud_route(algo, n);
+    route = multi_cloud_route(algo, n);
     if (route == 0)
         return fail(SD_ERR_UNSUPPORTED, "the LDS route holds clouds of up to %lld curves, got %lld (algo 0 or 2 takes them)",
                     (long long)MC_LDS_CAPACITY, (long long)n);
-    if (!ws || ws_bytes < multi_cloud_min_workspace_bytes(route, proj, n, d))
-        return fail(SD_ERR_WORKSPACE, "workspace too small for one timepoint per batch (sd_multi_%s_min_workspace_bytes)",
-                    proj ? "projection" : "halfspace");
-    if (m == 0) return SD_OK;
+    if (!ws || ws_bytes < multi_cloud_min_workspace_bytes(route, proj, n, d, extra))
+        return fail(SD_ERR_WORKSPACE, "workspace too small for one timepoint per batch (sd_multi_%s_min_workspace_bytes)", family);
+    return SD_OK;
+}
+
+static int multi_cloud_sums(bool proj, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets, i64 m,
+                            int algo, void *out, void *ws, size_t ws_bytes, void *stream) {
+    int route;
+    int rc = multi_cloud_checked(proj, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, 0,
+                                 proj ? "projection" : "halfspace", route);
+    if (rc || m == 0) return rc;
     return launch_multi_cloud(proj, route, P, n, T, d, U, k, targets, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -1141,6 +1149,28 @@ size_t sd_multi_projection_min_workspace_bytes(int64_t n, int64_t T, int d, int6
 int sd_multi_projection_sums(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k, const int64_t *targets,
                              int64_t m, int algo, double *out, void *ws, size_t ws_bytes, void *stream) {
     return multi_cloud_sums(true, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// K19
+// ---------------------------------------------------------------------------
+size_t sd_multi_outlyingness_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_workspace_bytes(route, true, n, T, d, k, DO_EXTRA) : 0;
+}
+
+size_t sd_multi_outlyingness_min_workspace_bytes(int64_t n, int64_t T, int d, int64_t k, int64_t m, int algo) {
+    const int route = multi_cloud_sized_route(n, T, d, k, m, algo);
+    return route ? multi_cloud_min_workspace_bytes(route, true, n, d, DO_EXTRA) : 0;
+}
+
+int sd_multi_outlyingness_moments(const double *P, int64_t n, int64_t T, int d, const double *U, int64_t k,
+                                  const int64_t *targets, int64_t m, int algo, double *out, int64_t *centres, double *curves,
+                                  void *ws, size_t ws_bytes, void *stream) {
+    int route;
+    int rc = multi_cloud_checked(true, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, DO_EXTRA, "outlyingness", route);
+    if (rc || m == 0) return rc;
+    return launch_multi_outlyingness(route, P, n, T, d, U, k, targets, m, out, centres, curves, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -174,10 +174,18 @@ int launch_central_regions(const double *Y, i64 T, i64 n, const uint8_t *level, 
 // per timepoint
 constexpr i64 MC_LDS_CAPACITY = 8192;                               // curves whose projections one workgroup sorts in LDS
 int multi_cloud_route(int algo, i64 n);                            // 0: algo = 1 (lds) above the capacity
-size_t multi_cloud_workspace_bytes(int route, bool proj, i64 n, i64 T, int d, i64 k);
-size_t multi_cloud_min_workspace_bytes(int route, bool proj, i64 n, int d);
+// extra: bytes per timepoint of a batch that the batch consumer asks for itself (McBatch::extra), padded to 256 as a whole
+size_t multi_cloud_workspace_bytes(int route, bool proj, i64 n, i64 T, int d, i64 k, size_t extra = 0);
+size_t multi_cloud_min_workspace_bytes(int route, bool proj, i64 n, int d, size_t extra = 0);
 int launch_multi_cloud(bool proj, int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets,
                        i64 m, void *out, void *ws, size_t ws_bytes, hipStream_t s);
+// (the batch loop that both families and K19 share: multi_cloud_batches.h)
+
+// K19 directional outlyingness of multivariate curves (directional_out.hip), a consumer of K18's projection batches: out =
+// m x (d + 1) Welford records (M_0 .. M_(d-1), Q); centres (T) and curves (m x T x d) may be null
+constexpr size_t DO_EXTRA = 8;                                     // Cn[tb]: the centre of each timepoint of the batch, int64
+int launch_multi_outlyingness(int route, const double *P, i64 n, i64 T, int d, const double *U, i64 k, const i64 *targets, i64 m,
+                              double *out, i64 *centres, double *curves, void *ws, size_t ws_bytes, hipStream_t s);
 
 // exact C(a,k) on the host in u64 with overflow detection (returns false on overflow)
 bool binom_u64_checked(u64 a, int k, u64 *out);

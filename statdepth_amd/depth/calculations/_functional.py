@@ -224,27 +224,17 @@ def _cloud_depth_values(records, n: int, T: int, containment: str, aggregate: st
     return 1.0 / (1.0 + R[:, 1])                         # OM = inf: 0.0
 
 
-def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, device=None, directions=1000, seed=0,
-                  aggregate='mean') -> pd.Series:
-    """The halfspace or the projection depth of curves over time (containment in _containment.CLOUD_DEPTHS): the depth of
-    the point X(t) inside the cloud of all curves' points at t -- PointcloudDepth's 'halfspace' / 'projection' over the
-    direction set (`directions`, `seed`), the same for every t -- averaged over t (aggregate='mean': the multivariate
-    functional halfspace depth of Claeskens et al. 2014, resp. the mean of 1 / (1 + O_t)) or its infimum over t ('inf').
-    One device call for the records (sd_multi_halfspace_sums / sd_multi_projection_sums), the normalisation on the host.
-    A list of n >= 2 frames (T x d each): the curves are the frames, `to_compute` and the result's index are list
-    positions, as for 'simplex'.  A list of one frame: its columns are the curves (d = 1, the direction [[1.0]]), labels
-    and `to_compute` as for 'r2'.  What cannot be computed is refused here, before anything is uploaded."""
+def _cloud_inputs(data, to_compute, what: str, projection: bool, deep_check=False, directions=1000, seed=0):
+    """The validation and the labels shared by the depths of curves over time (_cloud_depths) and their directional
+    outlyingness (_directional): (P [n, T, d], U [k, d], target positions, the result's index).  `what` names the caller in
+    the refusals; `projection`: the values also pass engine.projection_check.  Nothing is uploaded here."""
     def refuse(reason):
-        raise ValueError(f'containment \'{containment}\' {reason}')
+        raise ValueError(f'{what} {reason}')
 
     if not isinstance(data, list):
         raise ValueError('data must be passed as a list.')
     if len(data) == 0:
         raise ValueError('No data passed.')
-    if not isinstance(J, numbers.Integral) or isinstance(J, bool) or J != 2:
-        refuse(f'has no band size: J must be left at its default 2, got {J!r}.')
-    if aggregate not in ('mean', 'inf'):
-        refuse(f"takes aggregate='mean' (the average over the timepoints) or 'inf' (their infimum), got {aggregate!r}.")
     if deep_check:
         _deep_check(data)
     if len(data) == 1:                                   # univariate: the columns are the curves
@@ -271,19 +261,46 @@ def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, devic
         refuse(f'is implemented for at most 8 features, got {d}.')
     if not np.isfinite(P).all():
         refuse('does not take NaN or infinite values: drop or fill them first.')
-    if containment == 'projection':
+    if projection:
         engine.projection_check('coordinates', P)        # |x| <= 2^500: no projection or midpoint overflows
     if isinstance(directions, str):
         if directions != 'exact':
             refuse(f"takes a positive number of directions, a (k x {d}) array or 'exact', got directions={directions!r}.")
         if d != 1:
-            raise NotImplementedError(f"containment '{containment}' of curves with directions='exact' is implemented for "
+            raise NotImplementedError(f"{what} of curves with directions='exact' is implemented for "
                                       f"one feature (where the direction (1.0) is exact), got d = {d}")
         U = np.ones((1, 1), dtype=np.float64)
     else:
         U = _halfspace_directions(directions, seed, d)   # finite, no all-zero row
-    if containment == 'projection':
+    if projection:
         engine.projection_check('direction entries', U)
+    return P, U, targets, index
+
+
+def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, device=None, directions=1000, seed=0,
+                  aggregate='mean') -> pd.Series:
+    """The halfspace or the projection depth of curves over time (containment in _containment.CLOUD_DEPTHS): the depth of
+    the point X(t) inside the cloud of all curves' points at t -- PointcloudDepth's 'halfspace' / 'projection' over the
+    direction set (`directions`, `seed`), the same for every t -- averaged over t (aggregate='mean': the multivariate
+    functional halfspace depth of Claeskens et al. 2014, resp. the mean of 1 / (1 + O_t)) or its infimum over t ('inf').
+    One device call for the records (sd_multi_halfspace_sums / sd_multi_projection_sums), the normalisation on the host.
+    A list of n >= 2 frames (T x d each): the curves are the frames, `to_compute` and the result's index are list
+    positions, as for 'simplex'.  A list of one frame: its columns are the curves (d = 1, the direction [[1.0]]), labels
+    and `to_compute` as for 'r2'.  What cannot be computed is refused here, before anything is uploaded."""
+    def refuse(reason):
+        raise ValueError(f'containment \'{containment}\' {reason}')
+
+    if not isinstance(data, list):
+        raise ValueError('data must be passed as a list.')
+    if len(data) == 0:
+        raise ValueError('No data passed.')
+    if not isinstance(J, numbers.Integral) or isinstance(J, bool) or J != 2:
+        refuse(f'has no band size: J must be left at its default 2, got {J!r}.')
+    if aggregate not in ('mean', 'inf'):
+        refuse(f"takes aggregate='mean' (the average over the timepoints) or 'inf' (their infimum), got {aggregate!r}.")
+    P, U, targets, index = _cloud_inputs(data, to_compute, f'containment \'{containment}\'', containment == 'projection',
+                                         deep_check=deep_check, directions=directions, seed=seed)
+    n, T, d = P.shape
     sums = engine.multi_halfspace_sums if containment == 'halfspace' else engine.multi_projection_sums
     records = sums(P, U, targets, device=device)
     return pd.Series(index=index, data=_cloud_depth_values(records, n, T, containment, aggregate))

@@ -20,9 +20,12 @@ from .calculations._pointcloud import _pointwisedepth, _samplepointwisedepth
 from .calculations._uncertainty import _probabilistic_band_depth
 from .calculations import _boxplot
 from .calculations._boxplot import FunctionalBoxplotResult
+from .calculations import _directional
+from .calculations._directional import DirectionalOutlyingnessResult, MSPlotOutlierResult
 from . import _plotting
 
-__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot', 'TotalVariationOutliers']
+__all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot', 'TotalVariationOutliers',
+           'DirectionalOutlyingness', 'MSPlotOutliers']
 
 
 class AbstractDepth(ABC):
@@ -294,6 +297,37 @@ def TotalVariationOutliers(data, *, shape_factor=3.0, factor=1.5, alpha=0.5, dev
     flagged = is_shape | df.columns.isin(box.outliers)
     return TotalVariationOutlierResult(mss=mss, tvd=tvd, shape_fence=shape_fence, shape_outliers=shape_outliers, boxplot=box,
                                        magnitude_outliers=box.outliers, outliers=df.columns[flagged])
+
+
+def DirectionalOutlyingness(data, to_compute=None, *, directions=1000, seed=0, device=None, algo='auto',
+                            curves=False) -> DirectionalOutlyingnessResult:
+    """The directional outlyingness of multivariate curves (Dai & Genton 2018, 2019): why a curve is shallow.
+
+    Per timepoint the Stahel-Donoho outlyingness of the curve's point inside the cloud of all curves' points (what
+    containment='projection' turns into a depth, over the same `directions` and `seed`) is given a direction: the unit
+    vector from the cloud's deepest point to the curve's point.  Its mean over time, MO in R^d, is large for a curve that is
+    shifted (a magnitude outlier); its variation over time, VO, is large for a curve of another shape; FO = |MO|^2 + VO.
+    One device call (sd_multi_outlyingness_moments), the three numbers per curve on the host.
+    data, to_compute and the index of the result as for FunctionalDepth(containment='projection'): a list of n >= 2 frames
+    (T x d, d <= 8; list positions), or a list of one frame whose columns are the curves (d = 1; labels).  ValueError for
+    NaN, infinities, magnitudes above 2^500, frames of unequal shape or bad `directions`, before anything is uploaded.
+    Where more than half of a cloud's points share a projection (a direction's MAD is 0) the records of the curves off
+    that place are infinite or NaN, as the projection depth is 0 there.  curves=True keeps the m x T x d array itself."""
+    return _directional._directional_outlyingness(data, to_compute, directions=directions, seed=seed, device=device,
+                                                  algo=algo, curves=curves)
+
+
+def MSPlotOutliers(data, *, level=0.993, directions=1000, seed=0, mcd_seed=0, device=None) -> MSPlotOutlierResult:
+    """Magnitude and shape outliers among multivariate curves by the rule of the MS-plot (Dai & Genton 2018).
+
+    The points Y = (MO, VO) of DirectionalOutlyingness(data, directions=, seed=) in R^q, q = d + 1; their raw minimum
+    covariance determinant estimator on h = (n + q + 1) // 2 points (FAST-MCD in numpy, seeded by `mcd_seed`), scaled to
+    consistency at the normal model; a curve is flagged when its squared robust distance exceeds
+    (q m / (m - q + 1)) F_(q, m - q + 1; level) with m the degrees of freedom of Hardin & Rocke (2005).
+    ValueError for what DirectionalOutlyingness refuses, a level outside (0, 1), records that are not finite (the message
+    says how many curves and why), too few curves, or more than half of the points in a hyperplane."""
+    return _directional._ms_plot_outliers(data, level=level, directions=directions, seed=seed, mcd_seed=mcd_seed,
+                                          device=device)
 
 
 def ProbabilisticDepth(data: pd.DataFrame, sigma2: pd.DataFrame, to_compute=None, K=None, J=2, relax=False, *,

@@ -828,6 +828,52 @@ def multi_projection_sums(P, U, targets=None, device=None, algo="auto", ws_bytes
     return _multi_cloud_sums("projection", torch().float64, P, U, targets, device, algo, ws_bytes)
 
 
+def multi_outlyingness_workspace_bytes(n, T, d, k, m=None, algo="auto"):
+    """(recommended, floor) workspace sizes of sd_multi_outlyingness_moments: multi_projection_workspace_bytes' plus the
+    centres of a batch's timepoints."""
+    return _multi_cloud_workspace_bytes("outlyingness", n, T, d, k, m, algo)
+
+
+def multi_outlyingness_moments(P, U, targets=None, device=None, algo="auto", ws_bytes=None, centres=False, curves=False):
+    """float64[m, d + 1]: the Welford records (M_0 .. M_(d-1), Q) of the directional outlyingness of multivariate curves
+    (sd_multi_outlyingness_moments; Dai & Genton).  P: (n, T, d) curves, U: k x d directions.  Per timepoint the
+    Stahel-Donoho outlyingness o_t of multi_projection_sums is given the direction of the unit vector from the cloud's
+    deepest point c_t (the lowest index among the minimisers of o_t over all n curves) to the curve's point:
+    O_t = o_t (x - x_c) / |x - x_c|, the zero vector where |x - x_c| = 0; M is the running mean of O_t over ascending t
+    and Q the running sum of squared deviations (Welford).  MO = M, VO = Q / T, FO = |MO|^2 + VO.  Where a direction's MAD
+    is 0 at some timepoint a record is +-inf or NaN (IEEE, not special-cased).  centres=True adds the int64[T] array c_t,
+    curves=True the float64[m, T, d] array O_t to the result (a tuple in that order).  With an empty target list nothing
+    is launched and the library writes no centres: they come back as an empty array, not as T zeros that would read as
+    curve 0.  P and U: finite, magnitudes of at most 2^500 (projection_check, run here, so that the function is safe on
+    its own: it also keeps the sum of squared differences from overflowing.  DirectionalOutlyingness has checked already;
+    the second host pass over P is small against the call).  algo and
+    ws_bytes as for multi_halfspace_sums; the same bits whatever they are."""
+    t = torch()
+    lib = _lib()
+    dev = _device(device)
+    a = _multi_cloud_algo(algo)
+    shape = np.shape(P)
+    if len(shape) != 3:
+        raise ValueError("expected a 3-D array (curves x timepoints x features)")
+    n, T, d = shape
+    for what, A in (("coordinates", P), ("direction entries", U)):  # (a tensor comes to the host for it)
+        projection_check(what, A.detach().cpu().numpy() if isinstance(A, t.Tensor) else A)
+    td, m, tp = _targets_dev(targets, n, dev)                        # the indices first: refused before anything is uploaded
+    Pd = _upload(P, 3, dev)
+    Ud = _directions_dev(U, d, dev)
+    k = Ud.shape[0]
+    out = t.empty((m, d + 1), dtype=t.float64, device=dev)
+    cen = t.zeros(T if m else 0, dtype=t.int64, device=dev) if centres else None   # (no targets: nothing is launched)
+    cur = t.zeros((m, T, d), dtype=t.float64, device=dev) if curves else None
+    rec = _launch(dev, lib.sd_multi_outlyingness_moments, out, Pd.data_ptr(), n, T, d, Ud.data_ptr(), k, tp, m, a, _OUT,
+                  cen.data_ptr() if centres else None, cur.data_ptr() if curves else None,
+                  workspace=lambda: _sized(dev, lib.sd_multi_outlyingness_workspace_bytes(n, T, d, k, m, a)
+                                           if ws_bytes is None else ws_bytes))
+    if not centres and not curves:
+        return rec
+    return (rec,) + ((cen.cpu().numpy(),) if centres else ()) + ((cur.cpu().numpy(),) if curves else ())
+
+
 def halfspace_workspace_bytes(n, d, k):
     """(recommended, floor) workspace sizes of sd_halfspace_counts; the floor holds one direction per chunk."""
     lib = _native.load()
