@@ -733,6 +733,55 @@ int sd_multi_outlyingness_moments(const double *P, int64_t n, int64_t T, int d, 
                                   const int64_t *targets, int64_t m, int algo, double *out, int64_t *centres, double *curves,
                                   void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K20: squared L2 distances between curves, their k-th smallest, and the h-modal sums --------
+ * No reference code (the h-modal depth of Cuevas, Febrero & Fraiman 2006, depth.mode of fda.usc, and its substrate, the
+ * matrix of pairwise L2 distances).  X, T, n, st, sn as for sd_rank_depth_sums; the values are finite with |x| <= 2^480 (the
+ * caller checks; nothing then overflows for T < 2^31).  A target is a sample curve (targets: m int64 indices on the device,
+ * NULL = all, m == n; repeated and permuted entries are allowed) or, in the external forms, column q of Q (T x m, time-major
+ * dense, device, as in sd_mbd_external_counts).
+ * Squared distance of target x and sample curve j: one accumulator over ascending t from +0.0,
+ *   d = x[t] - X[t][j];   acc = fma(d, d, acc)                            two rounded operations per timepoint,
+ * never split over t, no Gram form, no matrix instructions.  So D2[i][j] and D2[j][i] hold the same bits, D2[i][i] = +0.0, and
+ * a subnormal product is kept.  The L2 distance is sqrt(D2); the library returns D2.
+ *   sd_curve_sqdist, sd_curve_sqdist_external:  out[q * n + j] = D2 of target q and sample curve j, m x n doubles.
+ *   sd_curve_sqdist_select:  out[0] = the k-th smallest (k 1-based, 1 <= k <= N = n (n - 1) / 2) of D2[i][j] over the pairs
+ *     i < j: a radix descent on the 64-bit images (nonnegative doubles order like them), digits of 11 bits from the top,
+ *     integer histograms in LDS and global memory, the digit of rank k picked on the device.  With room for the n x n matrix
+ *     in the workspace (at most 1 GiB) it is formed once and re-read per pass, otherwise every pass recomputes it; the result
+ *     is the same.
+ *   sd_hmodal_sums, sd_hmodal_external_sums:  out[q] = S = sum_j exp(-(D2[q][j] * g)) over all n sample curves (for a sample
+ *     target its own term, exactly 1.0, included); g = 1 / (2 h^2) is the caller's double.  The product is rounded once, exp
+ *     is the device math library's (within 1 ulp).  The terms are added in an order that depends on n alone (written out in
+ *     csrc/curve_dist.hip: tiles of 64 sample curves, inside a tile 16 lanes of 4 columns joined by a butterfly, the tiles
+ *     in ascending order), without floating-point atomics: S of a target holds the same bits whatever the target list, the
+ *     layout of X or the workspace size.
+ * One tile kernel serves all five: a workgroup per 128 targets x 64 sample curves, both panels staged in LDS 16 timepoints
+ * at a time, an 8 x 4 register tile per thread, and the epilogue (store, exp-and-add, histogram) chosen at compile time.
+ * Workspace, each part padded to 256 bytes: the time-major copy of a curve-major X (8 T n bytes); then for `what` =
+ *   0 (distances): nothing;   1 (h-modal sums): the tiles' partial sums of a batch of targets, 8 ceil(n / 64) bytes a target,
+ *   batches of whole blocks of 128 targets (the floor is one block; the recommended size holds all, up to 256 MiB);
+ *   2 (selection): histogram and state (16 640 bytes: the floor), then the n x n matrix where it is at most 1 GiB.
+ * sd_curve_sqdist_workspace_bytes recommends a size, sd_curve_sqdist_min_workspace_bytes is the floor (both may be 0: a
+ * time-major X and what = 0 need no workspace, and ws may then be NULL), sd_curve_sqdist_targets_per_batch says how many
+ * targets a batch of a call with ws_bytes takes (0 below the floor; all m for what = 0, all n for what = 2).  All three are 0
+ * for a shape or `what` the calls refuse.
+ * SD_ERR_INVALID for NULL X, Q or out, T < 1, n < 1, m < 0, k outside [1, N], g not positive and finite; SD_ERR_UNSUPPORTED for
+ * n < 2, for 2^31 or more curves or timepoints, or for more than 10^14 pair-timepoints (n m T; the selection counts 3 n^2 T);
+ * SD_ERR_WORKSPACE below the floor.  All before any device work.  Every launch is bounded in work. */
+size_t sd_curve_sqdist_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what);
+size_t sd_curve_sqdist_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what);
+int64_t sd_curve_sqdist_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what, size_t ws_bytes);
+int sd_curve_sqdist(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    void *ws, size_t ws_bytes, void *stream);
+int sd_curve_sqdist_external(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
+                             void *ws, size_t ws_bytes, void *stream);
+int sd_curve_sqdist_select(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, double *out, void *ws,
+                           size_t ws_bytes, void *stream);
+int sd_hmodal_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double g,
+                   double *out, void *ws, size_t ws_bytes, void *stream);
+int sd_hmodal_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double g,
+                            double *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

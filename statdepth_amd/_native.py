@@ -114,6 +114,14 @@ SIGNATURES = {
     "sd_multi_outlyingness_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
     "sd_multi_outlyingness_min_workspace_bytes": (_sz, [_i64, _i64, _int, _i64, _i64, _int]),
     "sd_multi_outlyingness_moments": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sd_curve_sqdist_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_curve_sqdist_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_curve_sqdist_targets_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _int, _sz]),
+    "sd_curve_sqdist": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sd_curve_sqdist_external": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sd_curve_sqdist_select": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "sd_hmodal_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
+    "sd_hmodal_external_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
 }
 
 

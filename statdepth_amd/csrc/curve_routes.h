@@ -1,6 +1,7 @@
 // curve_routes.h -- the curve depths on K14's pair image (K14 rank depths, K15 extremal depth, K17 total variation depth):
 // their one route rule, the plan of stage 1 that the size functions and the launchers read, and each family's own plan
-// built on it (internal; the K1+K2 rank routes: rank_routes.h, the strict path's: strict_routes.h).
+// built on it; and the batch plan of K20, the squared L2 distances of curves, which reads the doubles (internal; the K1+K2
+// rank routes: rank_routes.h, the strict path's: strict_routes.h).
 #pragma once
 #include "sd_common.h"
 
@@ -68,5 +69,21 @@ struct TvdPlan {
 TvdPlan tvd_plan(i64 T, i64 n, i64 m, int route, PlanSize size);
 int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
                     u32 *counts, void *ws, size_t ws_bytes, hipStream_t s);
+
+// ---- K20 squared L2 distances of curves, their k-th smallest and the h-modal sums (curve_dist.hip).  These read the doubles,
+// not the pair image; the plan is over blocks of 128 targets and is sized by PlanSize with its rows read as targets. ----
+constexpr int CD_WHAT_SQDIST = 0, CD_WHAT_HMODAL = 1, CD_WHAT_SELECT = 2;   // what a call forms: the `what` of the size functions
+struct CurveDistPlan {
+    int what;
+    i64 targets;                                                    // per batch; 0: below the floor
+    bool slab;                                                      // the selection keeps the n x n matrix
+    size_t bytes;                                                   // SQDIST: none; HMODAL: the partial sums of a batch;
+};                                                                  // SELECT: histogram and state, then the slab
+CurveDistPlan curve_dist_plan(int what, i64 n, i64 m, PlanSize size);
+// Q null: the targets are sample curves (targets null: all, m == n); else the m columns of Q (T x m, time-major dense)
+int launch_curve_sqdist(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, hipStream_t s);
+int launch_hmodal_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double g, double *out, void *ws,
+                       size_t ws_bytes, hipStream_t s);
+int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace sd

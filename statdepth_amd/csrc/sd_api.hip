@@ -132,6 +132,16 @@ static int launch_time_major(const double *X, i64 T, i64 n, i64 st, i64 sn, void
     return launch(Y, cv.take(rest), rest, s);
 }
 
+// The tail of an entry point of K20: launch_time_major with the family's floor, but a floor of 0 bytes (time-major X, nothing
+// to carve) takes a null workspace.
+template <typename Launch>
+static int launch_curve_dist(const double *X, i64 T, i64 n, i64 st, i64 sn, i64 m, int what, void *ws, size_t ws_bytes, void *stream,
+                             Launch launch) {
+    const size_t floor = sd_curve_sqdist_min_workspace_bytes(T, n, st, sn, m, what);
+    if (floor == 0) return launch(X, nullptr, 0, (hipStream_t)stream);
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, floor, "sd_curve_sqdist_min_workspace_bytes", stream, launch);
+}
+
 // wide[i] (two 64-bit limbs) (+)= part[i]: the chunk totals of sd_mbd_counts_wide
 __global__ void wide_add_kernel(const u64 *__restrict__ part, i64 count, u64 *__restrict__ wide, int first) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1079,6 +1089,95 @@ int sd_tvd_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, c
                              "sd_tvd_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
                                  return launch_tvd_sums(Y, T, n, targets, m, route, sd_sum, shape, counts, w, bytes, s);
                              });
+}
+
+// ---- K20 ----
+// does the family take the shape, the number of targets and `what` (CD_WHAT_*)?
+static bool curve_dist_sized(i64 T, i64 n, i64 m, int what) {
+    return T >= 1 && n >= 2 && m >= 0 && T < ((i64)1 << 31) && n < ((i64)1 << 31) && what >= CD_WHAT_SQDIST && what <= CD_WHAT_SELECT;
+}
+
+size_t sd_curve_sqdist_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what) {
+    if (!curve_dist_sized(T, n, m, what)) return 0;
+    return time_major_bytes(T, n, st, sn) + curve_dist_plan(what, n, m, PlanSize::of_rows(m > n ? m : n)).bytes;
+}
+
+size_t sd_curve_sqdist_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what) {
+    if (!curve_dist_sized(T, n, m, what) || m == 0) return 0;
+    return time_major_bytes(T, n, st, sn) + curve_dist_plan(what, n, m, PlanSize::of_rows(1)).bytes;
+}
+
+int64_t sd_curve_sqdist_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what, size_t ws_bytes) {
+    if (!curve_dist_sized(T, n, m, what)) return 0;
+    const size_t tm = time_major_bytes(T, n, st, sn);
+    return ws_bytes >= tm ? curve_dist_plan(what, n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+}
+
+// the refusals of the five entry points, in sd_tvd_sums' order: pointers, shape, size, matrix, work
+// (external: the targets are the m columns of Q, any m >= 0)
+static int check_curve_dist(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64 *targets, i64 m, bool external, const void *out,
+                            double passes) {
+    if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
+    if (n < 2) return fail(SD_ERR_UNSUPPORTED, "distances between curves need at least two curves, got %lld", (long long)n);
+    int rc = external ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, targets, m);
+    if (rc) return rc;
+    if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
+    const double work = passes * (double)n * (double)m * (double)T;
+    if (work > HS_MAX_WORK) return fail(SD_ERR_UNSUPPORTED, "%.3g pair-timepoints exceed the cap of %.0e", work, HS_MAX_WORK);
+    return SD_OK;
+}
+
+static int check_bandwidth_factor(double g) {
+    return g > 0.0 && g <= 1.79769313486231570815e308 ? SD_OK
+                                                      : fail(SD_ERR_INVALID, "g = 1 / (2 h^2) must be positive and finite, got %g", g);
+}
+
+int sd_curve_sqdist(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 1.0);
+    if (rc || m == 0) return rc;
+    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_SQDIST, ws, ws_bytes, stream,
+                             [&](const double *Y, void *, size_t, hipStream_t s) { return launch_curve_sqdist(Y, T, n, nullptr, targets, m, out, s); });
+}
+
+int sd_curve_sqdist_external(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
+                             void *ws, size_t ws_bytes, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 1.0);
+    if (rc || m == 0) return rc;
+    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_SQDIST, ws, ws_bytes, stream,
+                             [&](const double *Y, void *, size_t, hipStream_t s) { return launch_curve_sqdist(Y, T, n, Q, nullptr, m, out, s); });
+}
+
+int sd_curve_sqdist_select(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, double *out, void *ws,
+                           size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, nullptr, n, false, out, 3.0);                        // six passes over half the pairs
+    if (rc) return rc;
+    const i64 N = n * (n - 1) / 2;
+    if (k < 1 || k > N) return fail(SD_ERR_INVALID, "k=%lld outside [1, %lld], the pairs of %lld curves", (long long)k, (long long)N, (long long)n);
+    return launch_curve_dist(X, T, n, st, sn, n, CD_WHAT_SELECT, ws, ws_bytes, stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+        return launch_curve_sqdist_select(Y, T, n, (u64)k, out, w, bytes, s);
+    });
+}
+
+int sd_hmodal_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double g,
+                   double *out, void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 1.0);
+    if (rc || (rc = check_bandwidth_factor(g)) || m == 0) return rc;
+    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_HMODAL, ws, ws_bytes, stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+        return launch_hmodal_sums(Y, T, n, nullptr, targets, m, g, out, w, bytes, s);
+    });
+}
+
+int sd_hmodal_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double g,
+                            double *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 1.0);
+    if (rc || (rc = check_bandwidth_factor(g)) || m == 0) return rc;
+    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_HMODAL, ws, ws_bytes, stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+        return launch_hmodal_sums(Y, T, n, Q, nullptr, m, g, out, w, bytes, s);
+    });
 }
 
 // ---------------------------------------------------------------------------

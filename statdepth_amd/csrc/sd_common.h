@@ -159,7 +159,7 @@ int launch_projection_blocks(const double *P, i64 n, int d, const double *U, i64
                              hipStream_t s);
 
 // K14 rank depths, K15 extremal depth and K17 total variation depth of curves: the pair-image plan and the launchers are in
-// curve_routes.h
+// curve_routes.h; so are the plan and the launchers of K20 (squared L2 distances of curves, curve_dist.hip)
 
 // K16 central regions, fence, outside counts and whiskers of the functional boxplot (central_regions.hip).  Y time-major;
 // fence, outside and whisker may be null (all three are with box = -1).  The workspace behind the time-major copy: a

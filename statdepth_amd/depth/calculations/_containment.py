@@ -12,7 +12,8 @@ depth, _functional._extremal_depth), selected the same way.  SHAPE_DEPTHS names 
 consecutive timepoints (the total variation depth and the modified shape similarity, _shape.py), selected the same way.
 CLOUD_DEPTHS names the depths of the point X(t) inside the cloud of all curves' points at t, aggregated over time (the
 multivariate functional halfspace depth and its projection-depth sibling, _functional._cloud_depths): the only names of
-these four tuples that take multivariate curves.
+these tuples that take multivariate curves.  METRIC_DEPTHS names the depths built on the L2 distances between whole curves
+(the h-modal depth, _functional._metric_depths), for univariate curves.
 """
 from inspect import signature
 
@@ -21,13 +22,14 @@ RANK_DEPTHS = ('fm', 'mei', 'mhi', 'half_region', 'integrated_halfspace', 'infim
 ORDER_DEPTHS = ('extremal',)
 SHAPE_DEPTHS = ('tvd', 'mss')
 CLOUD_DEPTHS = ('halfspace', 'projection')
+METRIC_DEPTHS = ('hmodal',)
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS)}, '
                          f'for univariate or multivariate data one of {list(CLOUD_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
@@ -51,6 +53,10 @@ def _is_shape_depth(containment) -> bool:
 
 def _is_cloud_depth(containment) -> bool:
     return isinstance(containment, str) and containment in CLOUD_DEPTHS
+
+
+def _is_metric_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in METRIC_DEPTHS
 
 
 def _select_containment(containment):

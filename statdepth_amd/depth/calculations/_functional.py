@@ -17,13 +17,14 @@ from scipy.special import binom
 
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
-from ._containment import _is_cloud_depth, _is_order_depth, _is_rank_depth, _is_shape_depth, _select_containment
+from ._containment import (_is_cloud_depth, _is_metric_depth, _is_order_depth, _is_rank_depth, _is_shape_depth,
+                           _select_containment)
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._pointcloud import _halfspace_directions
 from ._rank import _rank_depth_values
 from ._shape import _shape_depth_values
 
-__all__ = ['_functionaldepth', '_samplefunctionaldepth']
+__all__ = ['_functionaldepth', '_samplefunctionaldepth', '_curve_distances']
 
 
 # tests switch this off to compare the one-launch strict estimator with the block-by-block evaluation
@@ -210,6 +211,111 @@ def _shape_depths(data, to_compute, J, containment: str, deep_check=False, devic
     return pd.Series(index=cols, data=_shape_depth_values(sd_sum, shape, n, T, containment))
 
 
+METRIC_MAX_ABS = 2.0 ** 480         # |x| up to here: no squared L2 distance over fewer than 2^31 timepoints overflows
+
+
+def _metric_frame(data, J, what: str, deep_check=False):
+    """_ranked_frame for what is built on the L2 distances between curves: also no infinite value and none above 2^480 in
+    magnitude (a squared difference would overflow).  `what` names the caller in the refusals."""
+    def refuse(reason):
+        raise ValueError(f'{what} {reason}')
+
+    if not isinstance(data, list):
+        raise ValueError('data must be passed as a list.')
+    if len(data) == 0:
+        raise ValueError('No data passed.')
+    if len(data) != 1:
+        refuse('is defined for univariate data only (a list of one DataFrame whose columns are the curves).')
+    if not isinstance(J, numbers.Integral) or isinstance(J, bool) or J != 2:
+        refuse(f'has no band size: J must be left at its default 2, got {J!r}.')
+    if deep_check:
+        _deep_check(data)
+    df = data[0]
+    _require_unique_labels(df)
+    X = df.to_numpy(dtype=np.float64, copy=False)      # keeps the frame's memory layout
+    T, n = X.shape
+    if n < 2:
+        refuse(f'needs at least 2 curves, got {n}.')
+    if T < 1:
+        refuse('needs at least one timepoint.')
+    if not np.isfinite(X).all():
+        refuse('does not take NaN or infinite values (they have no distance): drop or fill them first.')
+    if np.abs(X).max() > METRIC_MAX_ABS:
+        refuse('takes values up to 2^480 in magnitude (a squared difference beyond would overflow): rescale the curves.')
+    return df, X
+
+
+def _coincident_pairs(X: np.ndarray) -> int:
+    """The pairs i < j of columns of X that are equal entry by entry (0.0 and -0.0 are equal): their distance is 0."""
+    T, n = X.shape
+    rows = np.ascontiguousarray(X.T) + 0.0               # -0.0 -> 0.0: equal values, equal bytes
+    _, counts = np.unique(rows.view(np.dtype((np.void, 8 * T))).ravel(), return_counts=True)
+    counts = counts.astype(object)
+    return int((counts * (counts - 1) // 2).sum())
+
+
+def _metric_depths(data, to_compute, J, containment: str, deep_check=False, device=None, quantile=0.15,
+                   bandwidth=None) -> pd.Series:
+    """The h-modal depth (Cuevas, Febrero & Fraiman 2006; containment 'hmodal') of the columns `to_compute` of the single
+    frame in `data`: (1/n) sum_j exp(-||x - x_j||^2 / (2 h^2)) over all n curves, the curve itself included, in (0, 1].
+    h is `bandwidth`, or the quantile `quantile` of the L2 distances over the pairs of curves i < j as an order statistic:
+    h^2 = the k-th smallest squared distance, k = max(1, ceil(quantile n (n - 1) / 2)) (type 1; fda.usc's depth.mode
+    interpolates, type 7, so its h differs slightly).  Three device calls at most: the selection (sd_curve_sqdist_select),
+    the sums (sd_hmodal_sums), one division on the host.  The bandwidth used is in the result's attrs['bandwidth'].
+    Labels, `to_compute` and the result's order are those of 'r2'.  Refused before anything is uploaded: what the rank
+    depths refuse, infinite values or magnitudes above 2^480, a quantile outside (0, 1], a bandwidth that is not positive
+    and finite, both given, and a quantile at which the distance is 0 because that share of the pairs coincides."""
+    df, X = _metric_frame(data, J, f'containment \'{containment}\'', deep_check)
+    T, n = X.shape
+    default_q = isinstance(quantile, numbers.Real) and not isinstance(quantile, bool) and quantile == 0.15
+    if bandwidth is not None:
+        if not default_q:
+            raise ValueError(f'containment \'{containment}\' takes bandwidth or quantile, not both: got bandwidth={bandwidth!r} '
+                             f'and quantile={quantile!r}.')
+        if not isinstance(bandwidth, numbers.Real) or isinstance(bandwidth, bool) or not 0.0 < bandwidth < math.inf:
+            raise ValueError(f'containment \'{containment}\' takes a positive finite bandwidth, got {bandwidth!r}.')
+        h = float(bandwidth)
+        h2 = h * h
+    else:
+        if not isinstance(quantile, numbers.Real) or isinstance(quantile, bool) or not 0.0 < quantile <= 1.0:
+            raise ValueError(f'containment \'{containment}\' takes a quantile in (0, 1], got {quantile!r}.')
+        N = n * (n - 1) // 2
+        k = max(1, math.ceil(quantile * N))
+        same = _coincident_pairs(X)
+
+        def refuse_zero(share):
+            raise ValueError(f'containment \'{containment}\': the quantile {quantile!r} of the distances between the curves is 0, '
+                             f'because {share} of the pairs of curves coincide; pass a larger quantile or a bandwidth.')
+
+        if same >= k:
+            refuse_zero(f'{same / N:.1%}')
+    cols = df.columns if to_compute is None else to_compute
+    targets = _positions(df, cols)
+    M = engine.to_device_matrix(X, device)               # one upload for the selection and the sums
+    if bandwidth is None:
+        h2 = engine.curve_sqdist_select(M, k, device=device)
+        if h2 == 0.0:                                    # differences so small that their squares underflow
+            refuse_zero(f'at least {k / N:.1%}')
+        h = math.sqrt(h2)
+    g = 1.0 / (2.0 * h2) if h2 > 0.0 else math.inf       # (a given bandwidth whose square underflows)
+    if not g < math.inf:
+        raise ValueError(f'containment \'{containment}\': the bandwidth {h!r} is too small, 1 / (2 h^2) overflows.')
+    S = engine.hmodal_sums(M, g, targets, device=device)
+    depths = pd.Series(index=cols, data=np.asarray(S, dtype=np.float64) / n)
+    depths.attrs['bandwidth'] = h
+    return depths
+
+
+def _curve_distances(data, to_compute=None, device=None) -> pd.DataFrame:
+    """The L2 distances (the square roots of sd_curve_sqdist's matrix) of the columns `to_compute` (default: all) of a
+    frame, or of the single frame of a list, to all of its columns: rows `to_compute`, columns the frame's labels."""
+    frames = data if isinstance(data, list) else [data]
+    df, X = _metric_frame(frames, 2, 'CurveDistances')
+    rows = df.columns if to_compute is None else to_compute
+    D2 = engine.curve_sqdist(X, _positions(df, rows), device=device)
+    return pd.DataFrame(np.sqrt(D2), index=rows, columns=df.columns)
+
+
 def _cloud_depth_values(records, n: int, T: int, containment: str, aggregate: str) -> np.ndarray:
     """The records [m, 2] of engine.multi_halfspace_sums (SH, MH: int64) or engine.multi_projection_sums (PS, OM: fp64) of
     curves among n at T timepoints -> the fp64 depths: one division each ('projection', 'inf': one addition as well)."""
@@ -308,7 +414,10 @@ def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, devic
 
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
                      relax=False, deep_check=False, quiet=True, device=None, algo='auto', directions=1000, seed=0,
-                     aggregate='mean') -> pd.Series:
+                     aggregate='mean', quantile=0.15, bandwidth=None) -> pd.Series:
+    if _is_metric_depth(containment):                    # `relax` and `algo` have nothing to select
+        return _metric_depths(data, to_compute, J, containment, deep_check=deep_check, device=device, quantile=quantile,
+                              bandwidth=bandwidth)
     if _is_cloud_depth(containment):                     # multivariate too; `relax` and `algo` have nothing to select
         return _cloud_depths(data, to_compute, J, containment, deep_check=deep_check, device=device,
                              directions=directions, seed=seed, aggregate=aggregate)
@@ -378,7 +487,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     """
     samples = []
     if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
-            or _is_cloud_depth(containment)):
+            or _is_cloud_depth(containment) or _is_metric_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

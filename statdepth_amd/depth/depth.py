@@ -14,7 +14,7 @@ import numpy as np
 import pandas as pd
 
 from abc import ABC, abstractmethod
-from .calculations._functional import _functionaldepth, _samplefunctionaldepth
+from .calculations._functional import _curve_distances, _functionaldepth, _samplefunctionaldepth
 from .calculations._helper import DepthDegeneracy   # noqa: F401
 from .calculations._pointcloud import _pointwisedepth, _samplepointwisedepth
 from .calculations._uncertainty import _probabilistic_band_depth
@@ -25,7 +25,7 @@ from .calculations._directional import DirectionalOutlyingnessResult, MSPlotOutl
 from . import _plotting
 
 __all__ = ['FunctionalDepth', 'PointcloudDepth', 'ProbabilisticDepth', 'FunctionalBoxplot', 'TotalVariationOutliers',
-           'DirectionalOutlyingness', 'MSPlotOutliers']
+           'DirectionalOutlyingness', 'MSPlotOutliers', 'CurveDistances']
 
 
 class AbstractDepth(ABC):
@@ -179,7 +179,8 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
 
 
 def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, containment='r2', relax=False,
-                    deep_check=False, quiet=True, *, device=None, algo='auto', directions=1000, seed=0, aggregate='mean'):
+                    deep_check=False, quiet=True, *, device=None, algo='auto', directions=1000, seed=0, aggregate='mean',
+                    quantile=0.15, bandwidth=None):
     """Band depth of curves ('r2', 'r2_enum', 'simplex' or a callable), as in the reference.
 
     For univariate data (`data` a list of one frame whose columns are the curves) `containment` also names the integrated
@@ -206,17 +207,40 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     aggregated over t: aggregate='mean' averages (for 'halfspace' the multivariate functional halfspace depth of Claeskens,
     Hubert, Slaets & Vakili 2014), aggregate='inf' takes the infimum.  Every other containment ignores the three arguments.
     `relax` and `algo` are ignored; ValueError for `K` other than None, `J` other than 2, frames of unequal shape, NaN or
-    infinite values, fewer than 2 curves, no timepoint or more than 8 features."""
+    infinite values, fewer than 2 curves, no timepoint or more than 8 features.
+
+    containment='hmodal' (univariate data, under the rules of the rank depths) is the h-modal depth of Cuevas, Febrero &
+    Fraiman (2006), built on the L2 distances between whole curves, not on pointwise order: (1/n) sum_j exp(-||x - x_j||^2 /
+    (2 h^2)) over all n curves, the curve itself included, in (0, 1]; ||.||^2 is the plain sum of squared differences over the
+    timepoints.  `bandwidth` gives h (positive, finite); otherwise h is the quantile `quantile` in (0, 1] (default 0.15) of
+    the distances over the pairs of curves, taken as an order statistic: the k-th smallest, k = max(1, ceil(quantile n (n - 1)
+    / 2)).  fda.usc's depth.mode interpolates between order statistics (type 7), so its h differs slightly.  The bandwidth
+    used is the attribute `bandwidth` of the result.  ValueError also for infinite values or magnitudes above 2^480, for both
+    `bandwidth` and a `quantile` other than the default, and where the quantile of the distances is 0 (that share of the
+    pairs of curves coincides).  Every other containment ignores the two arguments."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)
     else:
         depth = _functionaldepth(data=data, to_compute=to_compute, J=J, containment=containment, relax=relax,
                                  deep_check=deep_check, quiet=quiet, device=device, algo=algo, directions=directions,
-                                 seed=seed, aggregate=aggregate)
+                                 seed=seed, aggregate=aggregate, quantile=quantile, bandwidth=bandwidth)
     if len(data) == 1:                                   # univariate by assumption (:399-400)
-        return _FunctionalDepthUnivariate(df=data[0], depths=depth)
+        result = _FunctionalDepthUnivariate(df=data[0], depths=depth)
+        if 'bandwidth' in depth.attrs:                   # 'hmodal': a plain attribute, as the result's other state
+            object.__setattr__(result, 'bandwidth', depth.attrs['bandwidth'])
+        return result
     return _FunctionalDepthSeries(df=data[0], depths=depth)   # multivariate (:401-402)
+
+
+def CurveDistances(data, to_compute=None, device=None) -> pd.DataFrame:
+    """The L2 distances between univariate curves: a DataFrame with one row per curve of `to_compute` (column labels;
+    default: all) and one column per curve of `data` (a DataFrame whose columns are the curves, or a list of one), entry
+    sqrt(sum_t (x(t) - y(t))^2) -- the plain sum over the timepoints, no quadrature weights.  The squares are accumulated on
+    the device in time order with one fused multiply-add per timepoint (sd_curve_sqdist), so the matrix of all curves is
+    exactly symmetric with a zero diagonal.  ValueError, before anything is uploaded: more than one frame, duplicate labels,
+    fewer than 2 curves, no timepoint, NaN or infinite values, magnitudes above 2^480."""
+    return _curve_distances(data, to_compute=to_compute, device=device)
 
 
 def FunctionalBoxplot(data, depths=None, *, alpha=0.5, factor=1.5, levels=(), device=None,

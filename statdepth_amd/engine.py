@@ -248,9 +248,9 @@ def mbd_counts_range(X, target_begin, m, J=2, algo="auto", device=None, return_t
     return _mbd_counts(lib, lib.sd_mbd_counts_range, M, int(target_begin), int(m), J, algo, return_tensor)
 
 
-def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes):
+def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strided=False):
     """fn(X, T, n, Q, m, *extra, out, ws, ws_bytes, stream) for the m columns of Q (T x m) against the n columns of X.
-    out: int64 (m, *cols); ws_bytes(T, n, m): the workspace size."""
+    out: (m, *cols), int64 or `dtype`; ws_bytes(T, n, m): the workspace size.  strided: fn takes (st, sn) behind n."""
     t = torch()
     dev = _device(device)
     Xd, Qd = _upload(X, 2, dev), _upload(Q, 2, dev)
@@ -258,8 +258,9 @@ def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes):
     if Qd.shape[0] != T:
         raise ValueError("Q must have the same number of timepoints as X")
     m = Qd.shape[1]
-    out = t.empty((m, *cols), dtype=t.int64, device=dev)
-    return _launch(dev, fn, out, Xd.data_ptr(), T, n, Qd.data_ptr(), m, *extra,
+    out = t.empty((m, *cols), dtype=t.int64 if dtype is None else dtype, device=dev)
+    strides = (n, 1) if strided else ()
+    return _launch(dev, fn, out, Xd.data_ptr(), T, n, *strides, Qd.data_ptr(), m, *extra,
                    workspace=lambda: _sized(dev, ws_bytes(T, n, m)))
 
 
@@ -381,20 +382,26 @@ def _strides(T, n, curve_major):
     return (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
 
 
-def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs):
+def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs, sized_by=None):
     """lib.sd_<family>_<what>(X, T, n, st, sn, targets, m, algo, *outputs, ws, ws_bytes, stream) with ws_bytes of workspace
     (None: what sd_<family>_workspace_bytes recommends).  outputs(t, dev, M, m): the output tensors in the order of the C
-    signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays."""
+    signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays.
+    sized_by=(family, what): an entry point without an algo, whose workspace sd_<family>_workspace_bytes(..., what) sizes;
+    `algo` is then the tuple of its own arguments between m and the outputs, passed as they are (algo_of is not called)."""
     t = torch()
     lib = _lib()
     M = to_device_matrix(X, device)
     dev = M.device
-    a = algo_of(algo)
+    if sized_by is None:
+        a = algo_of(algo)
+        own = (a,)
+    else:
+        a, own = sized_by[1], tuple(algo)
     td, m, tp = _targets_dev(targets, M.n, dev)
     outs = outputs(t, dev, M, m)
-    size = getattr(lib, f"sd_{family}_workspace_bytes")
-    _launch(dev, getattr(lib, f"sd_{family}_{what}"), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, a, _OUT,
-            *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
+    size = getattr(lib, f"sd_{family if sized_by is None else sized_by[0]}_workspace_bytes")
+    _launch(dev, getattr(lib, f"sd_{family}_{what}" if what else f"sd_{family}"), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st,
+            M.sn, tp, m, *own, _OUT, *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
             workspace=lambda: _sized(dev, size(M.T, M.n, M.st, M.sn, m, a) if ws_bytes is None else ws_bytes),
             return_tensor=True)
     return [o.cpu().numpy() if o is not None else None for o in outs]
@@ -490,6 +497,93 @@ def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=Fa
         t.empty((m,), dtype=t.int64, device=dev), t.empty((m, 3), dtype=t.float64, device=dev),
         t.empty((max(M.T - 1, 0), m), dtype=t.int32, device=dev) if counts else None])
     return (sd, shape, cnt.view(np.uint32)) if counts else (sd, shape)
+
+
+CURVE_DIST_WHAT = {"sqdist": 0, "hmodal": 1, "select": 2}
+
+
+def curve_sqdist_workspace_bytes(T, n, what="sqdist", curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of the K20 calls for a T x n matrix and m targets (default: all n).  what:
+    'sqdist' (nothing but the time-major copy of a curve-major matrix: both may be 0), 'hmodal' (the tiles' partial sums of
+    a batch of targets; the floor holds one block of 128) or 'select' (histogram and state; the recommended size also holds
+    the n x n matrix where that is at most 1 GiB).  (0, 0) for a shape the calls refuse."""
+    lib = _native.load()
+    T, n, w = int(T), int(n), CURVE_DIST_WHAT[what]
+    m = n if m is None else int(m)
+    st, sn = _strides(T, n, curve_major)
+    return (int(lib.sd_curve_sqdist_workspace_bytes(T, n, st, sn, m, w)),
+            int(lib.sd_curve_sqdist_min_workspace_bytes(T, n, st, sn, m, w)))
+
+
+def curve_sqdist_targets_per_batch(T, n, ws_bytes, what="sqdist", curve_major=False, m=None):
+    """Targets a batch of a K20 call takes with ws_bytes of workspace (all of them for 'sqdist' and 'select'); 0 below the
+    floor."""
+    lib = _native.load()
+    T, n, w = int(T), int(n), CURVE_DIST_WHAT[what]
+    m = n if m is None else int(m)
+    return int(lib.sd_curve_sqdist_targets_per_batch(T, n, *_strides(T, n, curve_major), m, w, int(ws_bytes)))
+
+
+def _bandwidth_factor(g):
+    g = float(g)
+    if not (0.0 < g < float("inf")):
+        raise ValueError(f"g = 1 / (2 h^2) must be positive and finite, got {g!r}")
+    return g
+
+
+def curve_sqdist(X, targets=None, device=None, ws_bytes=None):
+    """float64[m, n]: the squared L2 distances of the targets (indices of sample curves; None: all) to the n columns of X
+    (sd_curve_sqdist): per pair one accumulator over ascending t, d = x[t] - y[t], acc = fma(d, d, acc).  The matrix is
+    bitwise symmetric with a +0.0 diagonal.  X must be finite with |x| <= 2^480 (the depth layer checks; this function takes
+    its array as it is).  ws_bytes: the workspace size to run with (default: the recommended one); below the floor the
+    library refuses."""
+    return _curves("curve_sqdist", "", None, X, targets, device, (), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m, M.n), dtype=t.float64, device=dev)], sized_by=("curve_sqdist", 0))[0]
+
+
+def curve_sqdist_external(X, Q, device=None, ws_bytes=None):
+    """float64[m, n]: the squared L2 distances of the m columns of Q (T x m) to the n columns of X
+    (sd_curve_sqdist_external); the arithmetic of curve_sqdist.  X goes up time-major, so no workspace is needed."""
+    lib = _lib()
+    size = (lambda T, n, m: lib.sd_curve_sqdist_workspace_bytes(T, n, n, 1, m, 0)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
+    return _external_curves(lib.sd_curve_sqdist_external, (np.shape(X)[1],), X, Q, device, dtype=torch().float64, strided=True,
+                            ws_bytes=size)
+
+
+def curve_sqdist_select(X, k, device=None, ws_bytes=None):
+    """The k-th smallest (k = 1 .. n (n - 1) / 2) squared L2 distance over the pairs i < j of the columns of X, as a float
+    (sd_curve_sqdist_select): a radix descent on the distances' 64-bit images.  With the recommended workspace the matrix
+    is kept (where it is at most 1 GiB), with less every pass recomputes it; the result is the same."""
+    n = int(np.shape(X)[1]) if not isinstance(X, DeviceMatrix) else X.n
+    k = int(k)
+    if not 1 <= k <= n * (n - 1) // 2:
+        raise ValueError(f"k must lie in [1, {n * (n - 1) // 2}], the pairs of {n} curves, got {k}")
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    out = t.empty((1,), dtype=t.float64, device=dev)
+    size = lib.sd_curve_sqdist_workspace_bytes(M.T, M.n, M.st, M.sn, M.n, 2) if ws_bytes is None else ws_bytes
+    return float(_launch(dev, lib.sd_curve_sqdist_select, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, k,
+                         workspace=lambda: _sized(dev, size))[0])
+
+
+def hmodal_sums(X, g, targets=None, device=None, ws_bytes=None):
+    """float64[m]: S = sum_j exp(-(D2[q][j] * g)) over all n columns of X per target (sd_hmodal_sums), D2 as in
+    curve_sqdist and g = 1 / (2 h^2); the target's own term is 1.0.  The order of the sum depends on n alone, so S of a
+    target holds the same bits whatever the targets, the layout of X or ws_bytes.  targets, ws_bytes and the contract on X
+    as for curve_sqdist."""
+    return _curves("hmodal", "sums", None, X, targets, device, (_bandwidth_factor(g),), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m,), dtype=t.float64, device=dev)], sized_by=("curve_sqdist", 1))[0]
+
+
+def hmodal_external_sums(X, Q, g, device=None, ws_bytes=None):
+    """float64[m]: the sums of hmodal_sums for the m columns of Q (T x m) against the n columns of X
+    (sd_hmodal_external_sums); no term is the target's own."""
+    lib = _lib()
+    size = (lambda T, n, m: lib.sd_curve_sqdist_workspace_bytes(T, n, n, 1, m, 1)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
+    return _external_curves(lib.sd_hmodal_external_sums, (), X, Q, device, _bandwidth_factor(g), dtype=torch().float64,
+                            strided=True, ws_bytes=size)
 
 
 def central_regions_row_capacity():
