@@ -10,9 +10,14 @@
 //     = Phi(hmax) - Phi(hmin) + C(h_j h_k, (h_j - h_k)^2, 1 - rho^2)   for rho >= 0.925 (Genz's branch near |r| = 1; the
 //       two orthants share C, and only one of them carries the Phi difference)
 // which is BVND's P(D_j > 0, D_k < 0) + P(D_j < 0, D_k > 0), both orthants with correlation -rho.  Written so, p keeps its
-// relative accuracy where it is small (the target outside the band), which the strict product needs.  1 - rho^2 =
-// u_j + g_j^2 u_k with g_c = sigma_i / s_c and u_c = sigma_c^2 / s_c^2: no cancellation as rho -> 1 (sigma_i >> sigma_j,
-// sigma_k).  Degenerate cases, exact and without 0/0:
+// relative accuracy where it is small (the target outside the band), which the strict product needs -- for |h_j|,
+// |h_k| <= 12, where tests/test_prob_pairs_gpu.py holds every branch to 1.31e-12 relative against 40-digit values
+// (measured on an MI355X: 3.5e-14 in the Gauss-Legendre branches, 3.3e-13 near rho = 1, 2.5e-16 in the degenerate ones).
+// Beyond that only the absolute 5e-15 is promised: the 12-point branch still kept 2e-16 relative up to |h| = 38 at
+// rho = 0.5, but the branch near rho = 1 drops every term whose exponent is below -100, so from h_j h_k = 200
+// on it returns exactly 0 where h_j = h_k (p < 1e-43) and loses digits where they differ (1.3e-4 relative at h = 20, 21).
+// 1 - rho^2 = u_j + g_j^2 u_k with g_c = sigma_i / s_c and u_c = sigma_c^2 / s_c^2: no cancellation as rho -> 1
+// (sigma_i >> sigma_j, sigma_k).  Degenerate cases, exact and without 0/0:
 //   sigma_i = 0:               p = a_j b_k + b_j a_k + e_j + e_k - e_j e_k, a_c = P(X_c > mu_i), b_c = P(X_c < mu_i),
 //                              e_c = P(X_c = mu_i) (indicators for point masses; all variances zero: p is 0 or 1 and
 //                              the sums equal FunctionalDepth's integer counts)

@@ -6,8 +6,13 @@
 //   A(m, k) = int Phi_m phi_k     = Phi(h)
 //   B(k, m) = int Phi_k Phi_m phi_k = Phi2(0, h; rho) = Phi(h) / 2 + T(h, a),  rho = sigma_k / (sqrt(2) s) < 1/sqrt(2),
 //                                     a = rho / sqrt(1 - rho^2) = sigma_k / sqrt(2 sigma_m^2 + sigma_k^2) < 1,
-// T being Owen's T, here by 12-point Gauss-Legendre on [0, a] (its integrand is smooth and a < 1: within 1e-16 of the
-// reference value over |h| <= 12, and below the fp64 range beyond).  Counting how often each one appears in the pairs:
+// T being Owen's T, here by 12-point Gauss-Legendre on [0, a] (its integrand is smooth and a < 1).  A pair term A - B is
+// within 9.1e-17 absolute of its 40-digit value for every h (0, 1e-300 ... 1e5, inf) and every a (1e-150 ... 1), measured on
+// an MI355X; tests/test_prob_pairs_gpu.py holds 3.7e-16.  The bound is absolute: T keeps no relative accuracy where it
+// is small (2e-5 relative at h = 12, a -> 1, a CPU measurement).  h and a are ratios, so the means of a pair are scaled
+// by 2^-4 where one exceeds 2^1020, its stds by 2^-4 where one exceeds 2^1020 and by 2^106 where both are below 2^-969
+// (pn_kernel): every finite input with positive stds gives a finite output, subnormal stds beside 1e308 means included.
+// Counting how often each one appears in the pairs:
 //   out[q] = sum_{m != k} A(m, k) ((n - 1 - m) - [k > m])  -  sum_{m != k} B(k, m) (m - [k < m]),   k = targets[q]
 // O(n) per target.  A workgroup takes one (target, chunk of PN_CHUNK partners) unit; each lane keeps the two weighted sums in
 // fp64, the workgroup reduces them in a fixed tree and writes their difference; pn_fold_kernel adds a target's chunks in
@@ -30,7 +35,10 @@
 // p is Loader's saddle-point form exp(-stirlerr(z) - bd0(z, lam)) / sqrt(2 pi z) (no lam^z, no z!), seeded at each
 // chunk start and carried by p(z + 1) = p(z) (lam / (z + 1)) for at most PP_Z - 1 steps.  L is a forward running sum from
 // L(0) = e^-lam; U a backward running sum from the chunk-end seeds, themselves a backward running sum from U(lim) (see
-// pp_tail).  Every z of 1 .. lim - 1 is evaluated: nothing is cut short.
+// pp_tail).  Every z of 1 .. lim - 1 is evaluated: nothing is cut short.  Against exact sums (n = 3, T = 1, 40 digits;
+// tests/test_prob_pairs_gpu.py, rtol 1e-12) the worst relative errors measured on an MI355X are 2.5e-15 / 1.8e-15 /
+// 6.6e-15 / 1.1e-15 at stirlerr's seams z = 15|16, 35|36, 80|81, 500|501, 1.1e-14 at bd0's series switch, 1.1e-14 at
+// pp_tail's lam = lim branch and re-seeds, 2.4e-14 at the 16-z chunk edges of lim.
 //
 // fp64 VALU and transcendentals (erfc, exp, log) are the hot path; the guides give no fp64 rate for this part, so the
 // costs in DESIGN §3 K8 are measured, not derived from a peak.
@@ -79,10 +87,17 @@ __global__ __launch_bounds__(PN_THREADS) void pn_kernel(const double *__restrict
     for (int j = 0; j < PN_PER_THREAD; ++j) {
         const i64 m = c * PN_CHUNK + (i64)j * PN_THREADS + threadIdx.x;
         if (m < n && m != k) {
-            const double sm = sg[m];
-            const double h = (mk - mu[m]) / hypot(sm, sk);
+            const double mm = mu[m], smax = fmax(sg[m], sk);
+            // h and a are ratios, so the means and the stds each take a power of two of their own (exact; 1 in between,
+            // where every bit stays as it was) and h gets the quotient back: cm keeps the difference finite, cs keeps
+            // sqrt(2) sm and the hypots finite at the top of the range and the subnormal stds' bits at its bottom.  A
+            // partner that the small factor pushes below the subnormals is beyond 2^-2000 of the other: no digit of it counts
+            const double cm = fmax(fabs(mk), fabs(mm)) > 0x1p1020 ? 0x1p-4 : 1.0;
+            const double cs = smax > 0x1p1020 ? 0x1p-4 : (smax < 0x1p-969 ? 0x1p106 : 1.0);
+            const double sm = sg[m] * cs, skk = sk * cs;
+            const double h = (mk * cm - mm * cm) / hypot(sm, skk) * (cs / cm);
             const double Ph = pr_phi(h);
-            const double a = sk / hypot(M_SQRT2 * sm, sk);
+            const double a = skk / hypot(M_SQRT2 * sm, skk);
             const double B = 0.5 * Ph + pn_owen_t(h, a);
             const double wa = (double)((n - 1 - m) - (k > m ? 1 : 0));
             const double wb = (double)(m - (k < m ? 1 : 0));

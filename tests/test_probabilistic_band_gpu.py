@@ -39,6 +39,8 @@ def _noisy(T, n, seed, zero_frac=0.1):
 
 # ---------------------------------------------------------------- 1. single probabilities (n = 3, T = 1)
 def test_single_probabilities(eng):
+    """Absolute 5e-15 against `band_p`, whose own relative accuracy ends where p is small.  The relative bound of the
+    kernel (|h| <= 12, against 40-digit values) is in tests/test_prob_pairs_gpu.py::test_band_regime_a."""
     triples = special_triples() + random_triples(2, 180) + random_triples(3, 20, zero_frac=0.5)
     worst = 0.0
     for tr in triples:

