@@ -401,10 +401,12 @@ int sd_halfspace_subset_counts(const double *P, int64_t n, int d, const double *
  * closed halfplane is upper semicontinuous in its direction, so the minimum over all closed halfplanes through q is
  * reached at such lines: out / n is the halfspace depth of q in the sample, not a bound of it.
  * Predicate: sign(a b - c d) from p1 = fl(a b), p2 = fl(c d): where p1 != p2 the sign of p1 - p2 (rounding is monotone),
- * otherwise the sign of e1 - e2 with the exact rounding errors e = fma(a, b, -p).  Exact while no product overflows or
- * underflows: the data must be finite with |coordinate| <= 2^500 (the host layer raises otherwise), and every nonzero
- * coordinate difference must be at least 2^-500 in magnitude -- NOT checked: the differences are not known before the
- * kernel forms them.  The sign of the rounded cross product is not a substitute (it is wrong for nearly collinear triples).
+ * otherwise, while |p1| >= 2^-900, the sign of e1 - e2 with the exact rounding errors e = fma(a, b, -p) (fp64 numbers
+ * there), and below that -- zero and underflowing products included, where the fma would lose the errors -- the signs of
+ * the products, their exponent sums and the same comparison on the frexp mantissas.  Exact for every finite input whose
+ * products do not overflow: the data must be finite with |coordinate| <= 2^500 (the host layer raises otherwise); there
+ * is NO lower limit on the coordinate differences, subnormal ones included.  The sign of the rounded cross product is
+ * not a substitute (it is wrong for nearly collinear triples).
  * algo: 0 = auto, 1 = sweep, 2 = pairwise; the same integers from both.
  *   sweep     one workgroup per target: the nonzero v in LDS (16 bytes each), each read through its image in the
  *             half-plane y > 0 or (y = 0, x > 0) (exact negation, the flip recomputed from v), sorted by angle with the
@@ -480,8 +482,8 @@ int sd_projection_subset_outlyingness(const double *P, int64_t n, int d, const d
  * sum_{r < s} C(L + r, 2), so the sweep may order a class as it likes.
  * depth = out / C(N, 3) on the host, N the sample size INCLUDING the point (K4's normalisers): n for a row target, n + 1
  * for an external point, the block size for a block.
- * Predicate limits as K11: finite data with |coordinate| <= 2^500 (the host layer raises otherwise); nonzero coordinate
- * differences of at least 2^-500 in magnitude -- NOT checked.
+ * Predicate domain as K11: finite data with |coordinate| <= 2^500 (the host layer raises otherwise); no lower limit on
+ * the coordinate differences.
  * algo: 0 = auto, 1 = sweep, 2 = pairwise; the same integers from both.
  *   sweep     one workgroup per target: K11's compaction, sort and flag prefix over the nonzero vectors of the others;
  *             groups are runs of sorted neighbours with cross = 0; the element at position i of group [g0, g1] with flip

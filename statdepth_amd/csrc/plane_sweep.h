@@ -1,10 +1,18 @@
 // plane_sweep.h -- the angular sweep around one point of a planar cloud, shared by K11 (halfspace_exact.hip) and K13
 // (simplicial_exact.hip) (internal, device code).
 //
-// Predicate.  sign(a b - c d): p1 = fl(a b), p2 = fl(c d); rounding is monotone, so p1 != p2 decides.  Otherwise the
-// products' rounding errors e1 = fma(a, b, -p1), e2 = fma(c, d, -p2) are exact fp64 numbers and a b - c d = e1 - e2, so the
-// comparison of e1 with e2 decides.  Exact while no product overflows or underflows: |coordinates| <= 2^500 (the host
-// checks) and nonzero coordinate differences >= 2^-500 in magnitude (not checked: they are not known before they are formed).
+// Predicate.  sign(a b - c d): p1 = fl(a b), p2 = fl(c d); rounding is monotone, also where it is subnormal or flushes to
+// zero, so p1 != p2 decides.  Otherwise a b - c d = e1 - e2 with the products' rounding errors e1 = a b - p1, e2 = c d - p2,
+// and e = fma(a, b, -p) is that error whenever it is an fp64 number.  It is a multiple of ulp(a) ulp(b) > |a b| 2^-106 (the
+// ulp of a subnormal is 2^-1074) of magnitude at most ulp(p) / 2, so it is one while |p| >= 2^-900: ulp(a) ulp(b) is then
+// above 2^-1007.  Below that (the products of tiny differences; also p1 = p2 = 0, where the errors ARE the products, and
+// e1 = u^2 2^-972 was lost from the witness of tests/test_planar_scale_host.py) nothing is left to the fma: a zero operand
+// is settled by the signs of the other product; otherwise frexp takes the four operands to mantissas in [1/2, 1) (exact,
+// subnormals included), differing signs of the products decide, exponent sums two or more apart decide (a product of two
+// mantissas lies in [1/4, 1)), and the remaining case is the same two-branch comparison on the mantissas, one of them times
+// 2^-1, 2^0 or 2^1, where every product is in [1/8, 2) and no error can be lost.  So the sign is exact for every finite
+// a, b, c, d whose products do not overflow: |coordinates| <= 2^500 (the host checks; differences are then at most 2^501
+// and products at most 2^1002), with no lower limit on the differences.
 //
 // Sweep.  The vectors v_i = (fl(p_i0 - q0), fl(p_i1 - q1)) from the target q to its sample are streamed once, the nonzero
 // ones compacted into LDS (wave ballot + one LDS atomic per wave) as they are, 16 bytes each in two fp64 arrays (consecutive
@@ -32,12 +40,37 @@ static inline double hx_sweep_wg_work(int cap) {
 static inline int hx_tier(i64 cnt_max) { return cnt_max <= 64 ? 64 : cnt_max <= 512 ? 512 : cnt_max <= 2048 ? 2048 : 8192; }
 
 #ifdef __HIPCC__
+// sign(a b - c d) where fl(a b) = fl(c d) is below 2^-900 in magnitude and no operand is zero: by exponents and mantissas
+static __device__ __noinline__ int hx_sign_diff_tiny(double a, double b, double c, double d) {
+    int ea, eb, ec, ed;
+    double ma = frexp(a, &ea);
+    const double mb = frexp(b, &eb), mc = frexp(c, &ec), md = frexp(d, &ed);
+    const int s1 = (ma < 0.0) != (mb < 0.0) ? -1 : 1, s2 = (mc < 0.0) != (md < 0.0) ? -1 : 1;
+    if (s1 != s2) return s1;                                        // a b and c d on either side of zero
+    const int de = (ea + eb) - (ec + ed);                           // |a b| in [2^(ea+eb-2), 2^(ea+eb)), c d likewise
+    if (de >= 2) return s1;
+    if (de <= -2) return -s1;
+    ma = ldexp(ma, de);
+    const double p1 = __dmul_rn(ma, mb), p2 = __dmul_rn(mc, md);
+    if (p1 != p2) return p1 > p2 ? 1 : -1;
+    const double e1 = __fma_rn(ma, mb, -p1), e2 = __fma_rn(mc, md, -p2);
+    return e1 > e2 ? 1 : (e1 < e2 ? -1 : 0);
+}
+
 // exact sign of a b - c d (see the header of this file)
 __device__ __forceinline__ int hx_sign_diff(double a, double b, double c, double d) {
     const double p1 = __dmul_rn(a, b), p2 = __dmul_rn(c, d);
     if (p1 != p2) return p1 > p2 ? 1 : -1;
-    const double e1 = __fma_rn(a, b, -p1), e2 = __fma_rn(c, d, -p2);
-    return e1 > e2 ? 1 : (e1 < e2 ? -1 : 0);
+    if (fabs(p1) >= 0x1p-900) {                                     // the errors are fp64 numbers
+        const double e1 = __fma_rn(a, b, -p1), e2 = __fma_rn(c, d, -p2);
+        return e1 > e2 ? 1 : (e1 < e2 ? -1 : 0);
+    }
+    const bool z1 = a == 0.0 || b == 0.0, z2 = c == 0.0 || d == 0.0;
+    if (z1 || z2) {                                                 // a b - c d = - c d, a b or 0, by the signs alone
+        if (z1 && z2) return 0;
+        return z1 ? ((c < 0.0) != (d < 0.0) ? 1 : -1) : ((a < 0.0) != (b < 0.0) ? -1 : 1);
+    }
+    return hx_sign_diff_tiny(a, b, c, d);
 }
 __device__ __forceinline__ int hx_cross(double ax, double ay, double bx, double by) { return hx_sign_diff(ax, by, ay, bx); }
 __device__ __forceinline__ int hx_dot(double ax, double ay, double bx, double by) { return hx_sign_diff(ax, bx, -ay, by); }

@@ -42,7 +42,7 @@ def sign_diff(a, b, c, d):
     return out
 
 
-def _count_one(P, q, extra):
+def _count_one(P, q, extra, sign=sign_diff):
     V = P - np.asarray(q, dtype=np.float64)                            # one rounded subtraction per component
     nz = (V != 0.0).any(axis=1)
     c0 = int((~nz).sum()) + extra
@@ -53,26 +53,27 @@ def _count_one(P, q, extra):
     step = max(1, (1 << 20) // len(x))                                 # rows of the pair matrix at a time
     for j0 in range(0, len(x), step):
         xj, yj = x[j0:j0 + step], y[j0:j0 + step]
-        C = sign_diff(xj[:, None], y[None, :], yj[:, None], x[None, :])            # cross(v_j, v_k)
+        C = sign(xj[:, None], y[None, :], yj[:, None], x[None, :])                 # cross(v_j, v_k)
         L, R = (C > 0).sum(axis=1), (C < 0).sum(axis=1)
         j, k = np.nonzero(C == 0)                                      # dot(v_j, v_k) matters on the line of v_j only
-        D = sign_diff(xj[j], x[k], -yj[j], y[k])
+        D = sign(xj[j], x[k], -yj[j], y[k])
         S, O = np.bincount(j[D > 0], minlength=len(xj)), np.bincount(j[D < 0], minlength=len(xj))
         best = min(best, int(np.minimum.reduce([L + O, R + S, L + S, R + O]).min()))
     return c0 + best
 
 
-def exact_counts(P, targets=None):
-    """c0 + min_j min(L_j + O_j, R_j + S_j, L_j + S_j, R_j + O_j): the definition as it stands."""
+def exact_counts(P, targets=None, sign=sign_diff):
+    """c0 + min_j min(L_j + O_j, R_j + S_j, L_j + S_j, R_j + O_j): the definition as it stands.  sign: the predicate,
+    sign_diff unless given (tests/test_planar_scale_host.py passes the rational sign_exact)."""
     P = np.asarray(P, dtype=np.float64)
     targets = range(len(P)) if targets is None else targets
-    return np.array([_count_one(P, P[t], 0) for t in targets], dtype=np.int64)
+    return np.array([_count_one(P, P[t], 0, sign) for t in targets], dtype=np.int64)
 
 
-def exact_external(P, Q):
+def exact_external(P, Q, sign=sign_diff):
     """Counts of each external point g inside P u {g}: n + 1 points, g adds one to c0."""
     P = np.asarray(P, dtype=np.float64)
-    return np.array([_count_one(P, g, 1) for g in np.asarray(Q, dtype=np.float64)], dtype=np.int64)
+    return np.array([_count_one(P, g, 1, sign) for g in np.asarray(Q, dtype=np.float64)], dtype=np.int64)
 
 
 def _frac_cross(a, b):

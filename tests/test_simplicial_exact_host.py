@@ -53,10 +53,10 @@ def simplicial_counts(P, targets=None, sign=sign_diff):
     return np.array([_count_one(np.delete(P, t, axis=0) - P[t], sign) for t in targets], dtype=np.int64)
 
 
-def simplicial_external(P, Q):
+def simplicial_external(P, Q, sign=sign_diff):
     """Triples of ALL rows of P whose closed hull contains the external point g."""
     P = np.asarray(P, dtype=np.float64)
-    return np.array([_count_one(P - g) for g in np.asarray(Q, dtype=np.float64)], dtype=np.int64)
+    return np.array([_count_one(P - g, sign) for g in np.asarray(Q, dtype=np.float64)], dtype=np.int64)
 
 
 def simplicial_sampled(P, targets, K):

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Exact halfspace depth in the plane (K11) timings: the sweep against the pairwise kernel with every point a target at
-n = 64, 256, 1 024, 4 096, 8 192; 100 external targets against 8 192 points; the K = 10 estimator at n = 2 000 -- its
-400 000 blocks in one sd_halfspace2_subset_counts call, and the whole PointcloudDepth(K=10) call with its draws on the
-host.  Per case: the median over --reps calls after one warm-up call, each call ending in a device synchronise, data
-resident on the device.  The PointcloudDepth case is timed once after a one-target warm-up: the host's 400 000
-`Series.sample` draws take tens of seconds.
+n = 64, 256, 1 024, 4 096, 8 192; the tie-heavy 64 x 32 integer grid (n = 2 048, every point a target, where the
+predicate's equal-products branch is hot); 100 external targets against 8 192 points; the K = 10 estimator at
+n = 2 000 -- its 400 000 blocks in one sd_halfspace2_subset_counts call, and the whole PointcloudDepth(K=10) call with
+its draws on the host.  Per case: the median over --reps calls after one warm-up call, each call ending in a device
+synchronise, data resident on the device.  The PointcloudDepth case is timed once after a one-target warm-up: the
+host's 400 000 `Series.sample` draws take tens of seconds.
 
     python tools/time_halfspace_exact.py [--reps 5] [--only NAME ...] [--out profiles/halfspace_exact_times.txt]
 
@@ -26,6 +27,8 @@ CASES = {}
 for _n in SIZES:
     CASES[f"all_n{_n}_sweep"] = ("all", _n, "sweep", 120)
     CASES[f"all_n{_n}_pairwise"] = ("all", _n, "pairwise", 240)
+CASES["ties_n2048_sweep"] = ("ties", 2048, "sweep", 120)
+CASES["ties_n2048_pairwise"] = ("ties", 2048, "pairwise", 120)
 CASES["external_m100_n8192_sweep"] = ("external", 8192, "sweep", 120)
 CASES["external_m100_n8192_pairwise"] = ("external", 8192, "pairwise", 120)
 CASES["blocks_K10_n2000"] = ("blocks", 2000, "auto", 120)
@@ -58,6 +61,10 @@ def run_case(name, reps):
     res = {"case": name, "kind": kind, "n": n, "algo": algo}
     if kind == "all":
         fn = lambda: engine.halfspace_exact_counts(P, algo=algo)            # noqa: E731
+        res["targets"] = n
+    elif kind == "ties":                        # the 64 x 32 integer grid: collinear pairs and zero products throughout
+        G = torch.from_numpy(np.stack(np.meshgrid(np.arange(64.0), np.arange(32.0)), axis=-1).reshape(n, 2)).to(dev)
+        fn = lambda: engine.halfspace_exact_counts(G, algo=algo)            # noqa: E731
         res["targets"] = n
     elif kind == "external":
         Q = torch.from_numpy(rng.normal(size=(100, 2))).to(dev)
@@ -96,6 +103,8 @@ def table(rows):
         s, p = by.get(f"all_n{n}_sweep"), by.get(f"all_n{n}_pairwise")
         ratio = f"{p['ms_median'] / s['ms_median']:.2f}" if s and p else "-"
         lines.append(f"{n:>6} {ms(f'all_n{n}_sweep'):>12} {ms(f'all_n{n}_pairwise'):>12} {ratio:>15}")
+    lines += ["", f"tie-heavy: the 64 x 32 integer grid, every point a target: sweep {ms('ties_n2048_sweep')}, "
+                  f"pairwise {ms('ties_n2048_pairwise')}"]
     lines += ["", f"100 external targets against 8192 points: sweep {ms('external_m100_n8192_sweep')}, "
                   f"pairwise {ms('external_m100_n8192_pairwise')}",
               f"K = 10 estimator at n = 2000: its 400 000 blocks of 201 points in one subset call {ms('blocks_K10_n2000')}; "

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Exact simplicial depth in the plane (K13) timings: the sweep and the pairwise kernel with every point a target at
 n = 1 024, 4 096, 8 192, and K11's sweep (exact halfspace depth: the same compaction, sort and flag prefix) at the same
-shapes in the same run; 100 external targets against 8 192 points; K4's enumeration of all C(n - 1, 3) triangles per
+shapes in the same run; the tie-heavy 64 x 32 integer grid (n = 2 048, every point a target, where the predicate's
+equal-products branch is hot); 100 external targets against 8 192 points; K4's enumeration of all C(n - 1, 3) triangles per
 target at n = 256 (or the largest of 256, 128, 64 it finishes within a second).  Per case: the median over --reps calls
 after one warm-up call, each call ending in a device synchronise, data resident on the device.
 
@@ -27,6 +28,8 @@ for _n in SIZES:
     CASES[f"all_n{_n}_sweep"] = ("all", _n, "sweep", 120)
     CASES[f"all_n{_n}_pairwise"] = ("all", _n, "pairwise", 240)
     CASES[f"all_n{_n}_k11sweep"] = ("k11", _n, "sweep", 120)
+CASES["ties_n2048_sweep"] = ("ties", 2048, "sweep", 120)
+CASES["ties_n2048_pairwise"] = ("ties", 2048, "pairwise", 120)
 CASES["external_m100_n8192_sweep"] = ("external", 8192, "sweep", 120)
 CASES["external_m100_n8192_pairwise"] = ("external", 8192, "pairwise", 120)
 CASES["external_m100_n8192_k11sweep"] = ("k11external", 8192, "sweep", 120)
@@ -70,6 +73,10 @@ def run_case(name, reps):
     if kind == "all":
         fn = lambda: engine.simplicial_exact_counts(P, algo=algo)           # noqa: E731
         res["targets"] = n
+    elif kind == "ties":                        # the 64 x 32 integer grid: collinear pairs and zero products throughout
+        G = torch.from_numpy(np.stack(np.meshgrid(np.arange(64.0), np.arange(32.0)), axis=-1).reshape(n, 2)).to(dev)
+        fn = lambda: engine.simplicial_exact_counts(G, algo=algo)           # noqa: E731
+        res["targets"] = n
     elif kind == "k11":
         fn = lambda: engine.halfspace_exact_counts(P, algo=algo)            # noqa: E731
         res["targets"] = n
@@ -96,6 +103,8 @@ def table(rows):
         sh = f"{s['ms_median'] / h['ms_median']:.2f}" if s and h else "-"
         lines.append(f"{n:>6} {ms(f'all_n{n}_sweep'):>12} {ms(f'all_n{n}_pairwise'):>12} {ps:>15} "
                      f"{ms(f'all_n{n}_k11sweep'):>12} {sh:>10}")
+    lines += ["", f"tie-heavy: the 64 x 32 integer grid, every point a target: sweep {ms('ties_n2048_sweep')}, "
+                  f"pairwise {ms('ties_n2048_pairwise')}"]
     lines += ["", f"100 external targets against 8192 points: sweep {ms('external_m100_n8192_sweep')}, "
                   f"pairwise {ms('external_m100_n8192_pairwise')}, K11 sweep {ms('external_m100_n8192_k11sweep')}"]
     k4 = by.get("k4_enumeration")
