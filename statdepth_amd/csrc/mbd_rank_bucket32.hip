@@ -19,6 +19,12 @@
 // and settled exactly, in fp64, among themselves at the end of the workgroup (a group of equal images is complete in the list).
 // Tie-heavy rows (quantised data: a bucket of 16 keys or more whose keys share an image) are ranked in closed form when
 // every bucket of the row provably holds one value.
+// The histogram's words: word k counts buckets 2k and 2k + 1 in two 16-bit halves (phase 1: one atomic per key, whose return
+// value is the key's slot in its bucket).  The prefix sum turns word k of a row without a bucket of 64 keys into the PAIR WORD
+// count(2k) | count(2k + 1) << 8 | base(2k) << 16 and the scatter reads it ONCE per key, at the word address of the key's atomic
+// (round 10; r32_pair_word, r32_pair_decode below); a crowded row's word keeps base(2k) | base(2k + 1) << 16 and its keys
+// read the two halfwords b and b + 1 apart.  Word NB / 2 holds the number of non-NaN keys, word NB / 2 + 1 is the dummy counter
+// of the NaN image.
 // Rows this kernel does not take -- a NaN, an infinity, a bucket of 64 keys or more, ties mixed with near-ties, and
 // every row of a workgroup whose list of set-aside keys overflows -- are flagged and ranked by rank_bucket_kernel's
 // SEL form in a second launch that returns at once when nothing was flagged (gate word = the call's epoch).
@@ -48,6 +54,23 @@ constexpr double R32_BETA = 2.0;                // the central bracket is widene
 constexpr double R32_VBASE = 274877906944.0;    // 2^38: v = 2^38 + u has one ulp = 2^-14 image, its mantissa is the 45-bit image
 constexpr u32 R32_VBASE_HI = 0x42500000u;       // high word of 2^38
 constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the keys (masked off by the member pass: any value would do)
+
+// Round 10: the words a key carries and reads between its histogram atomic and the scatter.
+//   key word   (a register of the key, from its bucket b):  8 * (b & 1) | byte offset of histogram word b >> 1, << 5 | slot << 24.
+//              Its low five bits are all that v_bfe reads of an offset or a width: 0 for an even bucket, 8 for an odd one.
+//   pair word  (histogram word k behind the prefix sum of a row without a bucket of 64 keys: both counts are below 64):
+//              count(2k) | count(2k + 1) << 8 | base(2k) << 16.
+// With v = the key word: count = bfe(pair, v, 8) and base = (pair >> 16) + bfe(pair, 0, v), a field of no width for an even
+// bucket and count(2k) for an odd one -- no select and no compare for the parity.
+__device__ __forceinline__ u32 r32_key_word(u32 b) { return ((b & 1u) << 3) | ((b >> 1) << 7); }
+__device__ __forceinline__ u32 r32_key_word_offset(u32 kw) { return __builtin_amdgcn_ubfe(kw, 5u, 16u); }
+__device__ __forceinline__ u32 r32_key_word_bucket(u32 kw) { return (__builtin_amdgcn_ubfe(kw, 7u, 14u) << 1) | ((kw >> 3) & 1u); }
+// h = the word's two 16-bit counters: bytes 0 and 2 of h under bytes 0 and 1 of base, one v_perm_b32
+__device__ __forceinline__ u32 r32_pair_word(u32 base, u32 h) { return __builtin_amdgcn_perm(base, h, 0x05040200u); }
+__device__ __forceinline__ void r32_pair_decode(u32 pw, u32 kw, u32 &base, u32 &cnt) {
+    cnt = __builtin_amdgcn_ubfe(pw, kw, 8u);
+    base = (pw >> 16) + __builtin_amdgcn_ubfe(pw, 0u, kw);
+}
 
 template <int E, int LNB>
 struct R32Cfg {
@@ -277,7 +300,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 q[i] &= 0x7FFFFFFFu;
             }
         };
-        u32 bc[E];                                                    // bucket | slot << 16, then (at the scatter) base | count << 14
+        u32 bc[E];                                                    // bucket, r32_key_word | slot << 24, then (at the scatter) base | count << 14
         if (go) {
             // ---- (1) image, bucket, slot ----
 
@@ -309,13 +332,14 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                     if (e < E) {
                         const u32 b = bc[e];
                         old[i] = atomicAdd(&H[b >> 1], 1u << ((b & 1u) * 16u));
+                        bc[e] = r32_key_word(b);
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int e = e0 + i;
-                    if (e < E)   // a NaN key's slot is read from the wrong half: its row is not taken anyway
-                        bc[e] |= ((old[i] >> ((bc[e] & 1u) * 16u)) & 0xFFu) << 16;
+                    if (e < E)   // (v_bfe reads five bits of its offset: 16 * parity.)  A NaN key's slot is read from the wrong
+                        bc[e] |= __builtin_amdgcn_ubfe(old[i], bc[e] << 1, 8u) << 24;   // half: its row is not taken anyway
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i)                           // packed HERE: not (old, shift) pairs kept for the scatter
@@ -345,31 +369,57 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             const bool trypure = __ballot((wt & 0x40000000u) != 0) != 0;
             const u32 wscan = rb_row_incl_scan(wt & 0x3FFFFFFFu);
             const u32 woff = wave ? rb_readlane(wscan, wave - 1) : 0u;
+            // block-uniform.  No bucket of 64 keys: word k becomes the PAIR WORD of buckets 2k and 2k + 1 (r32_pair_word: both
+            // counts and the even bucket's base), one 4-byte read per key at the scatter.  A crowded row's counts do not fit
+            // it: that row keeps the two bases as halfwords and the two-read scatter.
 #pragma unroll
             for (int i = 0; i < QW; ++i) {
-                u32 base = woff + offq[i] + inclq[i] - runq[i];
+                const u32 b0 = woff + offq[i] + inclq[i] - runq[i];
+                const u32 b1 = b0 + (hq[i].x & 0xFFFFu) + (hq[i].x >> 16);
+                const u32 b2 = b1 + (hq[i].y & 0xFFFFu) + (hq[i].y >> 16);
+                const u32 b3 = b2 + (hq[i].z & 0xFFFFu) + (hq[i].z >> 16);
                 uint4 o;
-                o.x = base | ((base + (hq[i].x & 0xFFFFu)) << 16);
-                base += (hq[i].x & 0xFFFFu) + (hq[i].x >> 16);
-                o.y = base | ((base + (hq[i].y & 0xFFFFu)) << 16);
-                base += (hq[i].y & 0xFFFFu) + (hq[i].y >> 16);
-                o.z = base | ((base + (hq[i].z & 0xFFFFu)) << 16);
-                base += (hq[i].z & 0xFFFFu) + (hq[i].z >> 16);
-                o.w = base | ((base + (hq[i].w & 0xFFFFu)) << 16);
-                base += (hq[i].w & 0xFFFFu) + (hq[i].w >> 16);
+                if (!crowded) {
+                    o.x = r32_pair_word(b0, hq[i].x);
+                    o.y = r32_pair_word(b1, hq[i].y);
+                    o.z = r32_pair_word(b2, hq[i].z);
+                    o.w = r32_pair_word(b3, hq[i].w);
+                } else {
+                    o.x = b0 | ((b0 + (hq[i].x & 0xFFFFu)) << 16);
+                    o.y = b1 | ((b1 + (hq[i].y & 0xFFFFu)) << 16);
+                    o.z = b2 | ((b2 + (hq[i].z & 0xFFFFu)) << 16);
+                    o.w = b3 | ((b3 + (hq[i].w & 0xFFFFu)) << 16);
+                }
                 Hq[i * 64 + lane] = o;
-                if (i == QW - 1 && t == NT - 1) H[NB / 2] = base;     // base past the last bucket = number of non-NaN keys
+                if (i == QW - 1 && t == NT - 1)                       // base past the last bucket = number of non-NaN keys
+                    H[NB / 2] = b3 + (hq[i].w & 0xFFFFu) + (hq[i].w >> 16);
             }
             __syncthreads();                                          // barrier 4
             const u32 nv = H[NB / 2];
             // block-uniform.  A crowded row (a bucket of 64 keys or more) is scattered too: its slots wrap at 256 but stay inside
             // their buckets, which is all the closed form below asks of S; its member pass is never run.
             bool take = nv == (u32)n;
-            if (take) {
-                // ---- (3) scatter into bucket order ----
+            if (take && !crowded) {
+                // ---- (3) scatter into bucket order: ONE 4-byte read per key, of the pair word its histogram atomic went to.
+                //      One key at a time, read - decode - write: measured faster than batches of 2, 4, 5, 8 or 10 reads in
+                //      flight, in that order (DESIGN S3, round 10) ----
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
-                    const u32 b = bc[e] & 0xFFFFu, slot = bc[e] >> 16;
+                    const u32 pw = *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(H) + r32_key_word_offset(bc[e]));
+                    __builtin_amdgcn_sched_barrier(0);                // the next key's read is not moved up to this one
+                    u32 base, cnt;
+                    r32_pair_decode(pw, bc[e], base, cnt);
+                    const bool isk = e < E - 2 || t + e * NT < n;
+                    // (byte offsets: the slot sits two bits above the top byte's foot, so that kw >> 22 is 4 * slot)
+                    *reinterpret_cast<u32 *>(reinterpret_cast<char *>(S) + (isk ? (base << 2) + (bc[e] >> 22) : (u32)DUMMY * 4u)) = kb[e];
+                    // a slot beyond n carries the NaN image: its "bucket" is the dummy counter, not a range of S -- one key at 0
+                    bc[e] = isk ? base | (cnt << 14) : (1u << 14);
+                }
+            } else if (take) {
+                // ---- (3') a crowded row: the two bases of word k as halfwords (its member pass is never run) ----
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const u32 b = r32_key_word_bucket(bc[e]), slot = bc[e] >> 24;
                     // two 2-byte reads, kept apart: merged into one 4-byte read they sit on an odd halfword for every
                     // odd b, and the LDS replays such a read for 64 cycles (SQ_LDS_UNALIGNED_STALL)
                     u32 b1 = b + 1u;

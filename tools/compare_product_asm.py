@@ -25,8 +25,7 @@ import tempfile
 
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
 NEW_ARGUMENTS = ()             # short names of kernels whose argument list this change rewrites
-NEW_KERNELS = ("cd_tile_kernel", "cd_fold_kernel", "cd_slab_hist_kernel", "cd_select_init_kernel",
-               "cd_pick_kernel")   # short names of kernels this change adds to the product (K20)
+NEW_KERNELS = ()               # short names of kernels this change adds to the product
 PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
                     r"wavefront|workgroup|workitem")
 
