@@ -20,8 +20,9 @@
 // Tie-heavy rows (quantised data: a bucket of 16 keys or more whose keys share an image) are ranked in closed form when
 // every bucket of the row provably holds one value.
 // The histogram's words: word k counts buckets 2k and 2k + 1 in two 16-bit halves (phase 1: one atomic per key, whose return
-// value is the key's slot in its bucket).  The prefix sum turns word k of a row without a bucket of 64 keys into the PAIR WORD
-// count(2k) | count(2k + 1) << 8 | base(2k) << 16 and the scatter reads it ONCE per key, at the word address of the key's atomic
+// value is the key's slot in its bucket; word and half are read off the two image words, r32_word_offset below).  The prefix
+// sum turns word k of a row without a bucket of 64 keys into the PAIR WORD count(2k) | count(2k + 1) << 8 | base(2k) << 16
+// and the scatter reads it ONCE per key, at the word address of the key's atomic
 // (round 10; r32_pair_word, r32_pair_decode below); a crowded row's word keeps base(2k) | base(2k + 1) << 16 and its keys
 // read the two halfwords b and b + 1 apart.  Word NB / 2 holds the number of non-NaN keys, word NB / 2 + 1 is the dummy counter
 // of the NaN image.
@@ -62,7 +63,12 @@ constexpr u32 R32_SENT = 0x7FFFFFFFu;           // sentinel image behind the key
 //              count(2k) | count(2k + 1) << 8 | base(2k) << 16.
 // With v = the key word: count = bfe(pair, v, 8) and base = (pair >> 16) + bfe(pair, 0, v), a field of no width for an even
 // bucket and count(2k) for an odd one -- no select and no compare for the parity.
-__device__ __forceinline__ u32 r32_key_word(u32 b) { return ((b & 1u) << 3) | ((b >> 1) << 7); }
+// Round 11: the key word is made from the two IMAGE words (vh = the high word of 2^38 + image, q = the low one), the bucket
+// b = bits 31 .. 44 of the image is never put together.  Its histogram word b >> 1 is the low 14 bits of vh (13 bucket bits and
+// the one that lets the NaN image reach word NB / 2 + 1), its parity is bit 31 of q: off4 = the word's byte offset -- the
+// atomic's address and the field at bits 5 .. 20 -- and par = the parity give the word of bucket b = 2 * (off4 / 4) + par.
+__device__ __forceinline__ u32 r32_word_offset(u32 vh) { return (vh << 2) & 0xFFFCu; }
+__device__ __forceinline__ u32 r32_key_word(u32 off4, u32 par) { return (off4 << 5) | (par << 3); }
 __device__ __forceinline__ u32 r32_key_word_offset(u32 kw) { return __builtin_amdgcn_ubfe(kw, 5u, 16u); }
 __device__ __forceinline__ u32 r32_key_word_bucket(u32 kw) { return (__builtin_amdgcn_ubfe(kw, 7u, 14u) << 1) | ((kw >> 3) & 1u); }
 // h = the word's two 16-bit counters: bytes 0 and 2 of h under bytes 0 and 1 of base, one v_perm_b32
@@ -104,6 +110,10 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     // the run-time n only decides where the sentinels and the dummy lie inside it.
     constexpr size_t LDS = C::lds_bytes(E * NT);
     static_assert(2 * LDS <= 160 * 1024, "two workgroups per CU");
+    // The member pass reads the quad behind the one a bucket starts in whether the bucket reaches it or not.  A base is at
+    // most n - 1: its quad ends at word al4(n) - 1 and the next one at word al4(n) + 3, inside the dummy_pos(n) + 4 =
+    // al4(n) + R32_PAD + 4 words of S for every n of the class, the largest included (the static block).
+    static_assert(R32_PAD >= 0 && C::al4(E * NT) + 3 < C::dummy_pos(E * NT) + 4, "the second quad of the last bucket lies in S");
     __shared__ __attribute__((aligned(16))) double Sm[(LDS + 7) / 8];
     const int n = (int)n64;
     double *red = Sm;                                                 // [2][NW][4] min / max of the row, central bracket of its keys
@@ -117,7 +127,6 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     const double INF = __builtin_huge_val();
     const double QNAN = __builtin_nan("");
     const int DUMMY = C::dummy_pos(n);
-    const uint4 *SENT = reinterpret_cast<const uint4 *>(S + C::al4(n));   // a quad of sentinels, shared by every lane that needs one
     const u32 nm1 = (u32)n - 1u;
     const u32 ranksum = (u32)(((u64)n * (u64)(n - 1)) >> 1);          // sum of the ranks of a row without equal images
     int t = t0;
@@ -256,8 +265,12 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
         // images = one step of the high word: mh0 <= high word < mh0 + mhw is EXACTLY vlo <= v < vlo + mcw, and a NaN, a negative
         // v (sign bit: a huge unsigned word) or any other binade fails it.  The tail code is computed only when some lane of the
         // wave has a key outside the core; which side is read off v itself (monotone in x: v < vlo <=> below the core, also
-        // for the row's minimum when the offset's rounding puts it a hair under the bound).  Out: the bucket in bk, the
-        // bucket-local image in q (a tail key: its 31-bit image's low 17 bits, 14 zero bits behind them).  A slot that holds no
+        // for the row's minimum when the offset's rounding puts it a hair under the bound).  Out: the high image word in bk
+        // (its low 14 bits: the bucket's histogram word), the low one in q -- the bucket-local image in its 31 bits (a tail
+        // key: its 31-bit image's low 17 bits, 14 zero bits behind them) under the bucket's parity in bit 31, which STAYS there:
+        // images are only ever compared inside one bucket (the member pass counts the bucket's own positions, the closed forms
+        // read its first two slots), where it is the same bit for every key, and y - q has the sign of the 31-bit difference
+        // with it as without it.  A slot that holds no
         // curve (!isk: its x is the NaN of load_row) is given the NaN's image directly and does not send its wave through the
         // tail code: at n = 10 000 half the waves of a workgroup have such a slot in every row.
         auto convert4 = [&](const double (&xv)[4], const bool (&isk)[4], u32 (&q)[4], u32 (&bk)[4]) {
@@ -296,11 +309,10 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             for (int i = 0; i < 4; ++i) {
                 vh[i] = isk[i] ? vh[i] : NANIMG >> (SH + 1);          // the words of NANIMG << 14, as the tail code gives a NaN
                 q[i] = isk[i] ? q[i] : NANIMG << (31 - SH);
-                bk[i] = __builtin_amdgcn_alignbit(vh[i], q[i], 31) & 0x7FFFu;   // a NaN's image: the dummy counter NB + 2
-                q[i] &= 0x7FFFFFFFu;
+                bk[i] = vh[i];                                        // a NaN's image: the dummy counter NB + 2 (word NB / 2 + 1)
             }
         };
-        u32 bc[E];                                                    // bucket, r32_key_word | slot << 24, then (at the scatter) base | count << 14
+        u32 bc[E];                                                    // high image word, r32_key_word | slot << 24, then (at the scatter) base | count << 14
         if (go) {
             // ---- (1) image, bucket, slot ----
 
@@ -330,9 +342,16 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 for (int i = 0; i < 8; ++i) {
                     const int e = e0 + i;
                     if (e < E) {
-                        const u32 b = bc[e];
-                        old[i] = atomicAdd(&H[b >> 1], 1u << ((b & 1u) * 16u));
-                        bc[e] = r32_key_word(b);
+                        // six vector instructions in front of the atomic (they are issued at the LDS phases' priority, where
+                        // one costs about three times what it costs in the member pass: DESIGN S3, round 11)
+                        const u32 off4 = r32_word_offset(bc[e]);
+                        u32 par = kb[e] >> 31, one;
+                        // 1 << 16 * parity = 0xFFFF * parity + 1: one v_mad_u32_u24 (written out: the compiler makes it a compare
+                        // and a select, 20 cycles of issue), not two shifts
+                        asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(one) : "v"(par), "s"(0xFFFFu));
+                        asm("" : "+v"(par));                          // (the key word from par, not from q again)
+                        old[i] = atomicAdd(reinterpret_cast<u32 *>(reinterpret_cast<char *>(H) + off4), one);
+                        bc[e] = r32_key_word(off4, par);
                     }
                 }
 #pragma unroll
@@ -513,16 +532,17 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
             if (take) {
                 // ---- (4) rank inside the bucket: two quads from the 16-byte boundary at or below the bucket's base.  Images
                 //      are bucket-local, so only the bucket's own positions [off, off + cnt) of the window are counted (the
-                //      keys of other buckets around them are masked off; a quad of sentinels stands in for a second quad
-                //      the bucket does not reach).  Only `<` is counted: equal images show in the sum of the row's ranks
+                //      keys of other buckets around them are masked off; the second quad is read where it lies, through the
+                //      first one's address register, whether the bucket reaches it or not: the next buckets' keys, the
+                //      sentinels or the padding behind them).  Only `<` is counted: equal images show in the sum of the row's ranks
                 //      (fold below) ----
                 const uint4 *S4 = reinterpret_cast<const uint4 *>(S);
                 uint4 y0, y1;
                 auto window = [&](int e) {
-                    const u32 base = bc[e] & 0x3FFFu, cnt = bc[e] >> 14;
+                    const u32 base = bc[e] & 0x3FFFu;
                     const uint4 *p = S4 + (base >> 2);
                     y0 = p[0];
-                    y1 = *((cnt + (base & 3u) > 4u) ? p + 1 : SENT);
+                    y1 = p[1];                                        // whether the bucket reaches it or not (the static_assert above)
                 };
                 u32 sB = 0;
                 window(0);
@@ -530,7 +550,7 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
                 for (int e = 0; e < E; ++e) {
                     const u32 base = bc[e] & 0x3FFFu, cnt = bc[e] >> 14, off = base & 3u;
                     const u32 qe = kb[e];
-                    // y < q <=> bit 31 of y - q (images below 2^31); v_alignbit shifts it into a bit list (window position p
+                    // y < q <=> bit 31 of y - q (images below 2^31 under one parity bit); v_alignbit shifts it into a bit list (window position p
                     // at bit p): two full-rate instructions per member and no compare -> carry chain through vcc (gfx950
                     // pays wait states on those)
                     u32 lt = 0;

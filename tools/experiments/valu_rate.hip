@@ -36,6 +36,12 @@ __global__ __launch_bounds__(1024) void k(unsigned *out, unsigned seed) {
             if (OP == 20) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
             if (OP == 21) asm volatile("v_add_f32 %0, %0, %1" : "+v"(a[i]) : "v"(b));
             if (OP == 22) asm volatile("v_cmp_lt_u32 vcc, %0, %1\n\tv_cndmask_b32 %0, %0, %1, vcc" : "+v"(a[i]) : "v"(b) : "vcc");   // 2 instructions
+            // round 11: a sign bit dropped into one byte of a list (two operands, SDWA encoding), a byte operand, a literal
+            if (OP == 23) asm volatile("v_lshrrev_b32_sdwa %0, %2, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(a[i]) : "v"(b), "v"(c));
+            if (OP == 24) asm volatile("v_and_b32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "+v"(a[i]) : "v"(b));
+            if (OP == 25) asm volatile("v_bfe_u32 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b), "v"(c));
+            if (OP == 26) asm volatile("v_and_b32 %0, 0xfff0, %0" : "+v"(a[i]));
+            if (OP == 27) asm volatile("v_and_b32 %0, %1, %0" : "+v"(a[i]) : "s"(c));
         }
     }
     unsigned r = 0;
@@ -56,7 +62,7 @@ template <int OP> int run(const char *name, unsigned *out) {
     CHK(hipEventElapsedTime(&ms, e0, e1));
     const double winst = (double)blocks * 16 * ITER * CH;               // wave-instructions
     const double per_simd = winst / (256.0 * 4.0);
-    printf("%-16s %8.3f ms  %.3e wave-instr/s  %.2f ns per wave-instruction per SIMD (= %.2f cycles at 2.4 GHz)\n", name, ms,
+    printf("%-34s %8.3f ms  %.3e wave-instr/s  %.2f ns per wave-instruction per SIMD (= %.2f cycles at 2.4 GHz)\n", name, ms,
            winst / (ms * 1e-3), ms * 1e6 / per_simd, ms * 1e6 / per_simd * 2.4);
     return 0;
 }
@@ -70,5 +76,8 @@ int main() {
     run<21>("v_add_f32", out); run<20>("v_fma_f32", out); run<15>("v_mul_f64", out); run<16>("v_cvt_u32_f64", out);
     printf("pairs (two instructions per step; the figures are per PAIR):\n");
     run<12>("sub_co + addc_co", out); run<22>("cmp + cndmask", out);
+    printf("round 11:\n");
+    run<23>("v_lshrrev_b32_sdwa BYTE_1 PRESERVE", out); run<24>("v_and_b32_sdwa src1 BYTE_2", out); run<25>("v_bfe_u32", out);
+    run<26>("v_and_b32 (literal)", out); run<27>("v_and_b32 (sgpr)", out);
     return 0;
 }
