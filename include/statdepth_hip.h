@@ -784,6 +784,54 @@ int sd_hmodal_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn
 int sd_hmodal_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double g,
                             double *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K21: the functional spatial depth of curves -------------------------------------------------
+ * No reference code (Chakraborty & Chaudhuri 2014; Sguera, Galeano & Lillo 2014; depth.FSD of fda.usc):
+ *   FSD(x) = 1 - | (1/N) sum_j (x - x_j) / |x - x_j| |,  L2 norms over the time grid (uniform: the quadrature weight cancels, so
+ * this is the Euclidean spatial depth in R^T).  X, T, n, st, sn, the values' contract (finite, |x| <= 2^480), targets and Q as
+ * for K20.  Per target x, with Y the time-major X:
+ *   1. D2[j] = K20's squared distance on K20's bits: one accumulator over ascending t from +0.0, d = x[t] - Y[t][j];
+ *      acc = fma(d, d, acc).
+ *   2. w[j] = 0.0 where D2[j] == 0.0, else 1.0 / sqrt(D2[j]): a correctly rounded root, then one correctly rounded division.
+ *   3. A coincident curve (D2 == 0: the target's own column, a duplicate of it, or differences so small that every square
+ *      underflows inside the fma) adds nothing to the sum and still counts in the sample size: the papers' sum over
+ *      x_j != x.  K5 (sd_l1_depth) returns NaN for coincident points because its reference does; K21 differs on purpose.  No
+ *      target index is special-cased: repeated and permuted target lists work, and so do external targets equal to a sample
+ *      curve.
+ *   4. E[t], per timepoint one accumulator over ascending j = 0 .. n - 1 from +0.0: d = x[t] - Y[t][j]; E = fma(w[j], d, E).
+ *      The direct form, never split over j, no Gram form x sum w - sum w_j x_j (it cancels for curves that are close relative
+ *      to their level), no matrix instructions, no floating-point atomics: E holds the same bits whatever the target list,
+ *      the tiles, the layout of X or the workspace.
+ *   5. S, one accumulator over ascending t from +0.0: S = fma(E[t], E[t], S).
+ *   out[q] = S (m doubles);  field = NULL, or m x T doubles, target-major, that receive E (at no cost when NULL).
+ *   6. The caller forms depth = 1 - sqrt(S) / N, N = n for a sample target and n + 1 for an external one (K5's convention: the
+ *      sample the depth refers to includes the target).
+ * D2 < 2^993, w >= 2^-497, |E| <= about n, S <= about n^2: nothing overflows under the values' contract.
+ * Three kernels per batch of targets: K20's tile kernel with a fourth epilogue that stores w (csrc/curve_dist.hip); the sum
+ * kernel, a workgroup per 128 targets x 64 timepoints (x 32 where that leaves compute units idle) that walks all n sample
+ * curves in ascending order, 16 at a time through LDS, an 8 x 4 (8 x 2) register tile of accumulators and of the targets' own
+ * values per thread (csrc/spatial_depth.hip); and the fold, one thread per target.
+ * Workspace, each part padded to 256 bytes: the time-major copy of a curve-major X (8 T n bytes); the weights of a batch of
+ * targets, 8 n bytes a target; the field of a batch, 8 T bytes a target (with `field` given the kernel writes there instead).
+ * Batches are whole blocks of 128 targets; the floor is one block.  The recommended size holds all targets, up to 8 GiB of
+ * weights a batch: at 100 000 curves x 256 timepoints that is 83 blocks, 664 workgroups of the sum kernel, more than two for
+ * each of the 256 compute units, where 1 GiB would give 80.  sd_spatial_targets_per_batch says how many targets a batch of a
+ * call with ws_bytes takes (0 below the floor).  All three are 0 where T < 1, n < 2, m < 0 or T or n is 2^31 or more (what the
+ * calls refuse for another reason, the budget of pair-timepoints among it, still has its sizes); the floor is 0 for m == 0.
+ * sd_spatial_time_tile says which time tile the sum kernel takes for a batch of `targets` targets on the stream's device: 64,
+ * or 32 where the 128 x 64 tile would give fewer than two workgroups per compute unit (0 for T < 1 or targets < 1).  The
+ * results do not depend on it.
+ * The refusals are K20's, in K20's order, all before any device work: SD_ERR_INVALID for NULL X, Q or out, T < 1, n < 1, m < 0;
+ * SD_ERR_UNSUPPORTED for n < 2, for 2^31 or more curves or timepoints, or for more than 10^14 pair-timepoints (2 n m T: the two
+ * passes); SD_ERR_WORKSPACE below the floor.  Every launch is bounded in work; no workgroup waits for another. */
+size_t sd_spatial_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m);
+size_t sd_spatial_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m);
+int64_t sd_spatial_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes);
+int64_t sd_spatial_time_tile(int64_t T, int64_t targets, void *stream);
+int sd_spatial_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    double *field, void *ws, size_t ws_bytes, void *stream);
+int sd_spatial_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
+                             double *field, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,12 @@ SIGNATURES = {
     "sd_curve_sqdist_select": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "sd_hmodal_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
     "sd_hmodal_external_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _vp, _vp, _sz, _vp]),
+    "sd_spatial_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "sd_spatial_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "sd_spatial_targets_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _sz]),
+    "sd_spatial_time_tile": (_i64, [_i64, _i64, _vp]),
+    "sd_spatial_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "sd_spatial_external_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -34,7 +34,11 @@
 //   CD_STORE   D2 to out[q][j] (the m x n output, or the n x n slab of the selection, there the tiles with a pair i < j only);
 //   CD_HMODAL  the tile's partial sums P[b] of its 128 targets to part[q - row0][b]; cd_fold_kernel adds them (no
 //              floating-point atomics anywhere);
-//   CD_HIST    the digits of the tile's pairs i < j into the histogram (the targets are the sample curves in order).
+//   CD_HIST    the digits of the tile's pairs i < j into the histogram (the targets are the sample curves in order);
+//   CD_WEIGHT  K21's weights w = 1 / sqrt(D2) (0.0 where D2 == 0.0; one correctly rounded root, one correctly rounded
+//              division) to out[j][q - row0], sample-curve-major: the panel [j][q] that sp_sum_kernel (spatial_depth.hip)
+//              stages.  All 128 target columns of a tile are written, those past the last target too (finite values that
+//              nothing reads), so a batch's slab holds no byte that was not written.
 // The selection keeps the n x n slab when the workspace holds it (cd_slab_hist_kernel re-reads it per pass) and otherwise
 // recomputes the tiles in every pass; both count the same multiset of images, so the result is the same.
 // The batch plan (curve_dist_plan) is over blocks of 128 targets: the h-modal partial sums are the only per-target
@@ -46,7 +50,7 @@ namespace sd {
 
 constexpr int CD_TILE = 128, CD_COLS = 64;                          // targets and sample curves of a tile
 constexpr int CD_TK = 16, CD_THREADS = 256, CD_R = CD_TILE / 16, CD_C = CD_COLS / 16;
-constexpr int CD_STORE = 0, CD_HMODAL = 1, CD_HIST = 2;
+constexpr int CD_STORE = 0, CD_HMODAL = 1, CD_HIST = 2, CD_WEIGHT = 3;
 constexpr int CD_BINS = 2048, CD_PASSES = 6;
 constexpr int CD_STATE_WORDS = 32;                                  // prefix, k; the rest pads the region
 constexpr size_t CD_PART_MAX = (size_t)256 << 20;                   // partial sums of a batch (recommended size and launch)
@@ -87,7 +91,8 @@ __device__ __forceinline__ void cd_step(const double *__restrict__ As, const dou
 // Targets [q_first + 128 (blockIdx.x / nb) ...) x sample curves [64 (blockIdx.x % nb) ...).  P, ldp, targets: the targets'
 // panel, value (t, q) = P[t * ldp + (targets ? targets[q] : q)].  q_end: one past the last target.  upper: only tiles that
 // hold a pair q < j (CD_STORE for the slab; CD_HIST always).  out, row0, ldo: CD_STORE out[(q - row0) * ldo + j], CD_HMODAL
-// out[(q - row0) * ldo + tile].  hist, state, shift, bits: CD_HIST.
+// out[(q - row0) * ldo + tile], CD_WEIGHT out[j * ldo + (q - row0)] (ldo a multiple of 128, row0 = q_first of the batch's
+// first launch, out 16-byte aligned).  hist, state, shift, bits: CD_HIST.
 template <int EPI>
 __global__ __launch_bounds__(CD_THREADS, 2) void cd_tile_kernel(const double *__restrict__ Y, i64 T, i64 n, const double *__restrict__ P,
                                                              i64 ldp, const i64 *__restrict__ targets, i64 q_first, i64 q_end, i64 nb,
@@ -160,6 +165,20 @@ __global__ __launch_bounds__(CD_THREADS, 2) void cd_tile_kernel(const double *__
             v += __shfl_xor(v, 8);
             const i64 q = q0 + CD_R * y + r;
             if (x == 0 && q < q_end) out[(q - row0) * ldo + cb] = v;
+        }
+    } else if constexpr (EPI == CD_WEIGHT) {
+#pragma unroll
+        for (int c = 0; c < CD_C; ++c) {
+            const i64 j = j0 + 32 * (c >> 1) + 2 * x + (c & 1);
+            if (j >= n) continue;
+            double *col = out + j * ldo + (q0 - row0) + CD_R * y;
+#pragma unroll
+            for (int r = 0; r < CD_R; r += 2) {
+                double2 w;
+                w.x = acc[r][c] == 0.0 ? 0.0 : __ddiv_rn(1.0, __dsqrt_rn(acc[r][c]));
+                w.y = acc[r + 1][c] == 0.0 ? 0.0 : __ddiv_rn(1.0, __dsqrt_rn(acc[r + 1][c]));
+                *reinterpret_cast<double2 *>(col + r) = w;
+            }
         }
     } else {
         __shared__ u32 lh[CD_BINS];
@@ -332,6 +351,13 @@ int launch_hmodal_sums(const double *Y, i64 T, i64 n, const double *Q, const i64
         SD_HIP(hipGetLastError());
     }
     return SD_OK;
+}
+
+// K21's pass 1: the weights of the targets [q_begin, q_end) into W[j * ldw + (q - q_begin)]
+int launch_curve_weights(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, i64 q_begin, i64 q_end, double *W,
+                         i64 ldw, hipStream_t s) {
+    const CdPanel pan = Q ? CdPanel{Q, m, nullptr} : CdPanel{Y, n, targets};
+    return cd_launch_tiles<CD_WEIGHT>(Y, T, n, pan, q_begin, q_end, 0, 0.0, W, q_begin, ldw, nullptr, nullptr, 0, s);
 }
 
 int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s) {

@@ -1,7 +1,7 @@
 // curve_routes.h -- the curve depths on K14's pair image (K14 rank depths, K15 extremal depth, K17 total variation depth):
 // their one route rule, the plan of stage 1 that the size functions and the launchers read, and each family's own plan
-// built on it; and the batch plan of K20, the squared L2 distances of curves, which reads the doubles (internal; the K1+K2
-// rank routes: rank_routes.h, the strict path's: strict_routes.h).
+// built on it; and the batch plans of K20, the squared L2 distances of curves, and of K21, the functional spatial depth on
+// them, which read the doubles (internal; the K1+K2 rank routes: rank_routes.h, the strict path's: strict_routes.h).
 #pragma once
 #include "sd_common.h"
 
@@ -85,5 +85,24 @@ int launch_curve_sqdist(const double *Y, i64 T, i64 n, const double *Q, const i6
 int launch_hmodal_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double g, double *out, void *ws,
                        size_t ws_bytes, hipStream_t s);
 int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s);
+// K21's pass 1 (the tile kernel's fourth epilogue): W[j * ldw + (q - q_begin)] = 1 / sqrt(D2[q][j]), 0.0 where D2 == 0.0, for the
+// targets [q_begin, q_end) of the m; ldw a multiple of 128 that holds them, W 16-byte aligned
+int launch_curve_weights(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, i64 q_begin, i64 q_end, double *W,
+                         i64 ldw, hipStream_t s);
+
+// ---- K21 functional spatial depth of curves (spatial_depth.hip): out[q] = S = |E[q]|^2, E[q][t] = sum_j w[q][j] (x[t] - Y[t][j]);
+// field (null or m x T, target-major) = E.  The plan is over blocks of 128 targets, sized by PlanSize with its rows read as
+// targets: the weights of a batch (n x targets, 8 n bytes a target) and its field (8 T bytes a target). ----
+struct SpatialPlan {
+    i64 targets;                                                    // per batch; 0: below the floor
+    size_t weights, field;                                          // bytes of the two parts
+    size_t bytes;                                                   // both
+};
+SpatialPlan spatial_plan(i64 T, i64 n, i64 m, PlanSize size);
+// timepoints of the sum kernel's tile for a batch of `targets` targets on `cus` compute units: 64, or 32 where the 128 x 64
+// tile would give fewer than two workgroups per unit
+int spatial_time_tile(i64 T, i64 targets, i64 cus);
+int launch_spatial_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, double *field,
+                        void *ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace sd

@@ -1180,6 +1180,54 @@ int sd_hmodal_external_sums(const double *X, int64_t T, int64_t n, int64_t st, i
     });
 }
 
+// ---- K21 ----
+static bool spatial_sized(i64 T, i64 n, i64 m) {
+    return T >= 1 && n >= 2 && m >= 0 && T < ((i64)1 << 31) && n < ((i64)1 << 31);
+}
+
+size_t sd_spatial_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
+    if (!spatial_sized(T, n, m)) return 0;
+    return time_major_bytes(T, n, st, sn) + spatial_plan(T, n, m, PlanSize::of_rows(m > n ? m : n)).bytes;
+}
+
+size_t sd_spatial_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
+    if (!spatial_sized(T, n, m) || m == 0) return 0;
+    return time_major_bytes(T, n, st, sn) + spatial_plan(T, n, m, PlanSize::of_rows(1)).bytes;
+}
+
+int64_t sd_spatial_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes) {
+    if (!spatial_sized(T, n, m)) return 0;
+    const size_t tm = time_major_bytes(T, n, st, sn);
+    return ws_bytes >= tm ? spatial_plan(T, n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+}
+
+int64_t sd_spatial_time_tile(int64_t T, int64_t targets, void *stream) {
+    if (T < 1 || targets < 1) return 0;
+    return spatial_time_tile(T, targets, stream_cus((hipStream_t)stream));
+}
+
+// K20's refusals in K20's order; the two passes count 2 n m T pair-timepoints
+int sd_spatial_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    double *field, void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 2.0);
+    if (rc || m == 0) return rc;
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_spatial_min_workspace_bytes(T, n, st, sn, m),
+                             "sd_spatial_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_spatial_sums(Y, T, n, nullptr, targets, m, out, field, w, bytes, s);
+                             });
+}
+
+int sd_spatial_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
+                             double *field, void *ws, size_t ws_bytes, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 2.0);
+    if (rc || m == 0) return rc;
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_spatial_min_workspace_bytes(T, n, st, sn, m),
+                             "sd_spatial_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_spatial_sums(Y, T, n, Q, nullptr, m, out, field, w, bytes, s);
+                             });
+}
+
 // ---------------------------------------------------------------------------
 // K18
 // ---------------------------------------------------------------------------

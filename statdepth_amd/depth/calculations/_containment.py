@@ -13,7 +13,8 @@ consecutive timepoints (the total variation depth and the modified shape similar
 CLOUD_DEPTHS names the depths of the point X(t) inside the cloud of all curves' points at t, aggregated over time (the
 multivariate functional halfspace depth and its projection-depth sibling, _functional._cloud_depths): the only names of
 these tuples that take multivariate curves.  METRIC_DEPTHS names the depths built on the L2 distances between whole curves
-(the h-modal depth, _functional._metric_depths), for univariate curves.
+(the h-modal depth, _functional._metric_depths), for univariate curves.  SPATIAL_DEPTHS names the functional spatial depth
+(_functional._spatial_depths), built on the same distances and the unit vectors between whole curves, for univariate curves.
 """
 from inspect import signature
 
@@ -23,13 +24,14 @@ ORDER_DEPTHS = ('extremal',)
 SHAPE_DEPTHS = ('tvd', 'mss')
 CLOUD_DEPTHS = ('halfspace', 'projection')
 METRIC_DEPTHS = ('hmodal',)
+SPATIAL_DEPTHS = ('spatial',)
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS + SPATIAL_DEPTHS)}, '
                          f'for univariate or multivariate data one of {list(CLOUD_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
@@ -57,6 +59,10 @@ def _is_cloud_depth(containment) -> bool:
 
 def _is_metric_depth(containment) -> bool:
     return isinstance(containment, str) and containment in METRIC_DEPTHS
+
+
+def _is_spatial_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in SPATIAL_DEPTHS
 
 
 def _select_containment(containment):

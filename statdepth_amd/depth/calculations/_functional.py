@@ -18,7 +18,7 @@ from scipy.special import binom
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
 from ._containment import (_is_cloud_depth, _is_metric_depth, _is_order_depth, _is_rank_depth, _is_shape_depth,
-                           _select_containment)
+                           _is_spatial_depth, _select_containment)
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._pointcloud import _halfspace_directions
 from ._rank import _rank_depth_values
@@ -306,6 +306,28 @@ def _metric_depths(data, to_compute, J, containment: str, deep_check=False, devi
     return depths
 
 
+def _spatial_depths(data, to_compute, J, containment: str, deep_check=False, device=None, quantile=0.15,
+                    bandwidth=None) -> pd.Series:
+    """The functional spatial depth (Chakraborty & Chaudhuri 2014; Sguera, Galeano & Lillo 2014; containment 'spatial') of
+    the columns `to_compute` of the single frame in `data`: 1 - ||(1/n) sum_j (x - x_j) / ||x - x_j|| ||, the L2 norms as plain
+    sums over the timepoints, the sum over the curves x_j at a nonzero distance from x (x itself and its exact copies add
+    nothing and still count in n), in [0, 1].  One upload, one device call for the squared norms of the sums
+    (sd_spatial_sums), a root and a division on the host.  Labels, `to_compute` and the result's order are those of 'r2'.
+    Refused before anything is uploaded: what 'hmodal' refuses of the data, and `quantile` or `bandwidth`, which belong to
+    'hmodal' (there is no bandwidth here)."""
+    df, X = _metric_frame(data, J, f'containment \'{containment}\'', deep_check)
+    T, n = X.shape
+    default_q = isinstance(quantile, numbers.Real) and not isinstance(quantile, bool) and quantile == 0.15
+    if bandwidth is not None or not default_q:
+        raise ValueError(f'containment \'{containment}\' has no bandwidth: quantile and bandwidth belong to \'hmodal\' and must '
+                         f'be left at their defaults, got quantile={quantile!r}, bandwidth={bandwidth!r}.')
+    cols = df.columns if to_compute is None else to_compute
+    targets = _positions(df, cols)
+    M = engine.to_device_matrix(X, device)               # one upload
+    S = engine.spatial_sums(M, targets, device=device)
+    return pd.Series(index=cols, data=1.0 - np.sqrt(np.asarray(S, dtype=np.float64)) / n)
+
+
 def _curve_distances(data, to_compute=None, device=None) -> pd.DataFrame:
     """The L2 distances (the square roots of sd_curve_sqdist's matrix) of the columns `to_compute` (default: all) of a
     frame, or of the single frame of a list, to all of its columns: rows `to_compute`, columns the frame's labels."""
@@ -418,6 +440,9 @@ def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index]
     if _is_metric_depth(containment):                    # `relax` and `algo` have nothing to select
         return _metric_depths(data, to_compute, J, containment, deep_check=deep_check, device=device, quantile=quantile,
                               bandwidth=bandwidth)
+    if _is_spatial_depth(containment):                   # as 'hmodal'; `quantile` and `bandwidth` are refused
+        return _spatial_depths(data, to_compute, J, containment, deep_check=deep_check, device=device, quantile=quantile,
+                               bandwidth=bandwidth)
     if _is_cloud_depth(containment):                     # multivariate too; `relax` and `algo` have nothing to select
         return _cloud_depths(data, to_compute, J, containment, deep_check=deep_check, device=device,
                              directions=directions, seed=seed, aggregate=aggregate)
@@ -487,7 +512,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     """
     samples = []
     if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
-            or _is_cloud_depth(containment) or _is_metric_depth(containment)):
+            or _is_cloud_depth(containment) or _is_metric_depth(containment) or _is_spatial_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

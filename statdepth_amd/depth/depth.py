@@ -217,7 +217,18 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     / 2)).  fda.usc's depth.mode interpolates between order statistics (type 7), so its h differs slightly.  The bandwidth
     used is the attribute `bandwidth` of the result.  ValueError also for infinite values or magnitudes above 2^480, for both
     `bandwidth` and a `quantile` other than the default, and where the quantile of the distances is 0 (that share of the
-    pairs of curves coincides).  Every other containment ignores the two arguments."""
+    pairs of curves coincides).  Every other containment but 'spatial' ignores the two arguments.
+
+    containment='spatial' (univariate data, under the rules of 'hmodal') is the functional spatial depth of Chakraborty &
+    Chaudhuri (2014) and Sguera, Galeano & Lillo (2014), fda.usc's depth.FSD: 1 - ||(1/n) sum_j (x - x_j) / ||x - x_j|| ||, the
+    norm of the mean unit vector from the other curves to the curve, in [0, 1]; ||.|| is the root of the plain sum of squared
+    differences over the timepoints (a uniform grid: the quadrature weight cancels).  A curve at distance 0 from x -- x itself,
+    an exact copy of it, or one so close that every squared difference underflows -- adds nothing to the sum and still counts
+    in n (the papers' sum over x_j != x), so n identical curves all have depth 1; PointcloudDepth's 'l1', the same depth for
+    points, returns NaN for coincident points as its reference does.  The sum over the curves runs on the device in column
+    order with one fused multiply-add per term (sd_spatial_sums), so a curve's depth does not depend on `to_compute`.
+    ValueError for what 'hmodal' refuses of the data, for `K` other than None, `J` other than 2, and for a `quantile` or a
+    `bandwidth` other than the default (they belong to 'hmodal'); `relax` and `algo` are ignored."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)

@@ -248,9 +248,11 @@ def mbd_counts_range(X, target_begin, m, J=2, algo="auto", device=None, return_t
     return _mbd_counts(lib, lib.sd_mbd_counts_range, M, int(target_begin), int(m), J, algo, return_tensor)
 
 
-def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strided=False):
+def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strided=False, second=None):
     """fn(X, T, n, Q, m, *extra, out, ws, ws_bytes, stream) for the m columns of Q (T x m) against the n columns of X.
-    out: (m, *cols), int64 or `dtype`; ws_bytes(T, n, m): the workspace size.  strided: fn takes (st, sn) behind n."""
+    out: (m, *cols), int64 or `dtype`; ws_bytes(T, n, m): the workspace size.  strided: fn takes (st, sn) behind n.
+    second: None, or the trailing shape(T, n, m) of a second output (m, *shape) of out's dtype that fn takes behind out (a
+    shape of None: fn gets NULL there); the pair is then returned, the second None where it was not asked for."""
     t = torch()
     dev = _device(device)
     Xd, Qd = _upload(X, 2, dev), _upload(Q, 2, dev)
@@ -260,8 +262,14 @@ def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strid
     m = Qd.shape[1]
     out = t.empty((m, *cols), dtype=t.int64 if dtype is None else dtype, device=dev)
     strides = (n, 1) if strided else ()
-    return _launch(dev, fn, out, Xd.data_ptr(), T, n, *strides, Qd.data_ptr(), m, *extra,
-                   workspace=lambda: _sized(dev, ws_bytes(T, n, m)))
+    shape = second(T, n, m) if second is not None else None
+    more = t.empty((m, *shape), dtype=out.dtype, device=dev) if shape is not None else None
+    tail = () if second is None else (_OUT, more.data_ptr() if more is not None and more.numel() else None)
+    first = _launch(dev, fn, out, Xd.data_ptr(), T, n, *strides, Qd.data_ptr(), m, *extra, *tail,
+                    workspace=lambda: _sized(dev, ws_bytes(T, n, m)))
+    if second is None:
+        return first
+    return first, more.cpu().numpy() if more is not None else None
 
 
 def mbd_external_counts(X, Q, J=2, device=None):
@@ -386,8 +394,9 @@ def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs, 
     """lib.sd_<family>_<what>(X, T, n, st, sn, targets, m, algo, *outputs, ws, ws_bytes, stream) with ws_bytes of workspace
     (None: what sd_<family>_workspace_bytes recommends).  outputs(t, dev, M, m): the output tensors in the order of the C
     signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays.
-    sized_by=(family, what): an entry point without an algo, whose workspace sd_<family>_workspace_bytes(..., what) sizes;
-    `algo` is then the tuple of its own arguments between m and the outputs, passed as they are (algo_of is not called)."""
+    sized_by=(family, what): an entry point without an algo, whose workspace sd_<family>_workspace_bytes(..., what) sizes
+    (what None: the size function ends at m); `algo` is then the tuple of its own arguments between m and the outputs, passed
+    as they are (algo_of is not called)."""
     t = torch()
     lib = _lib()
     M = to_device_matrix(X, device)
@@ -402,7 +411,8 @@ def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs, 
     size = getattr(lib, f"sd_{family if sized_by is None else sized_by[0]}_workspace_bytes")
     _launch(dev, getattr(lib, f"sd_{family}_{what}" if what else f"sd_{family}"), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st,
             M.sn, tp, m, *own, _OUT, *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
-            workspace=lambda: _sized(dev, size(M.T, M.n, M.st, M.sn, m, a) if ws_bytes is None else ws_bytes),
+            workspace=lambda: _sized(dev, size(M.T, M.n, M.st, M.sn, m, *(() if a is None else (a,)))
+                                     if ws_bytes is None else ws_bytes),
             return_tensor=True)
     return [o.cpu().numpy() if o is not None else None for o in outs]
 
@@ -584,6 +594,60 @@ def hmodal_external_sums(X, Q, g, device=None, ws_bytes=None):
     size = (lambda T, n, m: lib.sd_curve_sqdist_workspace_bytes(T, n, n, 1, m, 1)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
     return _external_curves(lib.sd_hmodal_external_sums, (), X, Q, device, _bandwidth_factor(g), dtype=torch().float64,
                             strided=True, ws_bytes=size)
+
+
+def spatial_workspace_bytes(T, n, curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of sd_spatial_sums for a T x n matrix and m targets (default: all n): the weights
+    (8 n bytes a target) and the field (8 T bytes a target) of a batch of whole blocks of 128 targets, behind the time-major
+    copy of a curve-major matrix.  The floor holds one block; the recommended size holds all targets, up to 8 GiB of weights
+    a batch.  (0, 0) where T < 1, n < 2 or m < 0."""
+    lib = _native.load()
+    T, n = int(T), int(n)
+    m = n if m is None else int(m)
+    st, sn = _strides(T, n, curve_major)
+    return int(lib.sd_spatial_workspace_bytes(T, n, st, sn, m)), int(lib.sd_spatial_min_workspace_bytes(T, n, st, sn, m))
+
+
+def spatial_targets_per_batch(T, n, ws_bytes, curve_major=False, m=None):
+    """Targets a batch of sd_spatial_sums takes with ws_bytes of workspace; 0 below the floor."""
+    lib = _native.load()
+    T, n = int(T), int(n)
+    m = n if m is None else int(m)
+    return int(lib.sd_spatial_targets_per_batch(T, n, *_strides(T, n, curve_major), m, int(ws_bytes)))
+
+
+def spatial_time_tile(T, targets, device=None):
+    """Timepoints of the tile that the sum kernel of sd_spatial_sums takes for a batch of `targets` targets on the device's
+    current stream: 64, or 32 where the wider tile would give fewer than two workgroups per compute unit.  The results do
+    not depend on it."""
+    lib = _lib()
+    dev = _device(device)
+    with torch().cuda.device(dev):
+        return int(lib.sd_spatial_time_tile(int(T), int(targets), _stream_ptr(dev)))
+
+
+def spatial_sums(X, targets=None, device=None, ws_bytes=None, field=False):
+    """float64[m]: S = |E|^2 of the functional spatial depth per target (sd_spatial_sums), and with field=True the pair
+    (S, E), E float64[m, T].  E[t] = sum_j w_j (x[t] - x_j[t]) over all n columns of X in ascending j with one fma per term,
+    w_j = 1 / sqrt(D2_j) on curve_sqdist's D2, and w_j = 0.0 where D2_j == 0.0: a coincident curve (the target itself, a
+    duplicate) adds nothing; S = sum_t E[t]^2 in ascending t with one fma per term.  The depth is 1 - sqrt(S) / n.  S and E of
+    a target hold the same bits whatever the targets, the layout of X or ws_bytes.  targets, ws_bytes and the contract on X
+    as for curve_sqdist."""
+    S, E = _curves("spatial", "sums", None, X, targets, device, (), ws_bytes, lambda t, dev, M, m: [
+        t.empty((m,), dtype=t.float64, device=dev), t.empty((m, M.T), dtype=t.float64, device=dev) if field else None],
+        sized_by=("spatial", None))
+    return (S, E) if field else S
+
+
+def spatial_external_sums(X, Q, device=None, ws_bytes=None, field=False):
+    """float64[m], or (S, E) with field=True: the sums of spatial_sums for the m columns of Q (T x m) against the n columns
+    of X (sd_spatial_external_sums).  The depth is 1 - sqrt(S) / (n + 1): the sample it refers to includes the target.  A
+    column of Q equal to a sample curve gives that curve's S."""
+    lib = _lib()
+    size = (lambda T, n, m: lib.sd_spatial_workspace_bytes(T, n, n, 1, m)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
+    S, E = _external_curves(lib.sd_spatial_external_sums, (), X, Q, device, dtype=torch().float64, strided=True, ws_bytes=size,
+                            second=lambda T, n, m: (T,) if field else None)
+    return (S, E) if field else S
 
 
 def central_regions_row_capacity():
