@@ -24,7 +24,8 @@
 //      Rows much wider than their bulk (heavy tails, outlying curves): a row whose histogram shows a crowded bucket and
 //      whose range exceeds the central bracket of its threads' own keys many times over is histogrammed again under the
 //      three-piece map of rank_bucket.h (linear core + float-like tails, monotone for any data); the rows behind it take
-//      their bracket with their range.  The external-target and medium kernels below use the same map.
+//      their bracket with their range.  The external-target and medium kernels (mbd_rank_external.hip, mbd_rank_medium.hip)
+//      use the same map, through the row build of rank_bucket_row.h; the LDS layout of a row (RBCfg) is there too.
 //   Z  rank_finalize_kernel / rank_finalize4_kernel -- totals of the requested targets = sum of the workgroups'
 //      partials (+ the fold of pair-image rows when the caller supplies one).
 //
@@ -34,25 +35,17 @@
 #include "sd_common.h"
 #include "rank_routes.h"
 #include "rank_sort.h"
-#include "rank_bucket.h"
+#include "rank_bucket_row.h"
 
 namespace sd {
-
-constexpr u32 RB_AB_SPECIAL = 0xFFFFFFFFu;     // same encodings as mbd_rank_ab.hip
-constexpr int RB_MEDIUM_MAXN = 40960;          // rank_medium_image_kernel: 2 or 3 blocks (measured: 4 blocks lose to the large-n route)
-// Rows whose range is much wider than their bulk (heavy tails, outlying curves): the three-piece map of rank_bucket.h.  Rounds
-// 1 - 3 clamped the tails into the two end buckets of a range clipped to the waves' innermost extremes: three outlying curves
-// were fine, heavy tails at every timepoint set every row aside for the sort (n = 14 000 Cauchy rows: 3.4 x the Gaussian time).
-constexpr int RB_PAD = 8;                      // NaN sentinels behind the bucket-ordered keys (never < or <= anything)
 
 // ---------------------------------------------------------------------------------------------------
 // The row the bucket map cannot spread (an infinite bracket, a crowded bucket that mixes values): in-LDS sort of the
 // plain values + binary search, the method of rank_search_kernel (mbd_rank_ab.hip), for ONE row inside the
 // bucket kernel, run behind the main row loop for the rows it set aside.  Thread t gets the pairs
-// of its curves t + 1024 e in ab[e] (B | A << 16, RB_AB_SPECIAL where the curve is NaN or beyond n).
+// of its curves t + 1024 e in ab[e] (B | A << 16, AB_SPECIAL where the curve is NaN or beyond n).
 // The sort image overlays the LDS at Sm; s_cnt is one LDS word outside it.
 // ---------------------------------------------------------------------------------------------------
-constexpr int RB_SNT = 1024, RB_SE = 16;
 __device__ __forceinline__ void rb_slow_row(const double *__restrict__ row, int n, double *Sm, u32 *s_cnt, u32 *ab,
                                          u32 *nnan_out) {
     using SC = R2Cfg<RB_SNT, RB_SE>;
@@ -87,7 +80,7 @@ __device__ __forceinline__ void rb_slow_row(const double *__restrict__ row, int 
     const u32 nnan = *s_cnt;
 #pragma unroll 4
     for (int e = 0; e < RB_SE; ++e) {
-        u32 r = RB_AB_SPECIAL;
+        u32 r = AB_SPECIAL;
         if (t + e * RB_SNT < n) {
             const double x = row[t + e * RB_SNT];
             if (x == x) {
@@ -108,30 +101,6 @@ __device__ __forceinline__ void rb_slow_row(const double *__restrict__ row, int 
     *nnan_out = nnan;
     __syncthreads();                                                  // the image is free again
 }
-
-template <int NT, int E, int LNB, int U2>
-struct RBCfg {
-    static constexpr int NB = 1 << LNB;
-    static constexpr int NW = NT / 64;
-    static constexpr int W = NB / 2 / NT;                       // histogram words per thread in the prefix sum
-    static constexpr int QW = W / 4;                            // ... as 16-byte quads
-    static_assert(W >= 4 && W % 4 == 0, "whole quads of histogram words per thread");
-    static_assert(NW == 16 || NW == 8, "cross-wave reductions are laid out for rows of 16 lanes");
-    static_assert(NT == RB_SNT, "rb_slow_row is compiled for 1024 threads");
-    // positions: [0, n) keys, [n, n + RB_PAD) sentinels, DUMMY.. a scratch pair range for keys that are NaN
-    static __host__ __device__ constexpr int dummy_pos(int n) { return (n + RB_PAD + 1) & ~1; }
-    static __host__ __device__ constexpr size_t keys_slots(int n) { return (size_t)dummy_pos(n) + 2 * U2 + 2; }
-    static constexpr int DEFW = 64;                              // bitmap of set-aside rows: 2048 rows per workgroup and launch
-    // min/max partials, wave totals, bitmap, 64 spare bytes, the waves' brackets ([3][NW] float2: rb3_wave_bracket)
-    static constexpr size_t HDR = (size_t)4 * NW * 8 + (size_t)NW * 4 + (size_t)DEFW * 4 + 64 + (size_t)6 * NW * 4;
-    static constexpr int BRK_WORD = NW + DEFW + 16;                // of the brackets, in u32 words behind the min/max partials
-    static __host__ __device__ constexpr size_t lds_bytes(int n) {
-        const size_t a = keys_slots(n) * 8 + (size_t)(NB / 2 + 4) * 4;
-        const size_t n_act = (size_t)((n + 1023) / 1024) * 1024;
-        const size_t b = (n_act + n_act / 16) * 8;                  // sort image of rb_slow_row (R2Cfg<1024,16> slots)
-        return HDR + (a > b ? a : b);
-    }
-};
 
 // SEL (J == 2, every curve a target): the second and last launch behind rank_bucket32_kernel (mbd_rank_bucket32.hip).
 // (1) Each workgroup sums its slice of curves over that kernel's Gsum u32 partial blocks and adds the totals to out_tot
@@ -439,7 +408,7 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
                 if constexpr (J == 0) {
 #pragma unroll
                     for (int e = 0; e < E; ++e)
-                        if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = RB_AB_SPECIAL;
+                        if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = AB_SPECIAL;
                     if (t == 0) nnan_img[r] = (u32)n;
                 }
             } else {                                                  // set aside: sorted behind the loop
@@ -591,7 +560,7 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
                 const u32 base = bc[e] & 0xFFFFu, cnt = (bc[e] >> 16) & 0xFFu;
                 const u32 B = base + (pk[e] & 0xFFFFu), A = nv - base - (pk[e] >> 16);
                 if constexpr (J == 0) {
-                    if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = cnt ? (B | (A << 16)) : RB_AB_SPECIAL;
+                    if (e < E - 1 || t + (E - 1) * NT < n) ABimg[r * n + t + e * NT] = cnt ? (B | (A << 16)) : AB_SPECIAL;
                 } else if constexpr (J == 2) {
                     // 2 * contained_2 = 2 N (v - A - B) + v(v-1) - A(A-1) - B(B-1)   (all terms < 2^30)
                     u32 q = __umul24(A, A - 1u) + __umul24(B, B - 1u);   // A, B < 2^15: 24-bit multiplies are exact
@@ -645,7 +614,7 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
                 if constexpr (J == 0) {
                     if (t + e * NT < n) ABimg[r * n + t + e * NT] = ab[e];
                     if (e == 0 && t == 0) nnan_img[r] = nnan_s;
-                } else if (ab[e] != RB_AB_SPECIAL) {                         // implies t + e * NT < n
+                } else if (ab[e] != AB_SPECIAL) {                         // implies t + e * NT < n
                     u64 a7[JMAX - 1] = {0, 0, 0, 0, 0, 0, 0};
                     band_counts_add<(J > 0 ? J : 2)>(ab[e] >> 16, ab[e] & 0xFFFFu, nnan_s, (u64)(n - 1), a7);
                     if (SEL || (J == 2 && p32)) P32[t + e * NT] += (u32)a7[0];
@@ -708,227 +677,6 @@ __global__ __launch_bounds__(NT, 4) void rank_bucket_kernel(const double *__rest
 }
 
 // ---------------------------------------------------------------------------------------------------
-// X: band totals of EXTERNAL curves (targets that are not members of the set; the homogeneity coefficients'
-// `FunctionalDepth(F u {g}, to_compute=[g])`, homogeneity.py:101-128) through the same bucket structure.  Per row the
-// set is histogrammed, prefix-summed and scattered exactly as in rank_bucket_kernel; then every external value x looks
-// up its own bucket -- b(x) is monotone, so the keys of earlier buckets are below x and those of later ones above --
-// and compares itself with that bucket's members: B = base + #(y < x), A = n_valid - base - #(y <= x).  O(n + m)
-// per row instead of the pairwise kernel's O(n m).  No row is set aside: a row the map cannot spread (equal values,
-// an infinity) simply lands in one bucket, and m targets walking n keys is still cheap.
-// Thread t owns targets t, t + 1024, ... (EQ of them) and their totals for the whole launch.
-// ---------------------------------------------------------------------------------------------------
-template <int NT, int E, int LNB, int J, int EQ>
-__global__ __launch_bounds__(NT) void rank_external_kernel(const double *__restrict__ Y, i64 n64, i64 rows,
-                                                           const double *__restrict__ Q, i64 m64, i64 qstride,
-                                                           u64 *__restrict__ partial) {
-    using C = RBCfg<NT, E, LNB, 3>;
-    constexpr int NB = C::NB, NW = C::NW, QW = C::QW;
-    extern __shared__ double Sm[];
-    const int n = (int)n64, m = (int)m64;
-    double *red = Sm;                                                 // [2][NW][2] min/max partials
-    u32 *wtot = reinterpret_cast<u32 *>(red + 4 * NW);                // [NW]
-    float2 *brk = reinterpret_cast<float2 *>(wtot + C::BRK_WORD);     // [NW] the waves' brackets
-    u32 *H = reinterpret_cast<u32 *>(Sm + C::HDR / 8);                // NB packed u16 counters, then bases
-    double *S = reinterpret_cast<double *>(H + NB / 2 + 4);           // keys in bucket order
-    const unsigned short *H16 = reinterpret_cast<const unsigned short *>(H);
-    const int t0 = threadIdx.x;
-    const double INF = __builtin_huge_val();
-    const double QNAN = __builtin_nan("");
-    const int DUMMY = C::dummy_pos(n);
-    int t = t0;
-    {
-        uint4 *Hq = reinterpret_cast<uint4 *>(H);
-#pragma unroll
-        for (int i = 0; i < QW; ++i) Hq[i * NT + t] = make_uint4(0, 0, 0, 0);
-        if (t < 4) H[NB / 2 + t] = 0;
-    }
-    double k[E];
-    auto load_row = [&](i64 r) {
-        const double *rp = Y + r * n + t;
-#pragma unroll
-        for (int e = 0; e < E; ++e) k[e] = (e < E - 1 || t + (E - 1) * NT < n) ? rp[e * NT] : QNAN;
-    };
-    u64 acc[EQ][JMAX - 1];
-#pragma unroll
-    for (int q = 0; q < EQ; ++q)
-#pragma unroll
-        for (int j = 0; j < JMAX - 1; ++j) acc[q][j] = 0;
-    int par = 0;
-    bool heavy = false;                                               // block-uniform: the last row went under the three-piece map
-    if ((i64)blockIdx.x < rows) load_row(blockIdx.x);
-    for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
-        const i64 rnext = r + gridDim.x;
-        t = t0;
-        asm volatile("" : "+v"(t));                                   // per-row opaque thread id (see rank_bucket_kernel)
-        const int lane = t & 63;
-        const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-        // the row's external values (in flight under the set's phases)
-        double xq[EQ];
-#pragma unroll
-        for (int q = 0; q < EQ; ++q) xq[q] = (t + q * NT < m) ? Q[r * qstride + t + q * NT] : QNAN;
-        // ---- (0) range ----
-        double mn = INF, mx = -INF;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            mn = rb_mm<false>(mn, k[e]);
-            mx = rb_mm<true>(mx, k[e]);
-        }
-        const double tmn = mn, tmx = mx;                              // this thread's own extremes (the bracket's groups)
-        mn = rb_wave_allreduce<false>(mn);
-        mx = rb_wave_allreduce<true>(mx);
-        double *redp = red + par * 2 * NW;
-        if (lane == 63) { redp[2 * wave] = mn; redp[2 * wave + 1] = mx; }
-        par ^= 1;
-        __syncthreads();                                              // barrier 1
-        double lo, hi;
-        Rb3 m3;
-        m3.clip = false;
-        {
-            const double2 p = reinterpret_cast<const double2 *>(redp)[lane & (NW - 1)];
-            lo = rb_readlane_f64(rb_row_allreduce<false>(p.x), 0);
-            hi = rb_readlane_f64(rb_row_allreduce<true>(p.y), 0);
-        }
-        double scale = (double)NB / (hi - lo);
-        // equal values, an infinity in the range, a range too small or too large: everything into one bucket
-        if (!((hi > lo) && (scale < INF) && (lo > -INF) && (hi < INF))) scale = 0.0;
-        auto bucket_of = [&](double x) {
-            if (m3.clip) return rb3_bucket<NB>(m3, x);                // block-uniform
-            double u = (x - lo) * scale;
-            u = u > 0.0 ? u : 0.0;                                    // below the range, and NaN (0 * inf) -> 0
-            u = u < (double)(NB - 1) ? u : (double)(NB - 1);
-            return (u32)u;
-        };
-        // ---- (1) histogram (rows that resemble a clipped one take their bracket first: see rank_bucket_kernel) ----
-        auto bracket_map = [&]() -> Rb3 {
-            const float2 wb = rb3_wave_bracket<E, NT>(tmn, tmx);
-            if (lane == 63) brk[wave] = wb;
-            __syncthreads();
-            return rb3_make<NB>(lo, hi, brk[lane & (NW - 1)], n);
-        };
-        if (heavy) {                                                  // block-uniform
-            m3 = bracket_map();
-            heavy = m3.clip;
-        }
-        u32 bs[E];
-        auto histogram = [&]() {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const double x = k[e];
-                u32 b = bucket_of(x);
-                b = (x == x) ? b : (u32)(NB + 2);
-                const u32 sh = (b & 1u) * 16u;
-                const u32 old = atomicAdd(&H[b >> 1], 1u << sh);
-                bs[e] = b | (((old >> sh) & 0xFFFFu) << 16);
-            }
-        };
-        histogram();
-        __syncthreads();                                              // barrier 2
-        // ---- (2) exclusive prefix sum ----
-        {
-            uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
-            uint4 hq[QW];
-            u32 runq[QW], inclq[QW], offq[QW];
-            auto prefix_a = [&]() {
-                u32 wsum = 0, ov = 0;
-#pragma unroll
-                for (int i = 0; i < QW; ++i) {
-                    hq[i] = Hq[i * 64 + lane];
-                    const u32 lo16 = (hq[i].x & 0xFFFFu) + (hq[i].y & 0xFFFFu) + (hq[i].z & 0xFFFFu) + (hq[i].w & 0xFFFFu);
-                    const u32 hi16 = (hq[i].x >> 16) + (hq[i].y >> 16) + (hq[i].z >> 16) + (hq[i].w >> 16);
-                    ov |= hq[i].x | hq[i].y | hq[i].z | hq[i].w;      // bit k of a half set <=> some counter has it
-                    runq[i] = lo16 + hi16;                            // counters reach n here: no packed addition
-                    inclq[i] = rb_wave_incl_scan(runq[i]);
-                    offq[i] = wsum;
-                    wsum += rb_readlane(inclq[i], 63);
-                }
-                const bool wtry = __ballot((ov & 0xFFE0FFE0u) != 0) != 0;   // some bucket of 32 keys or more
-                if (lane == 63) wtot[wave] = wsum | (wtry ? 0x40000000u : 0u);
-            };
-            prefix_a();
-            __syncthreads();                                          // barrier 3
-            u32 wt = wtot[lane & 15];
-            if (__ballot((wt & 0x40000000u) != 0) != 0 && !m3.clip) { // block-uniform, rare: ties -- or a range much wider than
-                m3 = bracket_map();                                   // the bulk (see rank_bucket_kernel): again under core + tails
-                if (m3.clip) {
-                    heavy = true;
-#pragma unroll
-                    for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-                    if (t < 4) H[NB / 2 + t] = 0;
-                    __syncthreads();
-                    histogram();
-                    __syncthreads();
-                    prefix_a();
-                    __syncthreads();
-                    wt = wtot[lane & 15];
-                }
-            }
-            const u32 wscan = rb_row_incl_scan(wt & 0x3FFFFFFFu);
-            const u32 woff = wave ? rb_readlane(wscan, wave - 1) : 0u;
-#pragma unroll
-            for (int i = 0; i < QW; ++i) {
-                u32 base = woff + offq[i] + inclq[i] - runq[i];
-                uint4 o;
-                o.x = base | ((base + (hq[i].x & 0xFFFFu)) << 16);
-                base += (hq[i].x & 0xFFFFu) + (hq[i].x >> 16);
-                o.y = base | ((base + (hq[i].y & 0xFFFFu)) << 16);
-                base += (hq[i].y & 0xFFFFu) + (hq[i].y >> 16);
-                o.z = base | ((base + (hq[i].z & 0xFFFFu)) << 16);
-                base += (hq[i].z & 0xFFFFu) + (hq[i].z >> 16);
-                o.w = base | ((base + (hq[i].w & 0xFFFFu)) << 16);
-                base += (hq[i].w & 0xFFFFu) + (hq[i].w >> 16);
-                Hq[i * 64 + lane] = o;
-                if (i == QW - 1 && t == NT - 1) H[NB / 2] = base;     // number of non-NaN keys
-            }
-        }
-        __syncthreads();                                              // barrier 4
-        // ---- (3) scatter ----
-        const u32 nv = H[NB / 2];
-        const u32 nn = (u32)n - nv;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const u32 b = bs[e] & 0xFFFFu, slot = bs[e] >> 16;
-            const u32 base = H16[b];
-            S[(b < (u32)NB) ? base + slot : (u32)DUMMY] = k[e];
-        }
-        if (rnext < rows) load_row(rnext);
-        __syncthreads();                                              // barrier 5
-        // ---- (4x) every external value against the members of its bucket ----
-#pragma unroll
-        for (int q = 0; q < EQ; ++q) {
-            const double x = xq[q];
-            if (x == x) {                                             // NaN target (and target slots beyond m): nothing
-                const u32 b = bucket_of(x);
-                const u32 base = H16[b], end = H16[b + 1];
-                u32 less = 0, le = 0;
-                // a value outside the set's range sits in an end bucket and still compares correctly
-#pragma unroll 1
-                for (u32 j = base; j < end; ++j) {
-                    const double y = S[j];
-                    less += (y < x) ? 1u : 0u;
-                    le += (y <= x) ? 1u : 0u;
-                }
-                band_counts_add<J>(nv - base - le, base + less, nn, (u64)n, acc[q]);
-            }
-        }
-        __syncthreads();                                              // barrier 6: S and the bases have been read
-        {
-            uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
-#pragma unroll
-            for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-        }
-    }
-    t = t0;
-    u64 *P = partial + (size_t)blockIdx.x * (J - 1) * m;
-#pragma unroll
-    for (int q = 0; q < EQ; ++q)
-        if (t + q * NT < m) {
-#pragma unroll
-            for (int j = 0; j < J - 1; ++j) P[(size_t)j * m + t + q * NT] = acc[q][j];
-        }
-}
-
-
-// ---------------------------------------------------------------------------------------------------
 // Z: out[q][j] (+)= sum_g partial[g][j][i(q)] + fold of the pair-image rows flagged in rowflag.
 // block = 32 targets x 32 slices (of workgroups g, of rows), LDS tree over the slices.  rowflag == nullptr: no pair image
 // (the bucket kernel ranks every row itself).
@@ -969,7 +717,7 @@ __global__ __launch_bounds__(1024) void rank_finalize_kernel(const u64 *__restri
             for (i64 r = y; r < rows; r += 32) {
                 if (rowflag[r]) {
                     const u32 ab = AB[r * n + i];
-                    if (ab != RB_AB_SPECIAL) band_counts_add<J>(ab >> 16, ab & 0xFFFFu, nnan[r], (u64)(n - 1), acc);
+                    if (ab != AB_SPECIAL) band_counts_add<J>(ab >> 16, ab & 0xFFFFu, nnan[r], (u64)(n - 1), acc);
                 }
             }
         }
@@ -1038,11 +786,7 @@ static int launch_bucket_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64 *pa
     }
     const size_t lds = C::lds_bytes((int)n);
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
-    SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kf, dim3(G), dim3(NT), lds, s, Y, n, row0, rows, partial, p32, nnan_img, (const unsigned char *)nullptr,
-                       (const u32 *)nullptr, 0u, (u64 *)nullptr, 0, (u32 *)nullptr, (u32 *)nullptr, 1);
-    SD_HIP(hipGetLastError());
-    return SD_OK;
+    return rb_launch(kf, G, NT, lds, s, Y, n, row0, rows, partial, p32, nnan_img, nullptr, nullptr, 0u, nullptr, 0, nullptr, nullptr, 1);
 }
 
 // second launch behind rank_bucket32_kernel: the rows it flagged, totals added to its partial blocks
@@ -1054,13 +798,13 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
     auto kf = rank_bucket_kernel<1024, E, LNB, 2, RB_CAP, 3, true, true>;
     const size_t lds = C::lds_bytes((int)n) + 8192;
     if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "bucket kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
-    SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // workgroups that may wait for the others at the end of the kernel: fewer than the launch's CUs hold at once
     int kspin = 1;
     {
         static int occ_cached = 0;                            // per instantiation (benign race: same value)
         int occ = occ_cached;
-        if (occ <= 0) {
+        if (occ <= 0) {                                       // (asked once, with the kernel's LDS limit raised as for the launch)
+            SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kf, 1024, lds) != hipSuccess || occ < 1) occ = 1;
             occ_cached = occ;
         }
@@ -1074,17 +818,9 @@ static int launch_bucket_sel_cfg(const double *Y, i64 n, i64 row0, i64 rows, u64
         if (masked) kspin = 1;
         if (kspin < 1) kspin = 1;
     }
-    hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, partial, RB_PARTIAL_ACC32, (u32 *)nullptr, rowflag, gate, epoch, out,
-                       Gsum, fblocks, done, kspin);
-    SD_HIP(hipGetLastError());
-    return SD_OK;
+    return rb_launch(kf, G, 1024, lds, s, Y, n, row0, rows, partial, RB_PARTIAL_ACC32, nullptr, rowflag, gate, epoch, out, Gsum, fblocks,
+                     done, kspin);
 }
-
-// log2 of the buckets for E = ceil(n / 1024) keys per thread, J = 2, 3 or 0 (the pair-image mode): 8192 buckets up to n = 4096,
-// 16384 above while keys + histogram fit the 160 KiB of LDS (8192 at E = 16), 32768 at E = 10, 11 for J = 2 and the pair-image
-// mode (measured: -2..-3.5 % on continuous rows, -7 % with outlying curves, +6 % on tie-heavy rows whose closed form only
-// pays the longer prefix sum; J = 3 stays at 16384: the wider prefix arrays push it further into scratch)
-constexpr int rb_lnb(int E, int J) { return (E <= 4 || E == 16) ? 13 : ((E == 10 || E == 11) && J != 3) ? 15 : 14; }
 
 // fold (J = 2, 3) and image mode (J = 0, partial = the image, nnan_img = its NaN counts); first member pass: 3 x 16 bytes
 template <int J>
@@ -1193,360 +929,6 @@ int launch_rank_finalize(const u64 *partial, int G, int p32, const u32 *AB, cons
         hipLaunchKernelGGL((rank_finalize_kernel<3>), grid, dim3(1024), 0, s, partial, G, p32, AB, nnan, rowflag, rows, n, targets,
                            tbegin, m, out, first);
     SD_HIP(hipGetLastError());
-    return SD_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// M: pair image of rows of 16 384 < n <= 40 960 curves (the "medium" sizes a 2- to 4-GPU time-sharded step sees:
-// n = N * 10^4) as 2 or 3 column blocks through ONE workgroup.  Ranks are additive over column blocks: per row each
-// block in turn is histogrammed, prefix-summed and scattered exactly as in rank_external_kernel, and EVERY key of the
-// row -- the block's own (still in registers) and the other blocks' (read again: the row sits in L2) -- looks up its
-// bucket there: B += base + #(y < x), A += n_valid - base - #(y <= x) (a key meets itself in its own block: `<=` keeps
-// it out of A, `<` out of B).  The running counts wait in the image itself (this thread's own words).  One build and
-// NBLK look-ups per key: about the bucket kernel's cost per key at two blocks, against three passes over global memory
-// on the large-n route.  Output as the bucket kernel's image mode (B | A << 16, 0xFFFFFFFF for NaN; counts < 2^16),
-// folded by the same rank_accumulate kernels.
-// ---------------------------------------------------------------------------------------------------
-template <int NT, int E, int LNB>
-__global__ __launch_bounds__(NT) void rank_medium_image_kernel(const double *__restrict__ Y, i64 n64, i64 row0, i64 rows, int nblk,
-                                                               u32 *__restrict__ AB, u32 *__restrict__ nnan_img) {
-    using C = RBCfg<NT, E, LNB, 3>;
-    constexpr int NB = C::NB, NW = C::NW, QW = C::QW;
-    extern __shared__ double Sm[];
-    const int n = (int)n64;
-    constexpr int BS = E * NT;                                        // block j: curves [j BS, min((j + 1) BS, n))
-    double *red = Sm;                                                 // [2][NW][2] min/max partials
-    u32 *wtot = reinterpret_cast<u32 *>(red + 4 * NW);                // [NW]
-    float2 *brk = reinterpret_cast<float2 *>(wtot + C::BRK_WORD);     // [NW] the waves' brackets
-    u32 *H = reinterpret_cast<u32 *>(Sm + C::HDR / 8);                // NB packed u16 counters, then bases
-    double *S = reinterpret_cast<double *>(H + NB / 2 + 4);           // keys in bucket order
-    const unsigned short *H16 = reinterpret_cast<const unsigned short *>(H);
-    const int t0 = threadIdx.x;
-    const double INF = __builtin_huge_val();
-    const double QNAN = __builtin_nan("");
-    const int DUMMY = C::dummy_pos(BS);
-    int t = t0;
-    {
-        uint4 *Hq = reinterpret_cast<uint4 *>(H);
-#pragma unroll
-        for (int i = 0; i < QW; ++i) Hq[i * NT + t] = make_uint4(0, 0, 0, 0);
-        if (t < 4) H[NB / 2 + t] = 0;
-    }
-    int par = 0;
-    bool heavy = false;                                               // block-uniform: the last block went under the three-piece map
-    for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
-        t = t0;
-        asm volatile("" : "+v"(t));                                   // per-row opaque thread id (see rank_bucket_kernel)
-        const int lane = t & 63;
-        const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-        const double *row = Y + (row0 + r) * n;
-        u32 *img = AB + r * n;                                        // B | A << 16 so far, per key
-        u32 nn_tot = 0;
-        for (int jb = 0; jb < nblk; ++jb) {
-            const int boff = jb * BS;
-            const int bsz = n - boff < BS ? n - boff : BS;
-            double kk[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) kk[e] = (t + e * NT < bsz) ? row[boff + t + e * NT] : QNAN;
-            // ---- (0) range of the block ----
-            double mn = INF, mx = -INF;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const double xf = (kk[e] == INF || kk[e] == -INF) ? QNAN : kk[e];   // infinities take the end buckets anyway
-                mn = rb_mm<false>(mn, xf);
-                mx = rb_mm<true>(mx, xf);
-            }
-            const double tmn = mn, tmx = mx;                          // this thread's own extremes (the bracket's groups)
-            mn = rb_wave_allreduce<false>(mn);
-            mx = rb_wave_allreduce<true>(mx);
-            double *redp = red + par * 2 * NW;
-            if (lane == 63) { redp[2 * wave] = mn; redp[2 * wave + 1] = mx; }
-            par ^= 1;
-            __syncthreads();                                          // barrier 1
-            double lo, hi;
-            Rb3 m3;
-            m3.clip = false;
-            {
-                const double2 p = reinterpret_cast<const double2 *>(redp)[lane & (NW - 1)];
-                lo = rb_readlane_f64(rb_row_allreduce<false>(p.x), 0);
-                hi = rb_readlane_f64(rb_row_allreduce<true>(p.y), 0);
-            }
-            const bool flat = hi == lo;                               // every finite key of the block holds one value
-            double scale = (double)NB / (hi - lo);
-            // equal values, an infinity in the range, a range too small or too large: everything into one bucket
-            if (!((hi > lo) && (scale < INF) && (lo > -INF) && (hi < INF))) scale = 0.0;
-            auto bucket_of = [&](double x) {
-                if (m3.clip) return rb3_bucket<NB>(m3, x);            // block-uniform
-                double u = (x - lo) * scale;
-                u = u > 0.0 ? u : 0.0;                                // below the range, and NaN (0 * inf) -> 0
-                u = u < (double)(NB - 1) ? u : (double)(NB - 1);
-                return (u32)u;
-            };
-            // ---- (1) histogram ----
-            u32 bs[E];
-            bool trypure = false;                                     // block-uniform
-            auto bracket_map = [&]() -> Rb3 {
-                const float2 wb = rb3_wave_bracket<E, NT>(tmn, tmx);
-                if (lane == 63) brk[wave] = wb;
-                __syncthreads();
-                return rb3_make<NB>(lo, hi, brk[lane & (NW - 1)], bsz);
-            };
-            if (heavy && !flat) {                                     // block-uniform: the last block went under core + tails
-                m3 = bracket_map();
-                heavy = m3.clip;
-            }
-            auto histogram = [&]() {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const double x = kk[e];
-                    u32 b = bucket_of(x);
-                    b = (x == x) ? b : (u32)(NB + 2);
-                    const u32 sh = (b & 1u) * 16u;
-                    const u32 old = atomicAdd(&H[b >> 1], 1u << sh);
-                    bs[e] = b | (((old >> sh) & 0xFFFFu) << 16);
-                }
-            };
-            histogram();
-            __syncthreads();                                          // barrier 2
-            // ---- (2) exclusive prefix sum ----
-            {
-                uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
-                uint4 hq[QW];
-                u32 runq[QW], inclq[QW], offq[QW];
-                auto prefix_a = [&]() {
-                    u32 wsum = 0, ov = 0;
-#pragma unroll
-                    for (int i = 0; i < QW; ++i) {
-                        hq[i] = Hq[i * 64 + lane];
-                        const u32 lo16 = (hq[i].x & 0xFFFFu) + (hq[i].y & 0xFFFFu) + (hq[i].z & 0xFFFFu) + (hq[i].w & 0xFFFFu);
-                        const u32 hi16 = (hq[i].x >> 16) + (hq[i].y >> 16) + (hq[i].z >> 16) + (hq[i].w >> 16);
-                        ov |= hq[i].x | hq[i].y | hq[i].z | hq[i].w;  // bit k of a half set <=> some counter has it
-                        runq[i] = lo16 + hi16;
-                        inclq[i] = rb_wave_incl_scan(runq[i]);
-                        offq[i] = wsum;
-                        wsum += rb_readlane(inclq[i], 63);
-                    }
-                    // a bucket of 16 keys or more is tie-heavy data more often than a dense cluster (see rank_bucket_kernel)
-                    const bool wtry = __ballot((ov & 0xFFF0FFF0u) != 0) != 0;
-                    if (lane == 63) wtot[wave] = wsum | (wtry ? 0x40000000u : 0u);
-                };
-                prefix_a();
-                __syncthreads();                                      // barrier 3
-                u32 wt = wtot[lane & 15];
-                trypure = __ballot((wt & 0x40000000u) != 0) != 0;
-                if (trypure && !flat && !m3.clip) {                   // block-uniform, rare: ties -- or a range much wider than
-                    m3 = bracket_map();                               // the bulk (see rank_bucket_kernel): again under core + tails
-                    if (m3.clip) {
-                        heavy = true;
-#pragma unroll
-                        for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-                        if (t < 4) H[NB / 2 + t] = 0;
-                        __syncthreads();
-                        histogram();
-                        __syncthreads();
-                        prefix_a();
-                        __syncthreads();
-                        wt = wtot[lane & 15];
-                        trypure = __ballot((wt & 0x40000000u) != 0) != 0;
-                    }
-                }
-                const u32 wscan = rb_row_incl_scan(wt & 0x3FFFFFFFu);
-                const u32 woff = wave ? rb_readlane(wscan, wave - 1) : 0u;
-#pragma unroll
-                for (int i = 0; i < QW; ++i) {
-                    u32 base = woff + offq[i] + inclq[i] - runq[i];
-                    uint4 o;
-                    o.x = base | ((base + (hq[i].x & 0xFFFFu)) << 16);
-                    base += (hq[i].x & 0xFFFFu) + (hq[i].x >> 16);
-                    o.y = base | ((base + (hq[i].y & 0xFFFFu)) << 16);
-                    base += (hq[i].y & 0xFFFFu) + (hq[i].y >> 16);
-                    o.z = base | ((base + (hq[i].z & 0xFFFFu)) << 16);
-                    base += (hq[i].z & 0xFFFFu) + (hq[i].z >> 16);
-                    o.w = base | ((base + (hq[i].w & 0xFFFFu)) << 16);
-                    base += (hq[i].w & 0xFFFFu) + (hq[i].w >> 16);
-                    Hq[i * 64 + lane] = o;
-                    if (i == QW - 1 && t == NT - 1) H[NB / 2] = base; // number of non-NaN keys of the block
-                }
-            }
-            __syncthreads();                                          // barrier 4
-            // ---- (3) scatter ----
-            const u32 nv = H[NB / 2];
-            nn_tot += (u32)bsz - nv;                                  // pad slots beyond the block are NaN too: not in bsz
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const u32 b = bs[e] & 0xFFFFu, slot = bs[e] >> 16;
-                const u32 base = H16[b];
-                S[(b < (u32)NB) ? base + slot : (u32)DUMMY] = kk[e];
-            }
-            // Tie-heavy rows (values on a grid, duplicated curves): if every bucket of the block holds ONE value -- every key
-            // equals its bucket's first -- a look-up is a compare with that value, not a walk over hundreds of members
-            bool allpure = false;                                     // block-uniform
-            if (trypure && !flat) {
-                __syncthreads();
-                bool pure = true;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const u32 b = bs[e] & 0xFFFFu;
-                    if (b < (u32)NB) pure = pure && (S[H16[b]] == kk[e]);
-                }
-                allpure = __syncthreads_and(pure) != 0;
-            }
-            u32 flat_lo = 0, flat_hi = 0;                             // a flat block's -inf / +inf keys
-            if (flat) {
-                u32 ml = 0, mh = 0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) { ml += kk[e] == -INF; mh += kk[e] == INF; }
-                for (int k2 = 0; k2 < E; ++k2) {                      // block-wide sums, one count at a time (rare path)
-                    flat_lo += __syncthreads_count(k2 < (int)ml);
-                    flat_hi += __syncthreads_count(k2 < (int)mh);
-                }
-            }
-            __syncthreads();                                          // barrier 5
-            // ---- (4) every key of the row against the members of its bucket in this block ----
-            // (a six-key window read ahead of the compares, as in rank_bucket_kernel, was measured here and changed nothing
-            // at E = 10 and cost 15 % at E = 15: the look-ups are not what this kernel waits for -- its global loads are)
-            auto lookup = [&](double x) -> u32 {
-                if (flat) {                                           // block-uniform: one bucket of equal keys (and infinities)
-                    const u32 neq = nv - flat_lo - flat_hi;
-                    const u32 less = (x > -INF ? flat_lo : 0u) + (x > lo ? neq : 0u);
-                    const u32 le = flat_lo + (x >= lo ? neq : 0u) + (x >= INF ? flat_hi : 0u);
-                    return (x == x) ? (less | ((nv - le) << 16)) : 0u;
-                }
-                u32 c = 0;
-                if (x == x) {
-                    const u32 b = bucket_of(x);
-                    const u32 base = H16[b], end = H16[b + 1];
-                    u32 less = 0, le = 0;
-                    if (allpure) {                                    // block-uniform: one value per bucket
-                        const double y = S[base < end ? base : 0u];
-                        less = (base < end && y < x) ? end - base : 0u;
-                        le = (base < end && y <= x) ? end - base : 0u;
-                    } else
-#pragma unroll 1
-                    for (u32 j = base; j < end; ++j) {
-                        const double y = S[j];
-                        less += (y < x) ? 1u : 0u;
-                        le += (y <= x) ? 1u : 0u;
-                    }
-                    c = (base + less) | ((nv - base - le) << 16);
-                }
-                return c;
-            };
-            const bool first = jb == 0, last = jb == nblk - 1;
-            for (int ib = 0; ib < nblk; ++ib) {                       // block-uniform
-                const int ioff = ib * BS;
-                const int isz = n - ioff < BS ? n - ioff : BS;
-                // the other block's keys and the running counts first, all in flight together (one at a time they cost a
-                // trip to L2 per key: 48 us per row of 20 000 instead of 30), then the look-ups, then the stores
-                double xk[E];
-                u32 cw[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const bool in = t + e * NT < isz;
-                    xk[e] = ib == jb ? kk[e] : (in ? row[ioff + t + e * NT] : QNAN);
-                    cw[e] = (!first && in) ? img[ioff + t + e * NT] : 0u;
-                }
-#pragma unroll
-                for (int e = 0; e < E; ++e) cw[e] += lookup(xk[e]);
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (t + e * NT < isz) img[ioff + t + e * NT] = (last && !(xk[e] == xk[e])) ? RB_AB_SPECIAL : cw[e];
-            }
-            __syncthreads();                                          // barrier 6: S and the bases have been read
-            {
-                uint4 *Hq = reinterpret_cast<uint4 *>(H) + wave * (64 * QW);
-#pragma unroll
-                for (int i = 0; i < QW; ++i) Hq[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-            }
-        }
-        if (t == 0) nnan_img[r] = nn_tot;
-    }
-}
-
-// medium sizes: pair image through 2 or 3 column blocks of at most 16 384 curves per workgroup (10^7 keys, host call
-// included: n = 20 000: 0.159 ms against 0.223 on the large-n route; 30 000: 0.208 / 0.228; 40 000: 0.228 / 0.239;
-// 60 000 as four blocks: 0.355 / 0.243 -- not taken)
-bool rank_medium_supported(i64 n) { return n > 16384 && n <= RB_MEDIUM_MAXN; }
-int launch_rank_medium_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s) {
-    if (!rank_medium_supported(n)) return fail(SD_ERR_UNSUPPORTED, "medium image kernel covers 16384 < n <= %d", RB_MEDIUM_MAXN);
-    const int cus = device_cus();
-    const int G = (int)(rows < cus ? rows : cus);
-    const int nblk = (int)((n + 16383) / 16384);                                     // fewest blocks ...
-    const int E = (int)((n + (i64)nblk * 1024 - 1) / ((i64)nblk * 1024));             // ... of equal size, whole thousands
-#define RB_MD(E_, L_)                                                                                               \
-    case E_: {                                                                                                       \
-        using C = RBCfg<1024, E_, L_, 3>;                                                                            \
-        const size_t lds = C::lds_bytes(E_ * 1024);                                                                  \
-        auto kf = rank_medium_image_kernel<1024, E_, L_>;                                                            \
-        SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-        hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, row0, rows, nblk, AB, nnan);                       \
-    } break;
-    switch (E) {
-        RB_MD(9, 14) RB_MD(10, 14) RB_MD(11, 14) RB_MD(12, 14) RB_MD(13, 14) RB_MD(14, 14) RB_MD(15, 14) RB_MD(16, 13)
-        default: return fail(SD_ERR_UNSUPPORTED, "medium image kernel: no instantiation for n=%lld", (long long)n);
-    }
-#undef RB_MD
-    SD_HIP(hipGetLastError());
-    return SD_OK;
-}
-
-// ---- external targets through the bucket structure ----
-bool mbd_rank_external_supported(i64 T, i64 n, i64 m, int J) {
-    (void)T;
-    return n >= 2 && n <= 16384 && J >= 2 && J <= 3 && m >= 1;
-}
-
-size_t mbd_rank_external_workspace_bytes(i64 T, i64 n, i64 m, int J) {
-    if (!mbd_rank_external_supported(T, n, m, J)) return 0;
-    const i64 mc = m < 8192 ? m : 8192;
-    return align_up((size_t)device_cus() * (J - 1) * mc * 8, 256) + 512;
-}
-
-template <int E, int LNB, int J>
-static int launch_external_cfg(const double *Y, i64 n, i64 rows, const double *Q, i64 m, i64 qstride, u64 *partial, int G,
-                               hipStream_t s) {
-    using C = RBCfg<1024, E, LNB, 3>;
-    const size_t lds = C::lds_bytes((int)n);
-    if (lds > 163840) return fail(SD_ERR_UNSUPPORTED, "external kernel: %zu bytes of LDS for n=%lld", lds, (long long)n);
-#define RB_XL(EQ_)                                                                                                  \
-    {                                                                                                                \
-        auto kf = rank_external_kernel<1024, E, LNB, J, EQ_>;                                                        \
-        SD_HIP(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-        hipLaunchKernelGGL(kf, dim3(G), dim3(1024), lds, s, Y, n, rows, Q, m, qstride, partial);                              \
-    }
-    if (m <= 1024) RB_XL(1) else if (m <= 2048) RB_XL(2) else if (m <= 4096) RB_XL(4) else RB_XL(8)
-#undef RB_XL
-    SD_HIP(hipGetLastError());
-    return SD_OK;
-}
-
-// Q: T x m time-major; out[q][j] = totals.  Targets go in groups of 8 192 (8 per thread).
-int launch_mbd_external_rank(const double *Y, i64 T, i64 n, const double *Q, i64 m, int J, u64 *out, void *ws,
-                             size_t ws_bytes, hipStream_t s) {
-    if (!mbd_rank_external_supported(T, n, m, J)) return fail(SD_ERR_UNSUPPORTED, "external rank kernel: unsupported shape");
-    if (!ws || ws_bytes < mbd_rank_external_workspace_bytes(T, n, m, J))
-        return fail(SD_ERR_WORKSPACE, "external rank workspace too small");
-    u64 *partial = (u64 *)(((size_t)ws + 255) / 256 * 256);
-    const int cus = device_cus();
-    const int G = (int)(T < cus ? T : cus);
-    const int E = (int)((n + 1023) / 1024);
-    for (i64 q0 = 0; q0 < m; q0 += 8192) {
-        const i64 mc = m - q0 < 8192 ? m - q0 : 8192;
-        int rc = SD_OK;
-#define RB_XE(E_, L_) case E_: rc = (J == 2) ? launch_external_cfg<E_, L_, 2>(Y, n, T, Q + q0, mc, m, partial, G, s) \
-                                             : launch_external_cfg<E_, L_, 3>(Y, n, T, Q + q0, mc, m, partial, G, s); break;
-        switch (E) {
-            RB_XE(1, 13) RB_XE(2, 13) RB_XE(3, 13) RB_XE(4, 13) RB_XE(5, 14) RB_XE(6, 14) RB_XE(7, 14) RB_XE(8, 14)
-            RB_XE(9, 14) RB_XE(10, 14) RB_XE(11, 14) RB_XE(12, 14) RB_XE(13, 14) RB_XE(14, 14) RB_XE(15, 14) RB_XE(16, 13)
-            default: return fail(SD_ERR_UNSUPPORTED, "external rank kernel covers n <= 16384");
-        }
-#undef RB_XE
-        if (rc) return rc;
-        if ((rc = launch_rank_finalize(partial, G, 0, nullptr, nullptr, nullptr, T, mc, nullptr, 0, mc, J,
-                                       out + q0 * (J - 1), 1, s)))
-            return rc;
-    }
     return SD_OK;
 }
 

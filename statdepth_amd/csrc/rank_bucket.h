@@ -1,4 +1,5 @@
-// rank_bucket.h -- wave64 cross-lane helpers shared by the bucket-ranking kernels (mbd_rank_bucket.hip, mbd_rank_big.hip).
+// rank_bucket.h -- wave64 cross-lane helpers shared by the bucket-ranking kernels (mbd_rank_bucket*.hip,
+// mbd_rank_external.hip, mbd_rank_medium.hip through rank_bucket_row.h; mbd_rank_big.hip), and the three-piece bucket map.
 #pragma once
 #include "sd_common.h"
 

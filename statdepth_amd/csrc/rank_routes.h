@@ -39,7 +39,7 @@ size_t mbd_rank_routes_workspace_bytes(i64 T, i64 n, int J);
 int launch_mbd_rank(const MbdPlan &plan, const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out,
                     void *ws, hipStream_t s);
 
-// ---- mbd_rank_bucket.hip: the bucket kernel of n <= 16 384 and its column-block form up to 40 960 ----
+// ---- mbd_rank_bucket.hip: the bucket kernel of n <= 16 384 ----
 // the kernel's `p32` argument: how a workgroup's partial totals travel (J = 2 only above 0)
 enum : int {
     RB_PARTIAL_U64 = 0,    // u64 blocks
@@ -57,6 +57,9 @@ int launch_rank_gather_totals(const u64 *all, const i64 *targets, i64 tbegin, i6
 int launch_rank_finalize(const u64 *partial, int G, int p32, const u32 *AB, const u32 *nnan, const unsigned char *rowflag,
                          i64 rows, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out, int first,
                          hipStream_t s);
+
+// ---- mbd_rank_medium.hip: the bucket structure over 2 or 3 column blocks, 16 384 < n <= 40 960 (the external targets'
+// kernel, mbd_rank_external.hip, shares its row build -- rank_bucket_row.h; its entry points: sd_common.h) ----
 bool rank_medium_supported(i64 n);
 int launch_rank_medium_image(const double *Y, i64 n, i64 row0, i64 rows, u32 *AB, u32 *nnan, hipStream_t s);
 

@@ -314,7 +314,9 @@ def test_committed_profiles_are_of_the_shipped_kernels():
     assert "rank_bucket32_kernel" in names, "the committed headline profile is not of the two-launch path"
     t_prof = last_commit_time([newest])
     t_kern = last_commit_time(["statdepth_amd/csrc/mbd_rank_bucket32.hip", "statdepth_amd/csrc/mbd_rank_bucket.hip",
-                               "statdepth_amd/csrc/rank_bucket.h"])
+                               "statdepth_amd/csrc/rank_bucket.h", "statdepth_amd/csrc/rank_bucket_row.h",
+                               "statdepth_amd/csrc/rank_sort.h", "statdepth_amd/csrc/rank_routes.h",
+                               "statdepth_amd/csrc/sd_common.h"])
     if t_prof is None:
         pytest.skip("profile not committed yet")
     assert t_prof >= t_kern, f"{newest} predates the last change of the kernels it measures: run tools/collect_profiles.py"

@@ -12,6 +12,8 @@ MOVED_TO_XONLY, and then they must be in one of the new tree's XONLY translation
 whose argument list this change rewrites has another symbol in the new tree: those named in NEW_ARGUMENTS are paired by their
 demangled name without the arguments, and must keep the PINNED fields of the resource block and of the code object's metadata
 (registers, scratch, LDS, wavefront and workgroup set-up); their SGPR and instruction counts are reported, not judged.  A
+kernel whose body this change rewrites keeps its symbol: for those named in REWRITTEN no numeric PINNED field may be larger
+than the parent's (smaller is fine); their SGPR and instruction counts are reported, not judged.  A
 kernel that the change adds to the product is expected only when it is named in NEW_KERNELS; any other new symbol is a
 mismatch.  Needs hipcc only, no GPU.  Exit status 0: all of that holds.
 """
@@ -26,6 +28,7 @@ import tempfile
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
 NEW_ARGUMENTS = ()             # short names of kernels whose argument list this change rewrites
 NEW_KERNELS = ()               # short names of kernels this change adds to the product
+REWRITTEN = ("rank_external_kernel", "rank_medium_image_kernel")   # short names of kernels whose body this change rewrites
 PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
                     r"wavefront|workgroup|workitem")
 
@@ -132,7 +135,7 @@ def main():
                 where.setdefault(tag, {})[sym] = fn
         old, new = asm.get("parent", {}), asm.get("new", {})
         xonly_names = {demangle(s) for s in asm.get("xonly", {})}
-        same = moved = 0
+        same = moved = rewritten = 0
         renamed = {demangle(s): s for s in set(new) - set(old) if short_name(demangle(s)) in NEW_ARGUMENTS}
         for sym in sorted(old):
             name = demangle(sym)
@@ -155,6 +158,21 @@ def main():
                 report.append(f"{where['parent'][sym]}: {name}: left the product, " +
                               ("present in an XONLY unit: allowed" if allowed else "NOT ALLOWED"))
                 continue
+            if short_name(name) in REWRITTEN:
+                num = lambda res: {ln.split()[0]: int(ln.split()[-1]) for ln in res
+                                   if PINNED.search(ln) and ln.split()[-1].isdigit()}
+                was, now = num(old[sym][1]), num(new[sym][1])
+                grown = sorted(k for k in was.keys() | now.keys() if now.get(k, 0) > was.get(k, 0))
+                changed = sorted(k for k in was.keys() | now.keys() if now.get(k) != was.get(k))
+                sg = lambda res: next((ln.split()[-1] for ln in res if ln.startswith(".meta.sgpr_count")), "?")
+                rewritten += 1
+                report.append(f"{where['new'][sym]}: {name}: rewritten, pinned fields " +
+                              ("LARGER" if grown else "smaller" if changed else "same") +
+                              f"; SGPRs {sg(old[sym][1])} -> {sg(new[sym][1])}, instructions {len(old[sym][0])} -> "
+                              f"{len(new[sym][0])}")
+                report.extend(f"    {k} {was.get(k)}  ->  {now.get(k)}" for k in changed)
+                ok &= not grown
+                continue
             code = old[sym][0] == new[sym][0]
             resources = old[sym][1] == new[sym][1]
             if code and resources:
@@ -174,7 +192,7 @@ def main():
         insts = sum(len(old[s][0]) for s in old if s in new)
         report.append(f"{len(units['parent'])} product files in the parent, {len(units['new'])} in the new tree")
         report.append(f"{len(old)} kernels in the parent, {len(new)} in the new tree, {same} identical (instruction stream, "
-                      f"{insts} lines, and .amdhsa_ block), {moved} of them in another file")
+                      f"{insts} lines, and .amdhsa_ block), {moved} of them in another file, {rewritten} rewritten")
     report.append("RESULT: " + ("product kernels unchanged" if ok else "MISMATCH"))
     text = "\n".join(report) + "\n"
     sys.stdout.write(text)
