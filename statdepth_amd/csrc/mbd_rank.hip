@@ -26,7 +26,7 @@
 // Replaces the same reference loops as mbd_pairwise.hip (_functional.py:246-251,
 // _containment.py:75-77); results are bit-identical to it and to the oracle.
 #include "sd_common.h"
-#include "rank_routes.h"
+#include "rank_fold.h"
 
 namespace sd {
 
@@ -238,15 +238,7 @@ __global__ __launch_bounds__(1024) void rank_reduce_kernel(const u64 *__restrict
         u64 s = 0;
         if (q < m)
             for (int g = y; g < G; g += 16) s += partial[((size_t)g * jc + j) * n + i];
-        red[y][x] = s;
-        __syncthreads();
-        if (y == 0 && q < m) {
-            u64 tot = 0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) tot += red[k][x];
-            out[q * jc + j] = tot;
-        }
-        __syncthreads();
+        fold_store(red, x, y, s, q < m, out + q * jc + j, 1);
     }
 }
 

@@ -1,5 +1,4 @@
-// mbd_rank_ab.hip -- K1+K2 rank formulation: the route plan (mbd_plan) and the launcher of the rank path, and the kernels
-// that fold a pair image.
+// mbd_rank_ab.hip -- K1+K2 rank formulation: the route plan (mbd_plan) and the launcher of the rank path.
 //
 // Same integers as the pairwise kernel and the reference's enumeration (_functional.py:246-251,
 // _containment.py:75-77): per (curve, timepoint) the counts B (others strictly below) and A (strictly above), and
@@ -7,8 +6,8 @@
 //
 // The rows are ranked by rank_bucket_kernel (mbd_rank_bucket.hip): J <= 3 folds in registers,
 // J >= 4 writes the pairs (B, A) of every (row, curve) as a uint16 pair image and
-//  C  rank_accumulate_kernel / rank_accumulate4_kernel -- fold the pairs and the per-row NaN counts into the int64
-//     totals of the requested targets.
+//  C  fold_pair_image (mbd_rank_fold.hip: rank_accumulate_kernel / rank_accumulate4_kernel) folds the pairs and the
+//     per-row NaN counts into the int64 totals of the requested targets.
 // The sort-based predecessors the bucket kernel replaced live in mbd_rank_ab_retired.hip and mbd_rank.hip (cross-check
 // library only) and are reached through retired_rank_sorts / retired_rank_v1 (rank_routes.h) when SD_RANK_IMPL asks.
 
@@ -16,116 +15,6 @@
 #include "rank_routes.h"
 
 namespace sd {
-
-// ---------------------------------------------------------------------------------------------------
-// C: out[q][j] += sum over the batch's rows of the band counts of target q.
-// block = 64 targets x 16 row slices, LDS tree over the slices.
-// ---------------------------------------------------------------------------------------------------
-template <int J>
-__global__ __launch_bounds__(1024) void rank_accumulate_kernel(const u32 *__restrict__ AB, const u32 *__restrict__ nnan,
-                                                               i64 rows, i64 n, const i64 *__restrict__ targets,
-                                                               i64 tbegin, i64 m, u64 *__restrict__ out, int first) {
-    __shared__ u64 red[16][64];
-    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
-    const i64 q = (i64)blockIdx.x * 64 + x;
-    const i64 i = (q < m) ? (targets ? targets[q] : tbegin + q) : 0;
-    u64 acc[JMAX - 1];
-#pragma unroll
-    for (int j = 0; j < JMAX - 1; ++j) acc[j] = 0;
-    if (q < m) {
-        // 8 independent loads in flight per thread: this kernel is a pure stream over the pair image
-        i64 r = y;
-        for (; r + 16 * 7 < rows; r += 16 * 8) {
-            u32 ab[8], nn[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                ab[u] = AB[(r + 16 * u) * n + i];
-                nn[u] = nnan[r + 16 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (ab[u] != AB_SPECIAL) band_counts_add<J>(ab[u] >> 16, ab[u] & 0xFFFFu, nn[u], (u64)(n - 1), acc);
-        }
-        for (; r < rows; r += 16) {
-            const u32 ab = AB[r * n + i];
-            if (ab != AB_SPECIAL) band_counts_add<J>(ab >> 16, ab & 0xFFFFu, nnan[r], (u64)(n - 1), acc);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < J - 1; ++j) {
-        red[y][x] = acc[j];
-        __syncthreads();
-        if (y == 0 && q < m) {
-            u64 tot = 0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) tot += red[k][x];
-            if (first) out[q * (J - 1) + j] = tot;
-            else out[q * (J - 1) + j] += tot;
-        }
-        __syncthreads();
-    }
-}
-
-// Same fold for a contiguous, 4-aligned target block: 16-byte loads (4 curves per lane, 1 KiB per wave
-// instruction instead of 256 B).  block = 16 curve quads x 64 row slices.
-template <int J>
-__global__ __launch_bounds__(1024) void rank_accumulate4_kernel(const u32 *__restrict__ AB, const u32 *__restrict__ nnan,
-                                                                i64 rows, i64 n, i64 tbegin, i64 m,
-                                                                u64 *__restrict__ out, int first) {
-    __shared__ u64 red[64][65];
-    const int x = threadIdx.x & 15, y = threadIdx.x >> 4;            // quad within block, row slice
-    const i64 q4 = ((i64)blockIdx.x * 16 + x) * 4;                   // first of this thread's 4 targets
-    const bool live = q4 < m;
-    u64 acc[4][JMAX - 1];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < JMAX - 1; ++j) acc[c][j] = 0;
-    if (live) {
-        const u32 *src = AB + tbegin + q4;
-        i64 r = y;
-        for (; r + 64 * 3 < rows; r += 64 * 4) {
-            uint4 v[4];
-            u32 nn[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                v[u] = *reinterpret_cast<const uint4 *>(src + (r + 64 * u) * n);
-                nn[u] = nnan[r + 64 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const u32 ab[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (ab[c] != AB_SPECIAL) band_counts_add<J>(ab[c] >> 16, ab[c] & 0xFFFFu, nn[u], (u64)(n - 1), acc[c]);
-            }
-        }
-        for (; r < rows; r += 64) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(src + r * n);
-            const u32 nn = nnan[r];
-            const u32 ab[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (ab[c] != AB_SPECIAL) band_counts_add<J>(ab[c] >> 16, ab[c] & 0xFFFFu, nn, (u64)(n - 1), acc[c]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < J - 1; ++j) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) red[y][x * 4 + c] = acc[c][j];
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const i64 q = (i64)blockIdx.x * 64 + threadIdx.x;
-            if (q < m) {
-                u64 tot = 0;
-                for (int k = 0; k < 64; ++k) tot += red[k][threadIdx.x];
-                if (first) out[q * (J - 1) + j] = tot;
-                else out[q * (J - 1) + j] += tot;
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // the route plan (rank_routes.h): which route takes a shape, its batches and its workspace
@@ -198,21 +87,6 @@ MbdPlan mbd_plan(i64 T, i64 n, i64 m, int J, int algo, bool all_targets) {
 size_t mbd_rank_routes_workspace_bytes(i64 T, i64 n, int J) {
     const MbdPlan p = mbd_plan(T, n, n, J, SD_MBD_RANK, true);
     return p.ws_bytes + (p.route == MbdRoute::MediumImage ? mbd_rank_big_workspace_bytes(T, n, J) : 0);
-}
-
-// out (=|+=, first) the band counts of the targets over the rows of one pair image
-static int fold_pair_image(const u32 *AB, const u32 *nnan, i64 rows, i64 n, const i64 *targets, i64 tbegin, i64 m, int J,
-                           u64 *out, int first, hipStream_t s) {
-    dim3 grid((unsigned)((m + 63) / 64));
-    if (!targets && (n % 4) == 0 && (tbegin % 4) == 0 && (m % 4) == 0 && J <= 3) {
-        SD_DISPATCH_J(J, hipLaunchKernelGGL((rank_accumulate4_kernel<J_>), grid, dim3(1024), 0, s, AB, nnan, rows, n, tbegin, m,
-                                            out, first));
-    } else {
-        SD_DISPATCH_J(J, hipLaunchKernelGGL((rank_accumulate_kernel<J_>), grid, dim3(1024), 0, s, AB, nnan, rows, n, targets,
-                                            tbegin, m, out, first));
-    }
-    SD_HIP(hipGetLastError());
-    return SD_OK;
 }
 
 int launch_mbd_rank(const MbdPlan &plan, const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out,

@@ -3,7 +3,7 @@
 //
 // Same integers as the other K1+K2 kernels (reference loops _functional.py:246-251, _containment.py:75-77).
 // Per row the ranks B (others strictly below) and A (strictly above) of every curve are written as a pair image
-// (AB2, rank_big_common.h); rank_accumulate2_kernel and its wide forms fold C(v,j) - C(A,j) - C(B,j) over the rows.
+// (AB2, rank_big_common.h); fold_ab2_image (mbd_rank_fold.hip) folds C(v,j) - C(A,j) - C(B,j) over the rows.
 //
 // A row is sample-partitioned into value buckets, so that no rank needs another bucket's keys.  Four launches per batch:
 //   S3 bucket_setup_kernel      one workgroup per row sorts a strided sample in LDS (rank_sort.h) and publishes, per row:
@@ -676,238 +676,6 @@ __global__ __launch_bounds__(BIG_NT) void big_fallback_kernel(const double *__re
 }
 
 // =====================================================================================================
-// fold the pair image into the totals of the targets: block = 64 targets x 16 row slices
-// =====================================================================================================
-template <int J>
-__global__ __launch_bounds__(1024) void rank_accumulate2_kernel(AB2 ab, const u32 *__restrict__ nnan,
-                                                                i64 rows, i64 n, const i64 *__restrict__ targets,
-                                                                i64 tbegin, i64 m, u64 *__restrict__ out, int first) {
-    __shared__ u64 red[16][64];
-    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
-    const i64 q = (i64)blockIdx.x * 64 + x;
-    const i64 i = (q < m) ? (targets ? targets[q] : tbegin + q) : 0;
-    u64 acc[JMAX - 1];
-#pragma unroll
-    for (int j = 0; j < JMAX - 1; ++j) acc[j] = 0;
-    if (q < m) {
-        i64 r = y;
-        auto fold = [&](u32 w, u32 nn, i64 row) {
-            if (w == AB2_NAN) return;
-            const u32 B = w & ~AB2_TIE;
-            if (J == 2 && nn == 0 && !(w & AB2_TIE)) {                // untied key of a NaN-free row: contained = A * B
-                acc[0] += (u64)B * (u64)((u32)n - 1u - B);
-                return;
-            }
-            const u32 A = (w & AB2_TIE) ? ab.A[row * n + i] : (u32)n - nn - 1u - B;     // tied keys carry their A
-            band_counts_add<J>(A, B, nn, (u64)(n - 1), acc);
-        };
-        // the word of (row, curve): from the half-word image where there is one (min(A, B) of an untied key stands for B:
-        // the counts are symmetric in A and B), else / on its marker from the B image
-        auto word = [&](i64 row) -> u32 {
-            if (ab.H) {
-                const u32 h = ab.H[row * n + i];
-                if (h != (u32)AB2_H_WORD) return h;
-            }
-            return ab.B[row * n + i];
-        };
-        for (; r + 16 * 7 < rows; r += 16 * 8) {
-            u32 w[8], nn[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                w[u] = word(r + 16 * u);
-                nn[u] = nnan[r + 16 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) fold(w[u], nn[u], r + 16 * u);
-        }
-        for (; r < rows; r += 16) fold(word(r), nnan[r], r);
-    }
-#pragma unroll
-    for (int j = 0; j < J - 1; ++j) {
-        red[y][x] = acc[j];
-        __syncthreads();
-        if (y == 0 && q < m) {
-            u64 tot = 0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) tot += red[k][x];
-            if (first) out[q * (J - 1) + j] = tot;
-            else out[q * (J - 1) + j] += tot;
-        }
-        __syncthreads();
-    }
-}
-
-// The same fold for a contiguous, 4-aligned block of targets (the usual call: every curve): a thread takes FOUR neighbouring
-// curves through 16-byte loads, so half a wave reads 512 bytes of a row instead of 128.  block = 32 quads x 16 row slices;
-// needs n % 4 == 0 and tbegin % 4 == 0 (the image rows stay 16-byte aligned).  J <= 3 (accumulators in registers).
-template <int J>
-__global__ __launch_bounds__(512) void rank_accumulate2x4_kernel(AB2 ab, const u32 *__restrict__ nnan, i64 rows, i64 n,
-                                                                  i64 tbegin, i64 m, u64 *__restrict__ out, int first) {
-    __shared__ u64 red[16][32];
-    const int x = threadIdx.x & 31, y = threadIdx.x >> 5;
-    const i64 q0 = ((i64)blockIdx.x * 32 + x) * 4;                    // first of this thread's four targets
-    const i64 i0 = tbegin + q0;
-    u64 acc[4][JMAX - 1];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int j = 0; j < JMAX - 1; ++j) acc[c][j] = 0;
-    if (q0 < m) {
-        auto fold4 = [&](const uint4 w, u32 nn, i64 row) {
-            const u32 ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (ww[c] == AB2_NAN) continue;
-                const u32 B = ww[c] & ~AB2_TIE;
-                if (J == 2 && nn == 0 && !(ww[c] & AB2_TIE)) {
-                    // untied key of a NaN-free row: A + B = n - 1, and C(A+B, 2) - C(A, 2) - C(B, 2) = A * B
-                    acc[c][0] += (u64)B * (u64)((u32)n - 1u - B);
-                    continue;
-                }
-                const u32 A = (ww[c] & AB2_TIE) ? ab.A[row * n + i0 + c] : (u32)n - nn - 1u - B;
-                band_counts_add<J>(A, B, nn, (u64)(n - 1), acc[c]);
-            }
-        };
-        const uint4 *img = reinterpret_cast<const uint4 *>(ab.B);
-        const uint2 *himg = reinterpret_cast<const uint2 *>(ab.H);
-        // four half words (8-byte loads) where there is a half-word image; a marker sends that curve to the B image
-        auto words = [&](i64 row) -> uint4 {
-            if (!himg) return img[(row * n + i0) >> 2];
-            const uint2 h = himg[(row * n + i0) >> 2];
-            uint4 w = make_uint4(h.x & 0xFFFFu, h.x >> 16, h.y & 0xFFFFu, h.y >> 16);
-            if (w.x == (u32)AB2_H_WORD) w.x = ab.B[row * n + i0];
-            if (w.y == (u32)AB2_H_WORD) w.y = ab.B[row * n + i0 + 1];
-            if (w.z == (u32)AB2_H_WORD) w.z = ab.B[row * n + i0 + 2];
-            if (w.w == (u32)AB2_H_WORD) w.w = ab.B[row * n + i0 + 3];
-            return w;
-        };
-        i64 r = y;
-        for (; r + 16 * 3 < rows; r += 16 * 4) {
-            uint4 w[4];
-            u32 nn[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                w[u] = words(r + 16 * u);
-                nn[u] = nnan[r + 16 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) fold4(w[u], nn[u], r + 16 * u);
-        }
-        for (; r < rows; r += 16) fold4(words(r), nnan[r], r);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int j = 0; j < J - 1; ++j) {
-            red[y][x] = acc[c][j];
-            __syncthreads();
-            if (y == 0 && q0 + c < m) {
-                u64 tot = 0;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) tot += red[k][x];
-                if (first) out[(q0 + c) * (J - 1) + j] = tot;
-                else out[(q0 + c) * (J - 1) + j] += tot;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// The fold over the HALF-WORD image for a contiguous, 8-aligned block of targets: a thread takes EIGHT neighbouring curves
-// through 16-byte loads (16 lanes read 256 bytes of a row); block = 16 octets x 32 row slices.  A marker among the eight (NaN
-// / tied key: rare) sends that load through the B words.  Needs n % 8 == 0 and tbegin % 8 == 0.  J <= 3.
-template <int J>
-__global__ __launch_bounds__(512) void rank_accumulate_h8_kernel(AB2 ab, const u32 *__restrict__ nnan, i64 rows, i64 n,
-                                                                 i64 tbegin, i64 m, u64 *__restrict__ out, int first) {
-    __shared__ u64 red[32][16][9];                                    // (+1: the row slices fall on different banks)
-    const int x = threadIdx.x & 15, y = threadIdx.x >> 4;
-    const i64 q0 = ((i64)blockIdx.x * 16 + x) * 8;                    // first of this thread's eight targets
-    const i64 i0 = tbegin + q0;
-    u64 acc[8][JMAX - 1];
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int j = 0; j < JMAX - 1; ++j) acc[c][j] = 0;
-    if (q0 < m) {
-        const uint4 *himg = reinterpret_cast<const uint4 *>(ab.H);
-        const u32 nm1 = (u32)n - 1u;
-        auto fold8 = [&](const uint4 v, u32 nn, i64 row) {
-            const u32 p[4] = {v.x, v.y, v.z, v.w};
-            u32 anym = 0;                                             // a half word 0xFFFF <=> a zero half word in ~p
-#pragma unroll
-            for (int k = 0; k < 4; ++k) anym |= ((~p[k]) - 0x00010001u) & p[k] & 0x80008000u;
-            if (J == 2 && nn == 0 && !anym) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const u32 h = (c & 1) ? (p[c >> 1] >> 16) : (p[c >> 1] & 0xFFFFu);
-                    acc[c][0] += (u64)h * (u64)(nm1 - h);              // untied key of a NaN-free row: A * B
-                }
-                return;
-            }
-            // markers: the eight B words, and the eight A words when one of them is tied, through 16-byte loads as well (a
-            // tie-heavy row is markers throughout)
-            u32 bw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, aw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (anym) {
-                const uint4 *bp = reinterpret_cast<const uint4 *>(ab.B + row * n + i0);
-                const uint4 b0 = bp[0], b1 = bp[1];
-                bw[0] = b0.x; bw[1] = b0.y; bw[2] = b0.z; bw[3] = b0.w; bw[4] = b1.x; bw[5] = b1.y; bw[6] = b1.z; bw[7] = b1.w;
-                u32 anyt = 0;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const u32 h = (c & 1) ? (p[c >> 1] >> 16) : (p[c >> 1] & 0xFFFFu);
-                    anyt |= (h == (u32)AB2_H_WORD && bw[c] != AB2_NAN) ? (bw[c] & AB2_TIE) : 0u;
-                }
-                if (anyt) {
-                    const uint4 *ap = reinterpret_cast<const uint4 *>(ab.A + row * n + i0);
-                    const uint4 a0 = ap[0], a1 = ap[1];
-                    aw[0] = a0.x; aw[1] = a0.y; aw[2] = a0.z; aw[3] = a0.w; aw[4] = a1.x; aw[5] = a1.y; aw[6] = a1.z; aw[7] = a1.w;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                u32 w = (c & 1) ? (p[c >> 1] >> 16) : (p[c >> 1] & 0xFFFFu);
-                if (w == (u32)AB2_H_WORD) w = bw[c];
-                if (w == AB2_NAN) continue;
-                const u32 B = w & ~AB2_TIE;
-                const u32 A = (w & AB2_TIE) ? aw[c] : (u32)n - nn - 1u - B;
-                band_counts_add<J>(A, B, nn, (u64)(n - 1), acc[c]);
-            }
-        };
-        i64 r = y;
-        for (; r + 32 * 3 < rows; r += 32 * 4) {
-            uint4 w[4];
-            u32 nn[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                w[u] = himg[((r + 32 * u) * n + i0) >> 3];
-                nn[u] = nnan[r + 32 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) fold8(w[u], nn[u], r + 32 * u);
-        }
-        for (; r < rows; r += 32) fold8(himg[(r * n + i0) >> 3], nnan[r], r);
-    }
-#pragma unroll
-    for (int j = 0; j < J - 1; ++j) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) red[y][x][c] = acc[c][j];
-        __syncthreads();
-        if (threadIdx.x < 128) {
-            const int xx = threadIdx.x >> 3, c = threadIdx.x & 7;
-            const i64 q = ((i64)blockIdx.x * 16 + xx) * 8 + c;
-            if (q < m) {
-                u64 tot = 0;
-#pragma unroll
-                for (int k = 0; k < 32; ++k) tot += red[k][xx][c];
-                if (first) out[q * (J - 1) + j] = tot;
-                else out[q * (J - 1) + j] += tot;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// =====================================================================================================
 // host side
 // =====================================================================================================
 static inline i64 big_nchunks(i64 n) { return (n + BIG_C - 1) / BIG_C; }
@@ -1065,15 +833,13 @@ static int big_run(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin
             if (rc) return rc;
         } else {
             // ---- S3 -> P3 -> A3 (tied rows: its fp64 form) -> the fall-backs behind their gate words ----
-            if (NB <= S3_SMALL_NB)
-                hipLaunchKernelGGL(k_s3_small, dim3((unsigned)rows), dim3(128), lds_sp_small, s, Y, n, row0, NB, b.spl, b.mk,
-                                   b.tab, b.rp, b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
-            else if (NB <= S3_MID_NB)
-                hipLaunchKernelGGL(k_s3, dim3((unsigned)rows), dim3(256), lds_sp, s, Y, n, row0, NB, b.spl, b.mk, b.tab, b.rp,
+            auto s3 = [&](auto kernel, int threads, size_t lds) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(threads), lds, s, Y, n, row0, NB, b.spl, b.mk, b.tab, b.rp,
                                    b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
-            else
-                hipLaunchKernelGGL(k_s3_big, dim3((unsigned)rows), dim3(1024), lds_sp_big, s, Y, n, row0, NB, b.spl, b.mk,
-                                   b.tab, b.rp, b.rowtied, b.bcnt, b.bflag, b.nnanrow, b.ovf, b.nanf, b.meet);
+            };
+            if (NB <= S3_SMALL_NB) s3(k_s3_small, 128, lds_sp_small);
+            else if (NB <= S3_MID_NB) s3(k_s3, 256, lds_sp);
+            else s3(k_s3_big, 1024, lds_sp_big);
             hipLaunchKernelGGL(bucket_partition3_kernel, dim3((unsigned)((n + P3_C - 1) / P3_C), (unsigned)rows), dim3(P3_NT),
                                lds_p3, s, Y, n, row0, NBT, (const double *)b.spl, (const double *)b.mk, (const u32 *)b.tab,
                                (const double2 *)b.rp, (const u32 *)b.rowtied, b.bcnt, b.nnanrow, b.ovf, (u64 *)b.bval, b.bidx,
@@ -1091,22 +857,8 @@ static int big_run(const double *Y, i64 T, i64 n, const i64 *targets, i64 tbegin
             SD_HIP(hipMemcpyAsync(nnan_out + row0, nn_for_fold, (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
             continue;
         }
-        const AB2 &ab = b.ab;
-        const int first = row0 == 0;
-        if (ab.H && !targets && (n & 7) == 0 && (tbegin & 7) == 0 && J <= 3) {
-            dim3 grid8((unsigned)((m + 127) / 128));
-            if (J == 2) hipLaunchKernelGGL((rank_accumulate_h8_kernel<2>), grid8, dim3(512), 0, s, ab, nn_for_fold, rows, n, tbegin, m, out, first);
-            else hipLaunchKernelGGL((rank_accumulate_h8_kernel<3>), grid8, dim3(512), 0, s, ab, nn_for_fold, rows, n, tbegin, m, out, first);
-        } else if (!targets && (n & 3) == 0 && (tbegin & 3) == 0 && J <= 3) {
-            dim3 grid4((unsigned)((m + 127) / 128));
-            if (J == 2) hipLaunchKernelGGL((rank_accumulate2x4_kernel<2>), grid4, dim3(512), 0, s, ab, nn_for_fold, rows, n, tbegin, m, out, first);
-            else hipLaunchKernelGGL((rank_accumulate2x4_kernel<3>), grid4, dim3(512), 0, s, ab, nn_for_fold, rows, n, tbegin, m, out, first);
-        } else {
-            dim3 grid((unsigned)((m + 63) / 64));
-            SD_DISPATCH_J(J, hipLaunchKernelGGL((rank_accumulate2_kernel<J_>), grid, dim3(1024), 0, s, ab,
-                                                nn_for_fold, rows, n, targets, tbegin, m, out, first));
-        }
-        SD_HIP(hipGetLastError());
+        const int rc = fold_ab2_image(b.ab, nn_for_fold, rows, n, targets, tbegin, m, J, out, row0 == 0, s);
+        if (rc) return rc;
     }
     return SD_OK;
 }

@@ -36,6 +36,7 @@
 #include "rank_routes.h"
 #include "rank_sort.h"
 #include "rank_bucket_row.h"
+#include "rank_fold.h"
 
 namespace sd {
 
@@ -715,26 +716,12 @@ __global__ __launch_bounds__(1024) void rank_finalize_kernel(const u64 *__restri
         }
         if (any) {
             for (i64 r = y; r < rows; r += 32) {
-                if (rowflag[r]) {
-                    const u32 ab = AB[r * n + i];
-                    if (ab != AB_SPECIAL) band_counts_add<J>(ab >> 16, ab & 0xFFFFu, nnan[r], (u64)(n - 1), acc);
-                }
+                if (rowflag[r]) fold_pair16<J>(AB[r * n + i], nnan[r], n, acc);
             }
         }
     }
 #pragma unroll
-    for (int j = 0; j < J - 1; ++j) {
-        red[y][x] = acc[j];
-        __syncthreads();
-        if (y == 0 && q < m) {
-            u64 tot = 0;
-#pragma unroll
-            for (int k = 0; k < 32; ++k) tot += red[k][x];
-            if (first) out[q * (J - 1) + j] = tot;
-            else out[q * (J - 1) + j] += tot;
-        }
-        __syncthreads();
-    }
+    for (int j = 0; j < J - 1; ++j) fold_store(red, x, y, acc[j], q < m, out + q * (J - 1) + j, first);
 }
 
 // Z for the common case (J = 2, u32 partial totals, a contiguous 4-aligned block of targets, no pair image): thread
@@ -754,19 +741,8 @@ __global__ __launch_bounds__(256) void rank_finalize4_kernel(const u32 *__restri
             a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
         }
     }
-    red[y][x][0] = a0; red[y][x][1] = a1; red[y][x][2] = a2; red[y][x][3] = a3;
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        const int xx = threadIdx.x >> 2, c = threadIdx.x & 3;
-        const i64 qq = ((i64)blockIdx.x * 8 + xx) * 4 + c;
-        if (qq < m) {
-            u64 tot = 0;
-#pragma unroll
-            for (int k = 0; k < 32; ++k) tot += red[k][xx][c];
-            if (first) out[qq] = tot;
-            else out[qq] += tot;
-        }
-    }
+    const u64 a[4] = {a0, a1, a2, a3};
+    fold_store_w<32, 8, 4, 5, 8 * 5>(&red[0][0][0], x, y, a, (i64)blockIdx.x * 32, m, out, 1, first);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@
 //   rank_depth_fold_kernel<u64> folds it.  kc follows from the workspace as in K10.
 //
 // rank_depth_fold_kernel: block = 64 targets x 16 row slices, 8 independent loads in flight per thread (a pure stream
-// over the image, as rank_accumulate_kernel), LDS tree over the slices.  The first batch writes out =, later batches
+// over the image: the row loop of rank_fold.h, as rank_accumulate_kernel), its own LDS tree over the slices.  The first batch writes out =, later batches
 // add to the four sums and take the maximum for MM.  A (target, slice) pair has one owner and the batches follow each
 // other on the stream: no atomics, and integer sums and maxima do not depend on the batch size.  40 KB of LDS.
 //
@@ -33,7 +33,7 @@
 // the plan of this stage -- rows per batch and the bytes carved for them, which the size functions and the launchers of
 // all three read -- are curve_route and pair_image_plan below (curve_routes.h).
 #include "curve_routes.h"
-#include "rank_routes.h"
+#include "rank_fold.h"
 #include "halfspace_sort.h"
 
 namespace sd {
@@ -76,17 +76,9 @@ __global__ __launch_bounds__(1024) void rank_depth_fold_kernel(const IMG *__rest
     u64 acc[RD_WORDS];
 #pragma unroll
     for (int w = 0; w < RD_WORDS; ++w) acc[w] = 0;
-    if (q < m) {
-        i64 r = y;
-        for (; r + 16 * 7 < rows; r += 16 * 8) {
-            IMG v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = img[(r + 16 * u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) rd_add<IMG>(acc, v[u], n);
-        }
-        for (; r < rows; r += 16) rd_add<IMG>(acc, img[r * n + i], n);
-    }
+    if (q < m)
+        fold_rows<16, 8>(
+            rows, y, [&](i64 r) { return img[r * n + i]; }, [&](IMG v, i64) { rd_add<IMG>(acc, v, n); });
 #pragma unroll
     for (int w = 0; w < RD_WORDS; ++w) red[w][y][x] = acc[w];
     __syncthreads();

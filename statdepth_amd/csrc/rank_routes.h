@@ -76,6 +76,14 @@ int launch_mbd_rank_big(const double *Y, i64 T, i64 n, const i64 *targets, i64 t
                         u64 *out, void *ws, size_t ws_bytes, hipStream_t s);
 int launch_rank_big_image(const double *Y, i64 T, i64 n, u32 *img, u32 *nnan, void *ws, size_t ws_bytes, hipStream_t s);
 
+// ---- mbd_rank_fold.hip: out (=|+=, first) the band counts of the targets over the rows of one pair image: the 16-bit image
+// B | A << 16 of the routes above, the AB2 image of the large-n route (rank_big_common.h; skeleton: rank_fold.h) ----
+struct AB2;
+int fold_pair_image(const u32 *AB, const u32 *nnan, i64 rows, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out,
+                    int first, hipStream_t s);
+int fold_ab2_image(const AB2 &ab, const u32 *nnan, i64 rows, i64 n, const i64 *targets, i64 tbegin, i64 m, int J, u64 *out,
+                   int first, hipStream_t s);
+
 // ---- the retired generations, one hook per point where a cross-check switch diverts a product route ----
 // libstatdepth_hip_xcheck.so: defined next to the retired kernels (mbd_rank_ab_retired.hip, mbd_rank.hip,
 // mbd_rank_big_retired.hip).  The product library: xcheck.hip defines them to fail with SD_ERR_UNSUPPORTED; nothing

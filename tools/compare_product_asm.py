@@ -12,8 +12,10 @@ MOVED_TO_XONLY, and then they must be in one of the new tree's XONLY translation
 whose argument list this change rewrites has another symbol in the new tree: those named in NEW_ARGUMENTS are paired by their
 demangled name without the arguments, and must keep the PINNED fields of the resource block and of the code object's metadata
 (registers, scratch, LDS, wavefront and workgroup set-up); their SGPR and instruction counts are reported, not judged.  A
-kernel whose body this change rewrites keeps its symbol: for those named in REWRITTEN no numeric PINNED field may be larger
-than the parent's (smaller is fine); their SGPR and instruction counts are reported, not judged.  A
+kernel whose body this change rewrites keeps its symbol: for those named in REWRITTEN the LDS (group_segment_fixed_size) must
+be equal, the scratch (private_segment_fixed_size) no larger, and the waves per SIMD that the VGPRs allow -- min(8, 512 /
+(next_free_vgpr rounded up to 8)) -- no fewer: registers inside one occupancy step cost nothing, scratch and occupancy do.
+Their VGPR, SGPR and instruction counts are reported, not judged.  A
 kernel that the change adds to the product is expected only when it is named in NEW_KERNELS; any other new symbol is a
 mismatch.  Needs hipcc only, no GPU.  Exit status 0: all of that holds.
 """
@@ -28,7 +30,9 @@ import tempfile
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
 NEW_ARGUMENTS = ()             # short names of kernels whose argument list this change rewrites
 NEW_KERNELS = ()               # short names of kernels this change adds to the product
-REWRITTEN = ("rank_external_kernel", "rank_medium_image_kernel")   # short names of kernels whose body this change rewrites
+# short names of kernels whose body this change rewrites
+REWRITTEN = ("rank_accumulate_kernel", "rank_accumulate4_kernel", "rank_accumulate2_kernel", "rank_accumulate2x4_kernel",
+             "rank_accumulate_h8_kernel", "rank_depth_fold_kernel", "rank_finalize_kernel", "rank_finalize4_kernel")
 PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
                     r"wavefront|workgroup|workitem")
 
@@ -159,19 +163,22 @@ def main():
                               ("present in an XONLY unit: allowed" if allowed else "NOT ALLOWED"))
                 continue
             if short_name(name) in REWRITTEN:
-                num = lambda res: {ln.split()[0]: int(ln.split()[-1]) for ln in res
-                                   if PINNED.search(ln) and ln.split()[-1].isdigit()}
-                was, now = num(old[sym][1]), num(new[sym][1])
-                grown = sorted(k for k in was.keys() | now.keys() if now.get(k, 0) > was.get(k, 0))
-                changed = sorted(k for k in was.keys() | now.keys() if now.get(k) != was.get(k))
+                def num(res, field):
+                    return next(int(ln.split()[-1]) for ln in res if ln.split()[0] == field)
+                def waves(res):                          # per SIMD, as the registers allow: VGPRs are allocated in blocks of 8 of 512
+                    return min(8, 512 // (-(-num(res, ".amdhsa_next_free_vgpr") // 8) * 8))
+                was, now = old[sym][1], new[sym][1]
+                lds = [num(r, ".amdhsa_group_segment_fixed_size") for r in (was, now)]
+                scratch = [num(r, ".amdhsa_private_segment_fixed_size") for r in (was, now)]
+                occ = [waves(r) for r in (was, now)]
+                vg = [num(r, ".amdhsa_next_free_vgpr") for r in (was, now)]
+                good = lds[0] == lds[1] and scratch[1] <= scratch[0] and occ[1] >= occ[0]
                 sg = lambda res: next((ln.split()[-1] for ln in res if ln.startswith(".meta.sgpr_count")), "?")
                 rewritten += 1
-                report.append(f"{where['new'][sym]}: {name}: rewritten, pinned fields " +
-                              ("LARGER" if grown else "smaller" if changed else "same") +
-                              f"; SGPRs {sg(old[sym][1])} -> {sg(new[sym][1])}, instructions {len(old[sym][0])} -> "
-                              f"{len(new[sym][0])}")
-                report.extend(f"    {k} {was.get(k)}  ->  {now.get(k)}" for k in changed)
-                ok &= not grown
+                report.append(f"{where['new'][sym]}: {name}: rewritten, {'ok' if good else 'WORSE'}; LDS {lds[0]} -> {lds[1]}, "
+                              f"scratch {scratch[0]} -> {scratch[1]}, waves per SIMD {occ[0]} -> {occ[1]}; VGPRs {vg[0]} -> "
+                              f"{vg[1]}, SGPRs {sg(was)} -> {sg(now)}, instructions {len(old[sym][0])} -> {len(new[sym][0])}")
+                ok &= good
                 continue
             code = old[sym][0] == new[sym][0]
             resources = old[sym][1] == new[sym][1]

@@ -26,8 +26,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from statdepth_amd import engine  # noqa: E402
+from statdepth_amd import engine, _native  # noqa: E402
 from statdepth_amd._native import check  # noqa: E402
+if os.environ.get("SD_LIB"):                     # experiments: another build of the library (this tool only; the cross-check
+    _native.LIB_PATH = os.path.abspath(os.environ["SD_LIB"])      # build too, which the package itself refuses to load)
+    _native._LIB = _native.open_library(_native.LIB_PATH)
 from statdepth_amd.depth.calculations._pointcloud import _halfspace_directions  # noqa: E402
 
 # (case, entry point, n, T or k, algo)

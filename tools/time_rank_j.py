@@ -3,7 +3,10 @@ import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from statdepth_amd import engine
+from statdepth_amd import engine, _native
+if os.environ.get("SD_LIB"):                     # experiments: another build of the library (this tool only; the cross-check
+    _native.LIB_PATH = os.path.abspath(os.environ["SD_LIB"])      # build too, which the package itself refuses to load)
+    _native._LIB = _native.open_library(_native.LIB_PATH)
 n, T, J = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 X = np.random.default_rng(1234).normal(size=(T, n)).cumsum(axis=0)
 Xd = engine.to_device_matrix(X)
