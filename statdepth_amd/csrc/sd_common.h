@@ -103,6 +103,11 @@ int launch_multi_simplex(const double *P, i64 n, i64 T, int d, const i64 *target
                          double tol, i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws = nullptr, size_t ws_bytes = 0);
 // records of the sampled estimators' shared factorisation (a batch of (timepoint, sample) pairs)
 size_t simplex_sampled_workspace_bytes(i64 n, i64 T, int d, i64 samples);
+// SD_SIMPLEX_GENERIC = 1: one launch of the per-target route, targets [q0, q0 + grid.y), on the retired generic kernel.  A
+// hook like those of rank_routes.h: defined next to the kernel in simplex_retired.hip (cross-check library only); in the
+// product xcheck.hip defines it to fail with SD_ERR_UNSUPPORTED, and nothing calls it there.
+int retired_simplex_generic(const double *P, i64 n, i64 T, int d, const PointSel &sel, int relax, double tol, u64 total,
+                            u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *out, dim3 grid, hipStream_t s);
 
 // K6 componentwise band containment of multivariate curves (band_enum.hip)
 bool multi_band_supported(i64 n, i64 T, int d);

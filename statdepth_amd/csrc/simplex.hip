@@ -15,268 +15,15 @@
 // enumeration (unrank once, then step), or one sampled subset each in the sampled
 // estimators.  Small dense fp64 systems per thread: VALU bound, no MFMA (systems are
 // (d+1)x(d+1) with d <= 8 and data-dependent pivoting).
+//
+// The device code below the register-resident forms -- point_in_hull, the enumeration, the sampling -- is in simplex_hull.h,
+// shared with the generic scratch-memory generation (simplex_retired.hip, cross-check library only).  Which kernels a call
+// runs is stated once, at SxwPlan.
 #include <stdlib.h>
 
-#include "sd_common.h"
-#include "point_select.h"
+#include "simplex_hull.h"
 
 namespace sd {
-
-constexpr int SMAX = 10;   // d + 1 <= 9
-constexpr int SX_THREADS = 256;
-
-__device__ static bool solve_subset(const double (*R)[SMAX + 1], int rank, const int *cols, double tol,
-                                    double rank_eps) {
-    double A[SMAX][SMAX + 1];
-    for (int r = 0; r < rank; ++r) {
-        for (int c = 0; c < rank; ++c) A[r][c] = R[r][cols[c]];
-        A[r][rank] = R[r][SMAX];
-    }
-    for (int c = 0; c < rank; ++c) {
-        int p = c;
-        double best = fabs(A[c][c]);
-        for (int r = c + 1; r < rank; ++r)
-            if (fabs(A[r][c]) > best) { best = fabs(A[r][c]); p = r; }
-        if (best <= rank_eps) return false;
-        if (p != c)
-            for (int k = 0; k <= rank; ++k) { double tmp = A[c][k]; A[c][k] = A[p][k]; A[p][k] = tmp; }
-        for (int r = c + 1; r < rank; ++r) {
-            double f = A[r][c] / A[c][c];
-            for (int k = c; k <= rank; ++k) A[r][k] -= f * A[c][k];
-        }
-    }
-    double l[SMAX];
-    for (int c = rank - 1; c >= 0; --c) {
-        double s = A[c][rank];
-        for (int k = c + 1; k < rank; ++k) s -= A[c][k] * l[k];
-        l[c] = s / A[c][c];
-    }
-    for (int c = 0; c < rank; ++c)
-        if (!(l[c] >= -tol)) return false;
-    return true;
-}
-
-// The system every site eliminates is NORMALISED: after the NaN / infinity checks the members and x are
-// centred on the first member, and the coordinate rows, right-hand side included, are multiplied by 2^-e, e = ilogb of the
-// largest centred |entry| of the MEMBERS (of x where they all coincide).  Both steps are exact for data that the subtraction
-// does not round, so the decision is the same bit for bit under P -> 2^k P and under exact translations, and rank_eps and the
-// consistency threshold are relative to the simplex's own extent.  An infinity that the subtraction or the scaling makes:
-// outside.  The same statements, in the same order, as oracle_point_in_hull.
-__device__ __forceinline__ bool sx_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for a NaN
-
-// pts: kpts x d (row-major, local), x: d
-__device__ static bool point_in_hull(const double *pts, int kpts, int d, const double *x, double tol) {
-    int rows = d + 1;
-    for (int c = 0; c < kpts * d; ++c)
-        if (!sx_finite(pts[c])) return false;
-    for (int r = 0; r < d; ++r)
-        if (!sx_finite(x[r])) return false;
-    double R[SMAX][SMAX + 1];
-    double m = 0.0, mx = 0.0;                                    // the largest centred |entry| of the members, of x
-    for (int r = 0; r < d; ++r) {
-        for (int c = 0; c < kpts; ++c) {
-            double v = pts[c * d + r] - pts[r];
-            R[r][c] = v;
-            if (fabs(v) > m) m = fabs(v);
-        }
-        double v = x[r] - pts[r];
-        R[r][SMAX] = v;
-        if (fabs(v) > mx) mx = fabs(v);
-    }
-    if (isinf(m) || isinf(mx)) return false;                     // the subtraction overflowed
-    int e = m > 0.0 ? ilogb(m) : mx > 0.0 ? ilogb(mx) : 0;
-    double scale = 1.0;
-    for (int r = 0; r < d; ++r) {
-        for (int c = 0; c < kpts; ++c) {
-            R[r][c] = ldexp(R[r][c], -e);
-            if (fabs(R[r][c]) > scale) scale = fabs(R[r][c]);
-        }
-        R[r][SMAX] = ldexp(R[r][SMAX], -e);
-        if (fabs(R[r][SMAX]) > scale) scale = fabs(R[r][SMAX]);
-    }
-    for (int c = 0; c < kpts; ++c) R[d][c] = 1.0;
-    R[d][SMAX] = 1.0;
-    if (isinf(scale)) return false;                              // x that many extents away
-    double rank_eps = 1e-10 * scale;
-    int rank = 0;
-    int lim = rows < kpts ? rows : kpts;
-    for (; rank < lim; ++rank) {
-        int pr = -1, pc = -1;
-        double best = rank_eps;
-        for (int r = rank; r < rows; ++r)
-            for (int c = rank; c < kpts; ++c)
-                if (fabs(R[r][c]) > best) { best = fabs(R[r][c]); pr = r; pc = c; }
-        if (pr < 0) break;
-        if (pr != rank)
-            for (int k = 0; k <= SMAX; ++k) { double tmp = R[rank][k]; R[rank][k] = R[pr][k]; R[pr][k] = tmp; }
-        if (pc != rank)
-            for (int r = 0; r < rows; ++r) { double tmp = R[r][rank]; R[r][rank] = R[r][pc]; R[r][pc] = tmp; }
-        for (int r = rank + 1; r < rows; ++r) {
-            double f = R[r][rank] / R[rank][rank];
-            if (f != 0.0) {
-                for (int c = rank; c < kpts; ++c) R[r][c] -= f * R[rank][c];
-                R[r][SMAX] -= f * R[rank][SMAX];
-            }
-        }
-    }
-    for (int r = rank; r < rows; ++r)
-        if (fabs(R[r][SMAX]) > 1e-7 * scale) return false;
-    int cols[SMAX];
-    for (int c = 0; c < rank; ++c) cols[c] = c;
-    if (rank == kpts) return solve_subset(R, rank, cols, tol, rank_eps);
-    for (;;) {
-        if (solve_subset(R, rank, cols, tol, rank_eps)) return true;
-        int k = rank - 1;
-        while (k >= 0 && cols[k] == kpts - rank + k) --k;
-        if (k < 0) break;
-        ++cols[k];
-        for (int l = k + 1; l < rank; ++l) cols[l] = cols[l - 1] + 1;
-    }
-    return false;
-}
-
-__device__ static u64 binom_dev(u64 a, int k) {
-    if (k < 0 || (u64)k > a) return 0;
-    u64 c = 1;
-    for (int j = 1; j <= k; ++j) c = c * (a - (u64)j + 1) / (u64)j;
-    return c;
-}
-
-// lexicographic unranking of the r-th k-subset of {0..no-1}
-__device__ static void unrank_comb(u64 r, int k, i64 no, i64 *idx) {
-    i64 c = 0;
-    for (int p = 0; p < k; ++p) {
-        for (;; ++c) {
-            u64 cnt = binom_dev((u64)(no - 1 - c), k - 1 - p);   // subsets starting with c at position p
-            if (r < cnt) break;
-            r -= cnt;
-        }
-        idx[p] = c++;
-    }
-}
-
-__device__ static bool next_comb(i64 *idx, int k, i64 no) {
-    int i = k - 1;
-    while (i >= 0 && idx[i] == no - k + i) --i;
-    if (i < 0) return false;
-    ++idx[i];
-    for (int l = i + 1; l < k; ++l) idx[l] = idx[l - 1] + 1;
-    return true;
-}
-
-// splitmix64 finaliser: counter-based draws keyed by (seed, target, sample, draw)
-__device__ __host__ static inline u64 mix64(u64 z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// The sampled estimators' subsets (round 4): shared sample s is ONE (d+1)-subset of all n rows for every target -- k distinct rows
-// drawn with the counter generator keyed by (seed, s): index = floor(r * n / 2^64), rejection on duplicates, sorted ascending -- so
-// that its factorisation can be shared by all targets (sxw_factor_kernel / sxw_apply_kernel).  A target uses the FIRST `samples`
-// shared subsets that do not contain it (s = 0, 1, 2, ... in order): each is uniform over the subsets of the other rows.
-// Restated identically in oracle.c (sample_rows / oracle_simplex_sampled).
-constexpr u64 SX_SHARED_KEY = 0xFFFFFFFFFFFFFFFFull;
-__device__ static void sample_rows(u64 seed, u64 keyv, u64 sample, int k, i64 n, i64 *idx) {
-    u64 key = mix64(seed ^ mix64(keyv * 0xD1342543DE82EF95ull + sample));
-    u64 ctr = 0;
-    for (int p = 0; p < k;) {
-        u64 r = mix64(key + ctr++);
-        // index in [0, n) as the high half of r * n (a 64 x 64 -> 128 bit product: a handful of instructions; the 64-bit
-        // modulo it replaces was ~480 of the 715 lane-instructions of a sampled 4-point test, profiles/r02_issue_roofline.json)
-        i64 c = (i64)__umul64hi(r, (u64)n);
-        bool dup = false;
-        for (int l = 0; l < p; ++l) dup |= (idx[l] == c);
-        if (!dup) idx[p++] = c;
-    }
-    for (int a = 1; a < k; ++a) {   // insertion sort
-        i64 v = idx[a];
-        int b = a - 1;
-        while (b >= 0 && idx[b] > v) { idx[b + 1] = idx[b]; --b; }
-        idx[b + 1] = v;
-    }
-}
-// the next shared subset from index *s on that does not contain row tg; *s is left behind it
-__device__ static void sample_next_valid(u64 seed, i64 tg, u64 *s, int k, i64 n, i64 *idx) {
-    for (;;) {
-        sample_rows(seed, SX_SHARED_KEY, (*s)++, k, n, idx);
-        bool member = false;
-        for (int l = 0; l < k; ++l) member |= idx[l] == tg;
-        if (!member) return;
-    }
-}
-
-__device__ __forceinline__ u64 block_sum_u64(u64 v, u64 *scratch) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = 0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < SX_THREADS / 64; ++k) r += scratch[k];
-    return r;
-}
-
-// The targets are selected by a PointSel (point_select.h); the subsets are drawn from a target's others.  The external
-// and the block form are for point clouds only (T = 0); a block is enumerated exhaustively whatever `total` says.
-__device__ __forceinline__ u64 sx_total(const PointView &v, int k, u64 total) {
-    return v.mem ? binom_dev((u64)v.others(), k) : total;
-}
-
-// row of P behind index i of a subset.  direct (sx_direct, taken once per thread): i is a row already
-__device__ __forceinline__ bool sx_direct(const PointView &v, i64 samples) {
-    return samples >= 0 || v.tg < 0;                             // a sampled subset holds rows, never the target's; no row to skip
-}
-__device__ __forceinline__ i64 sx_src(const PointView &v, bool direct, i64 i) {
-    if (v.mem) return v.mem[i];
-    if (direct) return i;
-    return i < v.tg ? i : i + 1;                                 // skip the target itself
-}
-
-// grid = (chunks, m).  T == 0 selects the pointcloud form (P is n x d);
-// otherwise P is n x T x d and c counts timepoints (relax / strict reduction).
-__global__ __launch_bounds__(SX_THREADS) void simplex_kernel(
-    const double *__restrict__ P, i64 n, i64 T, int d, PointSel sel, int relax, double tol,
-    u64 total, u64 per_thread, i64 samples, u64 seed, i64 q0, u64 *__restrict__ out) {
-    __shared__ u64 scratch[SX_THREADS / 64];
-    i64 q = q0 + blockIdx.y;
-    int k = d + 1;
-    const PointView blk = point_view(sel, P, n, d, q);
-    const i64 tg = blk.tg, no = blk.others();
-    const bool direct = sx_direct(blk, samples);
-    total = sx_total(blk, k, total);
-    u64 tid = (u64)blockIdx.x * SX_THREADS + threadIdx.x;
-    u64 first = tid * per_thread;
-    u64 acc = 0;
-    if (first < total) {
-        u64 last = first + per_thread < total ? first + per_thread : total;
-        i64 idx[SMAX];
-        double pts[SMAX * 8], x[8];
-        if (samples < 0) unrank_comb(first, k, no, idx);
-        u64 snext = 0;                                                  // sampled: the shared index behind the last subset taken
-        if (samples >= 0)
-            for (u64 r = 0; r < first; ++r) sample_next_valid(seed, tg, &snext, k, n, idx);   // this thread's first valid subset
-        i64 TT = T > 0 ? T : 1;
-        for (u64 r = first; r < last; ++r) {
-            if (samples >= 0) sample_next_valid(seed, tg, &snext, k, n, idx);
-            u64 cnt = 0;
-            for (i64 t = 0; t < TT; ++t) {
-                for (int c = 0; c < k; ++c) {
-                    i64 src = sx_src(blk, direct, idx[c]);
-                    const double *pp = P + (src * TT + t) * d;
-                    for (int e = 0; e < d; ++e) pts[c * d + e] = pp[e];
-                }
-                const double *xx = T > 0 ? P + (tg * TT + t) * d : blk.x;  // curves (rows form only): the target at timepoint t
-                for (int e = 0; e < d; ++e) x[e] = xx[e];
-                cnt += point_in_hull(pts, k, d, x, tol);
-            }
-            acc += (T > 0 && !relax) ? (cnt / (u64)TT) : cnt;
-            if (samples < 0 && r + 1 < last) next_comb(idx, k, no);
-        }
-    }
-    u64 tot = block_sum_u64(acc, scratch);
-    if (threadIdx.x == 0 && tot) atomicAdd(&out[q], tot);
-}
 
 // The loaders of the register-resident forms.  sx_members: columns 0 .. D of R from the members row(0) .. row(D), centred on
 // row(0) (kept in p0) and scaled by 2^-e; `scale` = the scaled member maximum, in [1, 2), or 1 where all members coincide
@@ -434,7 +181,7 @@ __device__ __forceinline__ int hull_full_rank(double (&R)[D + 1][D + 2], double 
     return in ? 1 : 0;
 }
 
-// grid = (chunks, m), the work decomposition of simplex_kernel; D = d known at compile time.
+// grid = (chunks, m), the work decomposition of the generic kernel (simplex_retired.hip); D = d known at compile time.
 template <int D>
 __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
     const double *__restrict__ P, i64 n, i64 T, PointSel sel, int relax, double tol,
@@ -505,17 +252,9 @@ __global__ __launch_bounds__(SX_THREADS) void simplex_kernel_fast(
 // or an infinity, or exchanges rows in the second elimination, take the per-target code (point_in_hull), decision for decision
 // the old kernel's.  A target that is a MEMBER of the subset skips it and takes a spare shared subset instead (the first
 // `samples` shared subsets that do not contain it: sxw_members_kernel counts what it skips, sxw_spare_kernel makes it up).
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double scw_u(double v) {                    // a wave-uniform double into SGPRs
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)b), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Two kernels over a caller's workspace (sd_simplex_sampled_workspace_bytes): the records go to HBM, a thread per (timepoint,
-// sample) with the whole register file for its elimination, and the replay reads a record as one coalesced load per wave.
-// Batches of pairs as large as the workspace holds.  Without a workspace the per-target kernels run (same subsets).
+// Two kernels over a caller's workspace (SxwPlan): the records go to HBM, a thread per (timepoint, sample) with the whole
+// register file for its elimination, and the replay reads a record as one coalesced load per wave, in batches of pairs as
+// large as the workspace holds.
 // ---------------------------------------------------------------------------------------------------
 // the per-target code for a target the shared replay cannot serve (see above): out of line, so that its scratch arrays and
 // registers are not the replay loop's
@@ -865,34 +604,62 @@ __global__ __launch_bounds__(256) void sxw_spare_kernel(const double *__restrict
     if (acc) atomicAdd(&out[q], acc);
 }
 
-template <int D>
-static size_t sxw_pair_bytes() { return SxwCfg<D>::REC + (size_t)(D + 1) * D * 8; }
-size_t simplex_sampled_workspace_bytes(i64 n, i64 T, int d, i64 samples) {
-    if (d < 1 || d > 8 || samples <= 0) return 0;
+// ---------------------------------------------------------------------------------------------------
+// The routes of a call, and the workspace of the one that needs it.
+//   per target  simplex_kernel_fast<D>, a thread per range of subsets: every exhaustive call, and the sampled ones that the
+//               replay does not serve -- external targets, blocks, relax = False, n < d + 3, or a workspace below the floor
+//               (none: ws null).  Same subsets as the replay, so the counts are the same.
+//   replay      sampled, targets of the set, counts that add over the timepoints (point clouds, relax = True), n >= d + 3
+//               and ws_bytes >= floor: sxw_members_kernel, per batch of pairs sxw_factor_kernel + sxw_apply_kernel,
+//               sxw_spare_kernel.
+//   Cross-check library only: SD_SIMPLEX_PERTARGET = 1 keeps a call off the replay, SD_SIMPLEX_GENERIC = 1 runs the per-target
+//   route on the retired generic kernel (retired_simplex_generic).
+// The workspace behind its base rounded up to ALIGN: the member counts (an int per row), then a batch's records (recd,
+// reci) and first-elimination multipliers (m1g), `per` bytes a pair.  The recommended size holds every pair of the call up
+// to MAX_BATCH (~1.7 GB at d = 8); the floor is that of FLOOR_SAMPLES samples, a few hundred records.
+// ---------------------------------------------------------------------------------------------------
+struct SxwPlan {
+    static constexpr size_t ALIGN = 256, CARVE_SLACK = 768, SIZE_SLACK = 1024;   // set aside by the carve (the base's rounding); by the sizes
+    static constexpr i64 MAX_BATCH = (i64)1 << 20, FLOOR_SAMPLES = 256;
+    size_t per, cm_bytes;                                               // bytes per pair; of the member counts
+    size_t bytes, floor;                                                // recommended; the least the replay is taken with
+    i64 pairs, batch;                                                   // (timepoint, sample) pairs of the call; per round, 0: below the floor
+    size_t cmem, recd, m1g, reci;                                       // offsets behind the rounded base, for `batch` pairs
+};
+// ws_bytes: what is at hand (0: the sizes alone).  d outside [1, 8] or samples <= 0: all zero
+static SxwPlan sxw_plan(i64 n, i64 T, int d, i64 samples, size_t ws_bytes) {
+    SxwPlan p = {};
+    if (d < 1 || d > 8 || samples <= 0) return p;
+    size_t dw = 0;                                                      // bytes of a record's doubles
+    SD_DISPATCH_D(d, p.per = SxwCfg<D_>::REC + (size_t)(D_ + 1) * D_ * 8; dw = (size_t)SxwCfg<D_>::DW * 8)
     const i64 TT = T > 0 ? T : 1;
-    size_t per = 0;
-    SD_DISPATCH_D(d, per = sxw_pair_bytes<D_>())
-    i64 pairs = samples * TT;
-    if (pairs > ((i64)1 << 20)) pairs = (i64)1 << 20;                   // batches of up to 2^20 pairs: at most ~1.7 GB at d = 8
-    return (size_t)pairs * per + align_up((size_t)n * 4, 256) + 1024;
+    p.pairs = samples * TT;
+    p.cm_bytes = align_up((size_t)n * 4, SxwPlan::ALIGN);
+    auto size_of = [&](i64 pairs) {
+        return (size_t)(pairs < SxwPlan::MAX_BATCH ? pairs : SxwPlan::MAX_BATCH) * p.per + p.cm_bytes + SxwPlan::SIZE_SLACK;
+    };
+    p.bytes = size_of(p.pairs);
+    p.floor = size_of((samples < SxwPlan::FLOOR_SAMPLES ? samples : SxwPlan::FLOOR_SAMPLES) * TT);
+    if (ws_bytes < p.floor) return p;
+    p.batch = (i64)((ws_bytes - SxwPlan::CARVE_SLACK - p.cm_bytes) / p.per);
+    if (p.batch > p.pairs) p.batch = p.pairs;
+    p.recd = p.cmem + p.cm_bytes;
+    p.m1g = p.recd + (size_t)p.batch * dw;
+    p.reci = p.m1g + (size_t)p.batch * (size_t)((d + 1) * d) * 8;
+    return p;
 }
+
+size_t simplex_sampled_workspace_bytes(i64 n, i64 T, int d, i64 samples) { return sxw_plan(n, T, d, samples, 0).bytes; }
 
 template <int D>
 static int launch_simplex_ws(const double *P, i64 n, i64 T, const i64 *targets, i64 m, double tol, i64 samples, u64 seed, u64 *out,
-                             void *ws, size_t ws_bytes, hipStream_t s) {
+                             const SxwPlan &plan, void *ws, hipStream_t s) {
     using C = SxwCfg<D>;
     const i64 TT = T > 0 ? T : 1;
-    const i64 pairs = samples * TT;
-    const size_t per = sxw_pair_bytes<D>();
-    const size_t cm_bytes = align_up((size_t)n * 4, 256);
-    if (ws_bytes < 768 + cm_bytes + (size_t)(pairs < 256 ? pairs : 256) * per) return fail(SD_ERR_WORKSPACE, "sampled simplex workspace too small");
-    i64 batch = (i64)((ws_bytes - 768 - cm_bytes) / per);
-    if (batch > pairs) batch = pairs;
-    char *w = (char *)(((size_t)ws + 255) / 256 * 256);
-    int *cmem = (int *)w;
-    double *recd = (double *)(w + cm_bytes);
-    double *m1g = recd + (size_t)batch * C::DW;
-    int *reci = (int *)(m1g + (size_t)batch * (C::K * (C::K - 1)));
+    const i64 pairs = plan.pairs, batch = plan.batch;               // batch >= 1: the caller asked
+    char *w = (char *)align_up((size_t)ws, SxwPlan::ALIGN);
+    int *cmem = (int *)(w + plan.cmem), *reci = (int *)(w + plan.reci);
+    double *recd = (double *)(w + plan.recd), *m1g = (double *)(w + plan.m1g);
     SD_HIP(hipMemsetAsync(cmem, 0, (size_t)n * 4, s));
     hipLaunchKernelGGL(sxw_members_kernel, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, s, n, samples, seed, C::K, cmem);
     const i64 tiles = (m + 256 * C::TPT - 1) / (256 * C::TPT);
@@ -913,17 +680,17 @@ static int launch_simplex_ws(const double *P, i64 n, i64 T, const i64 *targets, 
 
 static int launch_simplex_common(const double *P, i64 n, i64 T, int d, const PointSel &sel, i64 m, int relax,
                                  double tol, i64 samples, u64 seed, u64 *out, hipStream_t s, void *ws, size_t ws_bytes) {
+    if (d < 1 || d > 8) return fail(SD_ERR_UNSUPPORTED, "simplex containment covers d in [1,8], got %d", d);
     SD_HIP(hipMemsetAsync(out, 0, sizeof(u64) * m, s));
     u64 total;
     if (samples >= 0) total = (u64)samples;                      // else the subsets of the most others a target has
     else if (!binom_u64_checked((u64)sel_others_max(sel, n), d + 1, &total)) return fail(SD_ERR_OVERFLOW, "subset count overflow");
     if (total == 0) return SD_OK;
-    // sampled, targets of the set, counts that add over the timepoints (point clouds, relax=True): the shared factorisation
-    if (samples > 0 && !sel.members && !sel.Q && (T == 0 || relax) && d >= 1 && d <= 8 && n >= d + 3 && xswitch("SD_SIMPLEX_GENERIC") != 1 &&
-        xswitch("SD_SIMPLEX_PERTARGET") != 1) {
-        // with a workspace that holds at least a few hundred records: factor into HBM, replay from there (else the per-target kernels)
-        if (ws && ws_bytes >= simplex_sampled_workspace_bytes(n, T, d, 256 < samples ? 256 : samples)) {
-            SD_DISPATCH_D(d, return launch_simplex_ws<D_>(P, n, T, sel.targets, m, tol, samples, seed, out, ws, ws_bytes, s))
+    const bool generic = xswitch("SD_SIMPLEX_GENERIC") == 1;
+    if (samples > 0 && !sel.members && !sel.Q && (T == 0 || relax) && n >= d + 3 && !generic && xswitch("SD_SIMPLEX_PERTARGET") != 1) {
+        const SxwPlan plan = sxw_plan(n, T, d, samples, ws ? ws_bytes : 0);
+        if (plan.batch > 0) {
+            SD_DISPATCH_D(d, return launch_simplex_ws<D_>(P, n, T, sel.targets, m, tol, samples, seed, out, plan, ws, s))
         }
     }
     // aim for ~2^18 threads over all targets, at least 1 subset per thread
@@ -937,13 +704,12 @@ static int launch_simplex_common(const double *P, i64 n, i64 T, int d, const Poi
     for (i64 q0 = 0; q0 < m; q0 += 65535) {   // grid.y limit: fold large m into several launches
         i64 mm = m - q0 < 65535 ? m - q0 : 65535;
         dim3 grid((unsigned)blocks, (unsigned)mm);
-        // the generic (scratch-memory) kernel where the cross-check builds ask for it
-        if (d < 1 || d > 8 || xswitch("SD_SIMPLEX_GENERIC") == 1)
-            hipLaunchKernelGGL(simplex_kernel, grid, dim3(SX_THREADS), 0, s, P, n, T, d, sel, relax, tol, total, per_thread,
-                               samples, seed, q0, out);
-        else
+        if (generic) {
+            if (int rc = retired_simplex_generic(P, n, T, d, sel, relax, tol, total, per_thread, samples, seed, q0, out, grid, s)) return rc;
+        } else {
             SD_DISPATCH_D(d, hipLaunchKernelGGL((simplex_kernel_fast<D_>), grid, dim3(SX_THREADS), 0, s, P, n, T, sel, relax,
                                                 tol, total, per_thread, samples, seed, q0, out))
+        }
     }
     SD_HIP(hipGetLastError());
     return SD_OK;

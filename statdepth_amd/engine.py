@@ -192,11 +192,12 @@ _OUT = object()                                                      # the place
 def _launch(dev, fn, out, *args, workspace=None, return_tensor=False):
     """fn(*args, out, [ws, ws_bytes,] stream) on dev's current stream, out at the place of _OUT where args name one; returns
     out as an ndarray, or the tensor itself with return_tensor.  Nothing is launched when out has no rows.  workspace:
-    None, or a function of no arguments returning (buffer, bytes), asked for only when there is something to launch."""
+    None, or a function of no arguments returning (buffer, bytes), asked for only when there is something to launch; a buffer
+    of None is passed as a null pointer."""
     t = torch()
     if out.shape[0]:
         ws = workspace() if workspace is not None else None
-        tail = (ws[0].data_ptr(), ws[1]) if ws is not None else ()
+        tail = (ws[0].data_ptr() if ws[0] is not None else None, ws[1]) if ws is not None else ()
         head = args if any(a is _OUT for a in args) else (*args, _OUT)
         with t.cuda.device(dev):
             check(fn(*(out.data_ptr() if a is _OUT else a for a in head), *tail, _stream_ptr(dev)))
@@ -759,15 +760,24 @@ def l1_depth(P, targets=None, device=None):
     return _points("sd_l1_depth", torch().float64, P, device, _ROWS, targets)
 
 
-def pointcloud_simplex_counts(P, targets=None, tol=1e-7, samples=None, seed=0, device=None):
+def _simplex_sampled_ws(dev, n, T, d, samples, ws_bytes):
+    """(buffer, bytes) of the sampled estimators' workspace: what sd_simplex_sampled_workspace_bytes recommends, or ws_bytes
+    (0: no workspace at all, a null pointer)."""
+    if ws_bytes is None:
+        return _sized(dev, _lib().sd_simplex_sampled_workspace_bytes(n, T, d, int(samples)))
+    return _sized(dev, ws_bytes) if ws_bytes else (None, 0)
+
+
+def pointcloud_simplex_counts(P, targets=None, tol=1e-7, samples=None, seed=0, device=None, ws_bytes=None):
+    """ws_bytes: the workspace size a sampled call runs with (default: the recommended one); the counts do not depend on it."""
     if samples is None:
         return _points("sd_pointcloud_simplex_counts", torch().int64, P, device, _ROWS, targets, tol)
     return _points("sd_pointcloud_simplex_sampled", torch().int64, P, device, _ROWS, targets, tol, int(samples), int(seed),
-                   workspace=lambda dev, n, d: _sized(dev, _lib().sd_simplex_sampled_workspace_bytes(n, 0, d, int(samples))))
+                   workspace=lambda dev, n, d: _simplex_sampled_ws(dev, n, 0, d, samples, ws_bytes))
 
 
-def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, seed=0, device=None):
-    """P: (n, T, d) curves."""
+def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, seed=0, device=None, ws_bytes=None):
+    """P: (n, T, d) curves.  ws_bytes as for pointcloud_simplex_counts."""
     t = torch()
     lib = _lib()
     dev = _device(device)
@@ -779,7 +789,7 @@ def multi_simplex_counts(P, targets=None, relax=True, tol=1e-7, samples=None, se
         return _launch(dev, lib.sd_multi_simplex_counts, out, Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol)
     return _launch(dev, lib.sd_multi_simplex_sampled, out, Pd.data_ptr(), n, T, d, tp, m, int(bool(relax)), tol,
                    int(samples), int(seed),
-                   workspace=lambda: _sized(dev, lib.sd_simplex_sampled_workspace_bytes(n, T, d, int(samples))))
+                   workspace=lambda: _simplex_sampled_ws(dev, n, T, d, samples, ws_bytes))
 
 
 def pointcloud_simplex_external_counts(P, Q, tol=1e-7, device=None):

@@ -48,7 +48,7 @@ def test_product_library_has_no_crosscheck_code(built):
     for name in _declared_symbols():
         assert hasattr(xchk, name)
     retired = ("rank_packed_kernel", "rank_search_kernel", "launch_mbd_rank_v1", "bucket_packed_kernel",
-               "bucket_partition_kernel")
+               "bucket_partition_kernel", "simplex_kernel")
     syms = {p: subprocess.run(["nm", "-C", p], capture_output=True, text=True).stdout for p in (built.LIB_PATH, built.XCHECK_LIB_PATH)}
     for r in retired:
         assert not re.search(rf"\b{r}\b", syms[built.LIB_PATH]), f"{r} is in the product library"

@@ -205,6 +205,29 @@ def test_sampled_route_switch(eng, d):
         assert np.array_equal(eng.pointcloud_simplex_counts(P * 2.0 ** -480, samples=16, seed=5), want), n
 
 
+@pytest.mark.parametrize("d", (1, 3, 8))
+def test_sampled_workspace_sizes_and_routes(eng, xcheck, oracle, d):
+    """300 samples, relax=True, every row a target (members of shared subsets take sxw_spare_kernel), on the curves
+    sampled_case(d, T=3) (900 pairs) and the point cloud sampled_case(d), with five workspace sizes: the recommended one (one
+    batch), the routing floor -- the size for 256 samples, which at T = 3 holds 768 to 899 pairs: two batches --, a third
+    of the way between them, one byte below the floor and none at all (both: the per-target route), and the retired generic
+    kernel through its hook.  All equal the C oracle's counts on the same subsets, which are neither all zero nor saturated."""
+    size = eng._lib().sd_simplex_sampled_workspace_bytes                 # (torch first: engine._lib)
+    seed = SAMPLED_SEED[d]
+    for P in (sampled_case(d, T=3), sampled_case(d)):
+        n, T = (P.shape[0], P.shape[1]) if P.ndim == 3 else (P.shape[0], 0)
+        call = (lambda **kw: eng.multi_simplex_counts(P, relax=True, samples=300, seed=seed, **kw)) if T else \
+               (lambda **kw: eng.pointcloud_simplex_counts(P, samples=300, seed=seed, **kw))
+        want = oracle.simplex_sampled(P, None, relax=True, samples=300, seed=seed)
+        floor, rec = size(n, T, d, 256), size(n, T, d, 300)
+        print(d, T, floor, rec, want.tolist())
+        assert 0 < floor < rec and want.any() and want.min() < 300 * max(T, 1)
+        for ws_bytes in (rec, floor, floor + (rec - floor) // 3, floor - 1, 0):
+            assert np.array_equal(call(ws_bytes=ws_bytes), want), ws_bytes
+        with xcheck(SD_SIMPLEX_GENERIC="1"):
+            assert np.array_equal(call(), want)
+
+
 # ---------------------------------------------------------------- (g) through the package
 def test_package_utm_and_simplex_exact():
     """PointcloudDepth(containment='simplex') on the UTM-like frame == on the centred frame == the exact counts / C(n, 3), and
