@@ -832,6 +832,50 @@ int sd_spatial_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t s
 int sd_spatial_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
                              double *field, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- K22: the lens, spherical and beta-skeleton depth of curves and point clouds -----------------
+ * No reference code (lens depth: Liu & Modarres 2011, Kleindessner & von Luxburg 2017, Geenens, Nieto-Reyes & Francisci 2023;
+ * spherical depth: Elmore, Hettmansperger & Xuan 2006; beta-skeleton depth: Yang & Modarres 2018).  The depth of x is the share
+ * of the pairs (x_i, x_j), i < j, of the sample whose beta-lune holds x.  It needs nothing of the data but distances, so X (T x n,
+ * st, sn, values, targets and Q as for K20) is as well a cloud of n points in R^T, any T >= 1.
+ * With D2 K20's squared distance on K20's bits (symmetric, +0.0 diagonal), a = D2(x, x_i), b = D2(x, x_j), c = D2(x_i, x_j) and
+ * kappa = 2 / beta - 1 in [-1, 1] (beta in [1, inf]; beta = 2: the lens, kappa = 0; beta = 1: the sphere, kappa = 1), x lies in
+ * the lune iff  a + kappa b <= c  and  b + kappa a <= c  (from |l u + (1 - l) v|^2 = l |u|^2 + (1 - l) |v|^2 - l (1 - l) |u - v|^2
+ * with l = beta / 2).  The device evaluates exactly
+ *   t1 = kappa * b;  s1 = a + t1;  t2 = kappa * a;  s2 = b + t2;  in = (s1 <= c) && (s2 <= c)
+ * with four separately rounded operations (no fused multiply-add), and
+ *   out[q] = G = #{i < j : in}  (m int64);  the caller forms depth = G / C(n, 2), for a sample and for an external target alike.
+ * Three compile-time forms give the same integers where they overlap: kappa == 0.0: a <= c && b <= c; kappa == 1.0:
+ * (a + b rounded) <= c, one test; and the general form, any kappa.  algo = 0 picks the form by kappa, algo = 1 forces the general
+ * form (the cross-check).  No index is special-cased: a sample target's own pairs (a = 0, c = b) satisfy the predicate and
+ * count, as in the papers' sum over all pairs; coincident curves (c = 0) count only for a coincident target (at kappa = -1, beta
+ * = inf, for every target: the slab between two equal hyperplanes is read as the whole space); repeated and
+ * permuted target lists work, and so do external targets equal to a sample curve, which get that curve's count.  D2 < 2^993,
+ * so nothing overflows.  On data whose right angles are exact in the reals but whose values are not representable (rounded to
+ * 0.1, say) the spherical count follows the rounded D2, not the real geometry; on integer-valued data of small magnitude D2
+ * is exact and the counts are the geometric ones.
+ * Stage 1 forms the whole n x n matrix through K20's tile kernel (and, for external targets, the m x n rows of a batch); a
+ * sample target's row is read from the matrix through the target list.  Stage 2 counts: a workgroup per 128 targets x 64
+ * sample curves i x a span of tiles of 64 sample curves j at or above the diagonal, an 8 x 4 register tile of a per thread, c
+ * and the targets' b staged in LDS 16 j at a time, 32-bit counters per lane, one integer atomic per target and workgroup
+ * (csrc/lens_depth.hip).  The counts are integers: they do not depend on the tiles, the target list, the layout of X or the
+ * workspace size.
+ * Workspace, each part padded to 256 bytes: the time-major copy of a curve-major X (8 T n bytes); the matrix, 8 n^2 bytes; the
+ * rows of a batch of external targets, 8 n bytes a target, whole blocks of 128 (the floor is one block; the recommended size
+ * holds all m, up to 1 GiB).  Both calls take the same sizes; sample targets use no rows and always go in one batch.
+ * sd_lens_targets_per_batch says how many external targets a batch of a call with ws_bytes takes (0 below the floor).  All
+ * three are 0 for a shape the calls refuse on shape; the floor is 0 for m == 0.
+ * The refusals, all before any device work: SD_ERR_INVALID for NULL X, Q or out, T < 1, n < 1, m < 0, kappa NaN or outside
+ * [-1, 1], algo outside {0, 1}; SD_ERR_UNSUPPORTED for n < 2, for n > 16 384 (the stored matrix is 2 GiB there and no route
+ * recomputes it), for 2^31 or more timepoints, or for more than 10^14 pair-timepoints (n (n + m) T); SD_ERR_WORKSPACE below
+ * the floor.  Every launch is bounded in work; no workgroup waits for another. */
+size_t sd_lens_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m);
+size_t sd_lens_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m);
+int64_t sd_lens_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes);
+int sd_lens_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double kappa,
+                   int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
+int sd_lens_external_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double kappa,
+                            int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

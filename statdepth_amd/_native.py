@@ -128,6 +128,11 @@ SIGNATURES = {
     "sd_spatial_time_tile": (_i64, [_i64, _i64, _vp]),
     "sd_spatial_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sd_spatial_external_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "sd_lens_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "sd_lens_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "sd_lens_targets_per_batch": (_i64, [_i64, _i64, _i64, _i64, _i64, _sz]),
+    "sd_lens_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
+    "sd_lens_external_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
 }
 
 

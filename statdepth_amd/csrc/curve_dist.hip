@@ -360,6 +360,11 @@ int launch_curve_weights(const double *Y, i64 T, i64 n, const double *Q, const i
     return cd_launch_tiles<CD_WEIGHT>(Y, T, n, pan, q_begin, q_end, 0, 0.0, W, q_begin, ldw, nullptr, nullptr, 0, s);
 }
 
+// K22's external rows: the distances of the targets [q_begin, q_end) of the m columns of Q into out[(q - q_begin) * n + j]
+int launch_curve_sqdist_rows(const double *Y, i64 T, i64 n, const double *Q, i64 m, i64 q_begin, i64 q_end, double *out, hipStream_t s) {
+    return cd_launch_tiles<CD_STORE>(Y, T, n, CdPanel{Q, m, nullptr}, q_begin, q_end, 0, 0.0, out, q_begin, n, nullptr, nullptr, 0, s);
+}
+
 int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s) {
     const CurveDistPlan plan = curve_dist_plan(CD_WHAT_SELECT, n, n, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);

@@ -1,7 +1,8 @@
 // curve_routes.h -- the curve depths on K14's pair image (K14 rank depths, K15 extremal depth, K17 total variation depth):
 // their one route rule, the plan of stage 1 that the size functions and the launchers read, and each family's own plan
-// built on it; and the batch plans of K20, the squared L2 distances of curves, and of K21, the functional spatial depth on
-// them, which read the doubles (internal; the K1+K2 rank routes: rank_routes.h, the strict path's: strict_routes.h).
+// built on it; and the batch plans of K20, the squared L2 distances of curves, of K21, the functional spatial depth on them,
+// and of K22, the lune depths on their matrix, which read the doubles (internal; the K1+K2 rank routes: rank_routes.h, the
+// strict path's: strict_routes.h).
 #pragma once
 #include "sd_common.h"
 
@@ -104,5 +105,25 @@ SpatialPlan spatial_plan(i64 T, i64 n, i64 m, PlanSize size);
 int spatial_time_tile(i64 T, i64 targets, i64 cus);
 int launch_spatial_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, double *field,
                         void *ws, size_t ws_bytes, hipStream_t s);
+
+// ---- K22 lens, spherical and beta-skeleton depth of curves (lens_depth.hip): out[q] = G = #{i < j : a + kappa b <= c and
+// b + kappa a <= c}, a = D2(q, i), b = D2(q, j), c = D2(i, j) on K20's bits.  The plan: the n x n matrix, then the rows of a
+// batch of external targets, whole blocks of 128 (8 n bytes a target), sized by PlanSize with its rows read as targets.
+// Sample targets read their rows from the matrix and go in one batch whatever the plan says. ----
+constexpr i64 LN_MAX_N = 16384;                                     // the stored matrix is 2 GiB there; the caller checks
+struct LensPlan {
+    i64 targets;                                                    // external targets per batch; 0: below the floor
+    size_t matrix, rows;                                            // bytes of the two parts
+    size_t bytes;                                                   // both
+};
+LensPlan lens_plan(i64 n, i64 m, PlanSize size);
+// the form (0 lens, 1 sphere, 2 general) of a kappa and an algo (0: by kappa, 1: general)
+int lens_form(double kappa, int algo);
+// tiles J of 64 sample curves that one workgroup of the count kernel walks, for a launch over `targets` targets
+i64 lens_span(i64 n, i64 targets);
+// K20's external distances of the targets [q_begin, q_end) of the m columns of Q: out[(q - q_begin) * n + j]
+int launch_curve_sqdist_rows(const double *Y, i64 T, i64 n, const double *Q, i64 m, i64 q_begin, i64 q_end, double *out, hipStream_t s);
+int launch_lens_counts(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double kappa, int algo, i64 *out,
+                       void *ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace sd

@@ -1228,6 +1228,66 @@ int sd_spatial_external_sums(const double *X, int64_t T, int64_t n, int64_t st, 
                              });
 }
 
+// ---- K22 ----
+static bool lens_sized(i64 T, i64 n, i64 m) { return T >= 1 && n >= 2 && n <= LN_MAX_N && m >= 0 && T < ((i64)1 << 31); }
+
+size_t sd_lens_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
+    if (!lens_sized(T, n, m)) return 0;
+    return time_major_bytes(T, n, st, sn) + lens_plan(n, m, PlanSize::of_rows(m > 0 ? m : 1)).bytes;
+}
+
+size_t sd_lens_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
+    if (!lens_sized(T, n, m) || m == 0) return 0;
+    return time_major_bytes(T, n, st, sn) + lens_plan(n, m, PlanSize::of_rows(1)).bytes;
+}
+
+int64_t sd_lens_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes) {
+    if (!lens_sized(T, n, m)) return 0;
+    const size_t tm = time_major_bytes(T, n, st, sn);
+    return ws_bytes >= tm ? lens_plan(n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+}
+
+// K20's refusals in K20's order, with kappa and algo behind the shape and the matrix' cap behind the two curves; the budget
+// counts the matrix and the targets' rows, n (n + m) T pair-timepoints
+static int check_lens(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64 *targets, i64 m, bool external, const void *out,
+                      double kappa, int algo) {
+    if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
+    if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
+    if (!(kappa >= -1.0 && kappa <= 1.0)) return fail(SD_ERR_INVALID, "kappa = 2 / beta - 1 must lie in [-1, 1], got %g", kappa);
+    if (algo < 0 || algo > 1) return fail(SD_ERR_INVALID, "algo=%d outside {0 (the form by kappa), 1 (the general form)}", algo);
+    if (n < 2) return fail(SD_ERR_UNSUPPORTED, "distances between curves need at least two curves, got %lld", (long long)n);
+    if (n > LN_MAX_N)
+        return fail(SD_ERR_UNSUPPORTED, "the lune depths keep the n x n matrix of distances: at most %lld curves, got %lld",
+                    (long long)LN_MAX_N, (long long)n);
+    int rc = external ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, targets, m);
+    if (rc) return rc;
+    const double work = (double)n * ((double)n + (double)m) * (double)T;
+    if (work > HS_MAX_WORK) return fail(SD_ERR_UNSUPPORTED, "%.3g pair-timepoints exceed the cap of %.0e", work, HS_MAX_WORK);
+    return SD_OK;
+}
+
+int sd_lens_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double kappa,
+                   int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_lens(X, T, n, st, sn, targets, m, false, out, kappa, algo);
+    if (rc || m == 0) return rc;
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_lens_min_workspace_bytes(T, n, st, sn, m), "sd_lens_min_workspace_bytes",
+                             stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_lens_counts(Y, T, n, nullptr, targets, m, kappa, algo, out, w, bytes, s);
+                             });
+}
+
+int sd_lens_external_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double kappa,
+                            int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!Q) return fail(SD_ERR_INVALID, "null pointer");
+    int rc = check_lens(X, T, n, st, sn, nullptr, m, true, out, kappa, algo);
+    if (rc || m == 0) return rc;
+    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_lens_min_workspace_bytes(T, n, st, sn, m), "sd_lens_min_workspace_bytes",
+                             stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
+                                 return launch_lens_counts(Y, T, n, Q, nullptr, m, kappa, algo, out, w, bytes, s);
+                             });
+}
+
 // ---------------------------------------------------------------------------
 // K18
 // ---------------------------------------------------------------------------

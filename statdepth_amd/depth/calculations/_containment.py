@@ -15,6 +15,9 @@ multivariate functional halfspace depth and its projection-depth sibling, _funct
 these tuples that take multivariate curves.  METRIC_DEPTHS names the depths built on the L2 distances between whole curves
 (the h-modal depth, _functional._metric_depths), for univariate curves.  SPATIAL_DEPTHS names the functional spatial depth
 (_functional._spatial_depths), built on the same distances and the unit vectors between whole curves, for univariate curves.
+LENS_DEPTHS names the lune depths (the lens, the spherical and the beta-skeleton depth, _functional._lens_depths): counts of
+the pairs of curves whose lune holds the target, read off the same distances; for univariate curves, and for point clouds
+(_pointcloud._lens_cloud_depths) of any dimension.
 """
 from inspect import signature
 
@@ -25,13 +28,14 @@ SHAPE_DEPTHS = ('tvd', 'mss')
 CLOUD_DEPTHS = ('halfspace', 'projection')
 METRIC_DEPTHS = ('hmodal',)
 SPATIAL_DEPTHS = ('spatial',)
+LENS_DEPTHS = ('lens', 'spherical', 'beta_skeleton')
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS + SPATIAL_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS + SPATIAL_DEPTHS + LENS_DEPTHS)}, '
                          f'for univariate or multivariate data one of {list(CLOUD_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
@@ -63,6 +67,10 @@ def _is_metric_depth(containment) -> bool:
 
 def _is_spatial_depth(containment) -> bool:
     return isinstance(containment, str) and containment in SPATIAL_DEPTHS
+
+
+def _is_lens_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in LENS_DEPTHS
 
 
 def _select_containment(containment):

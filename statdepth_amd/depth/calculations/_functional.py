@@ -18,7 +18,7 @@ from scipy.special import binom
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
 from ._containment import (_is_cloud_depth, _is_metric_depth, _is_order_depth, _is_rank_depth, _is_shape_depth,
-                           _is_spatial_depth, _select_containment)
+                           _is_lens_depth, _is_spatial_depth, _select_containment)
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._pointcloud import _halfspace_directions
 from ._rank import _rank_depth_values
@@ -328,6 +328,56 @@ def _spatial_depths(data, to_compute, J, containment: str, deep_check=False, dev
     return pd.Series(index=cols, data=1.0 - np.sqrt(np.asarray(S, dtype=np.float64)) / n)
 
 
+def _lens_kappa(containment: str, beta) -> tuple:
+    """(beta, kappa = 2 / beta - 1) of a lune depth: 'lens' is beta = 2 and 'spherical' beta = 1, and both refuse a `beta`;
+    'beta_skeleton' takes a real beta >= 1 or math.inf."""
+    if containment != 'beta_skeleton':
+        if beta is not None:
+            raise ValueError(f'containment \'{containment}\' has its beta fixed ({2 if containment == "lens" else 1}): beta belongs '
+                             f'to \'beta_skeleton\' and must be left at None, got {beta!r}.')
+        beta = 2.0 if containment == 'lens' else 1.0
+    elif not isinstance(beta, numbers.Real) or isinstance(beta, bool) or not beta >= 1:
+        raise ValueError(f'containment \'beta_skeleton\' takes a real beta >= 1 or math.inf (beta=2 is the lens depth, beta=1 the '
+                         f'spherical depth), got {beta!r}.')
+    beta = float(beta)
+    return beta, 2.0 / beta - 1.0
+
+
+def _lens_counts_to_depths(X, targets, cols, containment: str, beta, device) -> pd.Series:
+    """The tail shared by the curves and the point clouds: X (T x n, checked) goes up once, sd_lens_counts gives G, and the
+    depth is G / C(n, 2)."""
+    T, n = X.shape
+    beta, kappa = _lens_kappa(containment, beta)
+    if n > engine.LENS_MAX_N:
+        raise ValueError(f'containment \'{containment}\' keeps the n x n matrix of distances on the device and takes at most '
+                         f'{engine.LENS_MAX_N} curves or points, got {n}.')
+    M = engine.to_device_matrix(X, device)               # one upload
+    G = engine.lens_counts(M, kappa, targets, device=device)
+    depths = pd.Series(index=cols, data=np.asarray(G, dtype=np.float64) / np.float64(n * (n - 1) // 2))
+    depths.attrs['beta'] = beta
+    return depths
+
+
+def _lens_depths(data, to_compute, J, containment: str, deep_check=False, device=None, quantile=0.15, bandwidth=None,
+                 beta=None) -> pd.Series:
+    """The lune depths (containment in _containment.LENS_DEPTHS) of the columns `to_compute` of the single frame in `data`:
+    the share of the C(n, 2) pairs of curves (x_i, x_j) whose beta-lune holds the curve x -- 'lens' (beta = 2; Liu & Modarres
+    2011): ||x - x_i|| and ||x - x_j|| both at most ||x_i - x_j||; 'spherical' (beta = 1; Elmore, Hettmansperger & Xuan 2006): x in
+    the ball with diameter x_i x_j; 'beta_skeleton' (Yang & Modarres 2018): any beta in [1, inf].  L2 norms as plain sums over
+    the timepoints.  The curve's own pairs count, as in the papers.  One upload, one device call for the integer counts
+    (sd_lens_counts), one division.  The beta used is in the result's attrs['beta'].  Labels, `to_compute` and the result's
+    order are those of 'r2'.  Refused before anything is uploaded: what 'hmodal' refuses of the data, `quantile` or
+    `bandwidth` (they belong to 'hmodal'), a `beta` with 'lens' or 'spherical', none or one below 1 with 'beta_skeleton', and
+    more than 16 384 curves."""
+    df, X = _metric_frame(data, J, f'containment \'{containment}\'', deep_check)
+    default_q = isinstance(quantile, numbers.Real) and not isinstance(quantile, bool) and quantile == 0.15
+    if bandwidth is not None or not default_q:
+        raise ValueError(f'containment \'{containment}\' has no bandwidth: quantile and bandwidth belong to \'hmodal\' and must '
+                         f'be left at their defaults, got quantile={quantile!r}, bandwidth={bandwidth!r}.')
+    cols = df.columns if to_compute is None else to_compute
+    return _lens_counts_to_depths(X, _positions(df, cols), cols, containment, beta, device)
+
+
 def _curve_distances(data, to_compute=None, device=None) -> pd.DataFrame:
     """The L2 distances (the square roots of sd_curve_sqdist's matrix) of the columns `to_compute` (default: all) of a
     frame, or of the single frame of a list, to all of its columns: rows `to_compute`, columns the frame's labels."""
@@ -436,7 +486,10 @@ def _cloud_depths(data, to_compute, J, containment: str, deep_check=False, devic
 
 def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index] = None, J=2, containment='r2',
                      relax=False, deep_check=False, quiet=True, device=None, algo='auto', directions=1000, seed=0,
-                     aggregate='mean', quantile=0.15, bandwidth=None) -> pd.Series:
+                     aggregate='mean', quantile=0.15, bandwidth=None, beta=None) -> pd.Series:
+    if _is_lens_depth(containment):                      # as 'spatial', with `beta`
+        return _lens_depths(data, to_compute, J, containment, deep_check=deep_check, device=device, quantile=quantile,
+                            bandwidth=bandwidth, beta=beta)
     if _is_metric_depth(containment):                    # `relax` and `algo` have nothing to select
         return _metric_depths(data, to_compute, J, containment, deep_check=deep_check, device=device, quantile=quantile,
                               bandwidth=bandwidth)
@@ -512,7 +565,8 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     """
     samples = []
     if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
-            or _is_cloud_depth(containment) or _is_metric_depth(containment) or _is_spatial_depth(containment)):
+            or _is_cloud_depth(containment) or _is_metric_depth(containment) or _is_spatial_depth(containment)
+            or _is_lens_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

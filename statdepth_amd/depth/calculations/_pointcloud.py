@@ -245,6 +245,37 @@ def _pointwisedepth(data: pd.DataFrame, to_compute: Union[list, pd.Index] = None
     return pd.Series(index=to_compute, data=fam.depth(raw, n, d, vols))
 
 
+def _lens_cloud_depths(data: pd.DataFrame, to_compute=None, K=None, containment='lens', device=None) -> pd.Series:
+    """The lune depths with a fixed beta ('lens', 'spherical') of the rows `to_compute` of the n x d frame as points of
+    R^d, any d >= 1: the share of the C(n, 2) pairs of points whose beta-lune holds the point.  The frame is the curve-major
+    layout of FunctionalDepth's call with T = d, so nothing is transposed on the host: one upload, one device call
+    (sd_lens_counts), one division.  Refused before anything is uploaded: `K`, NaN or infinite values, magnitudes above 2^480,
+    fewer than 2 or more than 16 384 points, no column, and 'beta_skeleton', whose beta PointcloudDepth has no argument for."""
+    from ._functional import METRIC_MAX_ABS, _lens_counts_to_depths
+
+    def refuse(reason):
+        raise ValueError(f'containment \'{containment}\' {reason}')
+
+    if containment == 'beta_skeleton':
+        refuse('needs a beta, which PointcloudDepth has no argument for: call FunctionalDepth([data.T], '
+               'containment=\'beta_skeleton\', beta=...), whose curves are the points.')
+    if K is not None:
+        refuse('has no K-block estimator: K must be None.')
+    P = data.to_numpy(dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] < 1:
+        refuse('needs at least one column.')
+    n, d = P.shape
+    if n < 2:
+        refuse(f'needs at least 2 points, got {n}.')
+    if not np.isfinite(P).all():
+        refuse('does not take NaN or infinite values (they have no distance): drop or fill them first.')
+    if np.abs(P).max() > METRIC_MAX_ABS:
+        refuse('takes values up to 2^480 in magnitude (a squared difference beyond would overflow): rescale the points.')
+    if to_compute is None:
+        to_compute = data.index
+    return _lens_counts_to_depths(P.T, _row_positions(data, to_compute), to_compute, containment, None, device)
+
+
 def _block_depths(P: np.ndarray, blocks, containment: str, device=None, directions=None) -> np.ndarray:
     """Depth of each block's target (its LAST row) inside the block, every block in one launch.  `directions`: the
     direction array of a family that has one; None there asks for its exact kind."""

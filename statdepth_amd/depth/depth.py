@@ -16,7 +16,8 @@ import pandas as pd
 from abc import ABC, abstractmethod
 from .calculations._functional import _curve_distances, _functionaldepth, _samplefunctionaldepth
 from .calculations._helper import DepthDegeneracy   # noqa: F401
-from .calculations._pointcloud import _pointwisedepth, _samplepointwisedepth
+from .calculations._containment import _is_lens_depth
+from .calculations._pointcloud import _lens_cloud_depths, _pointwisedepth, _samplepointwisedepth
 from .calculations._uncertainty import _probabilistic_band_depth
 from .calculations import _boxplot
 from .calculations._boxplot import FunctionalBoxplotResult
@@ -168,7 +169,18 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
     1 / (1 + O); there 'exact' raises NotImplementedError.
     containment='simplex_exact' is 'simplex' for planar data (d = 2; any other d raises NotImplementedError) counted by an
     angular sweep with exact orientation signs, O(n log^2 n) per point: the closed triangles of the other points that
-    contain the point, over C(n, 3).  'simplex' itself keeps its enumeration and its tolerance."""
+    contain the point, over C(n, 3).  'simplex' itself keeps its enumeration and its tolerance.
+    containment='lens' and 'spherical' are FunctionalDepth's lune depths of the rows as points of R^d, any d >= 1 (they need
+    nothing of the data but Euclidean distances): the share of the C(n, 2) pairs of points whose lens (beta = 2), resp. whose
+    ball with the pair as a diameter (beta = 1), holds the point; the beta is in the result's attrs['beta'].  ValueError for
+    `K` other than None, NaN or infinite values, magnitudes above 2^480, fewer than 2 or more than 16 384 points.  This
+    function has no `beta` argument, so 'beta_skeleton' is refused here with the call that computes it:
+    FunctionalDepth([data.T], containment='beta_skeleton', beta=...), whose curves are the points."""
+    if _is_lens_depth(containment):
+        depth = _lens_cloud_depths(data=data, to_compute=to_compute, K=K, containment=containment, device=device)
+        result = _PointwiseDepth(df=data, depths=depth)
+        result.attrs['beta'] = depth.attrs['beta']
+        return result
     if K is not None:
         depth = _samplepointwisedepth(data=data, to_compute=to_compute, K=K, containment=containment,
                                       device=device, directions=directions, seed=seed)
@@ -180,7 +192,7 @@ def PointcloudDepth(data: pd.DataFrame, to_compute: pd.Index = None, K=None, con
 
 def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, containment='r2', relax=False,
                     deep_check=False, quiet=True, *, device=None, algo='auto', directions=1000, seed=0, aggregate='mean',
-                    quantile=0.15, bandwidth=None):
+                    quantile=0.15, bandwidth=None, beta=None):
     """Band depth of curves ('r2', 'r2_enum', 'simplex' or a callable), as in the reference.
 
     For univariate data (`data` a list of one frame whose columns are the curves) `containment` also names the integrated
@@ -228,16 +240,31 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     points, returns NaN for coincident points as its reference does.  The sum over the curves runs on the device in column
     order with one fused multiply-add per term (sd_spatial_sums), so a curve's depth does not depend on `to_compute`.
     ValueError for what 'hmodal' refuses of the data, for `K` other than None, `J` other than 2, and for a `quantile` or a
-    `bandwidth` other than the default (they belong to 'hmodal'); `relax` and `algo` are ignored."""
+    `bandwidth` other than the default (they belong to 'hmodal'); `relax` and `algo` are ignored.
+
+    containment='lens', 'spherical' and 'beta_skeleton' (univariate data, under the rules of 'hmodal') are the lune depths: the
+    share of the C(n, 2) pairs of curves (x_i, x_j) whose beta-lune holds the curve x, i.e. ||x - (l x_i + (1 - l) x_j)|| <= l ||x_i -
+    x_j|| and the same with i and j swapped, l = beta / 2.  'lens' is beta = 2 (Liu & Modarres 2011: both distances from x at
+    most ||x_i - x_j||), 'spherical' is beta = 1 (Elmore, Hettmansperger & Xuan 2006: x in the ball with diameter x_i x_j);
+    both refuse a `beta` other than None.  'beta_skeleton' (Yang & Modarres 2018) requires `beta`, a real number >= 1 or
+    math.inf.  The test runs on the squared L2 distances between whole curves (CurveDistances' numbers, squared) as
+    a + kappa b <= c and b + kappa a <= c with kappa = 2 / beta - 1, every product and sum rounded on its own; the counts are
+    integers (sd_lens_counts) and the depth is count / C(n, 2).  The curve's own pairs count, as in the papers' sum over all
+    pairs, and so do not depend on `to_compute`.  On data whose values are not exactly representable a pair at an exact right
+    angle in the reals is judged by the rounded distances.  The beta used is in the result's attrs['beta'].  ValueError for
+    what 'spatial' refuses and for more than 16 384 curves (the n x n matrix of distances is kept on the device).  Every other
+    containment ignores `beta`."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)
     else:
         depth = _functionaldepth(data=data, to_compute=to_compute, J=J, containment=containment, relax=relax,
                                  deep_check=deep_check, quiet=quiet, device=device, algo=algo, directions=directions,
-                                 seed=seed, aggregate=aggregate, quantile=quantile, bandwidth=bandwidth)
+                                 seed=seed, aggregate=aggregate, quantile=quantile, bandwidth=bandwidth, beta=beta)
     if len(data) == 1:                                   # univariate by assumption (:399-400)
         result = _FunctionalDepthUnivariate(df=data[0], depths=depth)
+        if 'beta' in depth.attrs:                        # the lune depths
+            result.attrs['beta'] = depth.attrs['beta']
         if 'bandwidth' in depth.attrs:                   # 'hmodal': a plain attribute, as the result's other state
             object.__setattr__(result, 'bandwidth', depth.attrs['bandwidth'])
         return result

@@ -651,6 +651,56 @@ def spatial_external_sums(X, Q, device=None, ws_bytes=None, field=False):
     return (S, E) if field else S
 
 
+LENS_MAX_N = 16384                                                   # curves whose n x n matrix sd_lens_counts keeps (2 GiB)
+
+
+def _kappa(kappa):
+    kappa = float(kappa)
+    if not -1.0 <= kappa <= 1.0:
+        raise ValueError(f"kappa = 2 / beta - 1 must lie in [-1, 1], got {kappa!r}")
+    return kappa
+
+
+def lens_workspace_bytes(T, n, curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of sd_lens_counts and sd_lens_external_counts for a T x n matrix and m targets
+    (default: all n): the n x n matrix of squared distances (8 n^2 bytes) and the rows of a batch of whole blocks of 128
+    external targets (8 n bytes a target), behind the time-major copy of a curve-major matrix.  The floor holds one block;
+    the recommended size holds all targets, up to 1 GiB of rows.  (0, 0) where T < 1, n < 2, n > 16 384 or m < 0."""
+    lib = _native.load()
+    T, n = int(T), int(n)
+    m = n if m is None else int(m)
+    st, sn = _strides(T, n, curve_major)
+    return int(lib.sd_lens_workspace_bytes(T, n, st, sn, m)), int(lib.sd_lens_min_workspace_bytes(T, n, st, sn, m))
+
+
+def lens_targets_per_batch(T, n, ws_bytes, curve_major=False, m=None):
+    """External targets a batch of sd_lens_external_counts takes with ws_bytes of workspace; 0 below the floor.  (Sample
+    targets read their rows from the matrix and go in one batch.)"""
+    lib = _native.load()
+    T, n = int(T), int(n)
+    m = n if m is None else int(m)
+    return int(lib.sd_lens_targets_per_batch(T, n, *_strides(T, n, curve_major), m, int(ws_bytes)))
+
+
+def lens_counts(X, kappa, targets=None, device=None, ws_bytes=None, algo=0):
+    """int64[m]: G of the lens (kappa = 0), spherical (kappa = 1) or beta-skeleton depth (kappa = 2 / beta - 1) per target
+    (sd_lens_counts) -- the pairs i < j of the n columns of X with a + kappa b <= c and b + kappa a <= c, where a, b are
+    curve_sqdist's D2 of the target to curves i, j and c that of the two curves, every product and sum rounded on its own.
+    The depth is G / C(n, 2).  A target's own pairs count.  algo: 0 takes the form that kappa names, 1 the general form (the
+    same integers).  targets, ws_bytes and the contract on X as for curve_sqdist; n is at most 16 384."""
+    return _curves("lens", "counts", None, X, targets, device, (_kappa(kappa), int(algo)), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m,), dtype=t.int64, device=dev)], sized_by=("lens", None))[0]
+
+
+def lens_external_counts(X, Q, kappa, device=None, ws_bytes=None, algo=0):
+    """int64[m]: the counts of lens_counts for the m columns of Q (T x m) against the pairs of the n columns of X
+    (sd_lens_external_counts).  The depth is G / C(n, 2) here too.  A column of Q equal to a sample curve gives that curve's
+    count."""
+    lib = _lib()
+    size = (lambda T, n, m: lib.sd_lens_workspace_bytes(T, n, n, 1, m)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
+    return _external_curves(lib.sd_lens_external_counts, (), X, Q, device, _kappa(kappa), int(algo), strided=True, ws_bytes=size)
+
+
 def central_regions_row_capacity():
     """The most curves of the row-resident route of sd_central_regions (whole rows in one workgroup's registers); above
     it the call goes through column blocks.  (torch first, as in _lib: a test may ask this before any device call.)"""
