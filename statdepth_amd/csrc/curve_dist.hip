@@ -41,21 +41,20 @@
 //              nothing reads), so a batch's slab holds no byte that was not written.
 // The selection keeps the n x n slab when the workspace holds it (cd_slab_hist_kernel re-reads it per pass) and otherwise
 // recomputes the tiles in every pass; both count the same multiset of images, so the result is the same.
-// The batch plan (curve_dist_plan) is over blocks of 128 targets: the h-modal partial sums are the only per-target
-// workspace, 8 ceil(n / 64) bytes a target; the distances go straight to the output and the selection's workspace does not
-// depend on the targets.
+// The batch plan (curve_dist_plan): the h-modal partial sums are the only per-target workspace, 8 ceil(n / 64) bytes a target,
+// in the blocks of curve_routes.h; the distances go straight to the output and the selection's workspace does not depend on
+// the targets.
 #include "curve_routes.h"
 
 namespace sd {
 
-constexpr int CD_TILE = 128, CD_COLS = 64;                          // targets and sample curves of a tile
+constexpr int CD_TILE = CV_BLOCK, CD_COLS = 64;                     // targets (the plan's block) and sample curves of a tile
 constexpr int CD_TK = 16, CD_THREADS = 256, CD_R = CD_TILE / 16, CD_C = CD_COLS / 16;
 constexpr int CD_STORE = 0, CD_HMODAL = 1, CD_HIST = 2, CD_WEIGHT = 3;
 constexpr int CD_BINS = 2048, CD_PASSES = 6;
 constexpr int CD_STATE_WORDS = 32;                                  // prefix, k; the rest pads the region
 constexpr size_t CD_PART_MAX = (size_t)256 << 20;                   // partial sums of a batch (recommended size and launch)
 constexpr size_t CD_SLAB_MAX = (size_t)1 << 30;                     // the selection's slab: above it every pass recomputes
-constexpr i64 CD_LAUNCH_TILES = (i64)1 << 30;                       // tiles of one launch
 
 static inline i64 cd_tiles(i64 n) { return (n + CD_COLS - 1) / CD_COLS; }   // column tiles
 
@@ -286,15 +285,10 @@ CurveDistPlan curve_dist_plan(int what, i64 n, i64 m, PlanSize size) {
         p.targets = m;
     } else if (what == CD_WHAT_HMODAL) {
         const size_t pb = cd_block_bytes(n);
-        i64 most = (m + CD_TILE - 1) / CD_TILE;                     // blocks of a batch: all, within the cap, at least one
-        const i64 cap = (i64)(CD_PART_MAX / pb);
-        most = most < cap ? most : cap;
-        most = most < 1 ? 1 : most;
-        i64 blocks = size.rows ? (size.rows + CD_TILE - 1) / CD_TILE : (i64)(size.bytes / pb);
-        blocks = blocks < most ? blocks : most;
-        if (blocks < 1) return p;
-        p.targets = blocks * CD_TILE < m ? blocks * CD_TILE : m;
-        p.bytes = align_up((size_t)blocks * pb, 256);
+        const TargetBlocks b = target_block_plan(m, size, pb, pb, CD_PART_MAX);
+        if (b.blocks < 1) return p;
+        p.targets = b.targets;
+        p.bytes = align_up((size_t)b.blocks * pb, 256);
     } else {
         const size_t fixed = cd_select_fixed(), slab = (size_t)n * (size_t)n * 8;
         const bool fits = slab <= CD_SLAB_MAX;
@@ -308,61 +302,47 @@ CurveDistPlan curve_dist_plan(int what, i64 n, i64 m, PlanSize size) {
 }
 
 // ---------------------------------------------------------------------------------------------- host
-struct CdPanel {
-    const double *P;
-    i64 ldp;
-    const i64 *targets;
-};
-
-// the tiles of the targets [q_begin, q_end), in launches of at most CD_LAUNCH_TILES tiles
+// the tiles of the targets [q_begin, q_end) of the m that sel names, nb tiles a target block
 template <int EPI>
-static int cd_launch_tiles(const double *Y, i64 T, i64 n, const CdPanel &pan, i64 q_begin, i64 q_end, int upper, double g,
-                           double *out, i64 row0, i64 ldo, u64 *hist, const u64 *state, int pass, hipStream_t s) {
+static int cd_launch_tiles(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, i64 q_begin, i64 q_end, int upper, double g, double *out,
+                           i64 row0, i64 ldo, u64 *hist, const u64 *state, int pass, hipStream_t s) {
     const i64 nb = cd_tiles(n);
-    i64 per = CD_LAUNCH_TILES / nb;                                 // target blocks of a launch
-    per = per < 1 ? 1 : per;
-    for (i64 q = q_begin; q < q_end; q += per * CD_TILE) {
-        const i64 left = (q_end - q + CD_TILE - 1) / CD_TILE, tb = left < per ? left : per;
-        hipLaunchKernelGGL(cd_tile_kernel<EPI>, dim3((unsigned)(tb * nb)), dim3(CD_THREADS), 0, s, Y, T, n, pan.P, pan.ldp, pan.targets, q,
-                           q_end, nb, upper, g, out, row0, ldo, hist, state, cd_pass_shift(pass), cd_pass_bits(pass));
+    return for_block_launches(q_begin, q_end, nb, [&](i64 q, i64 tb) -> int {
+        hipLaunchKernelGGL(cd_tile_kernel<EPI>, dim3((unsigned)(tb * nb)), dim3(CD_THREADS), 0, s, Y, T, n, sel.panel(Y), sel.ld(n, m),
+                           sel.targets, q, q_end, nb, upper, g, out, row0, ldo, hist, state, cd_pass_shift(pass), cd_pass_bits(pass));
         SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
+        return SD_OK;
+    });
 }
 
-int launch_curve_sqdist(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, hipStream_t s) {
-    const CdPanel pan = Q ? CdPanel{Q, m, nullptr} : CdPanel{Y, n, targets};
-    return cd_launch_tiles<CD_STORE>(Y, T, n, pan, 0, m, 0, 0.0, out, 0, n, nullptr, nullptr, 0, s);
+int launch_curve_sqdist(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double *out, hipStream_t s) {
+    return cd_launch_tiles<CD_STORE>(Y, T, n, sel, m, 0, m, 0, 0.0, out, 0, n, nullptr, nullptr, 0, s);
 }
 
-int launch_hmodal_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double g, double *out, void *ws,
-                       size_t ws_bytes, hipStream_t s) {
+int launch_hmodal_sums(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double g, double *out, void *ws, size_t ws_bytes,
+                       hipStream_t s) {
     const CurveDistPlan plan = curve_dist_plan(CD_WHAT_HMODAL, n, m, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);
     double *part = plan.targets > 0 ? (double *)cv.take(plan.bytes) : nullptr;
     if (!part) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_curve_sqdist_min_workspace_bytes)");
-    const CdPanel pan = Q ? CdPanel{Q, m, nullptr} : CdPanel{Y, n, targets};
     const i64 nb = cd_tiles(n);
-    for (i64 q = 0; q < m; q += plan.targets) {
-        const i64 count = m - q < plan.targets ? m - q : plan.targets;
-        int rc = cd_launch_tiles<CD_HMODAL>(Y, T, n, pan, q, q + count, 0, g, part, q, nb, nullptr, nullptr, 0, s);
+    return for_target_batches(m, plan.targets, [&](i64 q, i64 count) -> int {
+        int rc = cd_launch_tiles<CD_HMODAL>(Y, T, n, sel, m, q, q + count, 0, g, part, q, nb, nullptr, nullptr, 0, s);
         if (rc) return rc;
         hipLaunchKernelGGL(cd_fold_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, part, count, nb, out + q);
         SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
+        return SD_OK;
+    });
 }
 
 // K21's pass 1: the weights of the targets [q_begin, q_end) into W[j * ldw + (q - q_begin)]
-int launch_curve_weights(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, i64 q_begin, i64 q_end, double *W,
-                         i64 ldw, hipStream_t s) {
-    const CdPanel pan = Q ? CdPanel{Q, m, nullptr} : CdPanel{Y, n, targets};
-    return cd_launch_tiles<CD_WEIGHT>(Y, T, n, pan, q_begin, q_end, 0, 0.0, W, q_begin, ldw, nullptr, nullptr, 0, s);
+int launch_curve_weights(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, i64 q_begin, i64 q_end, double *W, i64 ldw, hipStream_t s) {
+    return cd_launch_tiles<CD_WEIGHT>(Y, T, n, sel, m, q_begin, q_end, 0, 0.0, W, q_begin, ldw, nullptr, nullptr, 0, s);
 }
 
 // K22's external rows: the distances of the targets [q_begin, q_end) of the m columns of Q into out[(q - q_begin) * n + j]
 int launch_curve_sqdist_rows(const double *Y, i64 T, i64 n, const double *Q, i64 m, i64 q_begin, i64 q_end, double *out, hipStream_t s) {
-    return cd_launch_tiles<CD_STORE>(Y, T, n, CdPanel{Q, m, nullptr}, q_begin, q_end, 0, 0.0, out, q_begin, n, nullptr, nullptr, 0, s);
+    return cd_launch_tiles<CD_STORE>(Y, T, n, select_columns(Q), m, q_begin, q_end, 0, 0.0, out, q_begin, n, nullptr, nullptr, 0, s);
 }
 
 int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s) {
@@ -372,11 +352,11 @@ int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out
     double *slab = hist && plan.slab ? (double *)cv.take((size_t)n * (size_t)n * 8) : nullptr;
     if (!hist || (plan.slab && !slab)) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_curve_sqdist_min_workspace_bytes)");
     u64 *state = hist + CD_BINS;
-    const CdPanel pan{Y, n, nullptr};
+    const CurveSel all = select_sample(nullptr);
     hipLaunchKernelGGL(cd_select_init_kernel, dim3(1), dim3(256), 0, s, hist, state, k);
     SD_HIP(hipGetLastError());
     if (slab) {
-        int rc = cd_launch_tiles<CD_STORE>(Y, T, n, pan, 0, n, 1, 0.0, slab, 0, n, nullptr, nullptr, 0, s);
+        int rc = cd_launch_tiles<CD_STORE>(Y, T, n, all, n, 0, n, 1, 0.0, slab, 0, n, nullptr, nullptr, 0, s);
         if (rc) return rc;
     }
     for (int pass = 0; pass < CD_PASSES; ++pass) {
@@ -386,7 +366,7 @@ int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out
                                cd_pass_bits(pass));
             SD_HIP(hipGetLastError());
         } else {
-            int rc = cd_launch_tiles<CD_HIST>(Y, T, n, pan, 0, n, 1, 0.0, nullptr, 0, 0, hist, state, pass, s);
+            int rc = cd_launch_tiles<CD_HIST>(Y, T, n, all, n, 0, n, 1, 0.0, nullptr, 0, 0, hist, state, pass, s);
             if (rc) return rc;
         }
         hipLaunchKernelGGL(cd_pick_kernel, dim3(1), dim3(256), 0, s, hist, state, cd_pass_shift(pass), pass == CD_PASSES - 1 ? 1 : 0, out);

@@ -1,8 +1,9 @@
 // curve_routes.h -- the curve depths on K14's pair image (K14 rank depths, K15 extremal depth, K17 total variation depth):
 // their one route rule, the plan of stage 1 that the size functions and the launchers read, and each family's own plan
-// built on it; and the batch plans of K20, the squared L2 distances of curves, of K21, the functional spatial depth on them,
-// and of K22, the lune depths on their matrix, which read the doubles (internal; the K1+K2 rank routes: rank_routes.h, the
-// strict path's: strict_routes.h).
+// built on it; and the metric depths, which read the doubles: K20, the squared L2 distances of curves, K21, the functional
+// spatial depth on them, and K22, the lune depths on their matrix -- their one target selector, their one plan over blocks of
+// targets and the two walks of their launchers (internal; the K1+K2 rank routes: rank_routes.h, the strict path's:
+// strict_routes.h).
 #pragma once
 #include "sd_common.h"
 
@@ -71,8 +72,62 @@ TvdPlan tvd_plan(i64 T, i64 n, i64 m, int route, PlanSize size);
 int launch_tvd_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *sd_sum, double *shape,
                     u32 *counts, void *ws, size_t ws_bytes, hipStream_t s);
 
-// ---- K20 squared L2 distances of curves, their k-th smallest and the h-modal sums (curve_dist.hip).  These read the doubles,
-// not the pair image; the plan is over blocks of 128 targets and is sized by PlanSize with its rows read as targets. ----
+// ---- The metric depths of curves: K20, K21 and K22 read the doubles, not the pair image.  What they share: ----
+// The targets of a call: sample curves (targets null: all in order, m == n) or the m columns of Q (T x m, time-major dense).  The
+// kernels take the panel as plain arguments and read the value (t, q) at P[t * ldp + (targets ? targets[q] : q)].
+struct CurveSel {
+    const double *Q;
+    const i64 *targets;
+    const double *panel(const double *Y) const { return Q ? Q : Y; }   // P
+    i64 ld(i64 n, i64 m) const { return Q ? m : n; }                    // ldp
+};
+static inline CurveSel select_sample(const i64 *targets) { return CurveSel{nullptr, targets}; }
+static inline CurveSel select_columns(const double *Q) { return CurveSel{Q, nullptr}; }
+
+// The plan of a batch is over whole blocks of CV_BLOCK targets, the target tile of every kernel of the three, and is sized by
+// PlanSize with its rows read as targets: all blocks of the m (at least one), as many as keep the `capped` bytes of a block
+// within `cap`; by rows the blocks that hold them, by bytes those that fit at `block` bytes each behind `fixed`.  blocks == 0:
+// below one block.
+constexpr int CV_BLOCK = 128;
+struct TargetBlocks {
+    i64 blocks, targets;                                            // per batch
+};
+static inline TargetBlocks target_block_plan(i64 m, PlanSize size, size_t block, size_t capped, size_t cap, size_t fixed = 0) {
+    i64 most = (m + CV_BLOCK - 1) / CV_BLOCK;
+    const i64 within = (i64)(cap / capped);
+    most = most < within ? most : within;
+    most = most < 1 ? 1 : most;
+    i64 blocks = size.rows ? (size.rows + CV_BLOCK - 1) / CV_BLOCK : size.bytes < fixed ? 0 : (i64)((size.bytes - fixed) / block);
+    blocks = blocks < most ? blocks : most;
+    if (blocks < 1) return {0, 0};
+    return {blocks, blocks * CV_BLOCK < m ? blocks * CV_BLOCK : m};
+}
+// run(q, count) for the batches [q, q + count) of the targets [0, m), `targets` a batch; the first failure ends the walk
+template <typename Run>
+static inline int for_target_batches(i64 m, i64 targets, Run run) {
+    for (i64 q = 0; q < m; q += targets) {
+        const int rc = run(q, m - q < targets ? m - q : targets);
+        if (rc) return rc;
+    }
+    return SD_OK;
+}
+// run(q, tb) for the launches over the targets [q_begin, q_end): tb whole blocks from target q on, as many as keep a grid of
+// `groups` workgroups a block within CV_LAUNCH_GROUPS, at least one
+constexpr i64 CV_LAUNCH_GROUPS = (i64)1 << 30;
+template <typename Run>
+static inline int for_block_launches(i64 q_begin, i64 q_end, i64 groups, Run run) {
+    i64 per = CV_LAUNCH_GROUPS / groups;                            // target blocks of a launch
+    per = per < 1 ? 1 : per;
+    for (i64 q = q_begin; q < q_end; q += per * CV_BLOCK) {
+        const i64 left = (q_end - q + CV_BLOCK - 1) / CV_BLOCK;
+        const int rc = run(q, left < per ? left : per);
+        if (rc) return rc;
+    }
+    return SD_OK;
+}
+
+// ---- K20 squared L2 distances of curves, their k-th smallest and the h-modal sums (curve_dist.hip).  Only the h-modal sums
+// have a plan over blocks: the tiles' partial sums of a batch. ----
 constexpr int CD_WHAT_SQDIST = 0, CD_WHAT_HMODAL = 1, CD_WHAT_SELECT = 2;   // what a call forms: the `what` of the size functions
 struct CurveDistPlan {
     int what;
@@ -81,19 +136,17 @@ struct CurveDistPlan {
     size_t bytes;                                                   // SQDIST: none; HMODAL: the partial sums of a batch;
 };                                                                  // SELECT: histogram and state, then the slab
 CurveDistPlan curve_dist_plan(int what, i64 n, i64 m, PlanSize size);
-// Q null: the targets are sample curves (targets null: all, m == n); else the m columns of Q (T x m, time-major dense)
-int launch_curve_sqdist(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, hipStream_t s);
-int launch_hmodal_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double g, double *out, void *ws,
-                       size_t ws_bytes, hipStream_t s);
+int launch_curve_sqdist(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double *out, hipStream_t s);
+int launch_hmodal_sums(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double g, double *out, void *ws, size_t ws_bytes,
+                       hipStream_t s);
 int launch_curve_sqdist_select(const double *Y, i64 T, i64 n, u64 k, double *out, void *ws, size_t ws_bytes, hipStream_t s);
 // K21's pass 1 (the tile kernel's fourth epilogue): W[j * ldw + (q - q_begin)] = 1 / sqrt(D2[q][j]), 0.0 where D2 == 0.0, for the
 // targets [q_begin, q_end) of the m; ldw a multiple of 128 that holds them, W 16-byte aligned
-int launch_curve_weights(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, i64 q_begin, i64 q_end, double *W,
-                         i64 ldw, hipStream_t s);
+int launch_curve_weights(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, i64 q_begin, i64 q_end, double *W, i64 ldw, hipStream_t s);
 
 // ---- K21 functional spatial depth of curves (spatial_depth.hip): out[q] = S = |E[q]|^2, E[q][t] = sum_j w[q][j] (x[t] - Y[t][j]);
-// field (null or m x T, target-major) = E.  The plan is over blocks of 128 targets, sized by PlanSize with its rows read as
-// targets: the weights of a batch (n x targets, 8 n bytes a target) and its field (8 T bytes a target). ----
+// field (null or m x T, target-major) = E.  The plan's blocks: the weights of a batch (n x targets, 8 n bytes a target) and its
+// field (8 T bytes a target). ----
 struct SpatialPlan {
     i64 targets;                                                    // per batch; 0: below the floor
     size_t weights, field;                                          // bytes of the two parts
@@ -103,13 +156,13 @@ SpatialPlan spatial_plan(i64 T, i64 n, i64 m, PlanSize size);
 // timepoints of the sum kernel's tile for a batch of `targets` targets on `cus` compute units: 64, or 32 where the 128 x 64
 // tile would give fewer than two workgroups per unit
 int spatial_time_tile(i64 T, i64 targets, i64 cus);
-int launch_spatial_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, double *field,
-                        void *ws, size_t ws_bytes, hipStream_t s);
+int launch_spatial_sums(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double *out, double *field, void *ws, size_t ws_bytes,
+                        hipStream_t s);
 
 // ---- K22 lens, spherical and beta-skeleton depth of curves (lens_depth.hip): out[q] = G = #{i < j : a + kappa b <= c and
-// b + kappa a <= c}, a = D2(q, i), b = D2(q, j), c = D2(i, j) on K20's bits.  The plan: the n x n matrix, then the rows of a
-// batch of external targets, whole blocks of 128 (8 n bytes a target), sized by PlanSize with its rows read as targets.
-// Sample targets read their rows from the matrix and go in one batch whatever the plan says. ----
+// b + kappa a <= c}, a = D2(q, i), b = D2(q, j), c = D2(i, j) on K20's bits.  The plan: the n x n matrix in front, then the blocks:
+// the rows of a batch of external targets (8 n bytes a target).  Sample targets read their rows from the matrix and go in one
+// batch whatever the plan says. ----
 constexpr i64 LN_MAX_N = 16384;                                     // the stored matrix is 2 GiB there; the caller checks
 struct LensPlan {
     i64 targets;                                                    // external targets per batch; 0: below the floor
@@ -123,7 +176,7 @@ int lens_form(double kappa, int algo);
 i64 lens_span(i64 n, i64 targets);
 // K20's external distances of the targets [q_begin, q_end) of the m columns of Q: out[(q - q_begin) * n + j]
 int launch_curve_sqdist_rows(const double *Y, i64 T, i64 n, const double *Q, i64 m, i64 q_begin, i64 q_end, double *out, hipStream_t s);
-int launch_lens_counts(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double kappa, int algo, i64 *out,
-                       void *ws, size_t ws_bytes, hipStream_t s);
+int launch_lens_counts(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double kappa, int algo, i64 *out, void *ws, size_t ws_bytes,
+                       hipStream_t s);
 
 }  // namespace sd

@@ -42,18 +42,17 @@
 //   lens_count_kernel<LN_LENS>     129 VGPRs, 3 waves a SIMD
 //   lens_count_kernel<LN_SPHERE>   131 VGPRs, 3 waves a SIMD
 //   lens_count_kernel<LN_GENERAL>  211 VGPRs, 2 waves a SIMD   (the second register tile, kappa * a)
-// The plan (lens_plan): the matrix, 8 n^2 bytes, then the rows of a batch of whole blocks of 128 external targets; sample
-// targets use no rows.
+// The plan (lens_plan): the matrix, 8 n^2 bytes, then the rows of a batch of external targets in the blocks of curve_routes.h;
+// sample targets use no rows.
 #include "curve_routes.h"
 
 namespace sd {
 
-constexpr int LN_TILE = 128, LN_COLS = 64;                          // targets of a block; sample curves of a tile (i and j alike)
+constexpr int LN_TILE = CV_BLOCK, LN_COLS = 64;                     // targets of a block; sample curves of a tile (i and j alike)
 constexpr int LN_JK = 16, LN_THREADS = 256, LN_R = LN_TILE / 16, LN_C = LN_COLS / 16;
 constexpr int LN_LDB = LN_TILE + 2;                                 // row of the targets' panel in LDS
 constexpr int LN_LENS = 0, LN_SPHERE = 1, LN_GENERAL = 2;
 constexpr size_t LN_ROWS_MAX = (size_t)1 << 30;                     // external rows of a batch (recommended size and launch)
-constexpr i64 LN_LAUNCH_GROUPS = (i64)1 << 30;                      // workgroups of one launch
 constexpr i64 LN_GROUPS_WANTED = 8192;                              // lens_span: workgroups (half of them empty) to aim for
 
 static inline i64 ln_tiles(i64 n) { return (n + LN_COLS - 1) / LN_COLS; }
@@ -175,15 +174,10 @@ LensPlan lens_plan(i64 n, i64 m, PlanSize size) {
     LensPlan p{0, 0, 0, 0};
     p.matrix = align_up((size_t)n * (size_t)n * 8, 256);
     const size_t rb = (size_t)LN_TILE * (size_t)n * 8;              // the rows of 128 external targets; a multiple of 256
-    i64 most = (m + LN_TILE - 1) / LN_TILE;                         // blocks of a batch: all, within the cap, at least one
-    const i64 cap = (i64)(LN_ROWS_MAX / rb);
-    most = most < cap ? most : cap;
-    most = most < 1 ? 1 : most;
-    i64 blocks = size.rows ? (size.rows + LN_TILE - 1) / LN_TILE : size.bytes < p.matrix ? 0 : (i64)((size.bytes - p.matrix) / rb);
-    blocks = blocks < most ? blocks : most;
-    if (blocks < 1) return p;
-    p.targets = blocks * LN_TILE < m ? blocks * LN_TILE : m;
-    p.rows = (size_t)blocks * rb;
+    const TargetBlocks b = target_block_plan(m, size, rb, rb, LN_ROWS_MAX, p.matrix);   // bytes below the matrix: no block
+    if (b.blocks < 1) return p;
+    p.targets = b.targets;
+    p.rows = (size_t)b.blocks * rb;
     p.bytes = p.matrix + p.rows;
     return p;
 }
@@ -196,20 +190,17 @@ i64 lens_span(i64 n, i64 targets) {
 }
 
 // ---------------------------------------------------------------------------------------------- host
-// the counts of the targets [q_begin, q_end) into out (zeroed by the caller), in launches of at most LN_LAUNCH_GROUPS workgroups
+// the counts of the targets [q_begin, q_end) into out (zeroed by the caller), nt * ng workgroups a target block
 template <int FORM>
 static int ln_launch(const double *D, i64 n, const double *R, const i64 *targets, i64 q_begin, i64 q_end, double kappa, i64 *out,
                      hipStream_t s) {
     const i64 nt = ln_tiles(n), span = lens_span(n, q_end - q_begin), ng = (nt + span - 1) / span;
-    i64 per = LN_LAUNCH_GROUPS / (nt * ng);                         // target blocks of a launch
-    per = per < 1 ? 1 : per;
-    for (i64 q = q_begin; q < q_end; q += per * LN_TILE) {
-        const i64 left = (q_end - q + LN_TILE - 1) / LN_TILE, tb = left < per ? left : per;
+    return for_block_launches(q_begin, q_end, nt * ng, [&](i64 q, i64 tb) -> int {
         hipLaunchKernelGGL(lens_count_kernel<FORM>, dim3((unsigned)(tb * nt * ng)), dim3(LN_THREADS), 0, s, D, n, R, targets, q_begin, q,
                            q_end, nt, ng, span, kappa, (unsigned long long *)out);
         SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
+        return SD_OK;
+    });
 }
 
 static int ln_launch_form(int form, const double *D, i64 n, const double *R, const i64 *targets, i64 q_begin, i64 q_end, double kappa,
@@ -221,24 +212,22 @@ static int ln_launch_form(int form, const double *D, i64 n, const double *R, con
 
 int lens_form(double kappa, int algo) { return algo == 1 ? LN_GENERAL : kappa == 0.0 ? LN_LENS : kappa == 1.0 ? LN_SPHERE : LN_GENERAL; }
 
-int launch_lens_counts(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double kappa, int algo, i64 *out,
-                       void *ws, size_t ws_bytes, hipStream_t s) {
+int launch_lens_counts(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double kappa, int algo, i64 *out, void *ws, size_t ws_bytes,
+                       hipStream_t s) {
     const LensPlan plan = lens_plan(n, m, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);
     double *D = plan.targets > 0 ? (double *)cv.take(plan.matrix) : nullptr;
     double *A = D ? (double *)cv.take(plan.rows) : nullptr;
     if (!D || !A) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_lens_min_workspace_bytes)");
     const int form = lens_form(kappa, algo);
-    int rc = launch_curve_sqdist(Y, T, n, nullptr, nullptr, n, D, s);
+    int rc = launch_curve_sqdist(Y, T, n, select_sample(nullptr), n, D, s);
     if (rc) return rc;
     SD_HIP(hipMemsetAsync(out, 0, (size_t)m * 8, s));
-    if (!Q) return ln_launch_form(form, D, n, D, targets, 0, m, kappa, out, s);   // targets null: all in order, row q of D
-    for (i64 q = 0; q < m; q += plan.targets) {
-        const i64 count = m - q < plan.targets ? m - q : plan.targets;
-        if ((rc = launch_curve_sqdist_rows(Y, T, n, Q, m, q, q + count, A, s))) return rc;
-        if ((rc = ln_launch_form(form, D, n, A, nullptr, q, q + count, kappa, out, s))) return rc;
-    }
-    return SD_OK;
+    if (!sel.Q) return ln_launch_form(form, D, n, D, sel.targets, 0, m, kappa, out, s);   // targets null: all in order, row q of D
+    return for_target_batches(m, plan.targets, [&](i64 q, i64 count) -> int {
+        const int rc = launch_curve_sqdist_rows(Y, T, n, sel.Q, m, q, q + count, A, s);
+        return rc ? rc : ln_launch_form(form, D, n, A, nullptr, q, q + count, kappa, out, s);
+    });
 }
 
 }  // namespace sd

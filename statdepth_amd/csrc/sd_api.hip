@@ -142,6 +142,22 @@ static int launch_curve_dist(const double *X, i64 T, i64 n, i64 st, i64 sn, i64 
     return launch_time_major(X, T, n, st, sn, ws, ws_bytes, floor, "sd_curve_sqdist_min_workspace_bytes", stream, launch);
 }
 
+// The three size functions of a metric depth of curves (K20 to K22), from `sized` (does it take the shape and the number of targets?) and plan(PlanSize),
+// its plan of what lies behind the time-major copy: the recommended size holds all targets, the floor one block.
+template <typename Plan>
+static size_t metric_workspace_bytes(bool sized, i64 T, i64 n, i64 st, i64 sn, i64 m, Plan plan) {
+    return sized ? time_major_bytes(T, n, st, sn) + plan(PlanSize::of_rows(m > n ? m : n)).bytes : 0;
+}
+template <typename Plan>
+static size_t metric_min_workspace_bytes(bool sized, i64 T, i64 n, i64 st, i64 sn, i64 m, Plan plan) {
+    return sized && m != 0 ? time_major_bytes(T, n, st, sn) + plan(PlanSize::of_rows(1)).bytes : 0;
+}
+template <typename Plan>
+static i64 metric_targets_per_batch(bool sized, i64 T, i64 n, i64 st, i64 sn, size_t ws_bytes, Plan plan) {
+    const size_t tm = sized ? time_major_bytes(T, n, st, sn) : 0;
+    return sized && ws_bytes >= tm ? plan(PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+}
+
 // wide[i] (two 64-bit limbs) (+)= part[i]: the chunk totals of sd_mbd_counts_wide
 __global__ void wide_add_kernel(const u64 *__restrict__ part, i64 count, u64 *__restrict__ wide, int first) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1098,29 +1114,24 @@ static bool curve_dist_sized(i64 T, i64 n, i64 m, int what) {
 }
 
 size_t sd_curve_sqdist_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what) {
-    if (!curve_dist_sized(T, n, m, what)) return 0;
-    return time_major_bytes(T, n, st, sn) + curve_dist_plan(what, n, m, PlanSize::of_rows(m > n ? m : n)).bytes;
+    return metric_workspace_bytes(curve_dist_sized(T, n, m, what), T, n, st, sn, m, [&](PlanSize z) { return curve_dist_plan(what, n, m, z); });
 }
 
 size_t sd_curve_sqdist_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what) {
-    if (!curve_dist_sized(T, n, m, what) || m == 0) return 0;
-    return time_major_bytes(T, n, st, sn) + curve_dist_plan(what, n, m, PlanSize::of_rows(1)).bytes;
+    return metric_min_workspace_bytes(curve_dist_sized(T, n, m, what), T, n, st, sn, m, [&](PlanSize z) { return curve_dist_plan(what, n, m, z); });
 }
 
 int64_t sd_curve_sqdist_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, int what, size_t ws_bytes) {
-    if (!curve_dist_sized(T, n, m, what)) return 0;
-    const size_t tm = time_major_bytes(T, n, st, sn);
-    return ws_bytes >= tm ? curve_dist_plan(what, n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+    return metric_targets_per_batch(curve_dist_sized(T, n, m, what), T, n, st, sn, ws_bytes, [&](PlanSize z) { return curve_dist_plan(what, n, m, z); });
 }
 
-// the refusals of the five entry points, in sd_tvd_sums' order: pointers, shape, size, matrix, work
-// (external: the targets are the m columns of Q, any m >= 0)
-static int check_curve_dist(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64 *targets, i64 m, bool external, const void *out,
-                            double passes) {
+// the refusals of K20's and K21's entry points, in sd_tvd_sums' order: pointers, shape, size, matrix, work
+// (the columns of Q: any m >= 0)
+static int check_curve_dist(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, const void *out, double passes) {
     if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
     if (n < 2) return fail(SD_ERR_UNSUPPORTED, "distances between curves need at least two curves, got %lld", (long long)n);
-    int rc = external ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, targets, m);
+    int rc = sel.Q ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, sel.targets, m);
     if (rc) return rc;
     if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
     const double work = passes * (double)n * (double)m * (double)T;
@@ -1133,26 +1144,29 @@ static int check_bandwidth_factor(double g) {
                                                       : fail(SD_ERR_INVALID, "g = 1 / (2 h^2) must be positive and finite, got %g", g);
 }
 
-int sd_curve_sqdist(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
-                    void *ws, size_t ws_bytes, void *stream) {
-    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 1.0);
+// Each pair of entry points, sample targets and columns of Q, is one function of the selector.
+static int curve_sqdist_of(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, double *out, void *ws, size_t ws_bytes,
+                           void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, sel, m, out, 1.0);
     if (rc || m == 0) return rc;
     return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_SQDIST, ws, ws_bytes, stream,
-                             [&](const double *Y, void *, size_t, hipStream_t s) { return launch_curve_sqdist(Y, T, n, nullptr, targets, m, out, s); });
+                             [&](const double *Y, void *, size_t, hipStream_t s) { return launch_curve_sqdist(Y, T, n, sel, m, out, s); });
+}
+
+int sd_curve_sqdist(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    void *ws, size_t ws_bytes, void *stream) {
+    return curve_sqdist_of(X, T, n, st, sn, select_sample(targets), m, out, ws, ws_bytes, stream);
 }
 
 int sd_curve_sqdist_external(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
                              void *ws, size_t ws_bytes, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 1.0);
-    if (rc || m == 0) return rc;
-    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_SQDIST, ws, ws_bytes, stream,
-                             [&](const double *Y, void *, size_t, hipStream_t s) { return launch_curve_sqdist(Y, T, n, Q, nullptr, m, out, s); });
+    return curve_sqdist_of(X, T, n, st, sn, select_columns(Q), m, out, ws, ws_bytes, stream);
 }
 
 int sd_curve_sqdist_select(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, double *out, void *ws,
                            size_t ws_bytes, void *stream) {
-    int rc = check_curve_dist(X, T, n, st, sn, nullptr, n, false, out, 3.0);                        // six passes over half the pairs
+    int rc = check_curve_dist(X, T, n, st, sn, select_sample(nullptr), n, out, 3.0);                // six passes over half the pairs
     if (rc) return rc;
     const i64 N = n * (n - 1) / 2;
     if (k < 1 || k > N) return fail(SD_ERR_INVALID, "k=%lld outside [1, %lld], the pairs of %lld curves", (long long)k, (long long)N, (long long)n);
@@ -1161,23 +1175,24 @@ int sd_curve_sqdist_select(const double *X, int64_t T, int64_t n, int64_t st, in
     });
 }
 
-int sd_hmodal_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double g,
-                   double *out, void *ws, size_t ws_bytes, void *stream) {
-    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 1.0);
+static int hmodal_sums_of(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, double g, double *out, void *ws,
+                          size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, sel, m, out, 1.0);
     if (rc || (rc = check_bandwidth_factor(g)) || m == 0) return rc;
     return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_HMODAL, ws, ws_bytes, stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-        return launch_hmodal_sums(Y, T, n, nullptr, targets, m, g, out, w, bytes, s);
+        return launch_hmodal_sums(Y, T, n, sel, m, g, out, w, bytes, s);
     });
+}
+
+int sd_hmodal_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double g,
+                   double *out, void *ws, size_t ws_bytes, void *stream) {
+    return hmodal_sums_of(X, T, n, st, sn, select_sample(targets), m, g, out, ws, ws_bytes, stream);
 }
 
 int sd_hmodal_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double g,
                             double *out, void *ws, size_t ws_bytes, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 1.0);
-    if (rc || (rc = check_bandwidth_factor(g)) || m == 0) return rc;
-    return launch_curve_dist(X, T, n, st, sn, m, CD_WHAT_HMODAL, ws, ws_bytes, stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-        return launch_hmodal_sums(Y, T, n, Q, nullptr, m, g, out, w, bytes, s);
-    });
+    return hmodal_sums_of(X, T, n, st, sn, select_columns(Q), m, g, out, ws, ws_bytes, stream);
 }
 
 // ---- K21 ----
@@ -1186,19 +1201,15 @@ static bool spatial_sized(i64 T, i64 n, i64 m) {
 }
 
 size_t sd_spatial_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
-    if (!spatial_sized(T, n, m)) return 0;
-    return time_major_bytes(T, n, st, sn) + spatial_plan(T, n, m, PlanSize::of_rows(m > n ? m : n)).bytes;
+    return metric_workspace_bytes(spatial_sized(T, n, m), T, n, st, sn, m, [&](PlanSize z) { return spatial_plan(T, n, m, z); });
 }
 
 size_t sd_spatial_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
-    if (!spatial_sized(T, n, m) || m == 0) return 0;
-    return time_major_bytes(T, n, st, sn) + spatial_plan(T, n, m, PlanSize::of_rows(1)).bytes;
+    return metric_min_workspace_bytes(spatial_sized(T, n, m), T, n, st, sn, m, [&](PlanSize z) { return spatial_plan(T, n, m, z); });
 }
 
 int64_t sd_spatial_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes) {
-    if (!spatial_sized(T, n, m)) return 0;
-    const size_t tm = time_major_bytes(T, n, st, sn);
-    return ws_bytes >= tm ? spatial_plan(T, n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+    return metric_targets_per_batch(spatial_sized(T, n, m), T, n, st, sn, ws_bytes, [&](PlanSize z) { return spatial_plan(T, n, m, z); });
 }
 
 int64_t sd_spatial_time_tile(int64_t T, int64_t targets, void *stream) {
@@ -1207,50 +1218,45 @@ int64_t sd_spatial_time_tile(int64_t T, int64_t targets, void *stream) {
 }
 
 // K20's refusals in K20's order; the two passes count 2 n m T pair-timepoints
-int sd_spatial_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
-                    double *field, void *ws, size_t ws_bytes, void *stream) {
-    int rc = check_curve_dist(X, T, n, st, sn, targets, m, false, out, 2.0);
+static int spatial_sums_of(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, double *out, double *field, void *ws,
+                           size_t ws_bytes, void *stream) {
+    int rc = check_curve_dist(X, T, n, st, sn, sel, m, out, 2.0);
     if (rc || m == 0) return rc;
     return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_spatial_min_workspace_bytes(T, n, st, sn, m),
                              "sd_spatial_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-                                 return launch_spatial_sums(Y, T, n, nullptr, targets, m, out, field, w, bytes, s);
+                                 return launch_spatial_sums(Y, T, n, sel, m, out, field, w, bytes, s);
                              });
+}
+
+int sd_spatial_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double *out,
+                    double *field, void *ws, size_t ws_bytes, void *stream) {
+    return spatial_sums_of(X, T, n, st, sn, select_sample(targets), m, out, field, ws, ws_bytes, stream);
 }
 
 int sd_spatial_external_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double *out,
                              double *field, void *ws, size_t ws_bytes, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_curve_dist(X, T, n, st, sn, nullptr, m, true, out, 2.0);
-    if (rc || m == 0) return rc;
-    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_spatial_min_workspace_bytes(T, n, st, sn, m),
-                             "sd_spatial_min_workspace_bytes", stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-                                 return launch_spatial_sums(Y, T, n, Q, nullptr, m, out, field, w, bytes, s);
-                             });
+    return spatial_sums_of(X, T, n, st, sn, select_columns(Q), m, out, field, ws, ws_bytes, stream);
 }
 
 // ---- K22 ----
 static bool lens_sized(i64 T, i64 n, i64 m) { return T >= 1 && n >= 2 && n <= LN_MAX_N && m >= 0 && T < ((i64)1 << 31); }
 
 size_t sd_lens_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
-    if (!lens_sized(T, n, m)) return 0;
-    return time_major_bytes(T, n, st, sn) + lens_plan(n, m, PlanSize::of_rows(m > 0 ? m : 1)).bytes;
+    return metric_workspace_bytes(lens_sized(T, n, m), T, n, st, sn, m, [&](PlanSize z) { return lens_plan(n, m, z); });
 }
 
 size_t sd_lens_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m) {
-    if (!lens_sized(T, n, m) || m == 0) return 0;
-    return time_major_bytes(T, n, st, sn) + lens_plan(n, m, PlanSize::of_rows(1)).bytes;
+    return metric_min_workspace_bytes(lens_sized(T, n, m), T, n, st, sn, m, [&](PlanSize z) { return lens_plan(n, m, z); });
 }
 
 int64_t sd_lens_targets_per_batch(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t m, size_t ws_bytes) {
-    if (!lens_sized(T, n, m)) return 0;
-    const size_t tm = time_major_bytes(T, n, st, sn);
-    return ws_bytes >= tm ? lens_plan(n, m, PlanSize::of_bytes(ws_bytes - tm)).targets : 0;
+    return metric_targets_per_batch(lens_sized(T, n, m), T, n, st, sn, ws_bytes, [&](PlanSize z) { return lens_plan(n, m, z); });
 }
 
-// K20's refusals in K20's order, with kappa and algo behind the shape and the matrix' cap behind the two curves; the budget
-// counts the matrix and the targets' rows, n (n + m) T pair-timepoints
-static int check_lens(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64 *targets, i64 m, bool external, const void *out,
-                      double kappa, int algo) {
+// K20's refusals, but in an order of their own that the refusal tests pin: m, kappa and algo behind the shape, the matrix' cap
+// behind the two curves; the budget counts the matrix and the targets' rows, n (n + m) T pair-timepoints
+static int check_lens(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, const void *out, double kappa, int algo) {
     if (!X || !out) return fail(SD_ERR_INVALID, "null pointer");
     if (T < 1 || n < 1) return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld): at least one timepoint", (long long)T, (long long)n);
     if (m < 0) return fail(SD_ERR_INVALID, "m < 0");
@@ -1260,32 +1266,32 @@ static int check_lens(const double *X, i64 T, i64 n, i64 st, i64 sn, const i64 *
     if (n > LN_MAX_N)
         return fail(SD_ERR_UNSUPPORTED, "the lune depths keep the n x n matrix of distances: at most %lld curves, got %lld",
                     (long long)LN_MAX_N, (long long)n);
-    int rc = external ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, targets, m);
+    int rc = sel.Q ? check_matrix(X, T, n, st, sn, nullptr, n) : check_matrix(X, T, n, st, sn, sel.targets, m);
     if (rc) return rc;
     const double work = (double)n * ((double)n + (double)m) * (double)T;
     if (work > HS_MAX_WORK) return fail(SD_ERR_UNSUPPORTED, "%.3g pair-timepoints exceed the cap of %.0e", work, HS_MAX_WORK);
     return SD_OK;
 }
 
-int sd_lens_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double kappa,
-                   int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
-    int rc = check_lens(X, T, n, st, sn, targets, m, false, out, kappa, algo);
+static int lens_counts_of(const double *X, i64 T, i64 n, i64 st, i64 sn, CurveSel sel, i64 m, double kappa, int algo, i64 *out, void *ws,
+                          size_t ws_bytes, void *stream) {
+    int rc = check_lens(X, T, n, st, sn, sel, m, out, kappa, algo);
     if (rc || m == 0) return rc;
     return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_lens_min_workspace_bytes(T, n, st, sn, m), "sd_lens_min_workspace_bytes",
                              stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-                                 return launch_lens_counts(Y, T, n, nullptr, targets, m, kappa, algo, out, w, bytes, s);
+                                 return launch_lens_counts(Y, T, n, sel, m, kappa, algo, out, w, bytes, s);
                              });
+}
+
+int sd_lens_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const int64_t *targets, int64_t m, double kappa,
+                   int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    return lens_counts_of(X, T, n, st, sn, select_sample(targets), m, kappa, algo, out, ws, ws_bytes, stream);
 }
 
 int sd_lens_external_counts(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *Q, int64_t m, double kappa,
                             int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
     if (!Q) return fail(SD_ERR_INVALID, "null pointer");
-    int rc = check_lens(X, T, n, st, sn, nullptr, m, true, out, kappa, algo);
-    if (rc || m == 0) return rc;
-    return launch_time_major(X, T, n, st, sn, ws, ws_bytes, sd_lens_min_workspace_bytes(T, n, st, sn, m), "sd_lens_min_workspace_bytes",
-                             stream, [&](const double *Y, void *w, size_t bytes, hipStream_t s) {
-                                 return launch_lens_counts(Y, T, n, Q, nullptr, m, kappa, algo, out, w, bytes, s);
-                             });
+    return lens_counts_of(X, T, n, st, sn, select_columns(Q), m, kappa, algo, out, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -38,7 +38,7 @@
 // workgroups share a CU, so the latency of a chunk's loads has to lie behind the arithmetic of the chunk before.  Measured
 // at 10 000 x 1 000: pass 2 takes 9.14 ms against 7.94 ms of the distance pass in the same run (DESIGN section 3 K21;
 // profiles/spatial_depth_times.txt).  Bounding <4> to 3 waves a SIMD (168 VGPRs) spills registers to scratch; it stays at 2.
-// The batch plan (spatial_plan) is over blocks of 128 targets: the weights of a batch, n x targets doubles, and its field,
+// The batch plan (spatial_plan), in the blocks of curve_routes.h: the weights of a batch, n x targets doubles, and its field,
 // targets x T doubles (with `field` given the kernel writes there and the plan's part stays unused).  The recommended size
 // holds all targets up to SP_WEIGHTS_MAX = 8 GiB of weights: at 100 000 x 256 that is 83 blocks a batch, 664 workgroups of
 // pass 2 at C = 2, more than two for each of the 256 CUs (1 GiB would give 10 blocks, 80 workgroups).
@@ -46,10 +46,9 @@
 
 namespace sd {
 
-constexpr int SP_TILE = 128;                                        // targets of a tile: the blocks of the plan, pass 1's tile
+constexpr int SP_TILE = CV_BLOCK;                                   // targets of a tile: the blocks of the plan, pass 1's tile
 constexpr int SP_JK = 16, SP_THREADS = 256, SP_R = SP_TILE / 16;    // sample curves of a chunk; targets of a thread
 constexpr size_t SP_WEIGHTS_MAX = (size_t)8 << 30;                  // weights of a batch (recommended size and launch)
-constexpr i64 SP_LAUNCH_TILES = (i64)1 << 30;                       // tiles of one launch
 
 // Targets [q_first + 128 (blockIdx.x / tt) ...) x timepoints [16 C (blockIdx.x % tt) ...).  P, ldp, targets: the targets'
 // panel, value (t, q) = P[t * ldp + (targets ? targets[q] : q)].  q_end: one past the last target.  row0: the batch's first
@@ -154,16 +153,11 @@ __global__ __launch_bounds__(256) void sp_fold_kernel(const double *__restrict__
 SpatialPlan spatial_plan(i64 T, i64 n, i64 m, PlanSize size) {
     SpatialPlan p{0, 0, 0, 0};
     const size_t wb = (size_t)SP_TILE * (size_t)n * 8, fb = (size_t)SP_TILE * (size_t)T * 8;   // of 128 targets; multiples of 256
-    i64 most = (m + SP_TILE - 1) / SP_TILE;                         // blocks of a batch: all, within the cap, at least one
-    const i64 cap = (i64)(SP_WEIGHTS_MAX / wb);
-    most = most < cap ? most : cap;
-    most = most < 1 ? 1 : most;
-    i64 blocks = size.rows ? (size.rows + SP_TILE - 1) / SP_TILE : (i64)(size.bytes / (wb + fb));
-    blocks = blocks < most ? blocks : most;
-    if (blocks < 1) return p;
-    p.targets = blocks * SP_TILE < m ? blocks * SP_TILE : m;
-    p.weights = (size_t)blocks * wb;
-    p.field = (size_t)blocks * fb;
+    const TargetBlocks b = target_block_plan(m, size, wb + fb, wb, SP_WEIGHTS_MAX);
+    if (b.blocks < 1) return p;
+    p.targets = b.targets;
+    p.weights = (size_t)b.blocks * wb;
+    p.field = (size_t)b.blocks * fb;
     p.bytes = p.weights + p.field;
     return p;
 }
@@ -175,43 +169,36 @@ int spatial_time_tile(i64 T, i64 targets, i64 cus) {
 
 // ---------------------------------------------------------------------------------------------- host
 template <int C>
-static int sp_launch_tiles(const double *Y, i64 T, i64 n, const double *P, i64 ldp, const i64 *targets, i64 q_begin, i64 q_end,
-                           const double *W, i64 ldw, double *E, hipStream_t s) {
-    const i64 tt = (T + 16 * C - 1) / (16 * C);
-    i64 per = SP_LAUNCH_TILES / tt;                                 // target blocks of a launch
-    per = per < 1 ? 1 : per;
-    for (i64 q = q_begin; q < q_end; q += per * SP_TILE) {
-        const i64 left = (q_end - q + SP_TILE - 1) / SP_TILE, tb = left < per ? left : per;
-        hipLaunchKernelGGL(sp_sum_kernel<C>, dim3((unsigned)(tb * tt)), dim3(SP_THREADS), 0, s, Y, T, n, P, ldp, targets, q, q_end, tt,
-                           q_begin, W, ldw, E, T);
+static int sp_launch_tiles(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, i64 q_begin, i64 q_end, const double *W, i64 ldw,
+                           double *E, hipStream_t s) {
+    const i64 tt = (T + 16 * C - 1) / (16 * C);                     // time tiles of a target block
+    return for_block_launches(q_begin, q_end, tt, [&](i64 q, i64 tb) -> int {
+        hipLaunchKernelGGL(sp_sum_kernel<C>, dim3((unsigned)(tb * tt)), dim3(SP_THREADS), 0, s, Y, T, n, sel.panel(Y), sel.ld(n, m),
+                           sel.targets, q, q_end, tt, q_begin, W, ldw, E, T);
         SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
+        return SD_OK;
+    });
 }
 
-int launch_spatial_sums(const double *Y, i64 T, i64 n, const double *Q, const i64 *targets, i64 m, double *out, double *field,
-                        void *ws, size_t ws_bytes, hipStream_t s) {
+int launch_spatial_sums(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double *out, double *field, void *ws, size_t ws_bytes,
+                        hipStream_t s) {
     const SpatialPlan plan = spatial_plan(T, n, m, PlanSize::of_bytes(ws_bytes));
     Carver cv(ws, ws_bytes);
     double *W = plan.targets > 0 ? (double *)cv.take(plan.weights) : nullptr;
     double *F = W ? (double *)cv.take(plan.field) : nullptr;
     if (!W || !F) return fail(SD_ERR_WORKSPACE, "workspace too small (sd_spatial_min_workspace_bytes)");
-    const double *P = Q ? Q : Y;
-    const i64 ldp = Q ? m : n, ldw = (plan.targets + SP_TILE - 1) / SP_TILE * SP_TILE;
-    const i64 cus = stream_cus(s);
-    for (i64 q = 0; q < m; q += plan.targets) {
-        const i64 count = m - q < plan.targets ? m - q : plan.targets;
-        int rc = launch_curve_weights(Y, T, n, Q, targets, m, q, q + count, W, ldw, s);
+    const i64 ldw = (plan.targets + SP_TILE - 1) / SP_TILE * SP_TILE, cus = stream_cus(s);
+    return for_target_batches(m, plan.targets, [&](i64 q, i64 count) -> int {
+        int rc = launch_curve_weights(Y, T, n, sel, m, q, q + count, W, ldw, s);
         if (rc) return rc;
         double *E = field ? field + q * T : F;
-        const i64 *tg = Q ? nullptr : targets;
-        rc = spatial_time_tile(T, count, cus) == 64 ? sp_launch_tiles<4>(Y, T, n, P, ldp, tg, q, q + count, W, ldw, E, s)
-                                                    : sp_launch_tiles<2>(Y, T, n, P, ldp, tg, q, q + count, W, ldw, E, s);
+        rc = spatial_time_tile(T, count, cus) == 64 ? sp_launch_tiles<4>(Y, T, n, sel, m, q, q + count, W, ldw, E, s)
+                                                    : sp_launch_tiles<2>(Y, T, n, sel, m, q, q + count, W, ldw, E, s);
         if (rc) return rc;
         hipLaunchKernelGGL(sp_fold_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, E, count, T, T, out + q);
         SD_HIP(hipGetLastError());
-    }
-    return SD_OK;
+        return SD_OK;
+    });
 }
 
 }  // namespace sd

@@ -249,11 +249,12 @@ def mbd_counts_range(X, target_begin, m, J=2, algo="auto", device=None, return_t
     return _mbd_counts(lib, lib.sd_mbd_counts_range, M, int(target_begin), int(m), J, algo, return_tensor)
 
 
-def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strided=False, second=None):
-    """fn(X, T, n, Q, m, *extra, out, ws, ws_bytes, stream) for the m columns of Q (T x m) against the n columns of X.
-    out: (m, *cols), int64 or `dtype`; ws_bytes(T, n, m): the workspace size.  strided: fn takes (st, sn) behind n.
-    second: None, or the trailing shape(T, n, m) of a second output (m, *shape) of out's dtype that fn takes behind out (a
-    shape of None: fn gets NULL there); the pair is then returned, the second None where it was not asked for."""
+def _external_curves(fn, X, Q, device, *extra, outputs, ws_bytes=None, family=None, variant=None):
+    """fn(X, T, n, [st, sn,] Q, m, *extra, *outputs, ws, ws_bytes, stream) for the m columns of Q (T x m) against the n columns
+    of X, which goes up time-major.  outputs(t, dev, T, n, m): the output tensors in the order of the C signature, None for one
+    not asked for (fn gets NULL there); returned as ndarrays.  family None: ws_bytes(T, n, m) is the workspace size.  A
+    family of _CURVE_FAMILIES: fn takes (st, sn) behind n, and ws_bytes is the size to run with (None: what the family
+    recommends for `variant`)."""
     t = torch()
     dev = _device(device)
     Xd, Qd = _upload(X, 2, dev), _upload(Q, 2, dev)
@@ -261,30 +262,32 @@ def _external_curves(fn, cols, X, Q, device, *extra, ws_bytes, dtype=None, strid
     if Qd.shape[0] != T:
         raise ValueError("Q must have the same number of timepoints as X")
     m = Qd.shape[1]
-    out = t.empty((m, *cols), dtype=t.int64 if dtype is None else dtype, device=dev)
-    strides = (n, 1) if strided else ()
-    shape = second(T, n, m) if second is not None else None
-    more = t.empty((m, *shape), dtype=out.dtype, device=dev) if shape is not None else None
-    tail = () if second is None else (_OUT, more.data_ptr() if more is not None and more.numel() else None)
-    first = _launch(dev, fn, out, Xd.data_ptr(), T, n, *strides, Qd.data_ptr(), m, *extra, *tail,
-                    workspace=lambda: _sized(dev, ws_bytes(T, n, m)))
-    if second is None:
-        return first
-    return first, more.cpu().numpy() if more is not None else None
+    outs = outputs(t, dev, T, n, m)
+    if family is None:
+        strides, size = (), lambda: ws_bytes(T, n, m)
+    else:
+        strides = (n, 1)
+        size = lambda: _curve_size(family, "workspace_bytes", T, n, strides, m, variant) if ws_bytes is None else ws_bytes
+    _launch(dev, fn, outs[0], Xd.data_ptr(), T, n, *strides, Qd.data_ptr(), m, *extra, _OUT,
+            *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
+            workspace=lambda: _sized(dev, size()), return_tensor=True)
+    return [o.cpu().numpy() if o is not None else None for o in outs]
 
 
 def mbd_external_counts(X, Q, J=2, device=None):
     """int64[m, J-1]: band totals of the m columns of Q (T x m) w.r.t. the n columns of X (sd_mbd_external_counts)."""
     lib = _lib()
-    return _external_curves(lib.sd_mbd_external_counts, (J - 1,), X, Q, device, J,
-                            ws_bytes=lambda T, n, m: lib.sd_mbd_external_workspace_bytes(T, n, m, J) + 1024)
+    return _external_curves(lib.sd_mbd_external_counts, X, Q, device, J,
+                            outputs=lambda t, dev, T, n, m: [t.empty((m, J - 1), dtype=t.int64, device=dev)],
+                            ws_bytes=lambda T, n, m: lib.sd_mbd_external_workspace_bytes(T, n, m, J) + 1024)[0]
 
 
 def bd_strict_external_counts(X, Q, device=None):
     """int64[m]: pairs of X's n columns whose band contains column q of Q (T x m) at every t (sd_bd_strict_external_counts)."""
     lib = _lib()
-    return _external_curves(lib.sd_bd_strict_external_counts, (), X, Q, device,
-                            ws_bytes=lib.sd_bd_strict_external_workspace_bytes)
+    return _external_curves(lib.sd_bd_strict_external_counts, X, Q, device,
+                            outputs=lambda t, dev, T, n, m: [t.empty((m,), dtype=t.int64, device=dev)],
+                            ws_bytes=lib.sd_bd_strict_external_workspace_bytes)[0]
 
 
 def _subset_curves(fn, cols, X, members, targets, device, *extra, ws_bytes=None):
@@ -378,12 +381,26 @@ def bd_strict_counts(X, targets=None, J=2, device=None, workspace_budget=None):
 
 
 RANK_DEPTH_ALGOS = {"auto": 0, "image": 1, "sort": 2}
+TVD_ALGOS = {"auto": 0, "lds": 1, "pairwise": 2}
+CURVE_DIST_WHAT = {"sqdist": 0, "hmodal": 1, "select": 2}
+# The curve families with a workspace plan, by the prefix of sd_<family>_workspace_bytes, _min_workspace_bytes and
+# _<rows or targets>_per_batch: the names of the algo that follows m in these and in the family's entry points (None: it has
+# none), and whether a `what` of CURVE_DIST_WHAT follows m in the size functions alone.  The `variant` of the helpers below is
+# that algo or `what`.
+_CURVE_FAMILIES = {"rank_depth": (RANK_DEPTH_ALGOS, False), "extremal": (RANK_DEPTH_ALGOS, False), "tvd": (TVD_ALGOS, False),
+                   "curve_sqdist": (None, True), "spatial": (None, False), "lens": (None, False)}
 
 
-def _rank_depth_algo(algo):
-    if isinstance(algo, str) and algo not in RANK_DEPTH_ALGOS:
-        raise ValueError(f"algo must be one of {sorted(RANK_DEPTH_ALGOS)}, got {algo!r}")
-    return RANK_DEPTH_ALGOS[algo] if isinstance(algo, str) else int(algo)
+def _variant(family, variant):
+    """What follows m in the family's size functions: (the number of the algo or of the `what`,), or ()."""
+    algos, what = _CURVE_FAMILIES[family]
+    if what:
+        return (CURVE_DIST_WHAT[variant],)
+    if algos is None:
+        return ()
+    if isinstance(variant, str) and variant not in algos:
+        raise ValueError(f"algo must be one of {sorted(algos)}, got {variant!r}")
+    return (algos[variant] if isinstance(variant, str) else int(variant),)
 
 
 def _strides(T, n, curve_major):
@@ -391,28 +408,38 @@ def _strides(T, n, curve_major):
     return (1, T) if curve_major and T > 1 and n > 1 else (n, 1)
 
 
-def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs, sized_by=None):
-    """lib.sd_<family>_<what>(X, T, n, st, sn, targets, m, algo, *outputs, ws, ws_bytes, stream) with ws_bytes of workspace
-    (None: what sd_<family>_workspace_bytes recommends).  outputs(t, dev, M, m): the output tensors in the order of the C
-    signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays.
-    sized_by=(family, what): an entry point without an algo, whose workspace sd_<family>_workspace_bytes(..., what) sizes
-    (what None: the size function ends at m); `algo` is then the tuple of its own arguments between m and the outputs, passed
-    as they are (algo_of is not called)."""
+def _curve_size(family, name, T, n, strides, m, variant, *more):
+    """sd_<family>_<name>(T, n, st, sn, m, [algo or what,] *more); m None: all n."""
+    fn, T, n = getattr(_native.load(), f"sd_{family}_{name}"), int(T), int(n)
+    return int(fn(T, n, *strides, n if m is None else int(m), *_variant(family, variant), *more))
+
+
+def _curve_sizes(family, T, n, variant, curve_major, m=None):
+    """(recommended, floor) workspace sizes of the family for a T x n matrix and m targets."""
+    st = _strides(int(T), int(n), curve_major)
+    return tuple(_curve_size(family, name, T, n, st, m, variant) for name in ("workspace_bytes", "min_workspace_bytes"))
+
+
+def _curve_per_batch(family, unit, T, n, ws_bytes, variant, curve_major, m=None):
+    """The rows or targets (`unit`) a batch of the family takes with ws_bytes of workspace."""
+    return _curve_size(family, f"{unit}_per_batch", T, n, _strides(int(T), int(n), curve_major), m, variant, int(ws_bytes))
+
+
+def _curves(fn, family, variant, X, targets, device, own, ws_bytes, outputs):
+    """lib.<fn>(X, T, n, st, sn, targets, m, [algo,] *own, *outputs, ws, ws_bytes, stream) with ws_bytes of workspace (None:
+    what the family of _CURVE_FAMILIES recommends for `variant`).  algo: the variant's number, where the family has algos.
+    own: the call's own arguments between there and the outputs.  outputs(t, dev, M, m): the output tensors in the order of
+    the C signature, None for one not asked for; nothing is launched when the first has no rows.  Returns them as ndarrays."""
     t = torch()
     lib = _lib()
     M = to_device_matrix(X, device)
     dev = M.device
-    if sized_by is None:
-        a = algo_of(algo)
-        own = (a,)
-    else:
-        a, own = sized_by[1], tuple(algo)
+    algo = _variant(family, variant) if _CURVE_FAMILIES[family][0] is not None else ()
     td, m, tp = _targets_dev(targets, M.n, dev)
     outs = outputs(t, dev, M, m)
-    size = getattr(lib, f"sd_{family if sized_by is None else sized_by[0]}_workspace_bytes")
-    _launch(dev, getattr(lib, f"sd_{family}_{what}" if what else f"sd_{family}"), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st,
-            M.sn, tp, m, *own, _OUT, *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
-            workspace=lambda: _sized(dev, size(M.T, M.n, M.st, M.sn, m, *(() if a is None else (a,)))
+    _launch(dev, getattr(lib, fn), outs[0], M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, *algo, *own, _OUT,
+            *(o.data_ptr() if o is not None and o.numel() else None for o in outs[1:]),
+            workspace=lambda: _sized(dev, _curve_size(family, "workspace_bytes", M.T, M.n, (M.st, M.sn), m, variant)
                                      if ws_bytes is None else ws_bytes),
             return_tensor=True)
     return [o.cpu().numpy() if o is not None else None for o in outs]
@@ -421,19 +448,13 @@ def _curves(family, what, algo_of, X, targets, device, algo, ws_bytes, outputs, 
 def rank_depth_workspace_bytes(T, n, algo="auto", curve_major=False):
     """(recommended, floor) workspace sizes of sd_rank_depth_sums for a T x n matrix; the floor holds one row per batch.
     curve_major: the matrix is F-contiguous and takes a time-major copy in the workspace as well."""
-    lib = _native.load()
-    T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    st, sn = _strides(T, n, curve_major)
-    return (int(lib.sd_rank_depth_workspace_bytes(T, n, st, sn, n, a)),
-            int(lib.sd_rank_depth_min_workspace_bytes(T, n, st, sn, n, a)))
+    return _curve_sizes("rank_depth", T, n, algo, curve_major)
 
 
 def rank_depth_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False):
     """Rows of the matrix a batch (image route) or a chunk (sort route) of sd_rank_depth_sums takes with ws_bytes of
     workspace; 0 below the floor.  At the recommended size this is all T rows whenever T is within the route's caps."""
-    lib = _native.load()
-    T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    return int(lib.sd_rank_depth_rows_per_batch(T, n, *_strides(T, n, curve_major), n, a, int(ws_bytes)))
+    return _curve_per_batch("rank_depth", "rows", T, n, ws_bytes, algo, curve_major)
 
 
 def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
@@ -442,7 +463,7 @@ def rank_depth_sums(X, targets=None, device=None, algo="auto", ws_bytes=None):
     of max(A, B).  X must not hold NaN (the depth layer checks; this function takes its array as it is).  algo: 'auto',
     'image' (n <= 16 384) or 'sort', or their numbers 0, 1, 2.  ws_bytes: the workspace size to run with (default: the
     recommended one); the records do not depend on it, below the floor the library refuses."""
-    return _curves("rank_depth", "sums", _rank_depth_algo, X, targets, device, algo, ws_bytes,
+    return _curves("sd_rank_depth_sums", "rank_depth", algo, X, targets, device, (), ws_bytes,
                    lambda t, dev, M, m: [t.empty((m, 5), dtype=t.int64, device=dev)])[0]
 
 
@@ -450,11 +471,7 @@ def extremal_workspace_bytes(T, n, algo="auto", curve_major=False):
     """(recommended, floor) workspace sizes of sd_extremal_counts for a T x n matrix: the extremity matrix (4 T n bytes)
     and the heads (8 n) in front of the batch of sd_rank_depth_sums; the floor holds one row per batch.  (0, 0) for a
     shape or algo the call refuses.  curve_major: the matrix is F-contiguous and takes a time-major copy as well."""
-    lib = _native.load()
-    T, n, a = int(T), int(n), _rank_depth_algo(algo)
-    st, sn = _strides(T, n, curve_major)
-    return (int(lib.sd_extremal_workspace_bytes(T, n, st, sn, n, a)),
-            int(lib.sd_extremal_min_workspace_bytes(T, n, st, sn, n, a)))
+    return _curve_sizes("extremal", T, n, algo, curve_major)
 
 
 def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
@@ -462,37 +479,21 @@ def extremal_counts(X, targets=None, device=None, algo="auto", ws_bytes=None):
     whose descending-sorted vector of pointwise extremities |A - B| is lexicographically at least the target's; the depth
     is G / n.  X must not hold NaN (the depth layer checks; this function takes its array as it is).  targets: indices of
     sample curves (None: all).  algo and ws_bytes as for rank_depth_sums; the counts do not depend on ws_bytes."""
-    return _curves("extremal", "counts", _rank_depth_algo, X, targets, device, algo, ws_bytes,
+    return _curves("sd_extremal_counts", "extremal", algo, X, targets, device, (), ws_bytes,
                    lambda t, dev, M, m: [t.empty((m,), dtype=t.int64, device=dev)])[0]
-
-
-TVD_ALGOS = {"auto": 0, "lds": 1, "pairwise": 2}
-
-
-def _tvd_algo(algo):
-    if isinstance(algo, str) and algo not in TVD_ALGOS:
-        raise ValueError(f"algo must be one of {sorted(TVD_ALGOS)}, got {algo!r}")
-    return TVD_ALGOS[algo] if isinstance(algo, str) else int(algo)
 
 
 def tvd_workspace_bytes(T, n, algo="auto", curve_major=False, m=None):
     """(recommended, floor) workspace sizes of sd_tvd_sums for a T x n matrix and m targets (default: all n); the floor holds
     one row per batch.  (0, 0) for a shape or algo the call refuses.  curve_major: the matrix is F-contiguous and takes a
     time-major copy in the workspace as well."""
-    lib = _native.load()
-    T, n, a = int(T), int(n), _tvd_algo(algo)
-    m = n if m is None else int(m)
-    st, sn = _strides(T, n, curve_major)
-    return (int(lib.sd_tvd_workspace_bytes(T, n, st, sn, m, a)), int(lib.sd_tvd_min_workspace_bytes(T, n, st, sn, m, a)))
+    return _curve_sizes("tvd", T, n, algo, curve_major, m)
 
 
 def tvd_rows_per_batch(T, n, ws_bytes, algo="auto", curve_major=False, m=None):
     """Rows of the matrix a batch of sd_tvd_sums takes with ws_bytes of workspace (all T on the pairwise route); 0 below
     the floor."""
-    lib = _native.load()
-    T, n, a = int(T), int(n), _tvd_algo(algo)
-    m = n if m is None else int(m)
-    return int(lib.sd_tvd_rows_per_batch(T, n, *_strides(T, n, curve_major), m, a, int(ws_bytes)))
+    return _curve_per_batch("tvd", "rows", T, n, ws_bytes, algo, curve_major, m)
 
 
 def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=False):
@@ -504,13 +505,10 @@ def tvd_sums(X, targets=None, device=None, algo="auto", ws_bytes=None, counts=Fa
     array as it is).  algo: 'auto', 'lds' (n <= 16 384) or 'pairwise', or their numbers 0, 1, 2.  ws_bytes: the workspace
     size to run with (default: the recommended one); the results do not depend on it, below the floor the library
     refuses."""
-    sd, shape, cnt = _curves("tvd", "sums", _tvd_algo, X, targets, device, algo, ws_bytes, lambda t, dev, M, m: [
+    sd, shape, cnt = _curves("sd_tvd_sums", "tvd", algo, X, targets, device, (), ws_bytes, lambda t, dev, M, m: [
         t.empty((m,), dtype=t.int64, device=dev), t.empty((m, 3), dtype=t.float64, device=dev),
         t.empty((max(M.T - 1, 0), m), dtype=t.int32, device=dev) if counts else None])
     return (sd, shape, cnt.view(np.uint32)) if counts else (sd, shape)
-
-
-CURVE_DIST_WHAT = {"sqdist": 0, "hmodal": 1, "select": 2}
 
 
 def curve_sqdist_workspace_bytes(T, n, what="sqdist", curve_major=False, m=None):
@@ -518,21 +516,13 @@ def curve_sqdist_workspace_bytes(T, n, what="sqdist", curve_major=False, m=None)
     'sqdist' (nothing but the time-major copy of a curve-major matrix: both may be 0), 'hmodal' (the tiles' partial sums of
     a batch of targets; the floor holds one block of 128) or 'select' (histogram and state; the recommended size also holds
     the n x n matrix where that is at most 1 GiB).  (0, 0) for a shape the calls refuse."""
-    lib = _native.load()
-    T, n, w = int(T), int(n), CURVE_DIST_WHAT[what]
-    m = n if m is None else int(m)
-    st, sn = _strides(T, n, curve_major)
-    return (int(lib.sd_curve_sqdist_workspace_bytes(T, n, st, sn, m, w)),
-            int(lib.sd_curve_sqdist_min_workspace_bytes(T, n, st, sn, m, w)))
+    return _curve_sizes("curve_sqdist", T, n, what, curve_major, m)
 
 
 def curve_sqdist_targets_per_batch(T, n, ws_bytes, what="sqdist", curve_major=False, m=None):
     """Targets a batch of a K20 call takes with ws_bytes of workspace (all of them for 'sqdist' and 'select'); 0 below the
     floor."""
-    lib = _native.load()
-    T, n, w = int(T), int(n), CURVE_DIST_WHAT[what]
-    m = n if m is None else int(m)
-    return int(lib.sd_curve_sqdist_targets_per_batch(T, n, *_strides(T, n, curve_major), m, w, int(ws_bytes)))
+    return _curve_per_batch("curve_sqdist", "targets", T, n, ws_bytes, what, curve_major, m)
 
 
 def _bandwidth_factor(g):
@@ -548,17 +538,15 @@ def curve_sqdist(X, targets=None, device=None, ws_bytes=None):
     bitwise symmetric with a +0.0 diagonal.  X must be finite with |x| <= 2^480 (the depth layer checks; this function takes
     its array as it is).  ws_bytes: the workspace size to run with (default: the recommended one); below the floor the
     library refuses."""
-    return _curves("curve_sqdist", "", None, X, targets, device, (), ws_bytes,
-                   lambda t, dev, M, m: [t.empty((m, M.n), dtype=t.float64, device=dev)], sized_by=("curve_sqdist", 0))[0]
+    return _curves("sd_curve_sqdist", "curve_sqdist", "sqdist", X, targets, device, (), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m, M.n), dtype=t.float64, device=dev)])[0]
 
 
 def curve_sqdist_external(X, Q, device=None, ws_bytes=None):
     """float64[m, n]: the squared L2 distances of the m columns of Q (T x m) to the n columns of X
     (sd_curve_sqdist_external); the arithmetic of curve_sqdist.  X goes up time-major, so no workspace is needed."""
-    lib = _lib()
-    size = (lambda T, n, m: lib.sd_curve_sqdist_workspace_bytes(T, n, n, 1, m, 0)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
-    return _external_curves(lib.sd_curve_sqdist_external, (np.shape(X)[1],), X, Q, device, dtype=torch().float64, strided=True,
-                            ws_bytes=size)
+    return _external_curves(_lib().sd_curve_sqdist_external, X, Q, device, ws_bytes=ws_bytes, family="curve_sqdist",
+                            variant="sqdist", outputs=lambda t, dev, T, n, m: [t.empty((m, n), dtype=t.float64, device=dev)])[0]
 
 
 def curve_sqdist_select(X, k, device=None, ws_bytes=None):
@@ -574,9 +562,9 @@ def curve_sqdist_select(X, k, device=None, ws_bytes=None):
     M = to_device_matrix(X, device)
     dev = M.device
     out = t.empty((1,), dtype=t.float64, device=dev)
-    size = lib.sd_curve_sqdist_workspace_bytes(M.T, M.n, M.st, M.sn, M.n, 2) if ws_bytes is None else ws_bytes
+    size = lambda: _curve_size("curve_sqdist", "workspace_bytes", M.T, M.n, (M.st, M.sn), None, "select")
     return float(_launch(dev, lib.sd_curve_sqdist_select, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, k,
-                         workspace=lambda: _sized(dev, size))[0])
+                         workspace=lambda: _sized(dev, size() if ws_bytes is None else ws_bytes))[0])
 
 
 def hmodal_sums(X, g, targets=None, device=None, ws_bytes=None):
@@ -584,17 +572,16 @@ def hmodal_sums(X, g, targets=None, device=None, ws_bytes=None):
     curve_sqdist and g = 1 / (2 h^2); the target's own term is 1.0.  The order of the sum depends on n alone, so S of a
     target holds the same bits whatever the targets, the layout of X or ws_bytes.  targets, ws_bytes and the contract on X
     as for curve_sqdist."""
-    return _curves("hmodal", "sums", None, X, targets, device, (_bandwidth_factor(g),), ws_bytes,
-                   lambda t, dev, M, m: [t.empty((m,), dtype=t.float64, device=dev)], sized_by=("curve_sqdist", 1))[0]
+    return _curves("sd_hmodal_sums", "curve_sqdist", "hmodal", X, targets, device, (_bandwidth_factor(g),), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m,), dtype=t.float64, device=dev)])[0]
 
 
 def hmodal_external_sums(X, Q, g, device=None, ws_bytes=None):
     """float64[m]: the sums of hmodal_sums for the m columns of Q (T x m) against the n columns of X
     (sd_hmodal_external_sums); no term is the target's own."""
-    lib = _lib()
-    size = (lambda T, n, m: lib.sd_curve_sqdist_workspace_bytes(T, n, n, 1, m, 1)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
-    return _external_curves(lib.sd_hmodal_external_sums, (), X, Q, device, _bandwidth_factor(g), dtype=torch().float64,
-                            strided=True, ws_bytes=size)
+    return _external_curves(_lib().sd_hmodal_external_sums, X, Q, device, _bandwidth_factor(g), ws_bytes=ws_bytes,
+                            family="curve_sqdist", variant="hmodal",
+                            outputs=lambda t, dev, T, n, m: [t.empty((m,), dtype=t.float64, device=dev)])[0]
 
 
 def spatial_workspace_bytes(T, n, curve_major=False, m=None):
@@ -602,19 +589,12 @@ def spatial_workspace_bytes(T, n, curve_major=False, m=None):
     (8 n bytes a target) and the field (8 T bytes a target) of a batch of whole blocks of 128 targets, behind the time-major
     copy of a curve-major matrix.  The floor holds one block; the recommended size holds all targets, up to 8 GiB of weights
     a batch.  (0, 0) where T < 1, n < 2 or m < 0."""
-    lib = _native.load()
-    T, n = int(T), int(n)
-    m = n if m is None else int(m)
-    st, sn = _strides(T, n, curve_major)
-    return int(lib.sd_spatial_workspace_bytes(T, n, st, sn, m)), int(lib.sd_spatial_min_workspace_bytes(T, n, st, sn, m))
+    return _curve_sizes("spatial", T, n, None, curve_major, m)
 
 
 def spatial_targets_per_batch(T, n, ws_bytes, curve_major=False, m=None):
     """Targets a batch of sd_spatial_sums takes with ws_bytes of workspace; 0 below the floor."""
-    lib = _native.load()
-    T, n = int(T), int(n)
-    m = n if m is None else int(m)
-    return int(lib.sd_spatial_targets_per_batch(T, n, *_strides(T, n, curve_major), m, int(ws_bytes)))
+    return _curve_per_batch("spatial", "targets", T, n, ws_bytes, None, curve_major, m)
 
 
 def spatial_time_tile(T, targets, device=None):
@@ -634,9 +614,8 @@ def spatial_sums(X, targets=None, device=None, ws_bytes=None, field=False):
     duplicate) adds nothing; S = sum_t E[t]^2 in ascending t with one fma per term.  The depth is 1 - sqrt(S) / n.  S and E of
     a target hold the same bits whatever the targets, the layout of X or ws_bytes.  targets, ws_bytes and the contract on X
     as for curve_sqdist."""
-    S, E = _curves("spatial", "sums", None, X, targets, device, (), ws_bytes, lambda t, dev, M, m: [
-        t.empty((m,), dtype=t.float64, device=dev), t.empty((m, M.T), dtype=t.float64, device=dev) if field else None],
-        sized_by=("spatial", None))
+    S, E = _curves("sd_spatial_sums", "spatial", None, X, targets, device, (), ws_bytes, lambda t, dev, M, m: [
+        t.empty((m,), dtype=t.float64, device=dev), t.empty((m, M.T), dtype=t.float64, device=dev) if field else None])
     return (S, E) if field else S
 
 
@@ -644,10 +623,9 @@ def spatial_external_sums(X, Q, device=None, ws_bytes=None, field=False):
     """float64[m], or (S, E) with field=True: the sums of spatial_sums for the m columns of Q (T x m) against the n columns
     of X (sd_spatial_external_sums).  The depth is 1 - sqrt(S) / (n + 1): the sample it refers to includes the target.  A
     column of Q equal to a sample curve gives that curve's S."""
-    lib = _lib()
-    size = (lambda T, n, m: lib.sd_spatial_workspace_bytes(T, n, n, 1, m)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
-    S, E = _external_curves(lib.sd_spatial_external_sums, (), X, Q, device, dtype=torch().float64, strided=True, ws_bytes=size,
-                            second=lambda T, n, m: (T,) if field else None)
+    outputs = lambda t, dev, T, n, m: [t.empty((m,), dtype=t.float64, device=dev),
+                                       t.empty((m, T), dtype=t.float64, device=dev) if field else None]
+    S, E = _external_curves(_lib().sd_spatial_external_sums, X, Q, device, ws_bytes=ws_bytes, family="spatial", outputs=outputs)
     return (S, E) if field else S
 
 
@@ -666,20 +644,13 @@ def lens_workspace_bytes(T, n, curve_major=False, m=None):
     (default: all n): the n x n matrix of squared distances (8 n^2 bytes) and the rows of a batch of whole blocks of 128
     external targets (8 n bytes a target), behind the time-major copy of a curve-major matrix.  The floor holds one block;
     the recommended size holds all targets, up to 1 GiB of rows.  (0, 0) where T < 1, n < 2, n > 16 384 or m < 0."""
-    lib = _native.load()
-    T, n = int(T), int(n)
-    m = n if m is None else int(m)
-    st, sn = _strides(T, n, curve_major)
-    return int(lib.sd_lens_workspace_bytes(T, n, st, sn, m)), int(lib.sd_lens_min_workspace_bytes(T, n, st, sn, m))
+    return _curve_sizes("lens", T, n, None, curve_major, m)
 
 
 def lens_targets_per_batch(T, n, ws_bytes, curve_major=False, m=None):
     """External targets a batch of sd_lens_external_counts takes with ws_bytes of workspace; 0 below the floor.  (Sample
     targets read their rows from the matrix and go in one batch.)"""
-    lib = _native.load()
-    T, n = int(T), int(n)
-    m = n if m is None else int(m)
-    return int(lib.sd_lens_targets_per_batch(T, n, *_strides(T, n, curve_major), m, int(ws_bytes)))
+    return _curve_per_batch("lens", "targets", T, n, ws_bytes, None, curve_major, m)
 
 
 def lens_counts(X, kappa, targets=None, device=None, ws_bytes=None, algo=0):
@@ -688,17 +659,16 @@ def lens_counts(X, kappa, targets=None, device=None, ws_bytes=None, algo=0):
     curve_sqdist's D2 of the target to curves i, j and c that of the two curves, every product and sum rounded on its own.
     The depth is G / C(n, 2).  A target's own pairs count.  algo: 0 takes the form that kappa names, 1 the general form (the
     same integers).  targets, ws_bytes and the contract on X as for curve_sqdist; n is at most 16 384."""
-    return _curves("lens", "counts", None, X, targets, device, (_kappa(kappa), int(algo)), ws_bytes,
-                   lambda t, dev, M, m: [t.empty((m,), dtype=t.int64, device=dev)], sized_by=("lens", None))[0]
+    return _curves("sd_lens_counts", "lens", None, X, targets, device, (_kappa(kappa), int(algo)), ws_bytes,
+                   lambda t, dev, M, m: [t.empty((m,), dtype=t.int64, device=dev)])[0]
 
 
 def lens_external_counts(X, Q, kappa, device=None, ws_bytes=None, algo=0):
     """int64[m]: the counts of lens_counts for the m columns of Q (T x m) against the pairs of the n columns of X
     (sd_lens_external_counts).  The depth is G / C(n, 2) here too.  A column of Q equal to a sample curve gives that curve's
     count."""
-    lib = _lib()
-    size = (lambda T, n, m: lib.sd_lens_workspace_bytes(T, n, n, 1, m)) if ws_bytes is None else (lambda T, n, m: ws_bytes)
-    return _external_curves(lib.sd_lens_external_counts, (), X, Q, device, _kappa(kappa), int(algo), strided=True, ws_bytes=size)
+    return _external_curves(_lib().sd_lens_external_counts, X, Q, device, _kappa(kappa), int(algo), ws_bytes=ws_bytes,
+                            family="lens", outputs=lambda t, dev, T, n, m: [t.empty((m,), dtype=t.int64, device=dev)])[0]
 
 
 def central_regions_row_capacity():

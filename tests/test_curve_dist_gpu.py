@@ -193,6 +193,22 @@ def test_forms_of_the_sums(n, T, kind):
         engine.hmodal_sums(X, 0.0)
 
 
+def test_external_sums_in_several_batches():
+    """External targets in more than one batch: 2 * 128 + 1 columns drawn from the sample with repeats take three batches
+    at the floor and one at the recommended size, and either way a column's S holds the bits of the sample curve's."""
+    n, T, kind = 129, 17, 'duplicated'
+    X, pick, exact, dev = case(n, T, kind)
+    g = case_g(n, T, kind)
+    full = engine.hmodal_sums(X, g)
+    t = np.random.default_rng(n + T).integers(0, n, size=2 * TILE + 1)
+    assert len(np.unique(t)) < len(t)
+    rec, floor = engine.curve_sqdist_workspace_bytes(T, n, 'hmodal', m=len(t))
+    assert engine.curve_sqdist_targets_per_batch(T, n, floor, 'hmodal', m=len(t)) == TILE     # three batches
+    assert engine.curve_sqdist_targets_per_batch(T, n, rec, 'hmodal', m=len(t)) == len(t)
+    for ws in (floor, rec):
+        assert same_bits(engine.hmodal_external_sums(X, X[:, t], g, ws_bytes=ws), full[t]), ws
+
+
 def test_public_api():
     df = two_outlier_example()
     X = df.to_numpy()

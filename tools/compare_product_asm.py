@@ -29,7 +29,7 @@ import tempfile
 
 MOVED_TO_XONLY = ()            # short names of kernels this change retires from the product into the cross-check library
 NEW_ARGUMENTS = ()             # short names of kernels whose argument list this change rewrites
-NEW_KERNELS = ("lens_count_kernel",)   # short names of kernels this change adds to the product
+NEW_KERNELS = ()               # short names of kernels this change adds to the product
 # short names of kernels whose body this change rewrites
 REWRITTEN = ()
 PINNED = re.compile(r"next_free_vgpr|accum_offset|vgpr_count|agpr_count|private_segment_fixed_size|group_segment_fixed_size|"
