@@ -24,6 +24,39 @@
  *    the fp64 normalisers (/T, /C(n,j) ...) stay on the host.
  *  - every function returns SD_OK (0) or an error code; sd_last_error() gives
  *    the message for the calling thread.
+ *
+ * Caller memory: the workspace and the outputs
+ * Every sd_* call that takes `ws` / `ws_bytes` or an output pointer keeps to this:
+ *  - `ws` may hold ANY bytes on entry.  Whatever a call reads from its
+ *    workspace, a launch of the same call has written before -- counters,
+ *    flags, slice records, carried rows and the words indices are read from
+ *    included.  The two rank routes whose gate words are never zeroed
+ *    (mbd_rank_bucket.hip, mbd_rank_big.hip: a word is "set" when it equals
+ *    the call's epoch) give the same results when a stale word happens to
+ *    equal the epoch; it costs time only.
+ *  - nothing in `ws` is needed after the call's work has run: the next call
+ *    on the stream may get the same buffer, or any other.  The library keeps
+ *    no pointer into it.
+ *  - the caller passes `ws` 256-byte aligned.
+ *  - no byte is written outside [ws, ws + ws_bytes), whatever ws_bytes is --
+ *    the recommended size, the floor of a family that has one, or anything
+ *    between; below what a call needs it returns SD_ERR_WORKSPACE.
+ *  - no byte is written outside the documented extent of an output (m int64,
+ *    m x (J - 1) int64, ... as each entry point states; nothing is rounded up
+ *    to a tile or a vector).
+ *  - outputs may hold ANY bytes on entry: a call that adds into an output or
+ *    takes minima on it initialises it on its own stream first.  No entry
+ *    point asks the caller to zero anything -- sd_mbd_counts_wide, and the
+ *    `centres` and `curves` of sd_multi_outlyingness_moments, store every
+ *    element they document.
+ *  - calls enqueue and return, with one documented exception: the strict
+ *    band depth (sd_bd_strict_counts, sd_bd_strict_j_counts,
+ *    sd_bd_strict_external_counts) of series of 6 to 8 timepoints at J = 2
+ *    waits for the stream once, in the middle of the call: a NaN flag comes
+ *    back to the host and decides between two routes.
+ * tests/workspace_contract.py enforces these at this boundary: guard bands
+ * around a workspace of exactly ws_bytes and around every output, three
+ * poison patterns in both, for every entry point and route.
  */
 #ifndef STATDEPTH_HIP_H
 #define STATDEPTH_HIP_H

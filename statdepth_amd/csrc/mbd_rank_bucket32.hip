@@ -706,7 +706,9 @@ __global__ __launch_bounds__(R32_NT, 4) void rank_bucket32_kernel(const double *
     } else if (stop) {
         for (i64 rr = r + (i64)t * gridDim.x; rr < rows; rr += (i64)NT * gridDim.x) rowflag[rr] = 1;   // rows left behind
     }
-    if (t == 0 && nbad) *gate = epoch;
+    // (stop with nbad == 0: gate[1] held this epoch's "eight contenders" before the launch -- stale workspace contents.  The rows
+    // left behind are flagged above, so the gate opens for them as for any other flagged row.)
+    if (t == 0 && (nbad || stop)) *gate = epoch;
     // ---- keys whose images coincide, settled among themselves in fp64 (their rows are NaN-free and finite, a group of equal
     //      images is complete in the list): wave 0, one listed key per lane, fetches the doubles (ONE round trip, issued ahead
     //      of the block's stores), compares within the groups of equal (row, B0) through readlane and adds each key's

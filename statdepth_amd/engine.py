@@ -89,9 +89,11 @@ def to_device_matrix(X, device=None):
 
 
 # One grow-only scratch buffer per (device, stream, host thread), reused by every call (the C ABI takes the workspace as an
-# argument and keeps nothing in it between calls): a repeated call of the same shape pays no allocation and no allocator round
-# trip.  The launchers are multi-launch pipelines with live state in the buffer between their launches, and ctypes releases
-# the GIL: two host threads on ONE stream must not share a buffer (their launches may interleave), hence the thread in the key.
+# argument, reads nothing from it that the same call has not written and keeps nothing in it between calls -- "Caller memory"
+# in include/statdepth_hip.h, which also lets every output be torch.empty): a repeated call of the same shape pays no
+# allocation and no allocator round trip.
+# The launchers are multi-launch pipelines with live state in the buffer between their launches, and ctypes releases the
+# GIL: two host threads on ONE stream must not share a buffer (their launches may interleave), hence the thread in the key.
 # Results handed out with return_tensor=True are separate tensors and stay valid.  Buffers above _WS_KEEP bytes are handed
 # out once and not kept (strict depth at large n asks for GiBs); at most _WS_SLOTS buffers are kept, least recently used
 # first out (side streams and worker threads that are gone).
@@ -231,7 +233,7 @@ def mbd_counts_wide(X, targets=None, J=2, algo="auto", device=None):
     dev = M.device
     td, m, tp = _targets_dev(targets, M.n, dev)
     a = ALGOS[algo] if isinstance(algo, str) else int(algo)
-    out = t.zeros((m, J - 1, 2), dtype=t.int64, device=dev)
+    out = t.empty((m, J - 1, 2), dtype=t.int64, device=dev)
     limbs = _launch(dev, lib.sd_mbd_counts_wide, out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, tp, m, J, a,
                     workspace=lambda: _sized(dev, lib.sd_mbd_wide_workspace_bytes(M.T, M.n, M.st, M.sn, m, J, a)))
     limbs = limbs.astype(np.uint64)
@@ -1051,8 +1053,8 @@ def multi_outlyingness_moments(P, U, targets=None, device=None, algo="auto", ws_
     Ud = _directions_dev(U, d, dev)
     k = Ud.shape[0]
     out = t.empty((m, d + 1), dtype=t.float64, device=dev)
-    cen = t.zeros(T if m else 0, dtype=t.int64, device=dev) if centres else None   # (no targets: nothing is launched)
-    cur = t.zeros((m, T, d), dtype=t.float64, device=dev) if curves else None
+    cen = t.empty(T if m else 0, dtype=t.int64, device=dev) if centres else None   # (no targets: nothing is launched)
+    cur = t.empty((m, T, d), dtype=t.float64, device=dev) if curves else None
     rec = _launch(dev, lib.sd_multi_outlyingness_moments, out, Pd.data_ptr(), n, T, d, Ud.data_ptr(), k, tp, m, a, _OUT,
                   cen.data_ptr() if centres else None, cur.data_ptr() if curves else None,
                   workspace=lambda: _sized(dev, lib.sd_multi_outlyingness_workspace_bytes(n, T, d, k, m, a)
