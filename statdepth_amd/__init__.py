@@ -6,9 +6,9 @@ objects; the arithmetic runs in hand-written gfx950 HIP kernels
 (statdepth_amd/csrc, C ABI in include/statdepth_hip.h).  No CPU fallback.
 """
 from .depth import FunctionalDepth, PointcloudDepth, ProbabilisticDepth, FunctionalBoxplot, DepthDegeneracy   # noqa: F401
-from .depth import TotalVariationOutliers, DirectionalOutlyingness, MSPlotOutliers, CurveDistances   # noqa: F401
+from .depth import TotalVariationOutliers, DirectionalOutlyingness, MSPlotOutliers, CurveDistances, CurveProjections   # noqa: F401
 from .depth.calculations._uncertainty import probabilistic_normal_depth, probabilistic_poisson_depth   # noqa: F401
 
 __all__ = ["FunctionalDepth", "PointcloudDepth", "ProbabilisticDepth", "FunctionalBoxplot", "TotalVariationOutliers", "DepthDegeneracy",
-           "DirectionalOutlyingness", "MSPlotOutliers", "CurveDistances", "probabilistic_normal_depth", "probabilistic_poisson_depth"]
+           "DirectionalOutlyingness", "MSPlotOutliers", "CurveDistances", "CurveProjections", "probabilistic_normal_depth", "probabilistic_poisson_depth"]
 __version__ = "0.1.0"

@@ -134,6 +134,19 @@ SIGNATURES = {
     "sd_lens_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
     "sd_lens_external_counts": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _dbl, _int, _vp, _vp, _sz, _vp]),
 }
+# K23, declared in include/statdepth_hip_projections.h.  A table of its own because the contract tests tie every key of
+# SIGNATURES to the rows and cases of existing test files (tests/workspace_contract.py); a change that may touch those tables
+# folds this one into SIGNATURES and the companion header into the main one.
+PROJECTION_SIGNATURES = {
+    "sd_curve_projections_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "sd_curve_projections": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "sd_rp_depth_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_rp_depth_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _int]),
+    "sd_rp_depth_sums": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "sd_rp_outlyingness_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "sd_rp_outlyingness_min_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "sd_rp_outlyingness": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+}
 
 
 class StatdepthHipError(RuntimeError):
@@ -148,13 +161,14 @@ _LIB = None
 
 
 def open_library(path):
-    """dlopen one build of the library and bind every symbol of include/statdepth_hip.h (no GPU needed)."""
+    """dlopen one build of the library and bind every symbol of include/statdepth_hip.h and of its companion
+    include/statdepth_hip_projections.h (no GPU needed)."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C statdepth_amd/csrc`. statdepth_amd has no CPU fallback.")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *PROJECTION_SIGNATURES.items()):
         fn = getattr(lib, name)       # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -47,8 +47,10 @@ int launch_rank_pair_images(const PairImagePlan &plan, const double *Y, i64 T, i
                             hipStream_t s);
 
 // ---- K14 integrated rank depths of curves (rank_depths.hip): out[q] = (SA, SB, SF, SM, MM).  Its plan is stage 1's. ----
+// first_rows: Y holds the first rows of the matrix, so its first batch starts the records; false where the caller feeds the
+// rows in chunks (K23) and this chunk adds to what the chunks before it left in out.
 int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
-                           size_t ws_bytes, hipStream_t s);
+                           size_t ws_bytes, hipStream_t s, bool first_rows = true);
 
 // ---- K15 extremal depth of curves (extremal.hip): out[q] = #{curves i : v_i >=lex v_q}, v the descending sort of |A - B|
 // over time.  The extremity matrix E and the heads H, then stage 1. ----
@@ -178,5 +180,26 @@ i64 lens_span(i64 n, i64 targets);
 int launch_curve_sqdist_rows(const double *Y, i64 T, i64 n, const double *Q, i64 m, i64 q_begin, i64 q_end, double *out, hipStream_t s);
 int launch_lens_counts(const double *Y, i64 T, i64 n, CurveSel sel, i64 m, double kappa, int algo, i64 *out, void *ws, size_t ws_bytes,
                        hipStream_t s);
+
+// ---- K23 projections of curves on k directions (curve_project.hip): Z[r][i] = ((x_0 u_r0 + x_1 u_r1) + x_2 u_r2) + ..., X in
+// either layout (st, sn), U k x T row-major, Z k x n.  The depths' records are K14's over the rows of Z, the outlyingness is
+// K12's over them. ----
+// Z[(r - r_first) * n + i] for the directions [r_first, r_end) and all n curves; no workspace
+int launch_curve_project(const double *X, i64 T, i64 n, i64 st, i64 sn, const double *U, i64 r_first, i64 r_end, double *Z,
+                         hipStream_t s);
+// The plan of sd_rp_depth_sums: a chunk of `rows` rows of Z in front (z bytes), then K14's stage 1 for them.  Sized by
+// PlanSize with its rows read as rows of Z; rows == 0: below the floor.
+struct RpDepthPlan {
+    i64 rows;                                                       // of Z per chunk
+    size_t z;                                                       // bytes of the chunk, padded to 256
+    size_t bytes;                                                   // the whole of it
+};
+RpDepthPlan rp_depth_plan(i64 n, i64 k, int route, PlanSize size);
+int launch_rp_depth_sums(const double *X, i64 T, i64 n, i64 st, i64 sn, const double *U, i64 k, const i64 *targets, i64 m,
+                         int route, i64 *out, void *ws, size_t ws_bytes, hipStream_t s);
+size_t rp_outlyingness_workspace_bytes(i64 n, i64 k);
+size_t rp_outlyingness_min_workspace_bytes(i64 n);
+int launch_rp_outlyingness(const double *X, i64 T, i64 n, i64 st, i64 sn, const double *U, i64 k, const i64 *targets, i64 m,
+                           double *out, void *ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace sd

@@ -188,6 +188,12 @@ __global__ __launch_bounds__(PD_THREADS) void pd_blocks_kernel(const double *__r
 static inline size_t pd_ws_fixed() { return (size_t)(HS_SORT_CARVES + 2) * 256; }
 static inline size_t pd_ws_per_direction(i64 n) { return hs_sort_bytes_per_direction(n) + 16; }
 
+int launch_pd_locscale(const double *K, i64 n, int kk, double *med, double *mad, hipStream_t s) {
+    hipLaunchKernelGGL(pd_locscale_kernel, dim3((unsigned)kk), dim3(PD_LOC_THREADS), 0, s, K, n, med, mad);
+    SD_HIP(hipGetLastError());
+    return SD_OK;
+}
+
 size_t projection_min_workspace_bytes(i64 n) { return pd_ws_fixed() + pd_ws_per_direction(n); }
 
 size_t projection_workspace_bytes(i64 n, i64 k) {
@@ -225,8 +231,7 @@ static int launch_pd_sorted_d(const double *P, i64 n, const double *U, i64 k, co
                 SD_HIP(hipGetLastError());
             }
         } else {
-            hipLaunchKernelGGL(pd_locscale_kernel, dim3((unsigned)kk), dim3(PD_LOC_THREADS), 0, s, b.K[src], n, med, mad);
-            SD_HIP(hipGetLastError());
+            if (const int rl = launch_pd_locscale(b.K[src], n, kk, med, mad, s)) return rl;
             hipLaunchKernelGGL((pd_outlyingness_kernel<D>), dim3((unsigned)((m + PD_THREADS - 1) / PD_THREADS)),
                                dim3(PD_THREADS), 0, s, P, Uc, kk, med, mad, sel.targets, m, c0 == 0 ? 1 : 0, out);
             SD_HIP(hipGetLastError());

@@ -2,9 +2,15 @@
 //
 // Shared by K12 (projection.hip: sorted global rows, rows with one value inserted, sorted LDS blocks) and K18
 // (multi_cloud.hip: a cloud's projections sorted in LDS).  The definition and its roundings are stated at the top of
-// projection.hip; a device-only header.
+// projection.hip; device code but for one launcher.  K23 (curve_project.hip) takes pd_outlyingness and that launcher for the
+// projections of curves.
 #pragma once
 #include "sd_common.h"
+
+namespace sd {
+// pd_locscale_kernel (projection.hip): med[r], mad[r] of the kk rows of K (kk x n), every row sorted ascending
+int launch_pd_locscale(const double *K, i64 n, int kk, double *med, double *mad, hipStream_t s);
+}  // namespace sd
 
 #ifdef __HIPCC__
 namespace sd {

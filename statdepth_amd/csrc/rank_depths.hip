@@ -226,18 +226,20 @@ struct RankDepthFold final : RankImageConsumer {
     i64 n, m;
     const i64 *targets;
     u64 *out;
-    RankDepthFold(i64 n_, const i64 *targets_, i64 m_, u64 *out_) : n(n_), m(m_), targets(targets_), out(out_) {}
+    bool first_rows;                                                // row 0 of Y starts the records (false: out holds earlier rows')
+    RankDepthFold(i64 n_, const i64 *targets_, i64 m_, u64 *out_, bool first_rows_)
+        : n(n_), m(m_), targets(targets_), out(out_), first_rows(first_rows_) {}
     int image32(const u32 *img, i64 row0, i64 rows, hipStream_t s) override {
-        return launch_rank_depth_fold<u32>(img, rows, n, targets, m, out, row0 == 0, s);
+        return launch_rank_depth_fold<u32>(img, rows, n, targets, m, out, first_rows && row0 == 0, s);
     }
     int image64(const u64 *img, i64 row0, i64 rows, hipStream_t s) override {
-        return launch_rank_depth_fold<u64>(img, rows, n, targets, m, out, row0 == 0, s);
+        return launch_rank_depth_fold<u64>(img, rows, n, targets, m, out, first_rows && row0 == 0, s);
     }
 };
 
 int launch_rank_depth_sums(const double *Y, i64 T, i64 n, const i64 *targets, i64 m, int route, i64 *out, void *ws,
-                           size_t ws_bytes, hipStream_t s) {
-    RankDepthFold fold(n, targets, m, (u64 *)out);
+                           size_t ws_bytes, hipStream_t s, bool first_rows) {
+    RankDepthFold fold(n, targets, m, (u64 *)out, first_rows);
     return launch_rank_pair_images(pair_image_plan(T, n, route, PlanSize::of_bytes(ws_bytes)), Y, T, n, fold, ws, s);
 }
 

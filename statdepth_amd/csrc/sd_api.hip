@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "sd_common.h"
+#include "statdepth_hip_projections.h"
 #include "rank_routes.h"
 #include "curve_routes.h"
 #include "point_select.h"
@@ -1384,6 +1385,83 @@ int sd_multi_outlyingness_moments(const double *P, int64_t n, int64_t T, int d, 
     int rc = multi_cloud_checked(true, P, n, T, d, U, k, targets, m, algo, out, ws, ws_bytes, DO_EXTRA, "outlyingness", route);
     if (rc || m == 0) return rc;
     return launch_multi_outlyingness(route, P, n, T, d, U, k, targets, m, out, centres, curves, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// K23: the projections of curves (include/statdepth_hip_projections.h, curve_project.hip)
+// ---------------------------------------------------------------------------
+// The refusals the three entry points share, in their order; n_min: the fewest curves (1 for the projections alone).
+// comparisons: per projected value, what the call does with Z (0 for the projections alone).
+static int check_curve_projections(const double *X, i64 T, i64 n, i64 st, i64 sn, const double *U, i64 k, const i64 *targets,
+                                   i64 m, const void *out, i64 n_min, int algo, double comparisons) {
+    if (!X || !U || !out) return fail(SD_ERR_INVALID, "null pointer");
+    if (T < 1 || k < 1 || n < n_min)
+        return fail(SD_ERR_INVALID, "bad shape (T=%lld, n=%lld, k=%lld): at least one timepoint, one direction and %lld curve(s)",
+                    (long long)T, (long long)n, (long long)k, (long long)n_min);
+    int rc;
+    if ((rc = refuse_algo(algo, RD_ALGO_NAMES)) || (rc = refuse_curves(n, "the projections of curves take"))) return rc;
+    if (T >= ((i64)1 << 31) || k >= ((i64)1 << 31))
+        return fail(SD_ERR_UNSUPPORTED, "the projections of curves take fewer than 2^31 timepoints and directions");
+    if ((rc = refuse_route1(algo, n, "image"))) return rc;
+    const double work = (double)k * (double)n * ((double)T + comparisons);
+    if (work > HS_MAX_WORK)
+        return fail(SD_ERR_UNSUPPORTED, "%.3g multiply-adds and comparisons exceed the cap of %.0e", work, HS_MAX_WORK);
+    return check_matrix(X, T, n, st, sn, targets, m);
+}
+
+static bool rp_shape(i64 T, i64 n, i64 k, i64 n_min) {
+    const i64 lim = (i64)1 << 31;
+    return T >= 1 && k >= 1 && n >= n_min && T < lim && n < lim && k < lim;
+}
+
+size_t sd_curve_projections_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k) {
+    (void)T, (void)n, (void)st, (void)sn, (void)k;
+    return 0;
+}
+
+int sd_curve_projections(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *U, int64_t k, double *out,
+                         void *ws, size_t ws_bytes, void *stream) {
+    (void)ws, (void)ws_bytes;
+    const int rc = check_curve_projections(X, T, n, st, sn, U, k, nullptr, n, out, 1, 0, 0.0);
+    return rc ? rc : launch_curve_project(X, T, n, st, sn, U, 0, k, out, (hipStream_t)stream);
+}
+
+size_t sd_rp_depth_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, int64_t m, int algo) {
+    (void)st, (void)sn, (void)m;
+    const int route = rp_shape(T, n, k, 2) ? curve_route(algo, k, n) : 0;
+    return route ? rp_depth_plan(n, k, route, PlanSize::of_rows(k)).bytes : 0;
+}
+
+size_t sd_rp_depth_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, int64_t m, int algo) {
+    (void)st, (void)sn, (void)m;
+    const int route = rp_shape(T, n, k, 2) ? curve_route(algo, k, n) : 0;
+    return route ? rp_depth_plan(n, k, route, PlanSize::of_rows(1)).bytes : 0;
+}
+
+int sd_rp_depth_sums(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *U, int64_t k,
+                     const int64_t *targets, int64_t m, int algo, int64_t *out, void *ws, size_t ws_bytes, void *stream) {
+    const int rc = check_curve_projections(X, T, n, st, sn, U, k, targets, m, out, 2, algo, log2_steps(n));
+    if (rc || m == 0) return rc;
+    if (!ws || ws_bytes < sd_rp_depth_min_workspace_bytes(T, n, st, sn, k, m, algo))
+        return fail(SD_ERR_WORKSPACE, "workspace below sd_rp_depth_min_workspace_bytes");
+    return launch_rp_depth_sums(X, T, n, st, sn, U, k, targets, m, curve_route(algo, k, n), out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t sd_rp_outlyingness_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, int64_t m) {
+    (void)st, (void)sn, (void)m;
+    return rp_shape(T, n, k, 2) ? rp_outlyingness_workspace_bytes(n, k) : 0;
+}
+
+size_t sd_rp_outlyingness_min_workspace_bytes(int64_t T, int64_t n, int64_t st, int64_t sn, int64_t k, int64_t m) {
+    (void)st, (void)sn, (void)m;
+    return rp_shape(T, n, k, 2) ? rp_outlyingness_min_workspace_bytes(n) : 0;
+}
+
+int sd_rp_outlyingness(const double *X, int64_t T, int64_t n, int64_t st, int64_t sn, const double *U, int64_t k,
+                       const int64_t *targets, int64_t m, double *out, void *ws, size_t ws_bytes, void *stream) {
+    const int rc = check_curve_projections(X, T, n, st, sn, U, k, targets, m, out, 2, 0, log2_steps(n));
+    if (rc || m == 0) return rc;
+    return launch_rp_outlyingness(X, T, n, st, sn, U, k, targets, m, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

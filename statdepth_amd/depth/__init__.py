@@ -1,3 +1,3 @@
 from .depth import FunctionalDepth, PointcloudDepth, ProbabilisticDepth, FunctionalBoxplot, TotalVariationOutliers   # noqa: F401  (reference: statdepth/depth/__init__.py:1)
-from .depth import DirectionalOutlyingness, MSPlotOutliers, CurveDistances   # noqa: F401
+from .depth import DirectionalOutlyingness, MSPlotOutliers, CurveDistances, CurveProjections   # noqa: F401
 from .calculations._helper import DepthDegeneracy     # noqa: F401

@@ -17,7 +17,10 @@ these tuples that take multivariate curves.  METRIC_DEPTHS names the depths buil
 (_functional._spatial_depths), built on the same distances and the unit vectors between whole curves, for univariate curves.
 LENS_DEPTHS names the lune depths (the lens, the spherical and the beta-skeleton depth, _functional._lens_depths): counts of
 the pairs of curves whose lune holds the target, read off the same distances; for univariate curves, and for point clouds
-(_pointcloud._lens_cloud_depths) of any dimension.
+(_pointcloud._lens_cloud_depths) of any dimension.  PROJECTED_DEPTHS names the random projection depths
+(_functional._projected_depths): a univariate depth of the curves' projections on a set of directions in R^T -- the random
+projection depth, its Fraiman-Muniz form, the random Tukey depth and the Stahel-Donoho outlyingness over them; for
+univariate curves, and through them for point clouds with any number of features.
 """
 from inspect import signature
 
@@ -29,13 +32,14 @@ CLOUD_DEPTHS = ('halfspace', 'projection')
 METRIC_DEPTHS = ('hmodal',)
 SPATIAL_DEPTHS = ('spatial',)
 LENS_DEPTHS = ('lens', 'spherical', 'beta_skeleton')
+PROJECTED_DEPTHS = ('rp_halfspace', 'rp_fm', 'random_tukey', 'rp_projection')
 
 
 def _is_valid_containment(containment):
     # a string that reaches this point is not a known definition (:34-35)
     if isinstance(containment, str):
         raise ValueError(f'containment argument \'{containment}\' is invalid. Use one of '
-                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS + SPATIAL_DEPTHS + LENS_DEPTHS)}, '
+                         f'[\'r2\', \'r2_enum\', \'simplex \'], for univariate data one of {list(RANK_DEPTHS + ORDER_DEPTHS + SHAPE_DEPTHS + METRIC_DEPTHS + SPATIAL_DEPTHS + LENS_DEPTHS + PROJECTED_DEPTHS)}, '
                          f'for univariate or multivariate data one of {list(CLOUD_DEPTHS)}, '
                          f'or a pass a custom containment function.')
     params = signature(containment).parameters
@@ -71,6 +75,10 @@ def _is_spatial_depth(containment) -> bool:
 
 def _is_lens_depth(containment) -> bool:
     return isinstance(containment, str) and containment in LENS_DEPTHS
+
+
+def _is_projected_depth(containment) -> bool:
+    return isinstance(containment, str) and containment in PROJECTED_DEPTHS
 
 
 def _select_containment(containment):

@@ -18,13 +18,13 @@ from scipy.special import binom
 from ... import engine
 from ..._native import SD_ERR_OVERFLOW, StatdepthHipError
 from ._containment import (_is_cloud_depth, _is_metric_depth, _is_order_depth, _is_rank_depth, _is_shape_depth,
-                           _is_lens_depth, _is_spatial_depth, _select_containment)
+                           _is_lens_depth, _is_projected_depth, _is_spatial_depth, _select_containment)
 from ._helper import DepthDegeneracy, _band_depth_sum, _deep_check, _handle_depth_errors, _padded_members
 from ._pointcloud import _halfspace_directions
-from ._rank import _rank_depth_values
+from ._rank import _projected_depth_values, _rank_depth_values
 from ._shape import _shape_depth_values
 
-__all__ = ['_functionaldepth', '_samplefunctionaldepth', '_curve_distances']
+__all__ = ['_functionaldepth', '_samplefunctionaldepth', '_curve_distances', '_curve_projections']
 
 
 # tests switch this off to compare the one-launch strict estimator with the block-by-block evaluation
@@ -173,6 +173,57 @@ def _rank_depths(data, to_compute, J, containment: str, deep_check=False, device
     cols = df.columns if to_compute is None else to_compute
     records = engine.rank_depth_sums(X, _positions(df, cols), device=device)
     return pd.Series(index=cols, data=_rank_depth_values(records, n, T, containment))
+
+
+PROJECTED_MAX_T = 2 ** 23          # timepoints of a projection: with |x|, |u| <= 2^500 no sum of T products overflows
+
+
+def _projected_inputs(data, J, what: str, deep_check=False, directions=1000, seed=0):
+    """(frame, its T x n fp64 matrix, U [k, T]) for the projections of univariate curves on a direction set, or the refusal,
+    raised before anything is uploaded: what the rank depths refuse (_ranked_frame), infinite values, magnitudes above 2^500,
+    2^23 or more timepoints; `directions` a positive int k (the rows of _halfspace_directions(k, seed, T): seeded unit
+    vectors of R^T) or a k x T array used as given -- finite, no all-zero row, magnitudes of at most 2^500."""
+    df, X = _ranked_frame(data, J, what, deep_check)
+    T, n = X.shape
+    if not np.isfinite(X).all():
+        raise ValueError(f'containment \'{what}\' does not take infinite values: drop or clip them first.')
+    engine.projection_check('values', X)                 # |x| <= 2^500: no projection or midpoint overflows
+    if T >= PROJECTED_MAX_T:
+        raise ValueError(f'containment \'{what}\' takes fewer than 2^23 timepoints, got {T}.')
+    if isinstance(directions, str):
+        if directions == 'exact':
+            raise NotImplementedError(f"containment '{what}' has no exact form: give a number of directions or a "
+                                      f"(k x {T}) array")
+        raise ValueError(f"containment '{what}' takes a positive number of directions or a (k x {T}) array, "
+                         f"got directions={directions!r}.")
+    U = _halfspace_directions(directions, seed, T)       # finite, no all-zero row
+    engine.projection_check('direction entries', U)
+    return df, X, U
+
+
+def _projected_depths(data, to_compute, J, containment: str, deep_check=False, device=None, directions=1000,
+                      seed=0) -> pd.Series:
+    """A random projection depth (containment in _containment.PROJECTED_DEPTHS) of the columns `to_compute` of the single
+    frame in `data`: every curve is projected on the k directions (`directions`, `seed`: as for PointcloudDepth's
+    'halfspace', in R^T) and a univariate depth of the projections is averaged or minimised over them -- 'rp_halfspace' the
+    mean Tukey depth (the random projection depth), 'rp_fm' the mean of 1 - |1/2 - F_r|, 'random_tukey' the minimum Tukey
+    depth, 'rp_projection' 1 / (1 + the largest |z - med| / MAD).  One device call for the records (sd_rp_depth_sums) or the
+    outlyingness (sd_rp_outlyingness), the normalisation of _rank.py on the host.  Labels, `to_compute` and the result's
+    order are those of 'r2'.  What cannot be computed is refused here, before anything is uploaded."""
+    df, X, U = _projected_inputs(data, J, containment, deep_check, directions, seed)
+    T, n = X.shape
+    cols = df.columns if to_compute is None else to_compute
+    call = engine.rp_outlyingness if containment == 'rp_projection' else engine.rp_depth_sums
+    values = call(X, U, _positions(df, cols), device=device)
+    return pd.Series(index=cols, data=_projected_depth_values(values, n, U.shape[0], containment))
+
+
+def _curve_projections(data, directions=1000, seed=0, device=None) -> pd.DataFrame:
+    """The projections of the columns of a frame (or of the single frame of a list) on the direction set: k rows, one
+    column per curve under its label (engine.curve_projections)."""
+    frames = data if isinstance(data, list) else [data]
+    df, X, U = _projected_inputs(frames, 2, 'CurveProjections', directions=directions, seed=seed)
+    return pd.DataFrame(engine.curve_projections(X, U, device=device), columns=df.columns)
 
 
 EXTREMAL_MAX_T = 16384             # timepoints a curve's sort holds on the device (sd_extremal_counts)
@@ -501,6 +552,9 @@ def _functionaldepth(data: List[pd.DataFrame], to_compute: Union[list, pd.Index]
                              directions=directions, seed=seed, aggregate=aggregate)
     if _is_rank_depth(containment):                      # not a band depth: `relax` and `algo` have nothing to select
         return _rank_depths(data, to_compute, J, containment, deep_check=deep_check, device=device)
+    if _is_projected_depth(containment):                 # as the rank depths, with `directions` and `seed`
+        return _projected_depths(data, to_compute, J, containment, deep_check=deep_check, device=device,
+                                 directions=directions, seed=seed)
     if _is_order_depth(containment):
         return _extremal_depth(data, to_compute, J, containment, deep_check=deep_check, device=device)
     if _is_shape_depth(containment):
@@ -566,7 +620,7 @@ def _samplefunctionaldepth(data: List[pd.DataFrame], K: int, to_compute: Union[l
     samples = []
     if (_is_rank_depth(containment) or _is_order_depth(containment) or _is_shape_depth(containment)
             or _is_cloud_depth(containment) or _is_metric_depth(containment) or _is_spatial_depth(containment)
-            or _is_lens_depth(containment)):
+            or _is_lens_depth(containment) or _is_projected_depth(containment)):
         raise ValueError(f'containment \'{containment}\' has no K-block estimator: K must be None.')
     _handle_depth_errors(data=data, J=J, containment=containment, relax=relax, deep_check=deep_check)
     cdef = _select_containment(containment=containment)

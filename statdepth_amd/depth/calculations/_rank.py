@@ -22,9 +22,9 @@ These are the integrated ("modified") forms: there is no strict variant to selec
 """
 import numpy as np
 
-from ._containment import RANK_DEPTHS
+from ._containment import PROJECTED_DEPTHS, RANK_DEPTHS
 
-__all__ = ['_rank_depth_values']
+__all__ = ['_rank_depth_values', '_projected_depth_values']
 
 
 def _rank_depth_values(records, n: int, T: int, name: str) -> np.ndarray:
@@ -47,3 +47,23 @@ def _rank_depth_values(records, n: int, T: int, name: str) -> np.ndarray:
     else:
         num, den = np.int64(n) - MM, np.int64(n)
     return num.astype(np.float64) / np.float64(den)
+
+
+# The random projection depths (K23) take the same record over the k rows of the curves' projections instead of the T
+# timepoints, and K12's outlyingness over the same rows:
+#
+#     'rp_halfspace'   (nk - SM) / (nk)      mean over the directions of the univariate Tukey depth (Cuevas, Febrero & Fraiman 2007)
+#     'rp_fm'          (2nk - SF) / (2nk)    mean over the directions of 1 - |1/2 - F_r|, i.e. 1 - SF / (2nk)
+#     'random_tukey'   (n - MM) / n          minimum over the directions: the random Tukey depth (Cuesta-Albertos & Nieto-Reyes 2008)
+#     'rp_projection'  1 / (1 + O)           O = max over the directions of |z_r - med_r| / mad_r (O = inf: 0.0)
+_PROJECTED_AS_RANK = {'rp_halfspace': 'integrated_halfspace', 'rp_fm': 'fm', 'random_tukey': 'infimal_halfspace'}
+
+
+def _projected_depth_values(values, n: int, k: int, name: str) -> np.ndarray:
+    """The fp64 depths `name` of curves among n over k directions: from the int64 records [m, 5] of engine.rp_depth_sums,
+    or for 'rp_projection' from the fp64 outlyingness [m] of engine.rp_outlyingness."""
+    if name not in PROJECTED_DEPTHS:
+        raise ValueError(f'{name!r} is not one of {list(PROJECTED_DEPTHS)}')
+    if name == 'rp_projection':
+        return 1.0 / (1.0 + np.asarray(values, dtype=np.float64).reshape(-1))
+    return _rank_depth_values(values, n, k, _PROJECTED_AS_RANK[name])

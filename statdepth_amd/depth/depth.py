@@ -14,7 +14,7 @@ import numpy as np
 import pandas as pd
 
 from abc import ABC, abstractmethod
-from .calculations._functional import _curve_distances, _functionaldepth, _samplefunctionaldepth
+from .calculations._functional import _curve_distances, _curve_projections, _functionaldepth, _samplefunctionaldepth
 from .calculations._helper import DepthDegeneracy   # noqa: F401
 from .calculations._containment import _is_lens_depth
 from .calculations._pointcloud import _lens_cloud_depths, _pointwisedepth, _samplepointwisedepth
@@ -253,7 +253,22 @@ def FunctionalDepth(data: List[pd.DataFrame], to_compute=None, K=None, J=2, cont
     pairs, and so do not depend on `to_compute`.  On data whose values are not exactly representable a pair at an exact right
     angle in the reals is judged by the rounded distances.  The beta used is in the result's attrs['beta'].  ValueError for
     what 'spatial' refuses and for more than 16 384 curves (the n x n matrix of distances is kept on the device).  Every other
-    containment ignores `beta`."""
+    containment ignores `beta`.
+
+    containment='rp_halfspace', 'rp_fm', 'random_tukey' and 'rp_projection' (univariate data, under the rules of the rank
+    depths) are the random projection depths: every curve is projected on k directions of R^T, z_r = sum_t x(t) u_r(t) (the
+    plain sum over the timepoints in order; fold quadrature weights or a smooth basis into the directions), and a univariate
+    depth of the n projections is taken per direction.  'rp_halfspace' averages the univariate Tukey depth min(#<=, #>=) / n
+    over the directions (the random projection depth of Cuevas, Febrero & Fraiman 2007, fda.usc's depth.RP), 'rp_fm' averages
+    1 - |1/2 - F_r(z_r)| with the "<=" empirical CDF, 'random_tukey' takes the minimum of the Tukey depth (the random Tukey
+    depth of Cuesta-Albertos & Nieto-Reyes 2008) and 'rp_projection' is 1 / (1 + O), O the largest |z_r - med_r| / MAD_r
+    (PointcloudDepth's 'projection' rules for median, MAD and a MAD of 0).  `directions` is an int k -- k unit vectors drawn
+    from `np.random.default_rng(seed)`, the direction set of PointcloudDepth's 'halfspace' in R^T -- or a (k x T) array used
+    as given; 'exact' raises NotImplementedError.  The projections themselves are CurveProjections.  A point cloud with any
+    number of features is a set of short curves: FunctionalDepth([df.T], containment='random_tukey', directions=U) is
+    PointcloudDepth(df, containment='halfspace', directions=U) and 'rp_projection' is its 'projection', without their limit
+    of 8 features.  ValueError for what the rank depths refuse, for infinite values, magnitudes above 2^500 and 2^23 or more
+    timepoints; `relax`, `algo`, `aggregate`, `quantile`, `bandwidth` and `beta` are ignored."""
     if K is not None:
         depth = _samplefunctionaldepth(data=data, to_compute=to_compute, K=K, J=J, containment=containment,
                                        relax=relax, deep_check=deep_check, quiet=quiet, device=device, algo=algo)
@@ -279,6 +294,17 @@ def CurveDistances(data, to_compute=None, device=None) -> pd.DataFrame:
     exactly symmetric with a zero diagonal.  ValueError, before anything is uploaded: more than one frame, duplicate labels,
     fewer than 2 curves, no timepoint, NaN or infinite values, magnitudes above 2^480."""
     return _curve_distances(data, to_compute=to_compute, device=device)
+
+
+def CurveProjections(data, directions=1000, seed=0, device=None) -> pd.DataFrame:
+    """The projections of univariate curves on a set of directions of R^T: a DataFrame with one row per direction and one
+    column per curve of `data` (a DataFrame whose columns are the curves, or a list of one) under its label, entry
+    ((x(0) u(0) + x(1) u(1)) + x(2) u(2)) + ... over the timepoints in order, every product and every sum rounded to fp64
+    (sd_curve_projections).  `directions` and `seed` as for FunctionalDepth's 'rp_halfspace': an int k asks for k seeded
+    unit vectors, a (k x T) array is used as given.  These are the numbers the random projection depths rank.  ValueError,
+    before anything is uploaded: more than one frame, duplicate labels, fewer than 2 curves, no timepoint, NaN or infinite
+    values, magnitudes above 2^500, directions of the wrong width, non-finite or with an all-zero row."""
+    return _curve_projections(data, directions=directions, seed=seed, device=device)
 
 
 def FunctionalBoxplot(data, depths=None, *, alpha=0.5, factor=1.5, levels=(), device=None,

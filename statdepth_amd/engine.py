@@ -1213,3 +1213,83 @@ def projection_subset_outlyingness(P, members, U, device=None):
     """float64[nb]: per block (rows of `members`, -1 padded, target last; at most 2048 members) the outlyingness of the
     block's target inside the block (sd_projection_subset_outlyingness); an empty block gives 0."""
     return _points("sd_projection_subset_outlyingness", torch().float64, P, device, _BLOCKS, members, U=U)
+
+
+# ---- K23: projections of curves on a direction set, and the random projection depths (statdepth_hip_projections.h) ----
+def _projected_size(name, T, n, k, curve_major, *more):
+    """sd_<name>(T, n, st, sn, k, *more)."""
+    T, n = int(T), int(n)
+    return int(getattr(_native.load(), f"sd_{name}")(T, n, *_strides(T, n, curve_major), int(k), *more))
+
+
+def curve_projections_workspace_bytes(T, n, k, curve_major=False):
+    """(recommended, floor) workspace sizes of sd_curve_projections: it needs none, both are 0."""
+    size = _projected_size("curve_projections_workspace_bytes", T, n, k, curve_major)
+    return size, size
+
+
+def rp_depth_workspace_bytes(T, n, k, algo="auto", curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of sd_rp_depth_sums for T x n curves and k directions: a chunk of rows of the
+    k x n projections and K14's need for it -- all k rows at the recommended size while they are within 1 GiB, one row at the
+    floor.  Neither layout takes a copy."""
+    tail = (int(n if m is None else m), RANK_DEPTH_ALGOS[algo] if isinstance(algo, str) else int(algo))
+    return tuple(_projected_size(f"rp_depth_{name}", T, n, k, curve_major, *tail) for name in ("workspace_bytes", "min_workspace_bytes"))
+
+
+def rp_outlyingness_workspace_bytes(T, n, k, curve_major=False, m=None):
+    """(recommended, floor) workspace sizes of sd_rp_outlyingness: about 32 n bytes a direction of a chunk, one direction
+    at the floor."""
+    tail = (int(n if m is None else m),)
+    return tuple(_projected_size(f"rp_outlyingness_{name}", T, n, k, curve_major, *tail)
+                 for name in ("workspace_bytes", "min_workspace_bytes"))
+
+
+def _projected(fn, sizes, X, U, targets, device, own, ws_bytes, output):
+    """lib.<fn>(X, T, n, st, sn, U, k, [targets, m,] *own, out, ws, ws_bytes, stream).  targets False: the entry point takes
+    none.  sizes(M, k, m): the (recommended, floor) pair; ws_bytes None runs with the recommended size.  output(t, dev, M, k, m):
+    the output tensor."""
+    t = torch()
+    lib = _lib()
+    M = to_device_matrix(X, device)
+    dev = M.device
+    Ud = _directions_dev(U, M.T, dev)
+    k = int(Ud.shape[0])
+    sel, m = (), M.n
+    if targets is not False:
+        td, m, tp = _targets_dev(targets, M.n, dev)
+        sel = (tp, m)
+    out = output(t, dev, M, k, m)
+
+    def workspace():
+        size = sizes(M, k, m)[0] if ws_bytes is None else int(ws_bytes)
+        return _sized(dev, size) if size else (None, 0)
+    return _launch(dev, getattr(lib, fn), out, M.tensor.data_ptr(), M.T, M.n, M.st, M.sn, Ud.data_ptr(), k, *sel, *own,
+                   workspace=workspace)
+
+
+def curve_projections(X, U, device=None):
+    """float64[k, n]: Z[r, i] = ((X[0, i] U[r, 0] + X[1, i] U[r, 1]) + X[2, i] U[r, 2]) + ... (sd_curve_projections): the
+    projections of the n curves (columns of the T x n matrix X, either memory order) on the k rows of U (k x T), timepoints
+    in increasing order, every product and every sum rounded separately to fp64 and the first term the product alone -- the
+    bits of the numpy loop `z = X[0] * u[0]; for t in 1 .. T-1: z = z + X[t] * u[t]`."""
+    return _projected("sd_curve_projections", lambda M, k, m: curve_projections_workspace_bytes(M.T, M.n, k, M.sn != 1), X, U,
+                      False, device, (), None, lambda t, dev, M, k, m: t.empty((k, M.n), dtype=t.float64, device=dev))
+
+
+def rp_depth_sums(X, U, targets=None, device=None, algo="auto", ws_bytes=None):
+    """int64[m, 5]: K14's records (SA, SB, SF, SM, MM) over the k rows of curve_projections(X, U) instead of timepoints
+    (sd_rp_depth_sums): per target the sums over the directions of A (other curves projected strictly above), of B (strictly
+    below), of |2A - n| and of max(A, B), and the maximum over the directions of max(A, B).  X and U finite (the depth layer
+    checks).  algo: 'auto', 'image' (n <= 16 384) or 'sort', or 0, 1, 2.  ws_bytes: the workspace size to run with (default:
+    the recommended one); the records do not depend on it, below the floor the library refuses."""
+    a = RANK_DEPTH_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    return _projected("sd_rp_depth_sums", lambda M, k, m: rp_depth_workspace_bytes(M.T, M.n, k, a, M.sn != 1, m), X, U, targets,
+                      device, (a,), ws_bytes, lambda t, dev, M, k, m: t.empty((m, 5), dtype=t.int64, device=dev))
+
+
+def rp_outlyingness(X, U, targets=None, device=None, ws_bytes=None):
+    """float64[m]: max over the rows r of curve_projections(X, U) of |z_r(q) - med_r| / mad_r, K12's median, MAD, division
+    and zero cases on every row (sd_rp_outlyingness); depth = 1 / (1 + outlyingness).  +inf where a direction has MAD 0 and
+    the target is off its median.  X and U: finite, magnitudes of at most 2^500 (projection_check; the depth layer checks)."""
+    return _projected("sd_rp_outlyingness", lambda M, k, m: rp_outlyingness_workspace_bytes(M.T, M.n, k, M.sn != 1, m), X, U,
+                      targets, device, (), ws_bytes, lambda t, dev, M, k, m: t.empty((m,), dtype=t.float64, device=dev))
